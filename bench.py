@@ -11,6 +11,10 @@ pass of the WCRBFNet (region gate + 4096 Gaussian centres + Dense) over one batc
 65 536-query shard; rank 0's parameters are broadcast once over RCCL before the timed region and there is no
 collective in the steady state.
 
+``--dump-outputs DIR`` writes the forward output of the last timed step (``out.npy``, float32 [B, O]; rank r > 0:
+``out_rank<r>.npy``) after the timed region.  Inputs and parameters are seeded, so two builds can be compared output
+for output at the same arguments.
+
 Prints ONE JSON line on rank 0 (contract in the task statement) with ``roofline`` (dominant kernel, HIP-event
 timing on the launch stream), ``cpu_baseline`` (the C restatement of the reference path, oracle/, timed on this
 box's host cores on a bounded sample; N = 1 only) and ``extras``.  At every N the extras hold the multi-GPU
@@ -52,6 +56,8 @@ def parse():
     ap.add_argument("--scaling-extras-only", action="store_true",
                     help="extras: only the multi-GPU numbers (broadcast, cfg-4 strong, cfg-3 weak), also at N = 1")
     ap.add_argument("--cpu-sample", type=int, default=65536)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -160,6 +166,26 @@ def timed_region(fn, steps, warmup, world):
     return _max_over_ranks(wall, world), e0.elapsed_time(e1)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, rank, world, limit=DUMP_LIMIT_BYTES):
+    """Writes each tensor of ``arrays`` (name -> tensor) as ``out_dir/<name>.npy`` (rank r > 0: ``<name>_rank<r>.npy``),
+    float64 kept, anything else as float32.  Above ``limit`` bytes over all ranks, every array keeps the same fixed,
+    seeded sample of its rows (in their original order), so that two runs with the same arguments write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = world * sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > limit and a.ndim and a.shape[0]:
+            keep = max(1, a.shape[0] * limit // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def main():
     args = parse()
     self_launch(args, sys.argv[1:])              # --gpus N > 1 typed directly: start the ranks, relay, exit
@@ -184,10 +210,16 @@ def main():
     x = torch.from_numpy(configs.synth_queries(idx, seed=1123 + rank)).cuda()
     torch.cuda.synchronize()
 
-    wall, ev_ms = timed_region(lambda: net(x), args.steps, args.warmup, world)
+    last = {}
+
+    def step():
+        last["out"] = net(x)
+    wall, ev_ms = timed_region(step, args.steps, args.warmup, world)
     launch = net.last_launch()                   # the kernel of the timed region (the extras launch others)
     ms_per_step = wall / args.steps * 1e3
     value = B * world * args.steps / wall
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank, world)
 
     # every rank stays in the group until the end: the multi-GPU extras below are collective
     extras = None

@@ -1,5 +1,5 @@
-"""Generates the committed golden fixtures under tests/golden/ (run once in the build container,
-where /root/reference is mounted; the GPU box only sees the generated files).
+"""Generates the committed golden fixtures under tests/golden/ from a checkout of the reference project:
+``python tests/golden/make_fixtures.py <reference checkout>`` (the tests only read the generated files).
 
 * ``kat.json``        KAT-1 (scripts/test_dynamics.ipynb cells 1-4, recorded float32 output),
                       KAT-2 / KAT-3 (CommonRoad derivative vectors,
@@ -30,7 +30,7 @@ sys.path.insert(0, ROOT)
 from oracle import irbfn_oracle as orc  # noqa: E402
 from irbfn_amd import configs  # noqa: E402
 
-REF = "/root/reference"
+REF = sys.argv[1] if len(sys.argv) > 1 else None
 CKPTS = [
     ("dnmpc_1regions_newdata_oldintloss_nomirror_highk", 999),
     ("dnmpc_128regions", 600),
@@ -138,6 +138,8 @@ def synth_cfg1():
 
 
 if __name__ == "__main__":
+    if REF is None:
+        raise SystemExit("usage: python tests/golden/make_fixtures.py <reference checkout>")
     with open(os.path.join(HERE, "kat.json"), "w") as f:
         json.dump(kat(), f, indent=1)
     for run, step in CKPTS:

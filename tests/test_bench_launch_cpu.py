@@ -46,3 +46,22 @@ def test_direct_form_takes_the_spawn_path_without_a_gpu():
     assert r.returncode != 0
     assert r.stderr.count("bench.py needs a GPU") == 2, r.stderr[-3000:]
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_above_the_limit(tmp_path):
+    """``--dump-outputs``: float32 (float64 kept) .npy per array; above the byte limit the same seeded rows every time."""
+    import numpy as np
+    import torch
+    b = _bench()
+    out = torch.arange(1000 * 10, dtype=torch.float32).reshape(1000, 10)
+    b.dump_outputs(str(tmp_path / "all"), {"out": out, "g": out.double()}, rank=0, world=1)
+    np.testing.assert_array_equal(np.load(tmp_path / "all" / "out.npy"), out.numpy())
+    assert np.load(tmp_path / "all" / "g.npy").dtype == np.float64
+    b.dump_outputs(str(tmp_path / "r1"), {"out": out.half()}, rank=1, world=2)
+    assert np.load(tmp_path / "r1" / "out_rank1.npy").dtype == np.float32
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), {"out": out}, rank=0, world=1, limit=4000)
+    s1, s2 = np.load(tmp_path / "s1" / "out.npy"), np.load(tmp_path / "s2" / "out.npy")
+    assert s1.nbytes <= 4000 and s1.shape == (100, 10) and np.array_equal(s1, s2)
+    rows = s1[:, 0].astype(np.int64) // 10
+    assert (np.diff(rows) > 0).all() and np.array_equal(s1, out.numpy()[rows])

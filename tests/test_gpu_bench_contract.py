@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -40,6 +41,24 @@ def test_single_gpu_line(gpu):
     cb = j["cpu_baseline"]
     assert {"value", "unit", "cores", "kind", "sample"} <= set(cb) and cb["kind"] == "port" and cb["value"] > 0
     assert cb["parity_rel_err_vs_f64"] < 1e-5
+
+
+def test_dump_outputs_holds_the_last_timed_step(gpu, tmp_path):
+    """``--dump-outputs DIR``: the forward output of the timed path, full size (2.6 MB), checked against the C oracle on
+    the same seeded inputs; ``--steps`` is the number of timed steps and ``ms_per_step`` one step's share of the wall."""
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "7", "--warmup", "1", "--no-extras", "--no-cpu-baseline",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = _json_line(r.stdout)
+    B, O = j["config"]["batch_per_gpu"], j["config"]["out_features"]
+    assert j["steps"] == 7 and abs(j["value"] * j["ms_per_step"] / 1e3 - B) <= 1e-6 * B
+    assert sorted(os.listdir(tmp_path)) == ["out.npy"]
+    out = np.load(tmp_path / "out.npy")
+    assert out.dtype == np.float32 and out.shape == (B, O)
+    from irbfn_amd import configs
+    from oracle import c_oracle
+    ref = c_oracle.wcrbf_forward(configs.model_card(2), configs.synth_params(2), configs.synth_queries(2)[:512], np.float64)
+    assert np.abs(out[:512] - ref).max() <= 1e-5 * np.abs(ref).max()
 
 
 def _rank_free_env(**kw):
