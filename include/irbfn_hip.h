@@ -104,23 +104,17 @@ int irbfn_net_set_params(irbfn_net* net, const float* centers_dev, const float* 
 
 /* Per-descriptor options: kernel selection and launch geometry.  The defaults are what the library ships
  * with; everything else exists for A/B measurements and for the reduced-precision report of BASELINE config 5.
- * Nothing on the launch path reads the process environment.  value 0 of a geometry option = automatic. */
+ * Nothing on the launch path reads the process environment.  value 0 of a geometry option = automatic.
+ * Numbers missing below belong to retired options: irbfn_net_set_option / irbfn_net_get_option answer
+ * IRBFN_ERR_BAD_ARG for them. */
 typedef enum irbfn_option {
   IRBFN_OPT_FWD_KERNEL = 0,    /* irbfn_fwd_kernel below; default IRBFN_FWD_AUTO */
-  IRBFN_OPT_FWD_SMALL = 1,     /* 1 (default): B <= 64 runs on the latency kernel K1s; 0: never */
   IRBFN_OPT_FWD_F16_TERMS = 2, /* MFMA operands of K1h.  3 (default): (hi, lo) f16 pairs, float32-grade result;
                                   1: plain f16 operands (~1e-4 relative), 2: plain bf16 operands (~4e-3; O <= 16 only)
                                   -- the two reduced-precision variants BASELINE config 5 asks to report */
-  IRBFN_OPT_FWD_F16_MINB = 3,  /* smallest batch K1h takes in automatic mode (default 65) */
-  IRBFN_OPT_FWD_Q = 4,         /* K1: queries per lane (1, 2) */
-  IRBFN_OPT_FWD_NW = 5,        /* K1 / K1m: waves per workgroup */
-  IRBFN_OPT_FWD_QJ = 6,        /* K1m: query tiles per wave (1, 2, 4) */
-  IRBFN_OPT_FWD_F16_S = 7,     /* K1h: centre slices per query group */
-  IRBFN_OPT_FWD_F16_QG = 8,    /* K1h: query groups of 32 per workgroup */
+  IRBFN_OPT_FWD_F16_S = 7,     /* K1h / K1g: centre slices per query group */
+  IRBFN_OPT_FWD_F16_QG = 8,    /* K1h / K1g: query groups of 32 per workgroup */
   IRBFN_OPT_VJP_KERNEL = 9,    /* irbfn_vjp_kernel below; default IRBFN_VJP_AUTO */
-  IRBFN_OPT_VJP_F16_CT = 10,   /* K2h: 16-centre tiles per wave (2 default, 4) */
-  IRBFN_OPT_LDS_PAD = 11,      /* diagnosis: extra dynamic LDS bytes per workgroup of K1h / K2h (lowers occupancy) */
-  IRBFN_OPT_FWD_WIDE_PIPE = 12,/* K1h, 16 < O <= 128: 1 (default) pipelined kernel (deferred MFMAs, LDS-DMA ring of three), 0: two-buffer kernel */
   IRBFN_OPT_TICK_FUSED = 13,   /* planning tick on the matrix-core kernels: 1 (default) one launch where the instance exists (wide: d = 7,
                                   O = 2T in (96, 112], single-track modes; narrow: O = 2T <= 16, d = 7 single-track / inline bicycle,
                                   d = 8 Frenet), 0: forward + sign flip + roll-out launches */
@@ -128,8 +122,6 @@ typedef enum irbfn_option {
                                   1: only the first one does and later calls keep its verdict -- for training loops, which re-bind every step.
                                   The kernels test the device-side verdict themselves and fall back to the VALU distances / to K2h, so a stale
                                   host verdict costs speed, never correctness */
-  IRBFN_OPT_VJP_QSB = 15,      /* K2g / K2h: query slices of the VJP grid (slabs summed in fixed order); 0 (default): automatic.  Never more than
-                                  the workspace was sized for (the automatic number of the all-float32 kernel) */
   IRBFN_OPT_COUNT = 16
 } irbfn_option;
 typedef enum irbfn_fwd_kernel {

@@ -67,9 +67,7 @@ int irbfn_net_create(irbfn_net** out_net, int D, int R, int K, int O, int basis,
   net->DC = DC; net->OP = OP; net->N = R * K;
   net->S = (DC + 1 + OP + 3) & ~3;
   net->nsplit = nsplit; net->max_ranges = max_ranges > 0 ? max_ranges : 1; net->n_ranges = n_ranges;
-  net->opt[IRBFN_OPT_FWD_SMALL] = 1;
   net->opt[IRBFN_OPT_FWD_F16_TERMS] = 3;
-  net->opt[IRBFN_OPT_FWD_WIDE_PIPE] = 1;
   net->opt[IRBFN_OPT_TICK_FUSED] = 1;
 
   const size_t tab = (size_t)(nsplit > 0 ? nsplit : 1) * net->max_ranges;
@@ -144,22 +142,29 @@ int irbfn_net_set_params(irbfn_net* net, const float* centers_dev, const float* 
   return rc;
 }
 
+// the option numbers in use; the others belong to retired options
+static bool option_known(int option) {
+  switch (option) {
+    case IRBFN_OPT_FWD_KERNEL:
+    case IRBFN_OPT_FWD_F16_TERMS:
+    case IRBFN_OPT_FWD_F16_S:
+    case IRBFN_OPT_FWD_F16_QG:
+    case IRBFN_OPT_VJP_KERNEL:
+    case IRBFN_OPT_TICK_FUSED:
+    case IRBFN_OPT_GRAM_STICKY: return true;
+    default: return false;
+  }
+}
+
 int irbfn_net_set_option(irbfn_net* net, int option, int value) {
-  if (!net || option < 0 || option >= IRBFN_OPT_COUNT || value < 0) return IRBFN_ERR_BAD_ARG;
+  if (!net || !option_known(option) || value < 0) return IRBFN_ERR_BAD_ARG;
   switch (option) {
     case IRBFN_OPT_FWD_KERNEL: if (value > IRBFN_FWD_K1G) return IRBFN_ERR_BAD_ARG; break;
     case IRBFN_OPT_VJP_KERNEL: if (value > IRBFN_VJP_K2G) return IRBFN_ERR_BAD_ARG; break;
-    case IRBFN_OPT_FWD_SMALL: if (value > 1) return IRBFN_ERR_BAD_ARG; break;
     case IRBFN_OPT_FWD_F16_TERMS: if (value != 1 && value != 2 && value != 3) return IRBFN_ERR_BAD_ARG; break;
-    case IRBFN_OPT_FWD_Q: if (value > 2) return IRBFN_ERR_BAD_ARG; break;
-    case IRBFN_OPT_FWD_NW: if (value > 16) return IRBFN_ERR_BAD_ARG; break;
-    case IRBFN_OPT_FWD_QJ: if (value != 0 && value != 1 && value != 2 && value != 4) return IRBFN_ERR_BAD_ARG; break;
     case IRBFN_OPT_FWD_F16_S:
     case IRBFN_OPT_FWD_F16_QG: if (value > 16) return IRBFN_ERR_BAD_ARG; break;
-    case IRBFN_OPT_VJP_F16_CT: if (value != 0 && value != 2 && value != 4) return IRBFN_ERR_BAD_ARG; break;
-    case IRBFN_OPT_LDS_PAD: if (value > 128 * 1024) return IRBFN_ERR_BAD_ARG; break;
     case IRBFN_OPT_GRAM_STICKY: if (value > 1) return IRBFN_ERR_BAD_ARG; break;
-    case IRBFN_OPT_VJP_QSB: if (value > 4096) return IRBFN_ERR_BAD_ARG; break;
     default: break;
   }
   net->opt[option] = value;
@@ -167,7 +172,7 @@ int irbfn_net_set_option(irbfn_net* net, int option, int value) {
 }
 
 int irbfn_net_get_option(const irbfn_net* net, int option, int* value_out) {
-  if (!net || !value_out || option < 0 || option >= IRBFN_OPT_COUNT) return IRBFN_ERR_BAD_ARG;
+  if (!net || !value_out || !option_known(option)) return IRBFN_ERR_BAD_ARG;
   *value_out = net->opt[option];
   return IRBFN_OK;
 }
@@ -299,8 +304,7 @@ int irbfn_net_forward_rollout(irbfn_net* net, int mode, const float* x_dev, cons
 
 int irbfn_net_tick_needs_controls(irbfn_net* net, int mode, int64_t B, int T) {
   if (!net || rollout_state_dim(mode) < 0) return IRBFN_ERR_BAD_ARG;
-  if (tick_f16_wide_available(net, mode, B, T) || tick_f16_narrow_available(net, mode, B, T)) return 0;    // one launch, controls stay in LDS
-  return tick_through_controls(net, B) ? 1 : 0;              // forward + split-row roll-out through the caller's buffer
+  return tick_needs_controls(net, mode, B, T);
 }
 
 int irbfn_net_forward_gamma(irbfn_net* net, const float* x_dev, const float* gamma_dev, float* out_dev, int64_t B,

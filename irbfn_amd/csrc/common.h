@@ -110,6 +110,51 @@ struct irbfn_net {
 };
 
 namespace irbfn {
+// The kernel a forward or planning tick runs and its launch geometry, decided in one place (plan_forward / plan_tick,
+// rbf_forward.hip); the launchers take the plan as it is.  record_launch writes irbfn_net_last_launch's name from it.
+enum LaunchKind : int {
+  LK_NONE = 0,       // nothing runs: `status` says why
+  LK_K1S,            // rbf_fwd_clane: small batches
+  LK_K1R,            // rbf_fwd_sparse: region-sparse gate (`roll`: the one-launch tick)
+  LK_K1G,            // rbf_fwd_f16gram
+  LK_K1G_WIDE,       // rbf_fwd_f16gram_wide
+  LK_K1H,            // rbf_fwd_f16mfma
+  LK_K1H_WIDE,       // rbf_fwd_f16mfma_wide[_pipe]
+  LK_K1M,            // rbf_fwd_mfma
+  LK_K1,             // rbf_fwd_qlane (`roll`: the roll-out epilogue)
+  LK_TICK_K1G,       // rbf_tick_f16gram
+  LK_TICK_K1H,       // rbf_tick_f16mfma
+  LK_TICK_K1G_WIDE,  // rbf_tick_f16gram_wide
+  LK_TICK_K1H_WIDE,  // rbf_tick_f16mfma_wide
+  LK_K2G             // rbf_vjp_f16gram (the VJP plan, rbf_vjp.hip, launches it; named here with the others)
+};
+
+struct F16Geom {           // K1h's block geometry where the dispatch reached K1h (forced AUTO / K1H, its image, B >= 65)
+  bool ok;
+  int S, QG;               // centre slices (SW of the wide kernel) x query groups of 32
+  bool pipe;               // wide: the pipelined ring fits
+};
+
+struct LaunchPlan {
+  int kind = LK_NONE;
+  int status = IRBFN_ERR_UNSUPPORTED;  // IRBFN_OK once a kernel is chosen
+  int S = 0, QG = 0;       // K1h / K1g and their ticks: centre slices (SW of the wide forms) x query groups of 32; K2g: QSB
+  int terms = 3;           // K1h narrow: 3 (hi, lo) f16 pairs, 1 plain f16, 2 plain bf16
+  bool pipe = false;       // K1h wide: the pipelined kernel
+  int Q = 1, QJ = 0;       // K1: queries per lane; K1m: query tiles per wave
+  int nw = 0;              // K1 / K1m: waves per workgroup
+  int QT = 1, nb = 0, cpl = 1;  // K1s: queries per tile, centre blocks, centres per lane
+  int gc = 0;              // K1r: centre table gathered from global memory
+  bool gated = false;      // K1: region weights
+  bool roll = false;       // K1 / K1r: the roll-out epilogue of a planning tick
+  bool split = false;      // tick: this forward into the caller's controls, then the split-row roll-out
+  int mode = -1;           // ticks: irbfn_rollout_mode
+  size_t lds = 0;
+  int grid = 0, block = 0;
+  F16Geom h = {};          // K1h's geometry behind the choice (K1g stands in front of K1h); the ticks read it
+};
+void record_launch(irbfn_net* net, const LaunchPlan& p);
+
 // launchers implemented per translation unit
 // K0 (pack_all.hip): every image of the net in two launches
 int launch_pack_all(irbfn_net* net, const float* centers, const float* log_sigs, const float* kernel, const float* bias,
@@ -121,33 +166,39 @@ int launch_cluster_gate(const float* x, const float* wc, const float* bc, float*
                         int R, hipStream_t s);
 bool mfma_eligible(const irbfn_net* net);
 size_t mfma_record_floats(int D, int O);
-int launch_forward_mfma(irbfn_net* net, const float* x, float* out, int64_t B, int QJ, int nw, hipStream_t s);
+size_t mfma_lds_bytes(const irbfn_net* net, int QJ, int nw);
+int launch_forward_mfma(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s);
 bool f16_eligible(const irbfn_net* net);
 size_t f16_image_bytes(const irbfn_net* net);
-int launch_forward_f16(irbfn_net* net, const float* x, float* out, int64_t B, int S, int QG, int terms, hipStream_t s);
+// LDS bytes of K1h's narrow kernel (tick: the one-launch tick's control and state tiles on top) and of its wide kernels
+size_t f16_lds_bytes(const irbfn_net* net, int S, int QG, bool tick);
+size_t f16_wide_lds_bytes(const irbfn_net* net, int SW, int QG, bool pipe);
+void f16_wide_normalize(const irbfn_net* net, int* SW, int* QG, bool* pipe);
+int launch_forward_f16(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s);
 bool gram_eligible(const irbfn_net* net);
-bool gram_preferred(const irbfn_net* net, int64_t B);
-bool gram_wide_preferred(const irbfn_net* net, int64_t B);
-void gram_geometry(const irbfn_net* net, int64_t B, int* S, int* QG);
 size_t gram_image_bytes(const irbfn_net* net);
 size_t gram_header_bytes();
-int launch_forward_gram(irbfn_net* net, const float* x, float* out, int64_t B, int S, int QG, hipStream_t s);
-int launch_tick_gram_narrow(irbfn_net* net, int mode, const float* x, const int* mirror, const float* state0, const DynParams& dp,
-                            float* controls, float* states, int64_t B, int T, hipStream_t s);
-bool tick_through_controls(const irbfn_net* net, int64_t B);
-bool f16_narrow_geometry(const irbfn_net* net, int64_t B, int* S, int* QG);
-bool tick_f16_narrow_available(const irbfn_net* net, int mode, int64_t B, int T);
-int launch_tick_f16_narrow(irbfn_net* net, int mode, const float* x, const int* mirror, const float* state0,
+size_t gram_lds_bytes(int S, int QG, bool tick);
+size_t gram_wide_ring_bytes(const irbfn_net* net, int SW);
+size_t gram_wide_lds_bytes(const irbfn_net* net, int SW, int QG, size_t extra_red_floats);
+int launch_forward_gram(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s);
+// the one-launch planning ticks: is an instance compiled for this net, mode and horizon; their LDS; the launchers
+bool tick_narrow_compiled(const irbfn_net* net, int mode, int T);
+bool tick_wide_compiled(const irbfn_net* net, int mode, int T);
+size_t f16_wide_tick_lds_bytes(const irbfn_net* net, int SW, int QG);
+size_t gram_wide_tick_lds_bytes(const irbfn_net* net, int SW, int QG);
+int launch_tick_gram_narrow(irbfn_net* net, const LaunchPlan& p, const float* x, const int* mirror, const float* state0,
+                            const DynParams& dp, float* controls, float* states, int64_t B, int T, hipStream_t s);
+int launch_tick_f16_narrow(irbfn_net* net, const LaunchPlan& p, const float* x, const int* mirror, const float* state0,
                            const DynParams& dp, float* controls, float* states, int64_t B, int T, hipStream_t s);
-bool f16_wide_geometry(const irbfn_net* net, int64_t B, int* SW, int* QG);
-void f16_wide_normalize(const irbfn_net* net, int* SW, int* QG, bool* pipe);
-bool tick_f16_wide_available(const irbfn_net* net, int mode, int64_t B, int T);
-int launch_tick_f16_wide(irbfn_net* net, int mode, const float* x, const int* mirror, const float* state0,
-                         const DynParams& dp, float* controls, float* states, int64_t B, int T, hipStream_t s);
+int launch_tick_wide(irbfn_net* net, const LaunchPlan& p, const float* x, const int* mirror, const float* state0,
+                     const DynParams& dp, float* controls, float* states, int64_t B, int T, hipStream_t s);
+int tick_needs_controls(const irbfn_net* net, int mode, int64_t B, int T);
 size_t small_workspace_floats(int OP);
 int small_ticket_count();
 bool small_eligible(const irbfn_net* net, int64_t B);
-int launch_forward_small(irbfn_net* net, const float* x, float* out, int64_t B, hipStream_t s);
+void small_geometry(const irbfn_net* net, int64_t B, LaunchPlan* p);
+int launch_forward_small(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s);
 int launch_gate(irbfn_net* net, const float* x, float* gamma, int64_t B, hipStream_t s);
 int64_t vjp_workspace_bytes(const irbfn_net* net, int64_t B);
 int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs,
@@ -163,7 +214,6 @@ int launch_rollout_forward(int mode, const float* x0u, const DynParams& dp, floa
                            int T, hipStream_t s);
 int launch_rollout_forward_split(int mode, const float* state0, const float* controls, const DynParams& dp,
                                  float* states, int64_t B, int T, hipStream_t s);
-bool prefer_mfma(const irbfn_net* net);
 int launch_rollout_vjp(int mode, const float* x0u, const DynParams& dp, const float* gstates,
                        float* g_x0u, int64_t B, int T, float clip_tie, hipStream_t s);
 int launch_unmirror(float* controls, const int* mirror, int64_t B, int O, int sv0, hipStream_t s);
@@ -177,12 +227,16 @@ void sparse_free(irbfn_net* net);
 bool sparse_preferred(const irbfn_net* net, int64_t B);
 void sparse_pack_tables(const irbfn_net* net, float** ctab, float** wtab, int* wp);   // K1r / K2r tables packed by pack_all.hip (role P)
 bool sparse_vjp_eligible(const irbfn_net* net);
+bool sparse_vjp_lds_fits(const irbfn_net* net);
 int sparse_vjp_slices(const irbfn_net* net, int64_t B);
 size_t sparse_vjp_workspace_bytes(const irbfn_net* net, int64_t B);
 int launch_vjp_sparse(irbfn_net* net, const float* x, const float* gout, int64_t B, void* spws, float* part, int SL, int Npad,
                       hipStream_t s);
-int launch_forward_sparse(irbfn_net* net, const float* x, float* out, int64_t B, const int* mirror, int sv0, int mode,
-                          const float* state0, const DynParams* dp, float* states, int T, hipStream_t s);
+// K1r's geometry for B queries (roll: the one-launch tick of `mode` / T): IRBFN_OK, IRBFN_ERR_UNSUPPORTED where it has no
+// instance or its LDS image does not fit, IRBFN_ERR_HIP
+int sparse_geometry(const irbfn_net* net, int64_t B, bool roll, int mode, int T, LaunchPlan* p);
+int launch_forward_sparse(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, const int* mirror, int sv0,
+                          int mode, const float* state0, const DynParams* dp, float* states, int T, hipStream_t s);
 int rollout_state_dim(int mode);
 int rollout_input_dim(int mode, int T);
 }  // namespace irbfn

@@ -5,8 +5,6 @@
 // the instance exists (d = 7, 96 < O <= 112, single-track modes); same bits as the separate launches (the forward's
 // arithmetic and geometry, the step functions and the flush are shared code).
 // Compiled with the roll-out's flags (the 50-knot register arrays need the full unroll).
-#include <stdio.h>
-
 #include "rbf_forward_gram_wide.h"
 
 namespace irbfn {
@@ -68,81 +66,49 @@ static int launch_tick_bc(int bc, const F16Args& a, const F16Roll& r, int grid, 
   }
 }
 
-struct TickPlan { int SW, QG; };
-
-// does the one-launch tick exist for this net / horizon / mode / batch (and is it enabled)?
-static bool tick_plan(const irbfn_net* net, int mode, int64_t B, int T, TickPlan* p) {
-  if (net->opt[IRBFN_OPT_TICK_FUSED] == 0 || B <= 64) return false;
+// is the one-launch tick compiled for this net / horizon / mode?
+bool tick_wide_compiled(const irbfn_net* net, int mode, int T) {
   if (mode != IRBFN_ROLLOUT_ST_SELECT && mode != IRBFN_ROLLOUT_ST_KS) return false;
-  if (net->DC != 7 || net->O != 2 * T || T > kTickTch || (net->O + 15) / 16 != 7) return false;
-  if (!f16_wide_geometry(net, B, &p->SW, &p->QG)) return false;                 // the forward would not run K1h-wide
-  bool pipe;
-  f16_wide_normalize(net, &p->SW, &p->QG, &pipe);
-  return pipe;
+  return net->DC == 7 && net->O == 2 * T && T <= kTickTch && (net->O + 15) / 16 == 7;
 }
 
-bool tick_f16_wide_available(const irbfn_net* net, int mode, int64_t B, int T) {
-  TickPlan p;
-  return tick_plan(net, mode, B, T, &p);
+// LDS floats of the trajectories' output tile, per query group
+static size_t tick_out_floats() {
+  constexpr int S = 7;
+  return (kPairRows * pair_pitch(S, pair_ts(S)) + 3) & ~3;
 }
 
-// IRBFN_ERR_UNSUPPORTED: no fused instance for this net / horizon / mode -> the caller takes the separate launches
-int launch_tick_f16_wide(irbfn_net* net, int mode, const float* x, const int* mirror, const float* state0,
-                         const DynParams& dp, float* controls, float* states, int64_t B, int T, hipStream_t s) {
-  TickPlan tp;
-  if (!tick_plan(net, mode, B, T, &tp)) return IRBFN_ERR_UNSUPPORTED;
-  if (net->opt[IRBFN_OPT_FWD_KERNEL] == IRBFN_FWD_AUTO && gram_wide_preferred(net, B)) {
-    // K1g's wide body: same conditions, the parameters fit the expansion
-    int SW, QG;
-    gram_wide_geometry(net, B, &SW, &QG);
-    GramArgs a;
-    gram_fill_args(net, x, controls, B, SW, QG, &a);
-    F16Roll r;
-    r.state0 = state0; r.states = states; r.mirror = mirror; r.T = T; r.dp = dp;
-    constexpr int S = 7;
-    r.wlds = (kPairRows * pair_pitch(S, pair_ts(S)) + 3) & ~3;
-    size_t lds = gram_wide_lds_bytes(net, SW, QG, (size_t)QG * 32 * (net->O | 1));
-    const size_t out = (size_t)QG * r.wlds * sizeof(float);
-    lds = lds > out ? lds : out;
-    if (lds <= 160 * 1024) {
-      const long groups = (B + 31) / 32;
-      const int grid = (int)((groups + QG - 1) / QG);
-      const int rc = mode == IRBFN_ROLLOUT_ST_KS ? launch_gtick_bc<IRBFN_ROLLOUT_ST_KS>(net->bclass, a, r, grid, SW * QG * 64, lds, s)
-                                                 : launch_gtick_bc<IRBFN_ROLLOUT_ST_SELECT>(net->bclass, a, r, grid, SW * QG * 64, lds, s);
-      if (rc == IRBFN_OK) {
-        snprintf(net->last_name, sizeof(net->last_name), "rbf_tick_f16gram_wide<D=7,BC=%d,NT=7,MODE=%d,SW=%d,QG=%d>", net->bclass, mode, SW, QG);
-        net->last_grid = grid;
-        net->last_block = SW * QG * 64;
-      }
-      return rc;
-    }
-  }
-  const int SW = tp.SW, QG = tp.QG;
-  const int NT = 7;
-  const int nchunks = (net->N + kF16Chunk - 1) / kF16Chunk;
-  F16Args a;
-  a.x = x; a.img = net->f16_img; a.oscale = net->f16_oscale; a.bias = net->bias; a.out = controls; a.gate = net->gate();
-  a.B = (long)B; a.Dreal = net->D; a.O = net->O; a.nchunks = nchunks; a.S = SW; a.QG = QG;
+size_t gram_wide_tick_lds_bytes(const irbfn_net* net, int SW, int QG) {
+  const size_t lds = gram_wide_lds_bytes(net, SW, QG, (size_t)QG * 32 * (net->O | 1));
+  const size_t out = (size_t)QG * tick_out_floats() * sizeof(float);
+  return lds > out ? lds : out;
+}
+
+size_t f16_wide_tick_lds_bytes(const irbfn_net* net, int SW, int QG) {
+  const size_t ring = (size_t)SW * kWideRing * f16_chunk_bytes(net->DC, 7);
+  const size_t red = ((size_t)SW * QG * 2 * 4 * 64 + (size_t)QG * 32 + (size_t)QG * 32 * (net->O | 1)) * sizeof(float);
+  const size_t out = (size_t)QG * tick_out_floats() * sizeof(float);
+  size_t lds = ring > red ? ring : red;
+  return lds > out ? lds : out;
+}
+
+int launch_tick_wide(irbfn_net* net, const LaunchPlan& p, const float* x, const int* mirror, const float* state0,
+                     const DynParams& dp, float* controls, float* states, int64_t B, int T, hipStream_t s) {
   F16Roll r;
   r.state0 = state0; r.states = states; r.mirror = mirror; r.T = T; r.dp = dp;
-  constexpr int S = 7;
-  r.wlds = (kPairRows * pair_pitch(S, pair_ts(S)) + 3) & ~3;
-  const size_t ring = (size_t)SW * kWideRing * f16_chunk_bytes(net->DC, NT);
-  const size_t red = ((size_t)SW * QG * 2 * 4 * 64 + (size_t)QG * 32 + (size_t)QG * 32 * (net->O | 1)) * sizeof(float);
-  const size_t out = (size_t)QG * r.wlds * sizeof(float);
-  size_t lds = ring > red ? ring : red;
-  lds = lds > out ? lds : out;
-  if (lds > 160 * 1024) return IRBFN_ERR_UNSUPPORTED;
-  const long groups = (B + 31) / 32;
-  const int grid = (int)((groups + QG - 1) / QG);
-  const int rc = mode == IRBFN_ROLLOUT_ST_KS ? launch_tick_bc<IRBFN_ROLLOUT_ST_KS>(net->bclass, a, r, grid, SW * QG * 64, lds, s)
-                                             : launch_tick_bc<IRBFN_ROLLOUT_ST_SELECT>(net->bclass, a, r, grid, SW * QG * 64, lds, s);
-  if (rc == IRBFN_OK) {
-    snprintf(net->last_name, sizeof(net->last_name), "rbf_tick_f16mfma_wide<D=7,BC=%d,NT=7,MODE=%d,SW=%d,QG=%d>", net->bclass, mode, SW, QG);
-    net->last_grid = grid;
-    net->last_block = SW * QG * 64;
+  r.wlds = (int)tick_out_floats();
+  const bool ks = p.mode == IRBFN_ROLLOUT_ST_KS;
+  if (p.kind == LK_TICK_K1G_WIDE) {                // K1g's wide body: the distances on the matrix cores as well
+    GramArgs a;
+    gram_fill_args(net, x, controls, B, p.S, p.QG, &a);
+    return ks ? launch_gtick_bc<IRBFN_ROLLOUT_ST_KS>(net->bclass, a, r, p.grid, p.block, p.lds, s)
+              : launch_gtick_bc<IRBFN_ROLLOUT_ST_SELECT>(net->bclass, a, r, p.grid, p.block, p.lds, s);
   }
-  return rc;
+  F16Args a;
+  a.x = x; a.img = net->f16_img; a.oscale = net->f16_oscale; a.bias = net->bias; a.out = controls; a.gate = net->gate();
+  a.B = (long)B; a.Dreal = net->D; a.O = net->O; a.nchunks = (net->N + kF16Chunk - 1) / kF16Chunk; a.S = p.S; a.QG = p.QG;
+  return ks ? launch_tick_bc<IRBFN_ROLLOUT_ST_KS>(net->bclass, a, r, p.grid, p.block, p.lds, s)
+            : launch_tick_bc<IRBFN_ROLLOUT_ST_SELECT>(net->bclass, a, r, p.grid, p.block, p.lds, s);
 }
 
 }  // namespace irbfn

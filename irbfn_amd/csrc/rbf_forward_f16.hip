@@ -428,46 +428,37 @@ static int launch_f16w_dc(const F16Args& a, int NT, int bc, int grid, int block,
 }
 
 // final block geometry of the wide kernels and the choice between them: the pipelined kernel (kWideRing chunk buffers
-// per slice) wherever its ring fits the 160 KB of LDS; IRBFN_OPT_FWD_WIDE_PIPE = 0 selects the two-buffer kernel
+// per slice) wherever its ring fits the 160 KB of LDS
 void f16_wide_normalize(const irbfn_net* net, int* SW, int* QG, bool* pipe) {
   const int nchunks = (net->N + kF16Chunk - 1) / kF16Chunk;
   while (*SW > 1 && nchunks / *SW < 2) *SW /= 2;
   if (*QG < 2 || *SW * *QG > 8) *QG = 8 / *SW;               // the copy team needs >= 128 threads per slice
-  *pipe = net->opt[IRBFN_OPT_FWD_WIDE_PIPE] != 0 &&
-          (size_t)*SW * kWideRing * f16_chunk_bytes(net->DC, f16_nt(net)) <= 160 * 1024;
+  *pipe = (size_t)*SW * kWideRing * f16_chunk_bytes(net->DC, f16_nt(net)) <= 160 * 1024;
 }
 
-// SW centre slices (1, 2 or 4) x QG = 8 / SW query groups of 32 per 512-thread block
-static int launch_forward_f16_wide(irbfn_net* net, const float* x, float* out, int64_t B, int SW, int QG, hipStream_t s) {
-  const int NT = f16_nt(net);
-  const int nchunks = (net->N + kF16Chunk - 1) / kF16Chunk;
-  if (SW != 1 && SW != 2 && SW != 4) return IRBFN_ERR_BAD_ARG;
-  bool pipe;
-  f16_wide_normalize(net, &SW, &QG, &pipe);
-  F16Args a;
-  a.x = x; a.img = net->f16_img; a.oscale = net->f16_oscale; a.bias = net->bias; a.out = out; a.gate = net->gate();
-  a.B = (long)B; a.Dreal = net->D; a.O = net->O; a.nchunks = nchunks; a.S = SW; a.QG = QG;
-  const size_t stream = (size_t)SW * (pipe ? kWideRing : 2) * f16_chunk_bytes(net->DC, NT);
+size_t f16_wide_lds_bytes(const irbfn_net* net, int SW, int QG, bool pipe) {
+  const size_t stream = (size_t)SW * (pipe ? kWideRing : 2) * f16_chunk_bytes(net->DC, f16_nt(net));
   const size_t red = ((size_t)SW * QG * 2 * 4 * 64 + (size_t)QG * 32) * sizeof(float);
-  const size_t lds = stream > red ? stream : red;
-  if (lds > 160 * 1024) return IRBFN_ERR_UNSUPPORTED;
-  const long groups = (B + 31) / 32;
-  const int grid = (int)((groups + QG - 1) / QG);
-  int rc;
+  return stream > red ? stream : red;
+}
+
+static void f16_fill_args(const irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, F16Args* a) {
+  a->x = x; a->img = net->f16_img; a->oscale = net->f16_oscale; a->bias = net->bias; a->out = out; a->gate = net->gate();
+  a->B = (long)B; a->Dreal = net->D; a->O = net->O; a->nchunks = (net->N + kF16Chunk - 1) / kF16Chunk; a->S = p.S; a->QG = p.QG;
+}
+
+// SW centre slices (1, 2 or 4) x QG query groups of 32 per 512-thread block
+static int launch_forward_f16_wide(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s) {
+  const int NT = f16_nt(net);
+  F16Args a;
+  f16_fill_args(net, p, x, out, B, &a);
   switch (net->DC) {
-    case 3: rc = launch_f16w_dc<3>(a, NT, net->bclass, grid, SW * QG * 64, lds, pipe, s); break;
-    case 4: rc = launch_f16w_dc<4>(a, NT, net->bclass, grid, SW * QG * 64, lds, pipe, s); break;
-    case 7: rc = launch_f16w_dc<7>(a, NT, net->bclass, grid, SW * QG * 64, lds, pipe, s); break;
-    case 8: rc = launch_f16w_dc<8>(a, NT, net->bclass, grid, SW * QG * 64, lds, pipe, s); break;
-    default: rc = IRBFN_ERR_UNSUPPORTED;
+    case 3: return launch_f16w_dc<3>(a, NT, net->bclass, p.grid, p.block, p.lds, p.pipe, s);
+    case 4: return launch_f16w_dc<4>(a, NT, net->bclass, p.grid, p.block, p.lds, p.pipe, s);
+    case 7: return launch_f16w_dc<7>(a, NT, net->bclass, p.grid, p.block, p.lds, p.pipe, s);
+    case 8: return launch_f16w_dc<8>(a, NT, net->bclass, p.grid, p.block, p.lds, p.pipe, s);
+    default: return IRBFN_ERR_UNSUPPORTED;
   }
-  if (rc == IRBFN_OK) {
-    snprintf(net->last_name, sizeof(net->last_name), "rbf_fwd_f16mfma_wide%s<D=%d,BC=%d,NT=%d,SW=%d,QG=%d>", pipe ? "_pipe" : "",
-             net->DC, net->bclass, NT, SW, QG);
-    net->last_grid = grid;
-    net->last_block = SW * QG * 64;
-  }
-  return rc;
 }
 
 template <int DC, int TERMS, bool BF = false>
@@ -500,85 +491,44 @@ static int launch_tick_narrow_bc(const F16Args& a, const F16Roll& rl, int mode, 
   return IRBFN_OK;
 }
 
-// does the one-launch tick of a narrow net exist (and is it enabled) for this net / mode / batch / horizon?
-static bool tick_narrow_plan(const irbfn_net* net, int mode, int64_t B, int T, int* S_out, int* QG_out, size_t* lds_out) {
-  if (net->opt[IRBFN_OPT_TICK_FUSED] == 0 || net->O > 16 || net->O != 2 * T || T > kTickNarrowT) return false;
+// is the one-launch tick of a narrow net compiled for this net / mode / horizon?
+bool tick_narrow_compiled(const irbfn_net* net, int mode, int T) {
+  if (net->O > 16 || net->O != 2 * T || T > kTickNarrowT) return false;
   const bool st = mode == IRBFN_ROLLOUT_ST_SELECT || mode == IRBFN_ROLLOUT_ST_KS || mode == IRBFN_ROLLOUT_FULLINT;
-  if (!((st && net->DC == 7) || (mode == IRBFN_ROLLOUT_FRENET_LS && net->DC == 8))) return false;
-  if (net->opt[IRBFN_OPT_FWD_F16_TERMS] != 3 && net->opt[IRBFN_OPT_FWD_F16_TERMS] != 0) return false;
-  int S, QG;
-  if (!f16_narrow_geometry(net, B, &S, &QG)) return false;   // the forward would not run K1h
-  const int waves = S * QG;
-  const size_t ring = (size_t)waves * 2 * (kF16Chunk * f16_rf(net->DC) * 4 + 2 * kF16WBytes);
-  const size_t red = ((size_t)waves * 2 * 4 * 64 + (size_t)QG * 32 + (size_t)QG * 32 * (kTickNarrowCP + kTickNarrowSP)) * sizeof(float);
-  const size_t lds = ring > red ? ring : red;
-  if (lds > 64 * 1024) return false;
-  *S_out = S; *QG_out = QG; *lds_out = lds;
-  return true;
-}
-
-bool tick_f16_narrow_available(const irbfn_net* net, int mode, int64_t B, int T) {
-  int S, QG;
-  size_t lds;
-  return tick_narrow_plan(net, mode, B, T, &S, &QG, &lds);
-}
-
-// IRBFN_ERR_UNSUPPORTED: no instance -> the caller takes another path
-int launch_tick_f16_narrow(irbfn_net* net, int mode, const float* x, const int* mirror, const float* state0,
-                           const DynParams& dp, float* controls, float* states, int64_t B, int T, hipStream_t s) {
-  int S, QG;
-  size_t lds;
-  if (!tick_narrow_plan(net, mode, B, T, &S, &QG, &lds)) return IRBFN_ERR_UNSUPPORTED;
-  const int nchunks = (net->N + kF16Chunk - 1) / kF16Chunk;
-  F16Args a;
-  a.x = x; a.img = net->f16_img; a.oscale = net->f16_oscale; a.bias = net->bias; a.out = controls; a.gate = net->gate();
-  a.B = (long)B; a.Dreal = net->D; a.O = net->O; a.nchunks = nchunks; a.S = S; a.QG = QG;
-  F16Roll rl;
-  rl.state0 = state0; rl.states = states; rl.mirror = mirror; rl.T = T; rl.wlds = 0; rl.dp = dp;
-  const long groups = (B + 31) / 32;
-  const int grid = (int)((groups + QG - 1) / QG);
-  const int rc = net->DC == 7 ? launch_tick_narrow_bc<7>(a, rl, mode, net->bclass, grid, S * QG * 64, lds, s)
-                              : launch_tick_narrow_bc<8>(a, rl, mode, net->bclass, grid, S * QG * 64, lds, s);
-  if (rc == IRBFN_OK) {
-    snprintf(net->last_name, sizeof(net->last_name), "rbf_tick_f16mfma<D=%d,BC=%d,MODE=%d,S=%d,QG=%d>", net->DC, net->bclass, mode, S, QG);
-    net->last_grid = grid;
-    net->last_block = S * QG * 64;
-  }
-  return rc;
+  return (st && net->DC == 7) || (mode == IRBFN_ROLLOUT_FRENET_LS && net->DC == 8);
 }
 
 // S = centre slices per query group, QG = query groups (of 32) per block; S * QG <= 8 waves
-int launch_forward_f16(irbfn_net* net, const float* x, float* out, int64_t B, int S, int QG, int terms, hipStream_t s) {
-  if (!net->f16_img || !f16_eligible(net)) return IRBFN_ERR_UNSUPPORTED;
-  if (net->O > 16) return launch_forward_f16_wide(net, x, out, B, S, QG, s);
-  const int nchunks = (net->N + kF16Chunk - 1) / kF16Chunk;
-  if (S < 1 || QG < 1 || S * QG > 8 || S > nchunks) return IRBFN_ERR_BAD_ARG;
-  F16Args a;
-  a.x = x; a.img = net->f16_img; a.oscale = net->f16_oscale; a.bias = net->bias; a.out = out; a.gate = net->gate();
-  a.B = (long)B; a.Dreal = net->D; a.O = net->O; a.nchunks = nchunks; a.S = S; a.QG = QG;
+size_t f16_lds_bytes(const irbfn_net* net, int S, int QG, bool tick) {
   const int waves = S * QG;
   const size_t ring = (size_t)waves * 2 * (kF16Chunk * f16_rf(net->DC) * 4 + 2 * kF16WBytes);
-  const size_t red = ((size_t)waves * 2 * 4 * 64 + (size_t)QG * 32) * sizeof(float);
-  size_t lds = ring > red ? ring : red;
-  lds += (size_t)net->opt[IRBFN_OPT_LDS_PAD];               // diagnosis only: lowers the occupancy
-  if (lds > 64 * 1024) return IRBFN_ERR_UNSUPPORTED;
-  const long groups = (B + 31) / 32;
-  const int grid = (int)((groups + QG - 1) / QG);
-  int rc;
+  size_t red = (size_t)waves * 2 * 4 * 64 + (size_t)QG * 32;
+  if (tick) red += (size_t)QG * 32 * (kTickNarrowCP + kTickNarrowSP);
+  red *= sizeof(float);
+  return ring > red ? ring : red;
+}
+
+int launch_tick_f16_narrow(irbfn_net* net, const LaunchPlan& p, const float* x, const int* mirror, const float* state0,
+                           const DynParams& dp, float* controls, float* states, int64_t B, int T, hipStream_t s) {
+  F16Args a;
+  f16_fill_args(net, p, x, controls, B, &a);
+  F16Roll rl;
+  rl.state0 = state0; rl.states = states; rl.mirror = mirror; rl.T = T; rl.wlds = 0; rl.dp = dp;
+  return net->DC == 7 ? launch_tick_narrow_bc<7>(a, rl, p.mode, net->bclass, p.grid, p.block, p.lds, s)
+                      : launch_tick_narrow_bc<8>(a, rl, p.mode, net->bclass, p.grid, p.block, p.lds, s);
+}
+
+int launch_forward_f16(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s) {
+  if (p.kind == LK_K1H_WIDE) return launch_forward_f16_wide(net, p, x, out, B, s);
+  F16Args a;
+  f16_fill_args(net, p, x, out, B, &a);
   switch (net->DC) {
-    case 3: rc = launch_f16_dc<3>(a, terms, net->bclass, grid, waves * 64, lds, s); break;
-    case 4: rc = launch_f16_dc<4>(a, terms, net->bclass, grid, waves * 64, lds, s); break;
-    case 7: rc = launch_f16_dc<7>(a, terms, net->bclass, grid, waves * 64, lds, s); break;
-    case 8: rc = launch_f16_dc<8>(a, terms, net->bclass, grid, waves * 64, lds, s); break;
-    default: rc = IRBFN_ERR_UNSUPPORTED;
+    case 3: return launch_f16_dc<3>(a, p.terms, net->bclass, p.grid, p.block, p.lds, s);
+    case 4: return launch_f16_dc<4>(a, p.terms, net->bclass, p.grid, p.block, p.lds, s);
+    case 7: return launch_f16_dc<7>(a, p.terms, net->bclass, p.grid, p.block, p.lds, s);
+    case 8: return launch_f16_dc<8>(a, p.terms, net->bclass, p.grid, p.block, p.lds, s);
+    default: return IRBFN_ERR_UNSUPPORTED;
   }
-  if (rc == IRBFN_OK) {
-    snprintf(net->last_name, sizeof(net->last_name), "rbf_fwd_f16mfma<D=%d,BC=%d,TERMS=%s,S=%d,QG=%d>", net->DC,
-             net->bclass, terms == 1 ? "1" : (terms == 2 ? "1,BF16" : "3"), S, QG);
-    net->last_grid = grid;
-    net->last_block = waves * 64;
-  }
-  return rc;
 }
 
 }  // namespace irbfn

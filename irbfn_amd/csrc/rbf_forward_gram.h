@@ -298,9 +298,7 @@ __device__ __forceinline__ void gram_valu_args(const F16Args& a, const long (&qr
 }
 
 // host side (rbf_forward_gram.hip, rbf_forward_gram_wide.hip, plan_tick_wide.hip)
-void gram_wide_geometry(const irbfn_net* net, int64_t B, int* SW, int* QG);
-size_t gram_wide_lds_bytes(const irbfn_net* net, int SW, int QG, size_t extra_red_floats);
 void gram_fill_args(const irbfn_net* net, const float* x, float* out, int64_t B, int S, int QG, GramArgs* a);
-int launch_forward_gram_wide(irbfn_net* net, const float* x, float* out, int64_t B, int SW, int QG, hipStream_t s);
+int launch_forward_gram_wide(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s);
 
 }  // namespace irbfn

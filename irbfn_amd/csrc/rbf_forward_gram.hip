@@ -256,38 +256,26 @@ static int launch_gram_bc(const GramArgs& a, int bc, int grid, int block, size_t
   return IRBFN_OK;
 }
 
-// S centre slices x QG query groups of 32 per block (S * QG <= 8 waves)
-int launch_forward_gram(irbfn_net* net, const float* x, float* out, int64_t B, int S, int QG, hipStream_t s) {
-  if (!net->gram_img || !net->f16_img || !gram_eligible(net)) return IRBFN_ERR_UNSUPPORTED;
-  if (net->O > 16) return launch_forward_gram_wide(net, x, out, B, S, QG, s);
-  const int nchunks = (net->N + kF16Chunk - 1) / kF16Chunk;
-  if (S < 1 || QG < 1 || S * QG > 16 || S > nchunks) return IRBFN_ERR_BAD_ARG;
-  GramArgs a;
-  a.f.x = x; a.f.img = net->f16_img; a.f.oscale = net->f16_oscale; a.f.bias = net->bias; a.f.out = out; a.f.gate = net->gate();
-  a.f.B = (long)B; a.f.Dreal = net->D; a.f.O = net->O; a.f.nchunks = nchunks; a.f.S = S; a.f.QG = QG;
-  a.gimg = net->gram_img;
-  a.hdr = reinterpret_cast<const GramHdr*>(net->gram_hdr);
-  const int waves = S * QG;
+// S centre slices x QG query groups of 32 per block (tick: the one-launch tick's control and state tiles on top)
+size_t gram_lds_bytes(int S, int QG, bool tick) {
   const size_t ring = (size_t)S * kGramRing * kGramChunkBytes;
-  const size_t red = ((size_t)waves * 2 * 4 * 64 + (size_t)QG * 32) * sizeof(float);
-  const size_t lds = ring > red ? ring : red;
-  if (lds > 160 * 1024) return IRBFN_ERR_UNSUPPORTED;
-  const long groups = (B + 31) / 32;
-  const int grid = (int)((groups + QG - 1) / QG);
-  int rc;
+  size_t red = (size_t)S * QG * 2 * 4 * 64 + (size_t)QG * 32;
+  if (tick) red += (size_t)QG * 32 * (kTickNarrowCP + kTickNarrowSP);
+  red *= sizeof(float);
+  return ring > red ? ring : red;
+}
+
+int launch_forward_gram(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s) {
+  if (p.kind == LK_K1G_WIDE) return launch_forward_gram_wide(net, p, x, out, B, s);
+  GramArgs a;
+  gram_fill_args(net, x, out, B, p.S, p.QG, &a);
   switch (net->DC) {
-    case 3: rc = launch_gram_bc<3>(a, net->bclass, grid, waves * 64, lds, s); break;
-    case 4: rc = launch_gram_bc<4>(a, net->bclass, grid, waves * 64, lds, s); break;
-    case 7: rc = launch_gram_bc<7>(a, net->bclass, grid, waves * 64, lds, s); break;
-    case 8: rc = launch_gram_bc<8>(a, net->bclass, grid, waves * 64, lds, s); break;
-    default: rc = IRBFN_ERR_UNSUPPORTED;
+    case 3: return launch_gram_bc<3>(a, net->bclass, p.grid, p.block, p.lds, s);
+    case 4: return launch_gram_bc<4>(a, net->bclass, p.grid, p.block, p.lds, s);
+    case 7: return launch_gram_bc<7>(a, net->bclass, p.grid, p.block, p.lds, s);
+    case 8: return launch_gram_bc<8>(a, net->bclass, p.grid, p.block, p.lds, s);
+    default: return IRBFN_ERR_UNSUPPORTED;
   }
-  if (rc == IRBFN_OK) {
-    snprintf(net->last_name, sizeof(net->last_name), "rbf_fwd_f16gram<D=%d,BC=%d,S=%d,QG=%d>", net->DC, net->bclass, S, QG);
-    net->last_grid = grid;
-    net->last_block = waves * 64;
-  }
-  return rc;
 }
 
 template <int DC>
@@ -314,40 +302,15 @@ static int launch_tick_gram_bc(const GramArgs& a, const F16Roll& rl, int mode, i
   return IRBFN_OK;
 }
 
-// The one-launch planning tick of a narrow net on K1g (rbf_tick_f16gram): same conditions as K1h's (launch_tick_f16_narrow),
-// and the parameters fit the expansion.  IRBFN_ERR_UNSUPPORTED: no instance -> the caller takes another path
-int launch_tick_gram_narrow(irbfn_net* net, int mode, const float* x, const int* mirror, const float* state0, const DynParams& dp,
-                            float* controls, float* states, int64_t B, int T, hipStream_t s) {
-  if (net->opt[IRBFN_OPT_FWD_KERNEL] != IRBFN_FWD_AUTO && net->opt[IRBFN_OPT_FWD_KERNEL] != IRBFN_FWD_K1G) return IRBFN_ERR_UNSUPPORTED;
-  if (!gram_preferred(net, B)) return IRBFN_ERR_UNSUPPORTED;
-  if (net->opt[IRBFN_OPT_TICK_FUSED] == 0 || net->O != 2 * T || T > kTickNarrowT) return IRBFN_ERR_UNSUPPORTED;
-  const bool st = mode == IRBFN_ROLLOUT_ST_SELECT || mode == IRBFN_ROLLOUT_ST_KS || mode == IRBFN_ROLLOUT_FULLINT;
-  if (!((st && net->DC == 7) || (mode == IRBFN_ROLLOUT_FRENET_LS && net->DC == 8))) return IRBFN_ERR_UNSUPPORTED;
-  int S, QG;
-  gram_geometry(net, B, &S, &QG);
-  const int nchunks = (net->N + kF16Chunk - 1) / kF16Chunk;
-  const int waves = S * QG;
-  const size_t ring = (size_t)S * kGramRing * kGramChunkBytes;
-  const size_t red = ((size_t)waves * 2 * 4 * 64 + (size_t)QG * 32 + (size_t)QG * 32 * (kTickNarrowCP + kTickNarrowSP)) * sizeof(float);
-  const size_t lds = ring > red ? ring : red;
-  if (lds > 160 * 1024 || S > nchunks) return IRBFN_ERR_UNSUPPORTED;
+// The one-launch planning tick of a narrow net on K1g (rbf_tick_f16gram)
+int launch_tick_gram_narrow(irbfn_net* net, const LaunchPlan& p, const float* x, const int* mirror, const float* state0,
+                            const DynParams& dp, float* controls, float* states, int64_t B, int T, hipStream_t s) {
   GramArgs a;
-  a.f.x = x; a.f.img = net->f16_img; a.f.oscale = net->f16_oscale; a.f.bias = net->bias; a.f.out = controls; a.f.gate = net->gate();
-  a.f.B = (long)B; a.f.Dreal = net->D; a.f.O = net->O; a.f.nchunks = nchunks; a.f.S = S; a.f.QG = QG;
-  a.gimg = net->gram_img;
-  a.hdr = reinterpret_cast<const GramHdr*>(net->gram_hdr);
+  gram_fill_args(net, x, controls, B, p.S, p.QG, &a);
   F16Roll rl;
   rl.state0 = state0; rl.states = states; rl.mirror = mirror; rl.T = T; rl.wlds = 0; rl.dp = dp;
-  const long groups = (B + 31) / 32;
-  const int grid = (int)((groups + QG - 1) / QG);
-  const int rc = net->DC == 7 ? launch_tick_gram_bc<7>(a, rl, mode, net->bclass, grid, waves * 64, lds, s)
-                              : launch_tick_gram_bc<8>(a, rl, mode, net->bclass, grid, waves * 64, lds, s);
-  if (rc == IRBFN_OK) {
-    snprintf(net->last_name, sizeof(net->last_name), "rbf_tick_f16gram<D=%d,BC=%d,MODE=%d,S=%d,QG=%d>", net->DC, net->bclass, mode, S, QG);
-    net->last_grid = grid;
-    net->last_block = waves * 64;
-  }
-  return rc;
+  return net->DC == 7 ? launch_tick_gram_bc<7>(a, rl, p.mode, net->bclass, p.grid, p.block, p.lds, s)
+                      : launch_tick_gram_bc<8>(a, rl, p.mode, net->bclass, p.grid, p.block, p.lds, s);
 }
 
 }  // namespace irbfn

@@ -175,11 +175,7 @@ __global__ __launch_bounds__((OP * Q > 48) ? 512 : 1024) void rbf_fwd_qlane(cons
     int n = n0;
     constexpr int G = IRBFN_FWD_G;
     if constexpr (BC != BC_GENERIC && G > 1 && (G * Q <= 16)) {
-#ifdef IRBFN_DBG_RECMASK      // diagnosis only: every wave re-reads the same few records (scalar-cache hits)
-      for (; n + G <= n1; n += G) group_body<D, OP, Q, BC, false, G>(a.rec + (size_t)(n & IRBFN_DBG_RECMASK) * S, S, xq, acc, gam);
-#else
       for (; n + G <= n1; n += G) group_body<D, OP, Q, BC, false, G>(a.rec + (size_t)n * S, S, xq, acc, gam);
-#endif
     }
 #pragma unroll 2
     for (; n < n1; ++n)

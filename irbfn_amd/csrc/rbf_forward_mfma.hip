@@ -242,38 +242,33 @@ static int launch_mfma_d(const MfmaArgs& a, int NT, int QJ, int bc, int nw, size
   return IRBFN_ERR_UNSUPPORTED;
 }
 
-int launch_forward_mfma(irbfn_net* net, const float* x, float* out, int64_t B, int QJ, int nw, hipStream_t s) {
-  const int D = net->D, NT = (net->O + 15) / 16, OW = 16 * NT;
+size_t mfma_lds_bytes(const irbfn_net* net, int QJ, int nw) {
+  const int D = net->D, OW = 16 * ((net->O + 15) / 16);
   const int RS = mfma_cw(D) + OW;
   const int ROWS = 16 * QJ;
-  const long tiles = (B + ROWS - 1) / ROWS;
-  size_t ring = (size_t)nw * kChunk * RS;
-  size_t stage = (size_t)ROWS * D;
-  size_t red = (size_t)nw * ROWS * (OW + 1) + ROWS;
+  const size_t ring = (size_t)nw * kChunk * RS;
+  const size_t stage = (size_t)ROWS * D;
+  const size_t red = (size_t)nw * ROWS * (OW + 1) + ROWS;
   size_t fl = ring > stage ? ring : stage;
   fl = fl > red ? fl : red;
-  const size_t lds = fl * sizeof(float);
-  if (lds > 160 * 1024) return IRBFN_ERR_UNSUPPORTED;
+  return fl * sizeof(float);
+}
+
+int launch_forward_mfma(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s) {
+  const int D = net->D, NT = (net->O + 15) / 16;
   MfmaArgs a;
   a.x = x; a.recm = net->recm; a.bias = net->bias; a.out = out; a.gate = net->gate(); a.B = (long)B;
   a.O = net->O; a.Npad = net->Npad; a.basis = net->basis;
-  int rc;
   switch (D) {
-    case 2: rc = launch_mfma_d<2>(a, NT, QJ, net->bclass, nw, lds, tiles, s); break;
-    case 3: rc = launch_mfma_d<3>(a, NT, QJ, net->bclass, nw, lds, tiles, s); break;
-    case 4: rc = launch_mfma_d<4>(a, NT, QJ, net->bclass, nw, lds, tiles, s); break;
-    case 5: rc = launch_mfma_d<5>(a, NT, QJ, net->bclass, nw, lds, tiles, s); break;
-    case 6: rc = launch_mfma_d<6>(a, NT, QJ, net->bclass, nw, lds, tiles, s); break;
-    case 7: rc = launch_mfma_d<7>(a, NT, QJ, net->bclass, nw, lds, tiles, s); break;
-    case 8: rc = launch_mfma_d<8>(a, NT, QJ, net->bclass, nw, lds, tiles, s); break;
-    default: rc = IRBFN_ERR_UNSUPPORTED;
+    case 2: return launch_mfma_d<2>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
+    case 3: return launch_mfma_d<3>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
+    case 4: return launch_mfma_d<4>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
+    case 5: return launch_mfma_d<5>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
+    case 6: return launch_mfma_d<6>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
+    case 7: return launch_mfma_d<7>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
+    case 8: return launch_mfma_d<8>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
+    default: return IRBFN_ERR_UNSUPPORTED;
   }
-  if (rc == IRBFN_OK) {
-    snprintf(net->last_name, sizeof(net->last_name), "rbf_fwd_mfma<D=%d,NT=%d,QJ=%d,BC=%d>", D, NT, QJ, net->bclass);
-    net->last_grid = (int)tiles;
-    net->last_block = nw * kWave;
-  }
-  return rc;
 }
 
 }  // namespace irbfn

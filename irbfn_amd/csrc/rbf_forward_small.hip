@@ -210,38 +210,37 @@ static int launch_small_d(const SmallArgs& a, int OP, int QT, int bc, dim3 grid,
 #undef IRBFN_SCASE
 }
 
-int launch_forward_small(irbfn_net* net, const float* x, float* out, int64_t B, hipStream_t s) {
-  SmallArgs a;
-  a.x = x; a.rec = net->rec; a.bias = net->bias; a.out = out; a.part = net->small_part;
-  a.ticket = net->small_ticket; a.gate = net->gate();
-  a.B = (int)B; a.Dreal = net->D; a.O = net->O; a.N = net->N; a.K = net->K; a.S = net->S; a.basis = net->basis;
+void small_geometry(const irbfn_net* net, int64_t B, LaunchPlan* p) {
   const int QT = B <= kSmallMaxB ? 1 : 8;
   const long qtiles = (B + QT - 1) / QT;
-  // enough workgroups to spread over the chip, bounded by the ticket / partial-sum workspace
+  // enough workgroups to spread over the chip, bounded by the ticket / partial-sum workspace (B <= kSmallMaxB: one block
+  // always fits it)
   int cpl = 1;
   long nb = ((long)net->N + 255) / 256;
   while (nb > 1 && (nb > kSmallMaxNB || nb * qtiles > 4096 || (size_t)nb * B * net->OP > kSmallWsFloats)) {
     cpl *= 2;
     nb = ((long)net->N + 256L * cpl - 1) / (256L * cpl);
   }
-  if ((size_t)nb * B * net->OP > kSmallWsFloats || qtiles > kSmallTickets) return IRBFN_ERR_UNSUPPORTED;
-  a.cpl = cpl;
-  const dim3 grid((unsigned)nb, (unsigned)qtiles);
-  int rc;
+  p->kind = LK_K1S; p->status = IRBFN_OK;
+  p->QT = QT; p->nb = (int)nb;
+  p->cpl = cpl;
+  p->grid = (int)(nb * qtiles); p->block = 256;
+}
+
+int launch_forward_small(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s) {
+  SmallArgs a;
+  a.x = x; a.rec = net->rec; a.bias = net->bias; a.out = out; a.part = net->small_part;
+  a.ticket = net->small_ticket; a.gate = net->gate();
+  a.B = (int)B; a.Dreal = net->D; a.O = net->O; a.N = net->N; a.K = net->K; a.S = net->S; a.basis = net->basis;
+  a.cpl = p.cpl;
+  const dim3 grid((unsigned)p.nb, (unsigned)((B + p.QT - 1) / p.QT));
   switch (net->DC) {
-    case 3: rc = launch_small_d<3>(a, net->OP, QT, net->bclass, grid, s); break;
-    case 4: rc = launch_small_d<4>(a, net->OP, QT, net->bclass, grid, s); break;
-    case 7: rc = launch_small_d<7>(a, net->OP, QT, net->bclass, grid, s); break;
-    case 8: rc = launch_small_d<8>(a, net->OP, QT, net->bclass, grid, s); break;
-    default: rc = IRBFN_ERR_UNSUPPORTED;
+    case 3: return launch_small_d<3>(a, net->OP, p.QT, net->bclass, grid, s);
+    case 4: return launch_small_d<4>(a, net->OP, p.QT, net->bclass, grid, s);
+    case 7: return launch_small_d<7>(a, net->OP, p.QT, net->bclass, grid, s);
+    case 8: return launch_small_d<8>(a, net->OP, p.QT, net->bclass, grid, s);
+    default: return IRBFN_ERR_UNSUPPORTED;
   }
-  if (rc == IRBFN_OK) {
-    snprintf(net->last_name, sizeof(net->last_name), "rbf_fwd_clane<D=%d,OP=%d,BC=%d,QT=%d>", net->DC, net->OP,
-             net->bclass, QT);
-    net->last_grid = (int)(nb * qtiles);
-    net->last_block = 256;
-  }
-  return rc;
 }
 
 }  // namespace irbfn

@@ -664,23 +664,13 @@ extern "C" int irbfn_debug_sparse_stamps(unsigned long long* out32) {
 }
 #endif
 
-// forward (states == nullptr) or the one-launch planning tick (states != nullptr, O == 2T, T*S <= 64)
-int launch_forward_sparse(irbfn_net* net, const float* x, float* out, int64_t B, const int* mirror, int sv0,
-                          int mode, const float* state0, const DynParams* dp, float* states, int T, hipStream_t s) {
+int sparse_geometry(const irbfn_net* net, int64_t B, bool roll, int mode, int T, LaunchPlan* p) {
   if (!net->sp_ok) return IRBFN_ERR_UNSUPPORTED;
-  const bool roll = states != nullptr;
-  if (roll) {
-    if (net->bclass == BC_GENERIC || net->O != 2 * T || T * rollout_state_dim(mode) > 64) return IRBFN_ERR_UNSUPPORTED;
+  if (roll) {                                    // the tick: O == 2T (checked by the caller), T*S <= 64
+    if (net->bclass == BC_GENERIC || T * rollout_state_dim(mode) > 64) return IRBFN_ERR_UNSUPPORTED;
     if (net->sp_OPS != 2 && net->sp_OPS != 10 && net->sp_OPS != 16) return IRBFN_ERR_UNSUPPORTED;
     if (net->DC != 7 && net->DC != 8) return IRBFN_ERR_UNSUPPORTED;
   }
-  SpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.out = out; a.bias = net->bias; a.img = net->sp_img;
-  a.B = (long)B; a.Dreal = net->D; a.O = net->O; a.K = net->K; a.nr = net->n_ranges; a.E = net->sp_E; a.ns = net->nsplit;
-  a.cap = net->sp_cap; a.RS = net->sp_RS; a.basis = net->basis; a.wide_list = net->n_ranges > 256 ? 1 : 0;
-  a.mirror = mirror; a.sv0 = sv0;
-  if (roll) { a.state0 = state0; a.states = states; a.T = T; a.mode = mode; a.dp = *dp; }
   // Where the centre table lives.  One workgroup per CU is all that fits with the table in LDS (93 KB on the 128-region
   // planner): best while the launch has at most one workgroup per CU (B = 65536: 22.2 vs 23.4 us; the tick 27.5 vs 37.4).
   // Beyond that the workgroups would queue up in rounds -- with the table gathered from global memory (L2-resident) three
@@ -692,29 +682,39 @@ int launch_forward_sparse(irbfn_net* net, const float* x, float* out, int64_t B,
     IRBFN_HIP_CHECK(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
     n_cu = v > 0 ? v : 256;
   }
-  a.gc = ((B + kSpNT - 1) / kSpNT > n_cu) ? 1 : 0;
-  const SpImg imh = sp_img_layout(a.nr, a.RS, a.E, a.K);
-  const SpLds L = sp_lds_layout(a.gc ? imh.small : imh.total, a.nr, a.E, a.cap, a.wide_list);
+  const int gc = ((B + kSpNT - 1) / kSpNT > n_cu) ? 1 : 0;
+  const SpImg imh = sp_img_layout(net->n_ranges, net->sp_RS, net->sp_E, net->K);
+  const SpLds L = sp_lds_layout(gc ? imh.small : imh.total, net->n_ranges, net->sp_E, net->sp_cap, net->n_ranges > 256 ? 1 : 0);
   size_t lds = (size_t)L.total * 4;
   if (roll) lds = std::max(lds, (size_t)kSpNT * 65 * 4);
   if (lds > kSpMaxLds) return IRBFN_ERR_UNSUPPORTED;
-  int grid = 0, rc;
+  p->kind = LK_K1R; p->status = IRBFN_OK;
+  p->gc = gc; p->roll = roll; p->mode = mode; p->lds = lds;
+  p->grid = (int)((B + kSpNT - 1) / kSpNT); p->block = kSpNT;
+  return IRBFN_OK;
+}
+
+// forward (states == nullptr) or the one-launch planning tick (states != nullptr)
+int launch_forward_sparse(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, const int* mirror, int sv0,
+                          int mode, const float* state0, const DynParams* dp, float* states, int T, hipStream_t s) {
+  SpArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.out = out; a.bias = net->bias; a.img = net->sp_img;
+  a.B = (long)B; a.Dreal = net->D; a.O = net->O; a.K = net->K; a.nr = net->n_ranges; a.E = net->sp_E; a.ns = net->nsplit;
+  a.cap = net->sp_cap; a.RS = net->sp_RS; a.basis = net->basis; a.wide_list = net->n_ranges > 256 ? 1 : 0;
+  a.mirror = mirror; a.sv0 = sv0;
+  if (p.roll) { a.state0 = state0; a.states = states; a.T = T; a.mode = mode; a.dp = *dp; }
+  a.gc = p.gc;
+  int grid = 0;
   switch (net->DC) {
-    case 3: rc = roll ? IRBFN_ERR_UNSUPPORTED : sp_launch_d<3, false>(a, net->sp_OPS, net->bclass, lds, s, &grid); break;
-    case 4: rc = roll ? IRBFN_ERR_UNSUPPORTED : sp_launch_d<4, false>(a, net->sp_OPS, net->bclass, lds, s, &grid); break;
-    case 7: rc = roll ? sp_launch_d<7, true>(a, net->sp_OPS, net->bclass, lds, s, &grid)
-                      : sp_launch_d<7, false>(a, net->sp_OPS, net->bclass, lds, s, &grid); break;
-    case 8: rc = roll ? sp_launch_d<8, true>(a, net->sp_OPS, net->bclass, lds, s, &grid)
-                      : sp_launch_d<8, false>(a, net->sp_OPS, net->bclass, lds, s, &grid); break;
-    default: rc = IRBFN_ERR_UNSUPPORTED;
+    case 3: return sp_launch_d<3, false>(a, net->sp_OPS, net->bclass, p.lds, s, &grid);
+    case 4: return sp_launch_d<4, false>(a, net->sp_OPS, net->bclass, p.lds, s, &grid);
+    case 7: return p.roll ? sp_launch_d<7, true>(a, net->sp_OPS, net->bclass, p.lds, s, &grid)
+                          : sp_launch_d<7, false>(a, net->sp_OPS, net->bclass, p.lds, s, &grid);
+    case 8: return p.roll ? sp_launch_d<8, true>(a, net->sp_OPS, net->bclass, p.lds, s, &grid)
+                          : sp_launch_d<8, false>(a, net->sp_OPS, net->bclass, p.lds, s, &grid);
+    default: return IRBFN_ERR_UNSUPPORTED;
   }
-  if (rc == IRBFN_OK) {
-    snprintf(net->last_name, sizeof(net->last_name), "rbf_fwd_sparse<D=%d,OP=%d,BC=%d,ROLL=%d,GC=%d>", net->DC, net->sp_OPS,
-             net->bclass, (int)roll, a.gc);
-    net->last_grid = grid;
-    net->last_block = kSpNT;
-  }
-  return rc;
 }
 
 
@@ -1188,10 +1188,21 @@ static SpWs sp_ws_layout(const irbfn_net* net, int64_t B) {
 }
 size_t sparse_vjp_workspace_bytes(const irbfn_net* net, int64_t B) { return sp_ws_layout(net, B).total; }
 
+static size_t sparse_pairs_lds(const irbfn_net* net) {
+  const int nr = net->n_ranges;
+  const SpImg im = sp_img_layout(nr, net->sp_RS, net->sp_E, net->K);
+  const size_t nr64 = ((size_t)nr + 63) & ~(size_t)63;
+  const size_t NW = kSpNT / kWave;
+  return ((size_t)im.small + (size_t)net->sp_E * kSpNT + 9 * kSpNT + (size_t)((nr + 31) / 32) * kSpNT + 2 * NW * nr64 + NW * nr64 +
+          nr64 + NW + 8) * 4;
+}
+
+// the pair-list kernel's tables fit its LDS (the plan's check in front of K2r)
+bool sparse_vjp_lds_fits(const irbfn_net* net) { return sparse_pairs_lds(net) <= kSpMaxLds; }
+
 // pair lists + K2r -> slab part[SL][V][Npad]; the caller runs the slab reduce and the bias sums
 int launch_vjp_sparse(irbfn_net* net, const float* x, const float* gout, int64_t B, void* spws, float* part, int SL, int Npad,
                       hipStream_t s) {
-  if (!sparse_vjp_eligible(net)) return IRBFN_ERR_UNSUPPORTED;
   const int nr = net->n_ranges;
   const SpWs w = sp_ws_layout(net, B);
   char* base = static_cast<char*>(spws);
@@ -1204,12 +1215,7 @@ int launch_vjp_sparse(irbfn_net* net, const float* x, const float* gout, int64_t
   memset(&pa, 0, sizeof(pa));
   pa.x = x; pa.img = net->sp_img; pa.B = (long)B; pa.Dreal = net->D; pa.nr = nr; pa.E = net->sp_E; pa.ns = net->nsplit;
   pa.RS = net->sp_RS; pa.K = net->K; pa.cap = net->sp_cap; pa.nblk = w.nblk; pa.cnt = cnt; pa.loff = loff; pa.pairs = pairs;
-  const SpImg im = sp_img_layout(nr, net->sp_RS, net->sp_E, net->K);
-  const size_t nr64 = ((size_t)nr + 63) & ~(size_t)63;
-  const size_t NW = kSpNT / kWave;
-  const size_t lds = ((size_t)im.small + (size_t)net->sp_E * kSpNT + 9 * kSpNT + (size_t)((nr + 31) / 32) * kSpNT +
-                      2 * NW * nr64 + NW * nr64 + nr64 + NW + 8) * 4;
-  if (lds > kSpMaxLds) return IRBFN_ERR_UNSUPPORTED;
+  const size_t lds = sparse_pairs_lds(net);
   const dim3 gridp((unsigned)w.nblk);
 #define IRBFN_SPP(DV)                                                                                                \
   do {                                                                                                               \

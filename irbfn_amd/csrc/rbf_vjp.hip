@@ -365,13 +365,15 @@ struct VjpPlan {
   int QS;
   bool use_h;      // K2h (matrix-core VJP) instead of K2
   bool use_g;      // K2g (u and the centre gradients on the matrix cores too) in front of K2h
-  int CT;
   bool use_sp;     // K2r (region-sparse VJP, rbf_sparse.hip) instead of K2
   int SL;          // K2r: slices per region (<= QSB slabs are allocated)
   size_t off_sp, off_sp_part;   // K2r: pair lists, slabs
+  int status;      // IRBFN_OK, or why nothing runs (a forced kernel that cannot take the net, LDS)
 };
 
-static VjpPlan make_plan(const irbfn_net* net, int64_t B) {
+// The VJP's kernel, its slab count and its workspace layout.  The layout depends on the net and B alone
+// (irbfn_net_vjp_workspace_bytes); gamma_ext: caller-provided region weights (ClusterWCRBFNet).
+static VjpPlan make_plan(const irbfn_net* net, int64_t B, const float* gamma_ext = nullptr) {
   VjpPlan p;
   p.groups = (net->N + kWave - 1) / kWave;
   p.Npad = p.groups * kWave;
@@ -399,12 +401,11 @@ static VjpPlan make_plan(const irbfn_net* net, int64_t B) {
   // K2h: packed 32-query blocks + (absmax, scales); IRBFN_OPT_VJP_KERNEL = IRBFN_VJP_K2 / IRBFN_VJP_K2H forces one
   const int vk = net->opt[IRBFN_OPT_VJP_KERNEL];
   p.use_h = vjph_eligible(net) && vk != IRBFN_VJP_K2 && B >= 2048;
-  p.CT = net->opt[IRBFN_OPT_VJP_F16_CT] == 4 ? 4 : 2;
   const size_t blkb = vjph_block_bytes(net) > vjpg_block_bytes() ? vjph_block_bytes(net) : vjpg_block_bytes();
   p.off_qblk = off;  off += al(vjph_eligible(net) ? (size_t)((B + 31) / 32) * blkb : 0);
   // K2g in front of K2h from 8192 queries and 2.5e7 (query, centre) pairs (tools/sweep_vjp_batch.py: 4096 centres: K2g 57.6 vs K2h 64.3 us at
   // B = 12288, a tie at 8192; 1000 centres: 50.1 vs 52.1 at 24576, 46.3 vs 45.0 at 16384)
-  p.use_g = p.use_h && vjpg_eligible(net) && (vk == IRBFN_VJP_K2G || (vk == IRBFN_VJP_AUTO && B >= 8192 && (long long)B * net->N >= 25000000LL)) && net->opt[IRBFN_OPT_VJP_F16_CT] == 0;
+  p.use_g = p.use_h && vjpg_eligible(net) && (vk == IRBFN_VJP_K2G || (vk == IRBFN_VJP_AUTO && B >= 8192 && (long long)B * net->N >= 25000000LL));
   p.off_misc = off;  off += al((size_t)(p.bias_blocks + 8) * sizeof(float));
   // K2r: several regions with a sparse gate (automatic where the forward takes K1r; IRBFN_VJP_K2R forces it where eligible)
   p.use_sp = sparse_vjp_eligible(net) && (vk == IRBFN_VJP_K2R || (vk == IRBFN_VJP_AUTO && sparse_preferred(net, B)));
@@ -427,12 +428,11 @@ static VjpPlan make_plan(const irbfn_net* net, int64_t B) {
     long q2 = (resident + gb - 1) / gb;
     if (q2 > 64) q2 = 64;                                  // small nets: the slab reduce grows with the slices (N = 1000, B = 80000: 64 slices 84 us, 96: 91)
     if (q2 * 8 > nqb) q2 = (nqb + 7) / 8;
-    if (net->opt[IRBFN_OPT_VJP_QSB] > 0) q2 = net->opt[IRBFN_OPT_VJP_QSB];
     if (q2 < 1) q2 = 1;
     if (q2 < p.QSB) p.QSB = (int)q2;          // never more slabs than were allocated above
   } else if (p.use_h) {
     // fewer, longer query slices than K2 (3 waves per SIMD resident): halves the slab traffic of the reduce kernel
-    const long gh = (net->N + 16 * p.CT - 1) / (16 * p.CT);
+    const long gh = (net->N + 31) / 32;                    // blocks of 4 waves x 2 tiles of 16 centres
     long q2 = (6144 + gh * 4 - 1) / (gh * 4);
     const long nqb = (B + 31) / 32;
     if (q2 * 4 > nqb) q2 = (nqb + 3) / 4;
@@ -440,6 +440,23 @@ static VjpPlan make_plan(const irbfn_net* net, int64_t B) {
     if (q2 < p.QSB) p.QSB = (int)q2;          // never more slabs than were allocated above
   }
   p.total = off;
+  // the kernel
+  p.status = IRBFN_OK;
+  if (gamma_ext) p.use_h = false;                // the gated K2 (with the slab count chosen above)
+  if (vk == IRBFN_VJP_K2G && !(p.use_h && p.use_g)) p.status = IRBFN_ERR_UNSUPPORTED;   // a forced kernel that cannot take the net
+  if (p.use_h && vjph_lds_bytes(net) > 64 * 1024) p.status = IRBFN_ERR_UNSUPPORTED;
+  if (p.use_h) return p;
+  if (gamma_ext) {
+    p.use_sp = false;
+  } else if (p.use_sp && !sparse_vjp_lds_fits(net)) {
+    p.use_sp = false;                            // K2r's pair tables do not fit: K2, unless K2r was forced
+    if (vk == IRBFN_VJP_K2R) p.status = IRBFN_ERR_UNSUPPORTED;
+  } else if (!p.use_sp && vk == IRBFN_VJP_K2R) {
+    p.status = IRBFN_ERR_UNSUPPORTED;            // a forced kernel that cannot take the net
+  }
+  if (p.use_sp) return p;
+  const size_t glds = ((size_t)net->nsplit * net->max_ranges * kWave + (size_t)net->gate().n_ranges * net->nsplit) * sizeof(float);
+  if (glds > 64 * 1024) p.status = IRBFN_ERR_UNSUPPORTED;     // K2's query packing: the gate tables
   return p;
 }
 
@@ -734,14 +751,12 @@ int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_cente
     IRBFN_HIP_CHECK(hipMemsetAsync(g_bias, 0, (size_t)net->O * sizeof(float), s));
     return IRBFN_OK;
   }
-  VjpPlan p = make_plan(net, B);
-  if (gamma_ext) p.use_h = false;                // caller-provided region weights (ClusterWCRBFNet): the gated K2
-  if (net->opt[IRBFN_OPT_VJP_KERNEL] == IRBFN_VJP_K2G && !(p.use_h && p.use_g)) return IRBFN_ERR_UNSUPPORTED;   // a forced kernel that cannot take the net
+  const VjpPlan p = make_plan(net, B, gamma_ext);
+  if (p.status != IRBFN_OK) return p.status;
   char* base = static_cast<char*>(ws);
   float* gamma = reinterpret_cast<float*>(base + p.off_gamma);
   float* part = reinterpret_cast<float*>(base + p.off_part);
   float* bpart = reinterpret_cast<float*>(base + p.off_bias);
-  const long total_h = n_c + n_l + n_k;
   if (p.use_h) {
     float* bmax = reinterpret_cast<float*>(base + p.off_misc);           // [bias_blocks] max |g| per block
     float* scales = bmax + p.bias_blocks;                                // [2]
@@ -759,38 +774,34 @@ int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_cente
       if (++net->vjp_gen <= 0) net->vjp_gen = 1;
       run_gen = net->vjp_gen;
       int* flag = net->vjp_flags + (run_gen & 63);
+      LaunchPlan k;
+      k.kind = LK_K2G; k.S = p.QSB;
+      k.grid = (int)((((net->N + 31) / 32 + 3) / 4) * p.QSB); k.block = 256;
+      record_launch(net, k);
       rch = launch_vjp_gram(net, x, gout, B, reinterpret_cast<unsigned char*>(base + p.off_qblk), bmax, p.bias_blocks, scales, flag,
                             run_gen, part, p.QSB, p.Npad, s);
       if (rch != IRBFN_OK) return rch;
       run_if = flag;
-    } else if (net->opt[IRBFN_OPT_VJP_KERNEL] == IRBFN_VJP_K2G) {
-      return IRBFN_ERR_UNSUPPORTED;
     }
     rch = launch_vjp_f16(net, x, gout, B, reinterpret_cast<unsigned char*>(base + p.off_qblk), bmax, p.bias_blocks,
-                         scales, part, p.QSB, p.Npad, p.CT, s, run_if, run_gen);
+                         scales, part, p.QSB, p.Npad, s, run_if, run_gen);
     if (rch != IRBFN_OK) return rch;
     return launch_vjp_reduce(net, part, g_centers, g_log_sigs, g_kernel, p.QSB, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks);
   }
 
-  if (p.use_sp && !gamma_ext) {
+  if (p.use_sp) {
     // K2r: pair lists per region -> one wave per (region, slice) -> the same fixed-order slab reduce; no query packing
     float* sp_part = reinterpret_cast<float*>(base + p.off_sp_part);
-    int rcs = launch_vjp_sparse(net, x, gout, B, base + p.off_sp, sp_part, p.SL, p.Npad, s);
-    if (rcs != IRBFN_ERR_UNSUPPORTED) {
-      if (rcs != IRBFN_OK) return rcs;
-      hipLaunchKernelGGL(colsum_partial_kernel, dim3(p.bias_blocks), dim3(256), 256 * sizeof(float), s, gout, bpart,
-                         (long)B, net->O, p.rows_per_block, (float*)nullptr);
-      IRBFN_HIP_CHECK(hipGetLastError());
-      return launch_vjp_reduce(net, sp_part, g_centers, g_log_sigs, g_kernel, p.SL, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks);
-    }
-    if (net->opt[IRBFN_OPT_VJP_KERNEL] == IRBFN_VJP_K2R) return IRBFN_ERR_UNSUPPORTED;
-  } else if (net->opt[IRBFN_OPT_VJP_KERNEL] == IRBFN_VJP_K2R && !gamma_ext) {
-    return IRBFN_ERR_UNSUPPORTED;                  // a forced kernel that cannot take the net
+    const int rcs = launch_vjp_sparse(net, x, gout, B, base + p.off_sp, sp_part, p.SL, p.Npad, s);
+    if (rcs != IRBFN_OK) return rcs;
+    hipLaunchKernelGGL(colsum_partial_kernel, dim3(p.bias_blocks), dim3(256), 256 * sizeof(float), s, gout, bpart,
+                       (long)B, net->O, p.rows_per_block, (float*)nullptr);
+    IRBFN_HIP_CHECK(hipGetLastError());
+    return launch_vjp_reduce(net, sp_part, g_centers, g_log_sigs, g_kernel, p.SL, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks);
   }
   float* qrec = reinterpret_cast<float*>(base + p.off_qrec);
   {
     const size_t glds = ((size_t)net->nsplit * net->max_ranges * kWave + (size_t)net->gate().n_ranges * net->nsplit) * sizeof(float);
-    if (glds > 64 * 1024) return IRBFN_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(vjp_pack_queries_kernel, dim3((unsigned)((B + kWave - 1) / kWave)), dim3(256), glds, s, x, gout,
                        qrec, gamma, net->gate(), (long)B, net->D, net->DC, net->O, net->OP, p.QS, net->R);
     IRBFN_HIP_CHECK(hipGetLastError());

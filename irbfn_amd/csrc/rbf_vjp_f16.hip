@@ -363,28 +363,30 @@ bool vjph_eligible(const irbfn_net* net) {
 
 size_t vjph_block_bytes(const irbfn_net* net) { return (size_t)32 * vjph_rfq(net->DC) * 4 + 4096; }
 
-template <int DC, int CT>
+// the launched instance: CT = 2 tiles of 16 centres per wave
+template <int DC>
 static int launch_vjph_bc(const VjpHArgs& a, int bc, dim3 grid, size_t lds, hipStream_t s) {
   switch (bc) {
-    case BC_GAUSS: hipLaunchKernelGGL((rbf_vjp_f16mfma<DC, BC_GAUSS, CT>), grid, dim3(256), lds, s, a); break;
-    case BC_IQ: hipLaunchKernelGGL((rbf_vjp_f16mfma<DC, BC_IQ, CT>), grid, dim3(256), lds, s, a); break;
-    case BC_IMQ: hipLaunchKernelGGL((rbf_vjp_f16mfma<DC, BC_IMQ, CT>), grid, dim3(256), lds, s, a); break;
+    case BC_GAUSS: hipLaunchKernelGGL((rbf_vjp_f16mfma<DC, BC_GAUSS, 2>), grid, dim3(256), lds, s, a); break;
+    case BC_IQ: hipLaunchKernelGGL((rbf_vjp_f16mfma<DC, BC_IQ, 2>), grid, dim3(256), lds, s, a); break;
+    case BC_IMQ: hipLaunchKernelGGL((rbf_vjp_f16mfma<DC, BC_IMQ, 2>), grid, dim3(256), lds, s, a); break;
     default: return IRBFN_ERR_UNSUPPORTED;
   }
   IRBFN_HIP_CHECK(hipGetLastError());
   return IRBFN_OK;
 }
 
-template <int DC>
-static int launch_vjph_dc(const VjpHArgs& a, int CT, int bc, dim3 grid, size_t lds, hipStream_t s) {
-  return CT == 4 ? launch_vjph_bc<DC, 4>(a, bc, grid, lds, s) : launch_vjph_bc<DC, 2>(a, bc, grid, lds, s);
+size_t vjph_lds_bytes(const irbfn_net* net) {
+  const int V = net->DC + 1 + net->OP;
+  const size_t ring = (size_t)4 * 2 * vjph_block_bytes(net);
+  const size_t red = (size_t)4 * V * (16 * 2 + 1) * sizeof(float);
+  return ring > red ? ring : red;
 }
 
 // x, gout -> slabs part[QSB][V][Npad] (QSB query-slice blocks of 4 waves).  qblk / scales: workspace; bmax: per-block
 // max |g| written by colsum_partial_kernel (no separate reduction pass, no atomics).
 int launch_vjp_f16(irbfn_net* net, const float* x, const float* gout, int64_t B, unsigned char* qblk, const float* bmax,
-                   int nbmax, float* scales, float* part, int QSB, int Npad, int CT, hipStream_t s, const int* run_if, int run_gen) {
-  if (!vjph_eligible(net)) return IRBFN_ERR_UNSUPPORTED;
+                   int nbmax, float* scales, float* part, int QSB, int Npad, hipStream_t s, const int* run_if, int run_gen) {
   const long nqb = (B + 31) / 32;
   hipLaunchKernelGGL(vjp_pack_blocks_kernel, dim3((unsigned)nqb), dim3(64), 0, s, x, gout, bmax, nbmax, net->f16_oscale,
                      qblk, scales, net->gate(), (long)B, net->D, vjph_rfq(net->DC), net->O, run_if, run_gen);
@@ -396,19 +398,13 @@ int launch_vjp_f16(irbfn_net* net, const float* x, const float* gout, int64_t B,
   a.bpw = (int)((nqb + slices - 1) / slices);
   a.gscale = gauss_scale(net->basis);
   a.run_if = run_if; a.run_gen = run_gen;
-  const int groups = (net->N + 16 * CT - 1) / (16 * CT);
-  const dim3 grid(groups, QSB);
-  const int V = net->DC + 1 + net->OP;
-  const size_t ring = (size_t)4 * 2 * vjph_block_bytes(net);
-  const size_t red = (size_t)4 * V * (16 * CT + 1) * sizeof(float);
-  size_t lds = ring > red ? ring : red;
-  lds += (size_t)net->opt[IRBFN_OPT_LDS_PAD];               // diagnosis only: lowers the occupancy
-  if (lds > 64 * 1024) return IRBFN_ERR_UNSUPPORTED;
+  const dim3 grid((net->N + 31) / 32, QSB);
+  const size_t lds = vjph_lds_bytes(net);
   switch (net->DC) {
-    case 3: return launch_vjph_dc<3>(a, CT, net->bclass, grid, lds, s);
-    case 4: return launch_vjph_dc<4>(a, CT, net->bclass, grid, lds, s);
-    case 7: return launch_vjph_dc<7>(a, CT, net->bclass, grid, lds, s);
-    case 8: return launch_vjph_dc<8>(a, CT, net->bclass, grid, lds, s);
+    case 3: return launch_vjph_bc<3>(a, net->bclass, grid, lds, s);
+    case 4: return launch_vjph_bc<4>(a, net->bclass, grid, lds, s);
+    case 7: return launch_vjph_bc<7>(a, net->bclass, grid, lds, s);
+    case 8: return launch_vjph_bc<8>(a, net->bclass, grid, lds, s);
     default: return IRBFN_ERR_UNSUPPORTED;
   }
 }

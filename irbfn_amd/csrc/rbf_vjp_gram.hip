@@ -477,7 +477,6 @@ static int launch_vjpg_dc(const VjpGArgs& a, int bc, dim3 grid, size_t lds, hipS
 // x, gout -> slabs part[QSB][V][Npad].  qblk / scales / flag: workspace; bmax: per-block max |g| written by colsum_partial_kernel
 int launch_vjp_gram(irbfn_net* net, const float* x, const float* gout, int64_t B, unsigned char* qblk, const float* bmax, int nbmax,
                     float* scales, int* flag, int gen, float* part, int QSB, int Npad, hipStream_t s) {
-  if (!vjpg_eligible(net)) return IRBFN_ERR_UNSUPPORTED;
   const long nqb = (B + 31) / 32;
   const GramHdr* hdr = reinterpret_cast<const GramHdr*>(net->gram_hdr);
   const dim3 pg((unsigned)nqb), pb(192);
@@ -499,9 +498,6 @@ int launch_vjp_gram(irbfn_net* net, const float* x, const float* gout, int64_t B
   a.gscale = gauss_scale(net->basis);
   const dim3 grid((a.nchunks + 3) / 4, QSB);
   const size_t lds = (size_t)3 * kVgBlock;
-  snprintf(net->last_name, sizeof(net->last_name), "rbf_vjp_f16gram<D=%d,BC=%d,QSB=%d>", net->DC, net->bclass, QSB);
-  net->last_grid = (int)(grid.x * grid.y);
-  net->last_block = 256;
   switch (net->DC) {
     case 3: return launch_vjpg_dc<3>(a, net->bclass, grid, lds, s);
     case 4: return launch_vjpg_dc<4>(a, net->bclass, grid, lds, s);

@@ -4,6 +4,8 @@ Phi x W.  Against the float64 oracle scaled by sum_k |phi_k W_k| (the natural er
 all-float32 kernel K1 and K1h, at 1e-5 relative to |ref| on ill-conditioned columns built without cancellation; queries
 outside the representable box (and non-finite ones) take K1h's distances wave by wave; parameters outside the exactness budget
 are refused."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -516,6 +518,10 @@ def test_gram_sticky_verdict_costs_speed_never_correctness(gpu):
     net.apply(P, x)
     assert net.last_launch()["kernel"].startswith("rbf_fwd_f16gram<")
     net.set_options(gram_sticky=1)
+    lib, h, v = _lib.load(), net._handle(torch), C.c_int()
+    assert lib.irbfn_net_get_option(h, _lib.OPTIONS["gram_sticky"], C.byref(v)) == 0 and v.value == 1
+    for retired in (1, 3, 4, 5, 6, 10, 11, 12, 15):                        # retired option numbers are refused
+        assert lib.irbfn_net_set_option(h, retired, 0) == -1 and lib.irbfn_net_get_option(h, retired, C.byref(v)) == -1
     P2 = {"params": {"rbf_list": {"centers": P["params"]["rbf_list"]["centers"].copy(),
                                   "log_sigs": np.full_like(P["params"]["rbf_list"]["log_sigs"], -7.0)},      # widths of 1e-3: outside the budget
                      "linear": P["params"]["linear"]}}
