@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "rollout_step.h"
 
 namespace irbfn {
 thread_local int g_last_hip_error = 0;

@@ -237,6 +237,4 @@ int launch_vjp_sparse(irbfn_net* net, const float* x, const float* gout, int64_t
 int sparse_geometry(const irbfn_net* net, int64_t B, bool roll, int mode, int T, LaunchPlan* p);
 int launch_forward_sparse(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, const int* mirror, int sv0,
                           int mode, const float* state0, const DynParams* dp, float* states, int T, hipStream_t s);
-int rollout_state_dim(int mode);
-int rollout_input_dim(int mode, int T);
 }  // namespace irbfn

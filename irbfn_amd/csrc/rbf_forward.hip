@@ -2,6 +2,7 @@
 // instantiations live in rbf_forward_kernels.hip (one object per compiled D).
 #include <math.h>
 #include "rbf_forward.h"
+#include "rollout_step.h"
 
 #include <stdio.h>
 #include <stdlib.h>

@@ -258,7 +258,11 @@ __global__ __launch_bounds__((OP * Q > 48) ? 512 : 1024) void rbf_fwd_qlane(cons
   // (round 1 stored them per lane, 4 bytes at a stride of T x S x 4)
   if constexpr (ROLL) {
     const int T = a.T;
-    const int Sdim = (a.mode == IRBFN_ROLLOUT_FULLINT) ? 5 : (a.mode == IRBFN_ROLLOUT_FRENET_LS ? 8 : 7);
+    // a tick runs ST_SELECT / ST_KS, FULLINT or FRENET_LS (launch_forward_rollout): rollout_state_dim's other cases would
+    // only cost the kernel scalar code
+    const int Sdim = a.mode == IRBFN_ROLLOUT_FULLINT     ? ModeTraits<IRBFN_ROLLOUT_FULLINT>::S
+                     : a.mode == IRBFN_ROLLOUT_FRENET_LS ? ModeTraits<IRBFN_ROLLOUT_FRENET_LS>::S
+                                                         : ModeTraits<IRBFN_ROLLOUT_ST_KS>::S;
     float* stage = ctrl + ROWS * a.O;            // [ROWS][kRollStagePitch]
     for (int row = tid; row < nvalid; row += nthreads) {
       const float* u = ctrl + row * a.O;

@@ -547,7 +547,11 @@ __global__ __launch_bounds__(kSpNT) void rbf_fwd_sparse(const SpArgs a) {
     // trajectory; the T x S states of the block's rows -- one contiguous piece of HBM -- leave through an LDS tile
     constexpr int TM = OP / 2;
     const int T = a.T;
-    const int Sdim = (a.mode == IRBFN_ROLLOUT_FULLINT) ? 5 : (a.mode == IRBFN_ROLLOUT_FRENET_LS ? 8 : 7);
+    // a tick runs ST_SELECT / ST_KS, FULLINT or FRENET_LS (launch_forward_rollout): rollout_state_dim's other cases would
+    // only cost the kernel scalar code
+    const int Sdim = a.mode == IRBFN_ROLLOUT_FULLINT     ? ModeTraits<IRBFN_ROLLOUT_FULLINT>::S
+                     : a.mode == IRBFN_ROLLOUT_FRENET_LS ? ModeTraits<IRBFN_ROLLOUT_FRENET_LS>::S
+                                                         : ModeTraits<IRBFN_ROLLOUT_ST_KS>::S;
     const int rowf = T * Sdim;                   // <= 64
     __syncthreads();
     float* stage = lds;                          // [NT][65] over the centre table and the columns (all dead)

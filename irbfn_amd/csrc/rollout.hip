@@ -13,28 +13,6 @@
 
 namespace irbfn {
 
-int rollout_state_dim(int mode) {
-  switch (mode) {
-    case IRBFN_ROLLOUT_ST_SELECT:
-    case IRBFN_ROLLOUT_ST_KS: return 7;
-    case IRBFN_ROLLOUT_FULLINT: return 5;
-    case IRBFN_ROLLOUT_FRENET_LS: return 8;
-    case IRBFN_ROLLOUT_SPIRAL: return 6;
-    default: return -1;
-  }
-}
-
-int rollout_input_dim(int mode, int T) {
-  switch (mode) {
-    case IRBFN_ROLLOUT_ST_SELECT:
-    case IRBFN_ROLLOUT_ST_KS: return 7 + 2 * T;
-    case IRBFN_ROLLOUT_FULLINT: return 1 + 2 * T;
-    case IRBFN_ROLLOUT_FRENET_LS: return 8 + 2 * T;
-    case IRBFN_ROLLOUT_SPIRAL: return 5;
-    default: return -1;
-  }
-}
-
 struct RollArgs {
   const float* __restrict__ x0;    // initial-state rows: row b at x0 + b*L0   (combined layout: x0u, L0 = L)
   const float* __restrict__ u;     // control rows [a_0.., sv_0..]: row b at u + b*LU (combined: x0u + S0, LU = L)
@@ -161,16 +139,12 @@ __global__ __launch_bounds__(64 * kRegsWaves, TCH > 8 ? IRBFN_ROLL_MINW : 4) voi
   [[maybe_unused]] float coef[4];
   [[maybe_unused]] float slen = 0.0f;
   [[maybe_unused]] float spc[2] = {0.0f, 1.0f};      // spiral: (sin, cos) of the current heading, carried step to step
-  if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) {
-    s[0] = 0.0f; s[1] = 0.0f; s[2] = 0.0f; s[4] = 0.0f;
-    s[3] = clipf(q0[0], 0.0f, 7.0f);             // train_nmpc.py:319
-  } else if constexpr (MODE == IRBFN_ROLLOUT_SPIRAL) {
+  if constexpr (MODE == IRBFN_ROLLOUT_SPIRAL) {
     spiral_coefs(q0, coef);
     slen = q0[4];
     s[0] = 0.0f; s[1] = 0.0f; s[2] = 0.0f; s[3] = coef[0]; s[4] = 0.0f; s[5] = 0.0f;   // planner_utils.py:67-70
   } else {
-#pragma unroll
-    for (int i = 0; i < S; ++i) s[i] = q0[i];
+    roll_init<MODE>(q0, s);
   }
 
   // ---- steps + whole-line flush ------------------------------------------------------------------------------
@@ -228,11 +202,8 @@ __global__ __launch_bounds__(64 * kRegsWaves, TCH > 8 ? IRBFN_ROLL_MINW : 4) voi
 #pragma unroll
         for (int tt = 0; tt < TS; ++tt) {
           if (t0 + tt < TCH && tt < n) {
-            if constexpr (MODE == IRBFN_ROLLOUT_ST_SELECT) st_step<true>(s, ua[t0 + tt], us[t0 + tt], a.dp);
-            else if constexpr (MODE == IRBFN_ROLLOUT_ST_KS) st_step<false>(s, ua[t0 + tt], us[t0 + tt], a.dp);
-            else if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) fullint_step(s, ua[t0 + tt], us[t0 + tt]);
-            else if constexpr (MODE == IRBFN_ROLLOUT_FRENET_LS) frenet_step(s, ua[t0 + tt], us[t0 + tt], a.dp);
-            else spiral_step(s, coef, slen, tg + t0 + tt, T, spc);
+            if constexpr (MODE == IRBFN_ROLLOUT_SPIRAL) spiral_step(s, coef, slen, tg + t0 + tt, T, spc);
+            else roll_step<MODE>(s, ua[t0 + tt], us[t0 + tt], a.dp);
 #pragma unroll
             for (int i = 0; i < S; ++i) wr[tt * S + i] = s[i];
           }
@@ -342,14 +313,7 @@ __global__ __launch_bounds__(64 * kPairWaves, IRBFN_PAIR_MINW) void rollout_fwd_
     for (int t = 0; t < TCH; ++t)
       if (t < T) ctl[t] = urow[t];
   }
-  if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) {
-    s[0] = 0.0f; s[1] = 0.0f; s[2] = 0.0f; s[4] = 0.0f;
-    s[3] = clipf(q0[0], 0.0f, 7.0f);             // train_nmpc.py:319
-  } else {
-#pragma unroll
-    for (int i = 0; i < S; ++i) s[i] = q0[i];
-  }
-
+  roll_init<MODE>(q0, s);
   pair_rollout_run<MODE, TCH, TS>(s, ctl, a.dp, tile, a.states + b0 * (long)T * S, T, nvalid, lane);
 }
 
@@ -392,10 +356,7 @@ __global__ __launch_bounds__(64 * kRollWaves, 3) void rollout_fwd_lean_kernel(co
   [[maybe_unused]] float coef[4];
   [[maybe_unused]] float slen = 0.0f;
   [[maybe_unused]] float spc[2] = {0.0f, 1.0f};      // spiral: (sin, cos) of the current heading, carried step to step
-  if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) {
-    s[0] = 0.0f; s[1] = 0.0f; s[2] = 0.0f; s[4] = 0.0f;
-    s[3] = clipf(row[0], 0.0f, 7.0f);
-  } else if constexpr (MODE == IRBFN_ROLLOUT_SPIRAL) {
+  if constexpr (MODE == IRBFN_ROLLOUT_SPIRAL) {
     float q[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) q[i] = row[i];
@@ -403,8 +364,7 @@ __global__ __launch_bounds__(64 * kRollWaves, 3) void rollout_fwd_lean_kernel(co
     slen = q[4];
     s[0] = 0.0f; s[1] = 0.0f; s[2] = 0.0f; s[3] = coef[0]; s[4] = 0.0f; s[5] = 0.0f;
   } else {
-#pragma unroll
-    for (int i = 0; i < S; ++i) s[i] = row[i];
+    roll_init<MODE>(row, s);
   }
 
   // control pieces: per row 2 streams x 2 aligned float4 (the 4 wanted floats lie inside 8 aligned ones);
@@ -479,11 +439,8 @@ __global__ __launch_bounds__(64 * kRollWaves, 3) void rollout_fwd_lean_kernel(co
     }
 #pragma unroll
     for (int tt = 0; tt < TS; ++tt) {
-      if constexpr (MODE == IRBFN_ROLLOUT_ST_SELECT) st_step<true>(s, ua[tt], us[tt], a.dp);
-      else if constexpr (MODE == IRBFN_ROLLOUT_ST_KS) st_step<false>(s, ua[tt], us[tt], a.dp);
-      else if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) fullint_step(s, ua[tt], us[tt]);
-      else if constexpr (MODE == IRBFN_ROLLOUT_FRENET_LS) frenet_step(s, ua[tt], us[tt], a.dp);
-      else spiral_step(s, coef, slen, t0 + tt, T, spc);
+      if constexpr (MODE == IRBFN_ROLLOUT_SPIRAL) spiral_step(s, coef, slen, t0 + tt, T, spc);
+      else roll_step<MODE>(s, ua[tt], us[tt], a.dp);
 #pragma unroll
       for (int i = 0; i < S; ++i) mine[myC + tt * S + i] = s[i];
     }
@@ -502,11 +459,8 @@ __global__ __launch_bounds__(64 * kRollWaves, 3) void rollout_fwd_lean_kernel(co
   int fill = myC;
   for (int t = done; t < T; ++t) {
     const float ca = has_ctrl ? urow[t] : 0.0f, cs = has_ctrl ? urow[T + t] : 0.0f;
-    if constexpr (MODE == IRBFN_ROLLOUT_ST_SELECT) st_step<true>(s, ca, cs, a.dp);
-    else if constexpr (MODE == IRBFN_ROLLOUT_ST_KS) st_step<false>(s, ca, cs, a.dp);
-    else if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) fullint_step(s, ca, cs);
-    else if constexpr (MODE == IRBFN_ROLLOUT_FRENET_LS) frenet_step(s, ca, cs, a.dp);
-    else spiral_step(s, coef, slen, t, T, spc);
+    if constexpr (MODE == IRBFN_ROLLOUT_SPIRAL) spiral_step(s, coef, slen, t, T, spc);
+    else roll_step<MODE>(s, ca, cs, a.dp);
 #pragma unroll
     for (int i = 0; i < S; ++i) mine[fill + i] = s[i];
     fill += S;
@@ -593,14 +547,6 @@ static int dispatch_mode(int mode, const RollArgs& a, hipStream_t s) {
 // Measured and rejected: splitting B > 131072 into several launches (hoping the 256 MB memory-side cache would
 // merge the partial lines of one launch): 216 vs 190 us at B = 262144 -- the 71 us seen for a single 131072
 // launch is an artefact of re-running on cache-resident buffers, not a property of the size.
-static int s0_of(int mode) {
-  switch (mode) {
-    case IRBFN_ROLLOUT_FULLINT: return 1;
-    case IRBFN_ROLLOUT_FRENET_LS: return 8;
-    case IRBFN_ROLLOUT_SPIRAL: return 5;
-    default: return 7;
-  }
-}
 
 // combined layout of the reference: row = [state, a_0..a_{T-1}, sv_0..sv_{T-1}]
 int launch_rollout_forward(int mode, const float* x0u, const DynParams& dp, float* states, int64_t B,
@@ -609,7 +555,7 @@ int launch_rollout_forward(int mode, const float* x0u, const DynParams& dp, floa
   RollArgs a;
   a.L = rollout_input_dim(mode, T);
   a.x0 = x0u;
-  a.u = x0u + s0_of(mode);
+  a.u = x0u + mode_dims(mode).S0;
   a.L0 = a.L;
   a.LU = a.L;
   a.states = states;
@@ -631,7 +577,7 @@ int launch_rollout_forward_split(int mode, const float* state0, const float* con
   a.L = rollout_input_dim(mode, T);
   a.x0 = state0;
   a.u = controls;
-  a.L0 = s0_of(mode);
+  a.L0 = mode_dims(mode).S0;
   a.LU = 2L * T;
   a.states = states;
   a.B = (long)B;

@@ -13,11 +13,6 @@ __device__ __forceinline__ float clipgrad(float v, float lo, float hi, float tie
   return (v > lo && v < hi) ? 1.0f : ((v == lo || v == hi) ? tie : 0.0f);
 }
 
-template <int MODE> struct VjpTraits;
-template <> struct VjpTraits<IRBFN_ROLLOUT_ST_KS> { static constexpr int S = 7, S0 = 7, NP = 3; };
-template <> struct VjpTraits<IRBFN_ROLLOUT_FULLINT> { static constexpr int S = 5, S0 = 1, NP = 3; };
-template <> struct VjpTraits<IRBFN_ROLLOUT_FRENET_LS> { static constexpr int S = 8, S0 = 8, NP = 4; };
-
 template <int MODE>
 __device__ __forceinline__ void vjp_park(const float* s, float* p) {
   if constexpr (MODE == IRBFN_ROLLOUT_FRENET_LS) { p[0] = s[1]; p[1] = s[2]; p[2] = s[3]; p[3] = s[6]; }
@@ -81,6 +76,17 @@ __device__ __forceinline__ void vjp_back_step(const float* p, float a_in, float 
     const float l6 = lam[6] + A * (-vx * se / den) + lam[1] * dt * vx * ce;
     const float l7 = lam[7] + A * (vx * ce * ey / (den * den)) - lam[6] * dt * d0;
     lam[1] = l1; lam[2] = l2; lam[3] = l3; lam[6] = l6; lam[7] = l7;
+  }
+}
+
+// cotangent of an input row's first S0 columns (roll_init) from the cotangent `lam` of the initial state
+template <int MODE>
+__device__ __forceinline__ void roll_init_grad(const float* row, const float* lam, float tie, float (&g)[ModeTraits<MODE>::S0]) {
+  if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) {
+    g[0] = clipgrad(row[0], 0.0f, 7.0f, tie) * lam[3];
+  } else {
+#pragma unroll
+    for (int i = 0; i < ModeTraits<MODE>::S0; ++i) g[i] = lam[i];
   }
 }
 

@@ -11,19 +11,6 @@
 
 namespace irbfn {
 
-template <int MODE>
-struct ModeTraits;
-template <>
-struct ModeTraits<IRBFN_ROLLOUT_ST_SELECT> { static constexpr int S = 7, S0 = 7; };
-template <>
-struct ModeTraits<IRBFN_ROLLOUT_ST_KS> { static constexpr int S = 7, S0 = 7; };
-template <>
-struct ModeTraits<IRBFN_ROLLOUT_FULLINT> { static constexpr int S = 5, S0 = 1; };
-template <>
-struct ModeTraits<IRBFN_ROLLOUT_FRENET_LS> { static constexpr int S = 8, S0 = 8; };
-template <>
-struct ModeTraits<IRBFN_ROLLOUT_SPIRAL> { static constexpr int S = 6, S0 = 5; };
-
 typedef float f4v __attribute__((ext_vector_type(4)));
 #ifndef IRBFN_ROLL_NT
 #define IRBFN_ROLL_NT 1            // whole-line stores non-temporal: 107 vs 149 us at B = 262144 (they need no merging in L2 / the
@@ -134,10 +121,7 @@ __device__ __forceinline__ void pair_rollout_run(float (&s)[ModeTraits<MODE>::S]
         const int cv = __builtin_bit_cast(int, ctl[tt]);
         const float ua = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(cv, 0xA0, 0xF, 0xF, true));   // even lane's knot
         const float us = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(cv, 0xF5, 0xF, 0xF, true));   // odd lane's knot
-        if constexpr (MODE == IRBFN_ROLLOUT_ST_SELECT) st_step<true>(s, ua, us, dp, trig);
-        else if constexpr (MODE == IRBFN_ROLLOUT_ST_KS) st_step<false>(s, ua, us, dp, trig);
-        else if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) fullint_step(s, ua, us, trig);
-        else frenet_step(s, ua, us, dp, trig);
+        roll_step<MODE>(s, ua, us, dp, trig);
         // even lane: components [0, SE), odd lane: [SE, S) (+ one spare slot that the next step overwrites)
 #pragma unroll
         for (int i = 0; i < SE; ++i) {

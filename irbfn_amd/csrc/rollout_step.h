@@ -257,4 +257,64 @@ __device__ __forceinline__ void spiral_step(float (&st)[6], const float (&c)[4],
   spiral_step(st, c, s, i, N, sc);
 }
 
+// Per-mode facts.  S: state components; S0: leading columns of an input row that give the initial state (FULLINT: v0 only,
+// spiral: the path parameters); NU: control streams after them, T knots each (the spiral has none); NP: floats vjp_park
+// keeps per step (rollout_adjoint.h; the differentiable modes only).
+template <int MODE>
+struct ModeTraits;
+template <>
+struct ModeTraits<IRBFN_ROLLOUT_ST_SELECT> { static constexpr int S = 7, S0 = 7, NU = 2; };
+template <>
+struct ModeTraits<IRBFN_ROLLOUT_ST_KS> { static constexpr int S = 7, S0 = 7, NU = 2, NP = 3; };
+template <>
+struct ModeTraits<IRBFN_ROLLOUT_FULLINT> { static constexpr int S = 5, S0 = 1, NU = 2, NP = 3; };
+template <>
+struct ModeTraits<IRBFN_ROLLOUT_FRENET_LS> { static constexpr int S = 8, S0 = 8, NU = 2, NP = 4; };
+template <>
+struct ModeTraits<IRBFN_ROLLOUT_SPIRAL> { static constexpr int S = 6, S0 = 5, NU = 0; };
+
+// the traits of a run-time mode; S = -1 for an unknown one
+struct ModeDims { int S, S0, NU; };
+__host__ __device__ constexpr ModeDims mode_dims(int mode) {
+  switch (mode) {
+#define IRBFN_DIMS(M) case M: return {ModeTraits<M>::S, ModeTraits<M>::S0, ModeTraits<M>::NU}
+    IRBFN_DIMS(IRBFN_ROLLOUT_ST_SELECT);
+    IRBFN_DIMS(IRBFN_ROLLOUT_ST_KS);
+    IRBFN_DIMS(IRBFN_ROLLOUT_FULLINT);
+    IRBFN_DIMS(IRBFN_ROLLOUT_FRENET_LS);
+    IRBFN_DIMS(IRBFN_ROLLOUT_SPIRAL);
+#undef IRBFN_DIMS
+    default: return {-1, -1, 0};
+  }
+}
+__host__ __device__ constexpr int rollout_state_dim(int mode) { return mode_dims(mode).S; }
+// columns of a combined input row [state, a_0..a_{T-1}, sv_0..sv_{T-1}]; -1 for an unknown mode
+__host__ __device__ constexpr int rollout_input_dim(int mode, int T) {
+  return mode_dims(mode).S < 0 ? -1 : mode_dims(mode).S0 + mode_dims(mode).NU * T;
+}
+
+// the initial state of a control-driven mode from the first S0 columns of its input row
+template <int MODE>
+__device__ __forceinline__ void roll_init(const float* row, float (&s)[ModeTraits<MODE>::S]) {
+  static_assert(MODE != IRBFN_ROLLOUT_SPIRAL, "the spiral starts from its coefficients: spiral_coefs");
+  if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) {
+    s[0] = 0.0f; s[1] = 0.0f; s[2] = 0.0f; s[4] = 0.0f;
+    s[3] = clipf(row[0], 0.0f, 7.0f);              // train_nmpc.py:319
+  } else {
+#pragma unroll
+    for (int i = 0; i < ModeTraits<MODE>::S; ++i) s[i] = row[i];
+  }
+}
+
+// one step of a control-driven mode: acceleration `a`, steering rate `sv` (the spiral's step takes no controls: spiral_step)
+template <int MODE, typename Trig = TrigDirect>
+__device__ __forceinline__ void roll_step(float (&s)[ModeTraits<MODE>::S], float a, float sv, const DynParams& dp,
+                                          const Trig trig = Trig()) {
+  static_assert(MODE != IRBFN_ROLLOUT_SPIRAL, "the spiral's step takes no controls: spiral_step");
+  if constexpr (MODE == IRBFN_ROLLOUT_ST_SELECT) st_step<true>(s, a, sv, dp, trig);
+  else if constexpr (MODE == IRBFN_ROLLOUT_ST_KS) st_step<false>(s, a, sv, dp, trig);
+  else if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) fullint_step(s, a, sv, trig);
+  else frenet_step(s, a, sv, dp, trig);
+}
+
 }  // namespace irbfn

@@ -1,5 +1,5 @@
 // K4: hand-derived VJPs of the roll-outs (reverse sweeps).  One lane per trajectory: the forward is
-// recomputed, the few pre-step quantities the adjoint needs are parked in LDS ([T][NS][64], one
+// recomputed, the few pre-step quantities the adjoint needs are parked in LDS ([T][NP][64], one
 // column per lane -> conflict-free), then the sweep runs backwards accumulating the seeds of every
 // step's state (`all_states` is the differentiated output).
 //
@@ -24,227 +24,59 @@ struct RollVjpArgs {
   DynParams dp;
 };
 
-// ---- single-track kinematic (dynamics.py:103-187 applied T times) --------------------------------
-__global__ __launch_bounds__(64) void rollout_vjp_st_ks(const RollVjpArgs a) {
-  extern __shared__ float lds[];                 // [T][3][64]: delta, V(raw), psi before step t
+// ---- the control-driven models (dynamics.py:103-187, scripts/train_nmpc.py:329-374, dynamics.py:190-290) ---------
+// The forward's pre-step quantities (vjp_park: NP floats per step) are parked in LDS, [T][NP][64], one column per lane.
+template <int MODE>
+__global__ __launch_bounds__(64) void rollout_vjp_park_kernel(const RollVjpArgs a) {
+  constexpr int S = ModeTraits<MODE>::S, S0 = ModeTraits<MODE>::S0, NP = ModeTraits<MODE>::NP;
+  extern __shared__ float lds[];
   const int lane = threadIdx.x;
   const long b = (long)blockIdx.x * kWave + lane;
   if (b >= a.B) return;
-  const int T = a.T, L = a.L;
-  const float* row = a.x0u + b * L;
-  float* grow = a.gx0u + b * L;
-  const float* gs = a.gstates + b * (long)T * 7;
-  const float lf = a.dp.p[3], lr = a.dp.p[4], dt = a.dp.p[8], sv_max = a.dp.p[9], a_max = a.dp.p[10],
-              s_max = a.dp.p[11], v_max = a.dp.p[12];
-  const float Lw = lr + lf;
-  float s[7];
-#pragma unroll
-  for (int i = 0; i < 7; ++i) s[i] = row[i];
+  const int T = a.T;
+  const float* row = a.x0u + b * a.L;
+  const float* u = row + S0;                     // a_t = u[t], sv_t = u[T + t]
+  float* grow = a.gx0u + b * a.L;
+  const float* gs = a.gstates + b * (long)T * S;
+  float s[S];
+  roll_init<MODE>(row, s);
+  [[maybe_unused]] const float cur = MODE == IRBFN_ROLLOUT_FRENET_LS ? s[S - 1] : 0.0f;   // Frenet: the curvature
   for (int t = 0; t < T; ++t) {
-    lds[(t * 3 + 0) * kWave + lane] = s[2];
-    lds[(t * 3 + 1) * kWave + lane] = s[3];
-    lds[(t * 3 + 2) * kWave + lane] = s[4];
-    st_step<false>(s, row[7 + t], row[7 + T + t], a.dp);
+    float pk[NP];
+    vjp_park<MODE>(s, pk);
+#pragma unroll
+    for (int i = 0; i < NP; ++i) lds[(t * NP + i) * kWave + lane] = pk[i];
+    roll_step<MODE>(s, u[t], u[T + t], a.dp);
   }
-  float lam[7] = {0, 0, 0, 0, 0, 0, 0};
+  float lam[S];
+#pragma unroll
+  for (int i = 0; i < S; ++i) lam[i] = 0.0f;
   for (int t = T - 1; t >= 0; --t) {
 #pragma unroll
-    for (int i = 0; i < 7; ++i) lam[i] += gs[t * 7 + i];
-    const float d_raw = lds[(t * 3 + 0) * kWave + lane];
-    const float v_raw = lds[(t * 3 + 1) * kWave + lane];
-    const float psi = lds[(t * 3 + 2) * kWave + lane];
-    const float DELTA = clipf(d_raw, -s_max, s_max), V = clipf(v_raw, -v_max, v_max);
-    const float md = clipgrad(d_raw, -s_max, s_max, a.tie), mv = clipgrad(v_raw, -v_max, v_max, a.tie);
-    const float ma = clipgrad(row[7 + t], -a_max, a_max, a.tie);
-    const float ms = clipgrad(row[7 + T + t], -sv_max, sv_max, a.tie);
-    const float cp = cosf(psi), sp = sinf(psi), td = tanf(DELTA);
-    grow[7 + t] = ma * dt * lam[3];
-    grow[7 + T + t] = ms * dt * lam[2];
-    const float l2 = lam[2] + md * lam[4] * (V / Lw) * (1.0f + td * td) * dt;
-    const float l3 = lam[3] + mv * dt * (lam[0] * cp + lam[1] * sp + lam[4] * td / Lw);
-    const float l4 = lam[4] + dt * V * (-lam[0] * sp + lam[1] * cp);
-    lam[2] = l2; lam[3] = l3; lam[4] = l4;
-  }
+    for (int i = 0; i < S; ++i) lam[i] += gs[t * S + i];
+    float pk[NP];
 #pragma unroll
-  for (int i = 0; i < 7; ++i) grow[i] = lam[i];
+    for (int i = 0; i < NP; ++i) pk[i] = lds[(t * NP + i) * kWave + lane];
+    float ga, gsv;
+    vjp_back_step<MODE>(pk, u[t], u[T + t], lam, cur, a.tie, a.dp, ga, gsv);
+    grow[S0 + t] = ga;
+    grow[S0 + T + t] = gsv;
+  }
+  float g0[S0];
+  roll_init_grad<MODE>(row, lam, a.tie, g0);
+#pragma unroll
+  for (int i = 0; i < S0; ++i) grow[i] = g0[i];
 }
 
-// ---- inline kinematic bicycle (scripts/train_nmpc.py:329-374) ------------------------------------
-__global__ __launch_bounds__(64) void rollout_vjp_fullint(const RollVjpArgs a) {
-  extern __shared__ float lds[];                 // [T][3][64]: delta, v, yaw before step t
-  const int lane = threadIdx.x;
-  const long b = (long)blockIdx.x * kWave + lane;
-  if (b >= a.B) return;
-  const int T = a.T, L = a.L;
-  const float DT = 0.1f, WB = 0.33f, VMAX = 7.0f, VMIN = 0.0f, SMAX = 0.4189f;
-  const float* row = a.x0u + b * L;
-  float* grow = a.gx0u + b * L;
-  const float* gs = a.gstates + b * (long)T * 5;
-  float s[5] = {0.0f, 0.0f, 0.0f, clipf(row[0], VMIN, VMAX), 0.0f};
-  for (int t = 0; t < T; ++t) {
-    lds[(t * 3 + 0) * kWave + lane] = s[2];
-    lds[(t * 3 + 1) * kWave + lane] = s[3];
-    lds[(t * 3 + 2) * kWave + lane] = s[4];
-    fullint_step(s, row[1 + t], row[1 + T + t]);
-  }
-  float lam[5] = {0, 0, 0, 0, 0};
-  for (int t = T - 1; t >= 0; --t) {
-#pragma unroll
-    for (int i = 0; i < 5; ++i) lam[i] += gs[t * 5 + i];
-    const float d0 = lds[(t * 3 + 0) * kWave + lane];
-    const float v0 = lds[(t * 3 + 1) * kWave + lane];
-    const float psi = lds[(t * 3 + 2) * kWave + lane];
-    const float dpre = d0 + row[1 + T + t] * DT, vpre = v0 + row[1 + t] * DT;
-    const float d1 = clipf(dpre, -SMAX, SMAX), v1 = clipf(vpre, VMIN, VMAX);
-    const float md = clipgrad(dpre, -SMAX, SMAX, a.tie), mv = clipgrad(vpre, VMIN, VMAX, a.tie);
-    const float td = tanf(d1), cp = cosf(psi), sp = sinf(psi);
-    const float Ld = lam[2] + lam[4] * (v1 / WB) * (1.0f + td * td) * DT;   // cotangent on delta'
-    const float Lv = lam[3] + lam[4] * td * DT / WB;                        // cotangent on v'
-    grow[1 + t] = mv * Lv * DT;
-    grow[1 + T + t] = md * Ld * DT;
-    const float l2 = md * Ld;
-    const float l3 = mv * Lv + DT * (lam[0] * cp + lam[1] * sp);
-    const float l4 = lam[4] + DT * v0 * (-lam[0] * sp + lam[1] * cp);
-    lam[2] = l2; lam[3] = l3; lam[4] = l4;
-  }
-  grow[0] = clipgrad(row[0], VMIN, VMAX, a.tie) * lam[3];
-}
-
-// ---- Frenet low-speed model (dynamics.py:190-290) --------------------------------------------------
-__global__ __launch_bounds__(64) void rollout_vjp_frenet(const RollVjpArgs a) {
-  extern __shared__ float lds[];                 // [T][4][64]: ey, delta, vx, epsi before step t
-  const int lane = threadIdx.x;
-  const long b = (long)blockIdx.x * kWave + lane;
-  if (b >= a.B) return;
-  const int T = a.T, L = a.L;
-  const float* row = a.x0u + b * L;
-  float* grow = a.gx0u + b * L;
-  const float* gs = a.gstates + b * (long)T * 8;
-  const float LF = a.dp.p[3], LR = a.dp.p[4], dt = a.dp.p[8], sv_max = a.dp.p[9], a_max = a.dp.p[10],
-              s_max = a.dp.p[11];
-  const float Lw = LR + LF;
-  float s[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) s[i] = row[i];
-  const float cur = s[7];
-  for (int t = 0; t < T; ++t) {
-    lds[(t * 4 + 0) * kWave + lane] = s[1];
-    lds[(t * 4 + 1) * kWave + lane] = s[2];
-    lds[(t * 4 + 2) * kWave + lane] = s[3];
-    lds[(t * 4 + 3) * kWave + lane] = s[6];
-    frenet_step(s, row[8 + t], row[8 + T + t], a.dp);
-  }
-  float lam[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int t = T - 1; t >= 0; --t) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) lam[i] += gs[t * 8 + i];
-    const float ey = lds[(t * 4 + 0) * kWave + lane];
-    const float d_raw = lds[(t * 4 + 1) * kWave + lane];
-    const float vx = lds[(t * 4 + 2) * kWave + lane];
-    const float epsi = lds[(t * 4 + 3) * kWave + lane];
-    const float dc = clipf(d_raw, -s_max, s_max);
-    const float md = clipgrad(d_raw, -s_max, s_max, a.tie);
-    const float ma = clipgrad(row[8 + t], -a_max, a_max, a.tie);
-    const float ms = clipgrad(row[8 + T + t], -sv_max, sv_max, a.tie);
-    const float ce = cosf(epsi), se = sinf(epsi), td = tanf(dc);
-    const float den = 1.0f - ey * cur;
-    const float d0 = vx * ce / den;
-    const float A = lam[0] * dt - lam[6] * dt * cur;      // total cotangent on d0
-    grow[8 + t] = ma * dt * lam[3];
-    grow[8 + T + t] = ms * dt * lam[2];
-    const float l1 = lam[1] + A * (vx * ce * cur / (den * den));
-    const float l2 = lam[2] + md * lam[6] * dt * vx * (1.0f + td * td) / Lw;
-    const float l3 = lam[3] + A * ce / den + lam[1] * dt * se + lam[6] * dt * td / Lw;
-    const float l6 = lam[6] + A * (-vx * se / den) + lam[1] * dt * vx * ce;
-    const float l7 = lam[7] + A * (vx * ce * ey / (den * den)) - lam[6] * dt * d0;
-    lam[1] = l1; lam[2] = l2; lam[3] = l3; lam[6] = l6; lam[7] = l7;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) grow[i] = lam[i];
-}
-
-// ---- cubic spiral (planner_utils.py:20-77); T = number of samples N --------------------------------
-__global__ __launch_bounds__(64) void rollout_vjp_spiral(const RollVjpArgs a) {
-  extern __shared__ float lds[];                 // [N][3][64]: theta_i, dx_i, dy_i
-  const int lane = threadIdx.x;
-  const long b = (long)blockIdx.x * kWave + lane;
-  if (b >= a.B) return;
-  const int N = a.T;
-  const float* row = a.x0u + b * 5;
-  float* grow = a.gx0u + b * 5;
-  const float* gs = a.gstates + b * (long)N * 6;
-  float q[5], c[4];
-#pragma unroll
-  for (int i = 0; i < 5; ++i) q[i] = row[i];
-  spiral_coefs(q, c);
-  const float slen = q[4];
-  float st[6] = {0.0f, 0.0f, 0.0f, c[0], 0.0f, 0.0f};
-  for (int i = 0; i < N; ++i) {
-    spiral_step(st, c, slen, i, N);
-    lds[(i * 3 + 0) * kWave + lane] = st[2];
-    lds[(i * 3 + 1) * kWave + lane] = st[4];
-    lds[(i * 3 + 2) * kWave + lane] = st[5];
-  }
-  float gc[4] = {0, 0, 0, 0};
-  float g_s = 0.0f, ldx = 0.0f, ldy = 0.0f, lth = 0.0f;
-  for (int i = N - 1; i >= 0; --i) {
-    const float tau = (i < N - 1) ? ((float)i / (float)(N - 1)) : 1.0f;
-    const float sk = (i < N - 1) ? slen * tau : slen;
-    const float k = (float)(i + 1);
-    const float th = lds[(i * 3 + 0) * kWave + lane];
-    const float dx = lds[(i * 3 + 1) * kWave + lane];
-    const float dy = lds[(i * 3 + 2) * kWave + lane];
-    const float thp = i > 0 ? lds[((i - 1) * 3 + 0) * kWave + lane] : 0.0f;
-    const float gx = gs[i * 6 + 0], gy = gs[i * 6 + 1], gth = gs[i * 6 + 2], gka = gs[i * 6 + 3],
-                gdx = gs[i * 6 + 4], gdy = gs[i * 6 + 5];
-    const float Gdx = gdx + ldx + sk * gx;
-    const float Gdy = gdy + ldy + sk * gy;
-    float gsk = gx * dx + gy * dy;
-    const float Gth = gth + lth + (Gdx * (-sinf(th)) + Gdy * cosf(th)) / (2.0f * k);
-    lth = (Gdx * (-sinf(thp)) + Gdy * cosf(thp)) / (2.0f * k);
-    ldx = Gdx * (1.0f - 1.0f / k);
-    ldy = Gdy * (1.0f - 1.0f / k);
-    // theta = sum_j c_j sk^(j+1)/(j+1); kappa = sum_j c_j sk^j
-    float pw = 1.0f, kap = 0.0f, dkap = 0.0f, pwm1 = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      gc[j] += Gth * (pw * sk) / (float)(j + 1) + gka * pw;
-      kap += c[j] * pw;
-      dkap += (float)j * c[j] * pwm1;
-      pwm1 = pw;
-      pw = pw * sk;
-    }
-    gsk += Gth * kap + gka * dkap;
-    g_s += gsk * tau;
-  }
-  // coefs -> (k0..k3, s): c_r = (PM_r . q) / s^r  (planner_utils.py:20-29)
-  const float PM[4][4] = {{1.0f, 0.0f, 0.0f, 0.0f},
-                          {-11.0f / 2, 9.0f, -9.0f / 2, 1.0f},
-                          {9.0f, -45.0f / 2, 18.0f, -9.0f / 2},
-                          {-9.0f / 2, 27.0f / 2, -27.0f / 2, 9.0f / 2}};
-  float inv = 1.0f;
-  float gq[4] = {0, 0, 0, 0};
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m) gq[m] += gc[r] * PM[r][m] * inv;
-    g_s += -(float)r * c[r] / slen * gc[r];
-    inv = inv / slen;
-  }
-#pragma unroll
-  for (int m = 0; m < 4; ++m) grow[m] = gq[m];
-  grow[4] = g_s;
-}
-
-// ---- cubic spiral, staged (N <= 256) -----------------------------------------------------------------------------------
-// The kernel above reads every seed as a per-lane dword at a stride of N * 24 bytes and parks theta / dx / dy of all N
-// samples in LDS (measured 0.75 TB/s at B = 262144, N = 100).  Here one wave owns 64 consecutive paths -- their seeds are ONE
-// contiguous block of HBM -- and walks the samples in chunks of G = 8, last chunk first:
+// ---- cubic spiral (planner_utils.py:20-77); T = number of samples N <= 256 ------------------------------------------------
+// Per-lane seed dwords at a stride of N * 24 bytes and a park of theta / dx / dy of all N samples in LDS measured 0.75 TB/s
+// (B = 262144, N = 100).  Here one wave owns 64 consecutive paths -- their seeds are ONE contiguous block of HBM -- and walks
+// the samples in chunks of G = 8, last chunk first:
 //  * the chunk's seeds (64 rows x 48 floats) are read by the whole wave as consecutive dwords (256 contiguous bytes per
 //    instruction, runs of 192 bytes per row) into an LDS tile of odd pitch and read back per row without bank conflicts;
 //  * no park of all samples: the forward pass keeps a checkpoint (theta, dx, dy before the chunk: 3 floats) per chunk in LDS,
 //    the reverse pass re-runs one chunk from its checkpoint into registers -- the forward's own values, same step function --
-//    and sweeps it backwards with the adjoint of the kernel above.
+//    and sweeps it backwards.
 constexpr int kSpiralG = 8;
 constexpr int kSpiralPitch = kSpiralG * 6 + 1;     // odd
 __global__ __launch_bounds__(64) void rollout_vjp_spiral_staged(const RollVjpArgs a) {
@@ -366,7 +198,7 @@ __global__ __launch_bounds__(64) void rollout_vjp_spiral_staged(const RollVjpArg
 }
 
 // ---- K4: the same reverse sweeps with the memory machinery of the forward roll-out (T <= 50) ---------------------
-// The kernels above touch HBM through per-lane strided dwords (measured 0.5-0.9 TB/s at T = 50).  Here:
+// The park kernel above touches HBM through per-lane strided dwords (measured 0.5-0.9 TB/s at T = 50).  Here:
 //  * input rows: whole-tile LDS-DMA, the 2T controls of a trajectory live in registers (as in rollout.hip);
 //  * no [T][3][64] park: the forward pass keeps a CHECKPOINT of the few state components the adjoint needs every
 //    G = 10 steps (15 registers); the reverse pass re-runs one 10-step segment at a time into registers
@@ -397,17 +229,10 @@ constexpr int vjp_group(int TCH) { return TCH >= 10 ? 5 : TCH; }
 constexpr int vjp_pieces(int S, int G) { return ((G * S + 6) / 4) | 1; }
 constexpr int vjp_pitch(int S, int G) { return 4 * vjp_pieces(S, G); }
 
-template <int MODE>
-__device__ __forceinline__ void vjp_fwd_step(float* s, float a_in, float sv_in, const DynParams& dp) {
-  if constexpr (MODE == IRBFN_ROLLOUT_ST_KS) st_step<false>(*reinterpret_cast<float(*)[7]>(s), a_in, sv_in, dp);
-  else if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) fullint_step(*reinterpret_cast<float(*)[5]>(s), a_in, sv_in);
-  else frenet_step(*reinterpret_cast<float(*)[8]>(s), a_in, sv_in, dp);
-}
-
 template <int MODE, int TCH>
 __global__ __launch_bounds__(64 * kVjpWaves, 2) void rollout_vjp_regs_kernel(const RollVjp2Args a) {
   extern __shared__ float lds[];
-  constexpr int S = VjpTraits<MODE>::S, S0 = VjpTraits<MODE>::S0, NP = VjpTraits<MODE>::NP;
+  constexpr int S = ModeTraits<MODE>::S, S0 = ModeTraits<MODE>::S0, NP = ModeTraits<MODE>::NP;
   constexpr int G = vjp_group(TCH), NG = TCH / G;
   constexpr int PITCH = vjp_pitch(S, G);
   constexpr int NPC = vjp_pieces(S, G);          // 16-byte pieces of a row's aligned seed chunk
@@ -459,13 +284,7 @@ __global__ __launch_bounds__(64 * kVjpWaves, 2) void rollout_vjp_regs_kernel(con
       if (t < T) { ua[t] = row[S0 + t]; us[t] = row[S0 + T + t]; }
   }
   float s[S];
-  if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) {
-    s[0] = 0.0f; s[1] = 0.0f; s[2] = 0.0f; s[4] = 0.0f;
-    s[3] = clipf(q0[0], 0.0f, 7.0f);
-  } else {
-#pragma unroll
-    for (int i = 0; i < S; ++i) s[i] = q0[i];
-  }
+  roll_init<MODE>(q0, s);
   [[maybe_unused]] float cur = 0.0f;
   if constexpr (MODE == IRBFN_ROLLOUT_FRENET_LS) cur = s[7];
 
@@ -515,7 +334,7 @@ __global__ __launch_bounds__(64 * kVjpWaves, 2) void rollout_vjp_regs_kernel(con
     }
 #pragma unroll
     for (int tt = 0; tt < G; ++tt)
-      if (gI * G + tt < T) vjp_fwd_step<MODE>(s, ua[tt], us[tt], a.dp);
+      if (gI * G + tt < T) roll_step<MODE>(s, ua[tt], us[tt], a.dp);
     if constexpr (NG > 1) {
       float ta[G], ts[G];
 #pragma unroll
@@ -561,7 +380,7 @@ __global__ __launch_bounds__(64 * kVjpWaves, 2) void rollout_vjp_regs_kernel(con
 #pragma unroll
       for (int tt = 0; tt < G; ++tt) {
         vjp_park<MODE>(ss, park[tt]);
-        if (tt < n) vjp_fwd_step<MODE>(ss, ua[TCH - G + tt], us[TCH - G + tt], a.dp);
+        if (tt < n) roll_step<MODE>(ss, ua[TCH - G + tt], us[TCH - G + tt], a.dp);
       }
 #pragma unroll
       for (int tt = G - 1; tt >= 0; --tt) {
@@ -592,11 +411,7 @@ __global__ __launch_bounds__(64 * kVjpWaves, 2) void rollout_vjp_regs_kernel(con
   }
   // cotangent of the initial state
   float g0[S0];
-  if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) g0[0] = clipgrad(q0[0], 0.0f, 7.0f, a.tie) * lam[3];
-  else {
-#pragma unroll
-    for (int i = 0; i < S0; ++i) g0[i] = lam[i];
-  }
+  roll_init_grad<MODE>(q0, lam, a.tie, g0);
 
   // ---- epilogue: gradient rows -> HBM, RPP rows per pass as one contiguous block of whole lines -----------------
   float* gout = a.gx0u + b0 * L;
@@ -631,21 +446,20 @@ __global__ __launch_bounds__(64 * kVjpWaves, 2) void rollout_vjp_regs_kernel(con
 }
 
 template <int MODE>
-static int launch_vjp_regs(const float* x0u, const DynParams& dp, const float* gstates, float* g_x0u, int64_t B, int T,
-                           float tie, hipStream_t s) {
-  constexpr int S = VjpTraits<MODE>::S;
+static int launch_vjp_regs(const RollVjpArgs& v, hipStream_t s) {
+  constexpr int S = ModeTraits<MODE>::S;
   RollVjp2Args a;
-  a.x0u = x0u; a.gstates = gstates; a.gx0u = g_x0u; a.B = (long)B; a.T = T; a.L = rollout_input_dim(MODE, T);
-  a.tie = tie; a.dp = dp;
-  const int TCH = T <= 8 ? 8 : 50;
+  a.x0u = v.x0u; a.gstates = v.gstates; a.gx0u = v.gx0u; a.B = v.B; a.T = v.T; a.L = v.L;
+  a.tie = v.tie; a.dp = v.dp;
+  const int TCH = a.T <= 8 ? 8 : 50;
   const int G = vjp_group(TCH);
   long w = (TCH / G > 1 ? 2L : 1L) * kWave * vjp_pitch(S, G);     // two seed tiles where there is a next group to prefetch
   if ((long)kVjpRPP * a.L > w) w = (long)kVjpRPP * a.L;
   a.wlds = (int)((w + 3) & ~3L);
-  a.dma_ok = ((reinterpret_cast<uintptr_t>(x0u) | reinterpret_cast<uintptr_t>(gstates) | reinterpret_cast<uintptr_t>(g_x0u)) & 15) == 0;
+  a.dma_ok = ((reinterpret_cast<uintptr_t>(a.x0u) | reinterpret_cast<uintptr_t>(a.gstates) | reinterpret_cast<uintptr_t>(a.gx0u)) & 15) == 0;
   const size_t lds = (size_t)kVjpWaves * a.wlds * sizeof(float);
   if (lds > 64 * 1024) return IRBFN_ERR_UNSUPPORTED;
-  const long waves = (B + kWave - 1) / kWave;
+  const long waves = (a.B + kWave - 1) / kWave;
   const dim3 grid((unsigned)((waves + kVjpWaves - 1) / kVjpWaves)), block(kWave * kVjpWaves);
   if (TCH == 8) hipLaunchKernelGGL((rollout_vjp_regs_kernel<MODE, 8>), grid, block, lds, s, a);
   else hipLaunchKernelGGL((rollout_vjp_regs_kernel<MODE, 50>), grid, block, lds, s, a);
@@ -653,51 +467,49 @@ static int launch_vjp_regs(const float* x0u, const DynParams& dp, const float* g
   return IRBFN_OK;
 }
 
+template <int MODE>
+static int launch_vjp_park(const RollVjpArgs& a, hipStream_t s) {
+  const size_t lds = (size_t)a.T * ModeTraits<MODE>::NP * kWave * sizeof(float);
+  if (lds > 150 * 1024) return IRBFN_ERR_UNSUPPORTED;
+  auto kern = rollout_vjp_park_kernel<MODE>;
+  if (lds > 48 * 1024)
+    IRBFN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)((a.B + kWave - 1) / kWave)), dim3(kWave), lds, s, a);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
+
+// K4 up to T = 50, the park kernel beyond
+template <int MODE>
+static int launch_vjp_mode(const RollVjpArgs& a, hipStream_t s) {
+  if (a.T <= 50) {
+    const int rc = launch_vjp_regs<MODE>(a, s);
+    if (rc != IRBFN_ERR_UNSUPPORTED) return rc;
+  }
+  return launch_vjp_park<MODE>(a, s);
+}
+
 int launch_rollout_vjp(int mode, const float* x0u, const DynParams& dp, const float* gstates,
                        float* g_x0u, int64_t B, int T, float clip_tie, hipStream_t s) {
   if (B == 0) return IRBFN_OK;
+  // ST_SELECT: the reference never differentiates it (SURVEY B-5)
+  if (mode == IRBFN_ROLLOUT_ST_SELECT || rollout_state_dim(mode) < 0) return IRBFN_ERR_UNSUPPORTED;
+  if (T == 0) {                                  // no step: the rows are the initial states, and nothing depends on them
+    IRBFN_HIP_CHECK(hipMemsetAsync(g_x0u, 0, (size_t)B * mode_dims(mode).S0 * sizeof(float), s));
+    return IRBFN_OK;
+  }
   RollVjpArgs a;
   a.x0u = x0u; a.gstates = gstates; a.gx0u = g_x0u; a.B = (long)B; a.T = T;
   a.L = rollout_input_dim(mode, T); a.tie = clip_tie; a.dp = dp;
-  if (T >= 1 && T <= 50) {                       // K4 with staged memory traffic (the kernels below: longer horizons)
-    int rc = IRBFN_ERR_UNSUPPORTED;
-    if (mode == IRBFN_ROLLOUT_ST_KS) rc = launch_vjp_regs<IRBFN_ROLLOUT_ST_KS>(x0u, dp, gstates, g_x0u, B, T, clip_tie, s);
-    else if (mode == IRBFN_ROLLOUT_FULLINT) rc = launch_vjp_regs<IRBFN_ROLLOUT_FULLINT>(x0u, dp, gstates, g_x0u, B, T, clip_tie, s);
-    else if (mode == IRBFN_ROLLOUT_FRENET_LS) rc = launch_vjp_regs<IRBFN_ROLLOUT_FRENET_LS>(x0u, dp, gstates, g_x0u, B, T, clip_tie, s);
-    if (rc != IRBFN_ERR_UNSUPPORTED) return rc;
-  }
-  if (mode == IRBFN_ROLLOUT_SPIRAL && T >= 1 && T <= 256) {          // 37 KB of LDS at N = 256
-    const size_t ldss = ((size_t)kWave * kSpiralPitch + (size_t)((T + kSpiralG - 1) / kSpiralG) * 3 * kWave) * sizeof(float);
-    hipLaunchKernelGGL(rollout_vjp_spiral_staged, dim3((unsigned)((B + kWave - 1) / kWave)), dim3(kWave), ldss, s, a);
-    IRBFN_HIP_CHECK(hipGetLastError());
-    return IRBFN_OK;
-  }
-  int ns;
   switch (mode) {
-    case IRBFN_ROLLOUT_ST_KS:
-    case IRBFN_ROLLOUT_FULLINT:
-    case IRBFN_ROLLOUT_SPIRAL: ns = 3; break;
-    case IRBFN_ROLLOUT_FRENET_LS: ns = 4; break;
-    default: return IRBFN_ERR_UNSUPPORTED;   // ST_SELECT: the reference never differentiates it (SURVEY B-5)
+    case IRBFN_ROLLOUT_ST_KS: return launch_vjp_mode<IRBFN_ROLLOUT_ST_KS>(a, s);
+    case IRBFN_ROLLOUT_FULLINT: return launch_vjp_mode<IRBFN_ROLLOUT_FULLINT>(a, s);
+    case IRBFN_ROLLOUT_FRENET_LS: return launch_vjp_mode<IRBFN_ROLLOUT_FRENET_LS>(a, s);
+    default: break;
   }
-  size_t lds = (size_t)(T > 0 ? T : 1) * ns * kWave * sizeof(float);
-  if (lds > 150 * 1024) return IRBFN_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)((B + kWave - 1) / kWave)), block(kWave);
-#define IRBFN_RV(KERN)                                                                                         \
-  do {                                                                                                         \
-    if (lds > 48 * 1024)                                                                                       \
-      IRBFN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(KERN),                                  \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));              \
-    hipLaunchKernelGGL(KERN, grid, block, lds, s, a);                                                          \
-  } while (0)
-  switch (mode) {
-    case IRBFN_ROLLOUT_ST_KS: IRBFN_RV(rollout_vjp_st_ks); break;
-    case IRBFN_ROLLOUT_FULLINT: IRBFN_RV(rollout_vjp_fullint); break;
-    case IRBFN_ROLLOUT_FRENET_LS: IRBFN_RV(rollout_vjp_frenet); break;
-    case IRBFN_ROLLOUT_SPIRAL: IRBFN_RV(rollout_vjp_spiral); break;
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-#undef IRBFN_RV
+  if (T > 256) return IRBFN_ERR_UNSUPPORTED;     // the spiral: 37 KB of LDS at N = 256
+  const size_t lds = ((size_t)kWave * kSpiralPitch + (size_t)((T + kSpiralG - 1) / kSpiralG) * 3 * kWave) * sizeof(float);
+  hipLaunchKernelGGL(rollout_vjp_spiral_staged, dim3((unsigned)((B + kWave - 1) / kWave)), dim3(kWave), lds, s, a);
   IRBFN_HIP_CHECK(hipGetLastError());
   return IRBFN_OK;
 }

@@ -17,10 +17,6 @@
 
 namespace irbfn {
 
-__device__ __forceinline__ float clipgrad_t(float v, float lo, float hi, float tie) {
-  return (v > lo && v < hi) ? 1.0f : ((v == lo || v == hi) ? tie : 0.0f);
-}
-
 __device__ __forceinline__ float block_sum_256(float v, float* sm) {
   const int t = threadIdx.x;
   sm[t] = v;
@@ -46,11 +42,12 @@ __global__ __launch_bounds__(256) void seeds_oneint_kernel(const float* __restri
   __shared__ float sm[256];
   float lsum = 0.0f;
   const float inv_y = 1.0f / ((float)B * (float)O), inv_s = 1.0f / ((float)B * 4.0f);
-  const float dt = dp.p[8], sv_max = dp.p[9], a_max = dp.p[10];
   for (long b = (long)blockIdx.x * 256 + threadIdx.x; b < B; b += (long)gridDim.x * 256) {
     const float* xb = x + b * D;
     float sp[7] = {0.0f, 0.0f, 0.0f, xb[0], 0.0f, xb[6], xb[5]};
     float sa[7] = {0.0f, 0.0f, 0.0f, xb[0], 0.0f, xb[6], xb[5]};
+    float pk[ModeTraits<IRBFN_ROLLOUT_ST_KS>::NP];
+    vjp_park<IRBFN_ROLLOUT_ST_KS>(sp, pk);
     const float ap = yp[b * O + 0], svp = yp[b * O + 1];
     st_step<false>(sp, ap, svp, dp);                       // predicted_integrated_states  (:276)
     st_step<false>(sa, y[b * O + 0], y[b * O + 1], dp);    // actual_integrated_states     (:275)
@@ -68,8 +65,10 @@ __global__ __launch_bounds__(256) void seeds_oneint_kernel(const float* __restri
       gy[b * O + o] = d * inv_y;
     }
     // adjoint of the kinematic step w.r.t. its controls (oracle/hand_vjp.py: vjp_st_ks, T = 1)
-    gy[b * O + 0] += clipgrad_t(ap, -a_max, a_max, tie) * dt * lam[3];
-    gy[b * O + 1] += clipgrad_t(svp, -sv_max, sv_max, tie) * dt * lam[2];
+    float ga, gsv;
+    vjp_back_step<IRBFN_ROLLOUT_ST_KS>(pk, ap, svp, lam, 0.0f, tie, dp, ga, gsv);
+    gy[b * O + 0] += ga;
+    gy[b * O + 1] += gsv;
   }
   const float tot = block_sum_256(lsum, sm);
   if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
@@ -159,13 +158,15 @@ __global__ __launch_bounds__(256) void seeds_fullint_kernel(const float* __restr
         gy[b * O + o_idx] = v;
       }
     };
+    // reverse sweep (oracle/hand_vjp.py: vjp_fullint): vjp_back_step<FULLINT> written out.  Calling it here changed which
+    // multiply-adds the compiler contracts, and with them the last bits of the T = 5 gradients.
 #pragma unroll
-    for (int t = TMAX - 1; t >= 0; --t) {                    // reverse sweep (oracle/hand_vjp.py: vjp_fullint)
+    for (int t = TMAX - 1; t >= 0; --t) {
       if (t < T) {
         const float a = prd(t, 0), dv = prd(t, 1);
         const float dpre = pd[t] + dv * DT, vpre = pv[t] + a * DT;
         const float d1 = clipf(dpre, -SMAX, SMAX), v1 = clipf(vpre, VMIN, VMAX);
-        const float md = clipgrad_t(dpre, -SMAX, SMAX, tie), mv = clipgrad_t(vpre, VMIN, VMAX, tie);
+        const float md = clipgrad(dpre, -SMAX, SMAX, tie), mv = clipgrad(vpre, VMIN, VMAX, tie);
         float sn, cs;
         sincos_fast(pp[t], sn, cs);
         const float td = tan_fast(d1);

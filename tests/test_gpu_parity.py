@@ -518,7 +518,7 @@ def test_net_vjp_cfg3_size_determinism_and_subset(gpu):
 
 def test_rollout_vjps_match_hand_adjoints(gpu):
     rng = np.random.default_rng(21)
-    for B, T in ((1, 1), (70, 5), (300, 50)):
+    for B, T in ((1, 1), (70, 5), (300, 50), (64, 64)):       # T <= 50: K4; T = 64: the park kernel
         xu = _st_inputs(B, T, seed=B)
         gs = rng.normal(size=(B, T, 7))
         ref = hv.vjp_st_ks(xu, DP, gs)
@@ -542,6 +542,18 @@ def test_rollout_vjps_match_hand_adjoints(gpu):
     ref = hv.vjp_spiral(q, g6)
     got = dyn.rollout_vjp(_lib.ROLLOUT_SPIRAL, q.astype(np.float32), None, g6.astype(np.float32), 9)
     assert np.abs(got - ref).max() <= 2e-4 * np.abs(ref).max()
+    q = np.hstack([rng.normal(size=(70, 4)) * .3, rng.uniform(1, 10, size=(70, 1))])
+    g6 = rng.normal(size=(70, 256, 6))                              # N = 256: the largest the staged kernel takes
+    ref = hv.vjp_spiral(q, g6, N=256)
+    got = dyn.rollout_vjp(_lib.ROLLOUT_SPIRAL, q.astype(np.float32), None, g6.astype(np.float32), 256)
+    assert np.abs(got - ref).max() <= 2e-4 * np.abs(ref).max()
+    # T = 0: no step, the cotangent of the rows is zero (a spiral of arc length 0 included)
+    for mode, S, dp, x0 in ((_lib.ROLLOUT_ST_KS, 7, DP, _st_inputs(9, 0, seed=9)),
+                            (_lib.ROLLOUT_FULLINT, 5, None, rng.uniform(-1, 8, (9, 1))),
+                            (_lib.ROLLOUT_FRENET_LS, 8, DP, _frenet_inputs(9, 0, rng)),
+                            (_lib.ROLLOUT_SPIRAL, 6, None, np.hstack([rng.normal(size=(9, 4)), np.r_[0.0, rng.uniform(1, 10, 8)][:, None]]))):
+        got = dyn.rollout_vjp(mode, x0.astype(np.float32), dp, np.zeros((9, 0, S), np.float32), 0)
+        assert got.shape == x0.shape and (got == 0).all()
     with pytest.raises(ValueError):      # ST_SELECT is never differentiated by the reference (App. B-5)
         dyn.rollout_vjp(_lib.ROLLOUT_ST_SELECT, np.zeros((4, 17), np.float32), DP, np.zeros((4, 5, 7), np.float32), 5)
 
