@@ -231,6 +231,26 @@ int irbfn_train_seeds_frenet_fullint(const float* x_dev, const float* y_pred_dev
 int irbfn_adam_clip_step(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev, int64_t n,
                          int* step_dev, float lr, float beta1, float beta2, float eps, float max_grad_norm,
                          float* partials_dev, void* stream);
+/* float64 twins of the four calls above, for a net trained under --use_float64 (scripts/train_nmpc.py:41-42: jax_enable_x64):
+ * double buffers and double dynamics parameters, the same argument rules and status codes.  partials_dev holds
+ * irbfn_train_loss_partials() doubles.
+ * irbfn_train_seeds_oneint_f64: loss_fn of train_step_oneint in float64 (scripts/train_nmpc.py:268-295).
+ * irbfn_train_seeds_fullint_f64: loss_fn of train_step_fullint in float64 (scripts/train_nmpc.py:306-390).
+ * irbfn_train_seeds_frenet_fullint_f64: loss_fn of the Frenet train_step_fullint in float64 (scripts/train_nmpc_frenet.py:394-421).
+ * irbfn_adam_clip_step_f64: optax.chain(clip_by_global_norm(max_grad_norm), adam(lr)) + apply_gradients in float64
+ *   (scripts/train_nmpc.py:231-233, :299). */
+int irbfn_train_seeds_oneint_f64(const double* x_dev, const double* y_pred_dev, const double* y_dev,
+                                 const double* dyn_params_host, double clip_tie, double* gy_dev, double* loss_dev,
+                                 double* partials_dev, int64_t B, int D, int O, void* stream);
+int irbfn_train_seeds_fullint_f64(const double* x_dev, const double* y_pred_dev, const double* y_dev, double clip_tie,
+                                  double* gy_dev, double* loss_dev, double* partials_dev, int64_t B, int D, int T,
+                                  void* stream);
+int irbfn_train_seeds_frenet_fullint_f64(const double* x_dev, const double* y_pred_dev, const double* y_dev,
+                                         const double* dyn_params_host, double clip_tie, double* gy_dev, double* loss_dev,
+                                         double* partials_dev, int64_t B, int D, int T, void* stream);
+int irbfn_adam_clip_step_f64(double* params_dev, const double* grads_dev, double* m_dev, double* v_dev, int64_t n,
+                             int* step_dev, double lr, double beta1, double beta2, double eps, double max_grad_norm,
+                             double* partials_dev, void* stream);
 
 /* ---- Batched planner front / back end ------------------------------------------------------
  * Query construction + mirror trick of IRBFNPlanner.plan (src/irbfn_mpc/irbfn_planner.py:181-201):

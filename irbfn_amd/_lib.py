@@ -24,7 +24,7 @@ FWD_AUTO, FWD_K1, FWD_K1M, FWD_K1H, FWD_K1R, FWD_K1G = 0, 1, 2, 3, 4, 5
 VJP_AUTO, VJP_K2, VJP_K2H, VJP_K2R, VJP_K2G = 0, 1, 2, 3, 4
 
 # every symbol include/irbfn_hip.h declares: (name, restype, argtypes)
-_vp, _fp, _ip, _i, _i64, _f = C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float
+_vp, _fp, _ip, _i, _i64, _f, _d = C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 SIGNATURES = {
     "irbfn_net_create": (_i, [C.POINTER(C.c_void_p), _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _ip, _i]),
     "irbfn_net_destroy": (_i, [_vp]),
@@ -45,6 +45,10 @@ SIGNATURES = {
     "irbfn_train_seeds_fullint": (_i, [_fp, _fp, _fp, _f, _fp, _fp, _fp, _i64, _i, _i, _vp]),
     "irbfn_train_seeds_frenet_fullint": (_i, [_fp, _fp, _fp, _fp, _f, _fp, _fp, _fp, _i64, _i, _i, _vp]),
     "irbfn_adam_clip_step": (_i, [_fp, _fp, _fp, _fp, _i64, _vp, _f, _f, _f, _f, _f, _fp, _vp]),
+    "irbfn_train_seeds_oneint_f64": (_i, [_fp, _fp, _fp, _fp, _d, _fp, _fp, _fp, _i64, _i, _i, _vp]),
+    "irbfn_train_seeds_fullint_f64": (_i, [_fp, _fp, _fp, _d, _fp, _fp, _fp, _i64, _i, _i, _vp]),
+    "irbfn_train_seeds_frenet_fullint_f64": (_i, [_fp, _fp, _fp, _fp, _d, _fp, _fp, _fp, _i64, _i, _i, _vp]),
+    "irbfn_adam_clip_step_f64": (_i, [_fp, _fp, _fp, _fp, _i64, _vp, _d, _d, _d, _d, _d, _fp, _vp]),
     "irbfn_plan_queries_cartesian": (_i, [_fp, _fp, _fp, _fp, _ip, _i64, _vp]),
     "irbfn_plan_queries_frenet": (_i, [_fp, _fp, _fp, _fp, _ip, _i64, _vp]),
     "irbfn_plan_tick": (_i, [_vp, _i, _fp, _ip, _fp, _fp, _fp, _fp, _i64, _i, _vp]),

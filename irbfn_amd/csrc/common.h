@@ -61,6 +61,12 @@ __host__ __device__ constexpr int mfma_cw(int D) { return (D + 1 + 3) & ~3; }   
 struct DynParams {         // dynamics.py:24-36
   float p[13];
 };
+struct DynParams64 {       // the same 13 entries for the float64 training steps (train_step.hip)
+  double p[13];
+};
+// the DynParams a one-step map of scalar type S reads (rollout_step.h)
+template <typename S> struct DynOf { using type = DynParams; };
+template <> struct DynOf<double> { using type = DynParams64; };
 
 }  // namespace irbfn
 

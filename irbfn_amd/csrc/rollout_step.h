@@ -1,6 +1,10 @@
 // One-step maps of the roll-outs (device functions shared by the stand-alone roll-out kernels and
 // the fused forward+roll-out kernel).  One lane integrates one trajectory; state lives in VGPRs.
+// st_step<false>, fullint_step and frenet_step take their scalar type S as a template parameter (float by default):
+// S = double with TrigF64 and DynParams64 are the float64 training steps (train_step.hip).
 #pragma once
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -71,6 +75,8 @@ __device__ __forceinline__ float fdiv_fast(float a, float b) {
   return __builtin_fmaf(__builtin_fmaf(-b, q, a), rc, q);
 #endif
 }
+// float64 steps: IEEE division, no shortcut
+__device__ __forceinline__ double fdiv_fast(double a, double b) { return a / b; }
 
 __device__ __forceinline__ float tan_fast(float x) {
   float sn, cs;
@@ -85,11 +91,16 @@ __device__ __forceinline__ float tan_clipped(float x, bool small) {
   return fdiv_fast(sn, cs);
 }
 
-__device__ __forceinline__ float clipf(float v, float lo, float hi) {
-  // jnp.clip = min(max(v, lo), hi), nan propagates.  v_med3_f32 (nan in -> min3) + one select: 3 instructions
-  // (fminf(fmaxf()) canonicalises every operand: 7)
-  const float m = __builtin_amdgcn_fmed3f(v, lo, hi);
-  return v != v ? v : m;
+template <typename S>
+__device__ __forceinline__ S clipf(S v, S lo, S hi) {
+  // jnp.clip = min(max(v, lo), hi), nan propagates.  float: v_med3_f32 (nan in -> min3) + one select: 3 instructions
+  // (fminf(fmaxf()) canonicalises every operand: 7).  double: fmin(fmax()), which drops a nan operand, so the select too
+  if constexpr (std::is_same<S, float>::value) {
+    const float m = __builtin_amdgcn_fmed3f(v, lo, hi);
+    return v != v ? v : m;
+  } else {
+    return v != v ? v : fmin(fmax(v, lo), hi);
+  }
 }
 
 // How a step gets its trigonometry: sincos(A) of the heading-like angle and tan(B) of the (clipped) steering angle.
@@ -103,22 +114,31 @@ struct TrigDirect {
   }
   __device__ __forceinline__ void sincos(float A, float& sn, float& cs) const { sincos_fast(A, sn, cs); }
 };
+// The float64 steps (S = double): ocml's double sincos / tan, as jnp.sin / jnp.tan under jax_enable_x64.
+struct TrigF64 {
+  __device__ __forceinline__ void sincos_tan(double A, double B, bool, double& sn, double& cs, double& tn) const {
+    ::sincos(A, &sn, &cs);
+    tn = ::tan(B);
+  }
+  __device__ __forceinline__ void sincos(double A, double& sn, double& cs) const { ::sincos(A, &sn, &cs); }
+};
 
 // Single-track model, src/irbfn_mpc/dynamics.py:9-91.  SELECT=true: x + select(V>3, f, f_ks)*dt (:90);
 // SELECT=false: kinematic RHS only = dynamic_st_onestep_aux (:103-187).
-template <bool SELECT, typename Trig = TrigDirect>
-__device__ __forceinline__ void st_step(float (&s)[7], float accl_in, float sv_in, const DynParams& dp, const Trig trig = Trig()) {
+template <bool SELECT, typename Trig = TrigDirect, typename S = float>
+__device__ __forceinline__ void st_step(S (&s)[7], S accl_in, S sv_in, const typename DynOf<S>::type& dp, const Trig trig = Trig()) {
 #pragma clang fp contract(off)   // same mul/add sequence in every kernel that inlines this (fused == stand-alone)
-  const float g = 9.81f;                                 // dynamics.py:6
-  const float mu = dp.p[0], m = dp.p[1], I = dp.p[2], lf = dp.p[3], lr = dp.p[4], C_Sf = dp.p[5],
-              C_Sr = dp.p[6], h = dp.p[7], dt = dp.p[8], sv_max = dp.p[9], a_max = dp.p[10],
-              s_max = dp.p[11], v_max = dp.p[12];
-  const float DELTA = clipf(s[2], -s_max, s_max);        // :40
-  const float V = clipf(s[3], -v_max, v_max);            // :41
-  const float PSI = s[4], PSI_DOT = s[5], BETA = s[6];
-  const float ACCL = clipf(accl_in, -a_max, a_max);      // :46
-  const float SV = clipf(sv_in, -sv_max, sv_max);        // :47
-  float f0, f1, f4, f5, f6;
+  static_assert(!SELECT || std::is_same<S, float>::value, "the select model runs in float32 only");
+  const S g = S(9.81);                                   // dynamics.py:6
+  const S mu = dp.p[0], m = dp.p[1], I = dp.p[2], lf = dp.p[3], lr = dp.p[4], C_Sf = dp.p[5],
+          C_Sr = dp.p[6], h = dp.p[7], dt = dp.p[8], sv_max = dp.p[9], a_max = dp.p[10],
+          s_max = dp.p[11], v_max = dp.p[12];
+  const S DELTA = clipf(s[2], -s_max, s_max);            // :40
+  const S V = clipf(s[3], -v_max, v_max);                // :41
+  const S PSI = s[4], PSI_DOT = s[5], BETA = s[6];
+  const S ACCL = clipf(accl_in, -a_max, a_max);          // :46
+  const S SV = clipf(sv_in, -sv_max, sv_max);            // :47
+  S f0, f1, f4, f5, f6;
   if constexpr (SELECT) {
     // lax.select(V > 3, f, f_ks) (:90) WITHOUT a branch.  The batch mixes fast and slow trajectories in every wave, so a
     // branch ran both right-hand sides one after the other, each with its own trigonometry (191 us against 107 us for the
@@ -145,7 +165,7 @@ __device__ __forceinline__ void st_step(float (&s)[7], float accl_in, float sv_i
     f5 = dyn ? f5d : 0.0f;
     f6 = dyn ? f6d : 0.0f;
   } else {                                               // :78-88
-    float sn, cs, tn;
+    S sn, cs, tn;
     trig.sincos_tan(PSI, DELTA, s_max < 4194304.0f, sn, cs, tn);
     f0 = V * cs;
     f1 = V * sn;
@@ -163,12 +183,12 @@ __device__ __forceinline__ void st_step(float (&s)[7], float accl_in, float sv_i
 }
 
 // Inline kinematic bicycle of train_step_fullint, scripts/train_nmpc.py:329-347 / :356-374.
-template <typename Trig = TrigDirect>
-__device__ __forceinline__ void fullint_step(float (&s)[5], float a, float dv, const Trig trig = Trig()) {
+template <typename Trig = TrigDirect, typename S = float>
+__device__ __forceinline__ void fullint_step(S (&s)[5], S a, S dv, const Trig trig = Trig()) {
 #pragma clang fp contract(off)   // same mul/add sequence in every kernel that inlines this (fused == stand-alone)
-  const float DT = 0.1f, WB = 0.33f, VMAX = 7.0f, VMIN = 0.0f, SMAX = 0.4189f;   // :307-311
-  const float dnew = clipf(s[2] + dv * DT, -SMAX, SMAX); // :362-363
-  float sn, cs, tn;
+  const S DT = S(0.1), WB = S(0.33), VMAX = S(7.0), VMIN = S(0.0), SMAX = S(0.4189);   // :307-311
+  const S dnew = clipf(s[2] + dv * DT, -SMAX, SMAX);     // :362-363
+  S sn, cs, tn;
   trig.sincos_tan(s[4], dnew, true, sn, cs, tn);
   s[0] = s[0] + s[3] * cs * DT;                          // :360
   s[1] = s[1] + s[3] * sn * DT;                          // :361
@@ -178,27 +198,27 @@ __device__ __forceinline__ void fullint_step(float (&s)[5], float a, float dv, c
 }
 
 // Frenet model, low-speed RHS only, src/irbfn_mpc/dynamics.py:190-281 (:267-280).
-template <typename Trig = TrigDirect>
-__device__ __forceinline__ void frenet_step(float (&s)[8], float a_in, float dv_in, const DynParams& dp, const Trig trig = Trig()) {
+template <typename Trig = TrigDirect, typename S = float>
+__device__ __forceinline__ void frenet_step(S (&s)[8], S a_in, S dv_in, const typename DynOf<S>::type& dp, const Trig trig = Trig()) {
 #pragma clang fp contract(off)   // same mul/add sequence in every kernel that inlines this (fused == stand-alone)
-  const float LF = dp.p[3], LR = dp.p[4], dt = dp.p[8], sv_max = dp.p[9], a_max = dp.p[10],
-              s_max = dp.p[11];
-  const float ey = s[1], delta = clipf(s[2], -s_max, s_max), vx = s[3], epsi = s[6], cur = s[7];
-  const float a = clipf(a_in, -a_max, a_max);            // :235
-  const float dv = clipf(dv_in, -sv_max, sv_max);        // :236
-  float se, ce, td;
+  const S LF = dp.p[3], LR = dp.p[4], dt = dp.p[8], sv_max = dp.p[9], a_max = dp.p[10],
+          s_max = dp.p[11];
+  const S ey = s[1], delta = clipf(s[2], -s_max, s_max), vx = s[3], epsi = s[6], cur = s[7];
+  const S a = clipf(a_in, -a_max, a_max);                // :235
+  const S dv = clipf(dv_in, -sv_max, sv_max);            // :236
+  S se, ce, td;
   trig.sincos_tan(epsi, delta, s_max < 4194304.0f, se, ce, td);
-  const float d0 = (vx * ce) / (1.0f - ey * cur);        // :268
-  const float d1 = vx * se;                              // :269
-  const float d6 = fdiv_fast(vx * td, LR + LF) - cur * ((vx * ce) / (1.0f - cur * ey));  // :274-275
+  const S d0 = (vx * ce) / (S(1.0) - ey * cur);          // :268
+  const S d1 = vx * se;                                  // :269
+  const S d6 = fdiv_fast(vx * td, LR + LF) - cur * ((vx * ce) / (S(1.0) - cur * ey));  // :274-275
   s[0] = s[0] + d0 * dt;
   s[1] = s[1] + d1 * dt;
   s[2] = s[2] + dv * dt;
   s[3] = s[3] + a * dt;
-  s[4] = s[4] + 0.0f * dt;
-  s[5] = s[5] + 0.0f * dt;
+  s[4] = s[4] + S(0.0) * dt;
+  s[5] = s[5] + S(0.0) * dt;
   s[6] = s[6] + d6 * dt;
-  s[7] = s[7] + 0.0f * dt;
+  s[7] = s[7] + S(0.0) * dt;
 }
 
 // Cubic spiral: params_to_coefs (planner_utils.py:20-29)

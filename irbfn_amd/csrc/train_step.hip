@@ -9,6 +9,10 @@
 //   adam_clip     : optax.chain(clip_by_global_norm(max_norm), adam(lr)) + apply_gradients
 //                   (scripts/train_nmpc.py:231-233, :299)
 // All reductions are two-stage with a fixed order (deterministic).
+//
+// The float64 twins (*_f64) are the same compositions for a net trained under the reference's --use_float64
+// (scripts/train_nmpc.py:41-42): the one-step maps and adjoints of rollout_step.h / rollout_adjoint.h with S = double and
+// ocml's double trigonometry.  They are plain loops of their own: the float32 kernels keep their register-resident forms.
 #include <string.h>
 
 #include "common.h"
@@ -17,7 +21,8 @@
 
 namespace irbfn {
 
-__device__ __forceinline__ float block_sum_256(float v, float* sm) {
+template <typename S>
+__device__ __forceinline__ S block_sum_256(S v, S* sm) {
   const int t = threadIdx.x;
   sm[t] = v;
   __syncthreads();
@@ -25,7 +30,7 @@ __device__ __forceinline__ float block_sum_256(float v, float* sm) {
     if (t < w) sm[t] += sm[t + w];
     __syncthreads();
   }
-  const float r = sm[0];
+  const S r = sm[0];
   __syncthreads();
   return r;
 }
@@ -305,6 +310,178 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, c
   }
 }
 
+// ---- float64 twins ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double sgn64(double d) { return d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0); }   // d|.| = sign
+
+// train_step_oneint in float64 (scripts/train_nmpc.py:268-295): as seeds_oneint_kernel
+__global__ __launch_bounds__(256) void seeds_oneint_f64_kernel(const double* __restrict__ x, const double* __restrict__ yp,
+                                                               const double* __restrict__ y, double* __restrict__ gy,
+                                                               double* __restrict__ loss_part, long B, int D, int O,
+                                                               DynParams64 dp, double tie) {
+  __shared__ double sm[256];
+  double lsum = 0.0;
+  const double inv_y = 1.0 / ((double)B * (double)O), inv_s = 1.0 / ((double)B * 4.0);
+  for (long b = (long)blockIdx.x * 256 + threadIdx.x; b < B; b += (long)gridDim.x * 256) {
+    const double* xb = x + b * D;
+    double sp[7] = {0.0, 0.0, 0.0, xb[0], 0.0, xb[6], xb[5]};
+    double sa[7] = {0.0, 0.0, 0.0, xb[0], 0.0, xb[6], xb[5]};
+    double pk[ModeTraits<IRBFN_ROLLOUT_ST_KS>::NP];
+    vjp_park<IRBFN_ROLLOUT_ST_KS>(sp, pk);
+    const double ap = yp[b * O + 0], svp = yp[b * O + 1];
+    st_step<false, TrigF64>(sp, ap, svp, dp);                       // predicted_integrated_states  (:276)
+    st_step<false, TrigF64>(sa, y[b * O + 0], y[b * O + 1], dp);    // actual_integrated_states     (:275)
+    double lam[7] = {0, 0, 0, 0, 0, 0, 0};
+    const int idx[4] = {0, 1, 3, 4};
+    for (int k = 0; k < 4; ++k) {
+      const double d = sp[idx[k]] - sa[idx[k]];
+      lsum += 0.5 * d * d * inv_s;
+      lam[idx[k]] = d * inv_s;
+    }
+    for (int o = 0; o < O; ++o) {
+      const double d = yp[b * O + o] - y[b * O + o];
+      lsum += 0.5 * d * d * inv_y;
+      gy[b * O + o] = d * inv_y;
+    }
+    double ga, gsv;
+    vjp_back_step<IRBFN_ROLLOUT_ST_KS, TrigF64>(pk, ap, svp, lam, 0.0, tie, dp, ga, gsv);
+    gy[b * O + 0] += ga;
+    gy[b * O + 1] += gsv;
+  }
+  const double tot = block_sum_256(lsum, sm);
+  if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
+}
+
+// train_step_fullint in float64 (scripts/train_nmpc.py:306-390): as seeds_fullint_kernel, the reverse sweep is
+// vjp_back_step<FULLINT>.  O = 2T, T <= TMAX.
+template <int TMAX>
+__global__ __launch_bounds__(256) void seeds_fullint_f64_kernel(const double* __restrict__ x, const double* __restrict__ yp,
+                                                                const double* __restrict__ y, double* __restrict__ gy,
+                                                                double* __restrict__ loss_part, long B, int D, int T,
+                                                                double tie) {
+  __shared__ double sm[256];
+  const int O = 2 * T;
+  const DynParams64 dp = {};                                 // the inline bicycle has its own constants (:307-311)
+  const double inv_y = 1.0 / ((double)B * 2.0), inv_s = 1.0 / ((double)B * 5.0);
+  double lsum = 0.0;
+  for (long b = (long)blockIdx.x * 256 + threadIdx.x; b < B; b += (long)gridDim.x * 256) {
+    const double* yr = y + b * O;
+    const double* pr = yp + b * O;
+    double* gr = gy + b * O;
+    const double v0 = clipf(x[b * D + 0], 0.0, 7.0);       // :319
+    double sa[5] = {0.0, 0.0, 0.0, v0, 0.0};
+    for (int t = 0; t < T; ++t) fullint_step<TrigF64>(sa, yr[t], yr[T + t]);       // :329-347
+    double sp[5] = {0.0, 0.0, 0.0, v0, 0.0};
+    double pk[TMAX][ModeTraits<IRBFN_ROLLOUT_FULLINT>::NP];
+    for (int t = 0; t < T; ++t) {
+      vjp_park<IRBFN_ROLLOUT_FULLINT>(sp, pk[t]);
+      fullint_step<TrigF64>(sp, pr[t], pr[T + t]);                                 // :356-374
+    }
+    double lam[5];
+    for (int i = 0; i < 5; ++i) {
+      const double d = sp[i] - sa[i];
+      lsum += fabs(d) * inv_s;
+      lam[i] = sgn64(d) * inv_s;
+    }
+    for (int t = T - 1; t >= 0; --t) {
+      double ga, gsv;
+      vjp_back_step<IRBFN_ROLLOUT_FULLINT, TrigF64>(pk[t], pr[t], pr[T + t], lam, 0.0, tie, dp, ga, gsv);
+      gr[t] = ga;
+      gr[T + t] = gsv;
+    }
+    for (int k = 0; k < 2; ++k) {                            // y_predictions[:, [0, T]]  (:387)
+      const double d = pr[k * T] - yr[k * T];
+      lsum += fabs(d) * inv_y;
+      gr[k * T] += sgn64(d) * inv_y;
+    }
+  }
+  const double tot = block_sum_256(lsum, sm);
+  if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
+}
+
+// Frenet train_step_fullint in float64 (scripts/train_nmpc_frenet.py:394-421): as seeds_frenet_fullint_kernel
+template <int TMAX>
+__global__ __launch_bounds__(256) void seeds_frenet_fullint_f64_kernel(const double* __restrict__ x, const double* __restrict__ yp,
+                                                                       const double* __restrict__ y, double* __restrict__ gy,
+                                                                       double* __restrict__ loss_part, long B, int D, int T,
+                                                                       DynParams64 dp, double tie) {
+  __shared__ double sm[256];
+  const int O = 2 * T;
+  const double inv_y = 1.0 / ((double)B * (double)O), inv_s = 1.0 / ((double)B * (double)T * 8.0);
+  double lsum = 0.0;
+  for (long b = (long)blockIdx.x * 256 + threadIdx.x; b < B; b += (long)gridDim.x * 256) {
+    const double* xb = x + b * D;
+    double sa[8] = {xb[0], xb[0], xb[1], xb[2], xb[3], xb[5], xb[6], xb[7]};
+    double sp[8] = {xb[0], xb[0], xb[1], xb[2], xb[3], xb[5], xb[6], xb[7]};
+    const double cur = sp[7];
+    double park[TMAX][ModeTraits<IRBFN_ROLLOUT_FRENET_LS>::NP], seed[TMAX][8];
+    for (int t = 0; t < T; ++t) {
+      frenet_step<TrigF64>(sa, y[b * O + t], y[b * O + T + t], dp);       // actual_states (:407)
+      vjp_park<IRBFN_ROLLOUT_FRENET_LS>(sp, park[t]);
+      frenet_step<TrigF64>(sp, yp[b * O + t], yp[b * O + T + t], dp);     // pred_states   (:408)
+      for (int i = 0; i < 8; ++i) {
+        const double d = sp[i] - sa[i];
+        lsum += fabs(d) * inv_s;
+        seed[t][i] = sgn64(d) * inv_s;
+      }
+    }
+    double lam[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int t = T - 1; t >= 0; --t) {
+      for (int i = 0; i < 8; ++i) lam[i] += seed[t][i];
+      double ga, gsv;
+      vjp_back_step<IRBFN_ROLLOUT_FRENET_LS, TrigF64>(park[t], yp[b * O + t], yp[b * O + T + t], lam, cur, tie, dp, ga, gsv);
+      gy[b * O + t] = ga;
+      gy[b * O + T + t] = gsv;
+    }
+    for (int o = 0; o < O; ++o) {                            // pred_loss = |y_pred - y|.mean()  (:401)
+      const double d = yp[b * O + o] - y[b * O + o];
+      lsum += fabs(d) * inv_y;
+      gy[b * O + o] += sgn64(d) * inv_y;
+    }
+  }
+  const double tot = block_sum_256(lsum, sm);
+  if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(256) void final_sum_f64_kernel(const double* __restrict__ part, int n, double* __restrict__ out) {
+  __shared__ double sm[256];
+  double v = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) v += part[i];
+  const double tot = block_sum_256(v, sm);
+  if (threadIdx.x == 0) out[0] = tot;
+}
+
+// the step count travels in the int at the start of the double part[kRedBlocks], as in sqnorm_partial_kernel
+__global__ __launch_bounds__(256) void sqnorm_partial_f64_kernel(const double* __restrict__ g, long n, double* __restrict__ part,
+                                                                 const int* __restrict__ step) {
+  __shared__ double sm[256];
+  if (blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<int*>(part + kRedBlocks)[0] = step[0] + 1;
+  double v = 0.0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) v += g[i] * g[i];
+  const double tot = block_sum_256(v, sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(256) void adam_clip_f64_kernel(double* __restrict__ p, const double* __restrict__ g,
+                                                            double* __restrict__ m, double* __restrict__ v, long n,
+                                                            int* __restrict__ step, const double* __restrict__ part,
+                                                            double lr, double b1, double b2, double eps, double max_norm) {
+  __shared__ double sm[256];
+  const double sq = block_sum_256(threadIdx.x < kRedBlocks ? part[threadIdx.x] : 0.0, sm);
+  const double gn = sqrt(sq);
+  const double scale = (max_norm > 0.0 && !(gn < max_norm)) ? max_norm / gn : 1.0;
+  const int t = reinterpret_cast<const int*>(part + kRedBlocks)[0];
+  if (blockIdx.x == 0 && threadIdx.x == 0) step[0] = t;
+  const double c1 = 1.0 - pow(b1, (double)t), c2 = 1.0 - pow(b2, (double)t);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const double gi = g[i] * scale;
+    const double mi = b1 * m[i] + (1.0 - b1) * gi;
+    const double vi = b2 * v[i] + (1.0 - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = p[i] - lr * (mi / c1) / (sqrt(vi / c2) + eps);
+  }
+}
+
 }  // namespace irbfn
 
 using namespace irbfn;
@@ -393,6 +570,83 @@ int irbfn_adam_clip_step(float* params_dev, const float* grads_dev, float* m_dev
   if (blocks > 1024) blocks = 1024;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, s, params_dev, grads_dev, m_dev, v_dev,
+                     (long)n, step_dev, partials_dev, lr, beta1, beta2, eps, max_grad_norm);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
+
+// ---- float64 entry points: the argument rules and status codes of their float32 twins above -------------------------------
+
+int irbfn_train_seeds_oneint_f64(const double* x_dev, const double* y_pred_dev, const double* y_dev,
+                                 const double* dyn_params_host, double clip_tie, double* gy_dev, double* loss_dev,
+                                 double* partials_dev, int64_t B, int D, int O, void* stream) {
+  if (B < 0 || D < 7 || O < 2 || !dyn_params_host) return IRBFN_ERR_BAD_ARG;
+  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
+  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
+  DynParams64 dp;
+  memcpy(dp.p, dyn_params_host, sizeof(dp.p));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(seeds_oneint_f64_kernel, dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
+                     partials_dev, (long)B, D, O, dp, clip_tie);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(final_sum_f64_kernel, dim3(1), dim3(256), 0, s, partials_dev, seed_blocks(B), loss_dev);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
+
+int irbfn_train_seeds_fullint_f64(const double* x_dev, const double* y_pred_dev, const double* y_dev, double clip_tie,
+                                  double* gy_dev, double* loss_dev, double* partials_dev, int64_t B, int D, int T,
+                                  void* stream) {
+  if (B < 0 || D < 1 || T < 1) return IRBFN_ERR_BAD_ARG;
+  if (T > 64) return IRBFN_ERR_UNSUPPORTED;
+  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
+  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (T <= 8)
+    hipLaunchKernelGGL((seeds_fullint_f64_kernel<8>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
+                       partials_dev, (long)B, D, T, clip_tie);
+  else
+    hipLaunchKernelGGL((seeds_fullint_f64_kernel<64>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
+                       partials_dev, (long)B, D, T, clip_tie);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(final_sum_f64_kernel, dim3(1), dim3(256), 0, s, partials_dev, seed_blocks(B), loss_dev);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
+
+int irbfn_train_seeds_frenet_fullint_f64(const double* x_dev, const double* y_pred_dev, const double* y_dev,
+                                         const double* dyn_params_host, double clip_tie, double* gy_dev, double* loss_dev,
+                                         double* partials_dev, int64_t B, int D, int T, void* stream) {
+  if (B < 0 || D < 8 || T < 1 || T > 16 || !dyn_params_host) return IRBFN_ERR_BAD_ARG;
+  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
+  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
+  DynParams64 dp;
+  memcpy(dp.p, dyn_params_host, sizeof(dp.p));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (T <= 5)
+    hipLaunchKernelGGL((seeds_frenet_fullint_f64_kernel<5>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev,
+                       gy_dev, partials_dev, (long)B, D, T, dp, clip_tie);
+  else
+    hipLaunchKernelGGL((seeds_frenet_fullint_f64_kernel<16>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev,
+                       gy_dev, partials_dev, (long)B, D, T, dp, clip_tie);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(final_sum_f64_kernel, dim3(1), dim3(256), 0, s, partials_dev, seed_blocks(B), loss_dev);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
+
+int irbfn_adam_clip_step_f64(double* params_dev, const double* grads_dev, double* m_dev, double* v_dev, int64_t n,
+                             int* step_dev, double lr, double beta1, double beta2, double eps, double max_grad_norm,
+                             double* partials_dev, void* stream) {
+  if (n < 0 || !step_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
+  if (n > 0 && (!params_dev || !grads_dev || !m_dev || !v_dev)) return IRBFN_ERR_BAD_ARG;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(sqnorm_partial_f64_kernel, dim3(kRedBlocks), dim3(256), 0, s, grads_dev, (long)n, partials_dev, step_dev);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  long blocks = (n + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adam_clip_f64_kernel, dim3((unsigned)blocks), dim3(256), 0, s, params_dev, grads_dev, m_dev, v_dev,
                      (long)n, step_dev, partials_dev, lr, beta1, beta2, eps, max_grad_norm);
   IRBFN_HIP_CHECK(hipGetLastError());
   return IRBFN_OK;

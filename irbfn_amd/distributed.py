@@ -30,15 +30,16 @@ def default_device() -> torch.device:
     return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
 
 
-def params_to_device(params: dict, device: Optional[torch.device] = None) -> dict:
-    """numpy / torch pytree -> float32 tensors on ``device`` (same nesting as the checkpoint)."""
+def params_to_device(params: dict, device: Optional[torch.device] = None, dtype: torch.dtype = torch.float32) -> dict:
+    """numpy / torch pytree -> ``dtype`` tensors on ``device`` (same nesting as the checkpoint); float64 for the
+    float64 training state of a ``use_float64`` net."""
     device = device or default_device()
     p = params["params"] if "params" in params else params
     out = {"rbf_list": {}, "linear": {}}
     for grp, name in _LEAVES:
         a = p[grp][name]
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
-        out[grp][name] = t.to(device=device, dtype=torch.float32).contiguous()
+        out[grp][name] = t.to(device=device, dtype=dtype).contiguous()
     return {"params": out}
 
 

@@ -13,11 +13,11 @@ from . import _lib
 from .model import _ptr, _stream_ptr, like_input, to_device_f32
 
 
-def _dyn(params):
+def _dyn(params, dtype=np.float32):
     if params is None:
         return None, C.c_void_p(None)
     p = np.ascontiguousarray(np.asarray(params.detach().cpu() if hasattr(params, "detach") else params,
-                                        dtype=np.float32).reshape(-1))
+                                        dtype=dtype).reshape(-1))
     if p.size != 13:
         raise ValueError("dynamics params must have 13 entries (dynamics.py:24-36)")
     return p, p.ctypes.data_as(C.c_void_p)

@@ -116,8 +116,9 @@ class WCRBFNet:
     @classmethod
     def from_config(cls, cfg, use_float64: bool = False) -> "WCRBFNet":
         """cfg: dict, argparse.Namespace or path of a YAML model card (the file the reference writes at
-        scripts/train_nmpc.py:431-450 and reloads at src/irbfn_mpc/irbfn_planner.py:46-79).  The card does not record
-        --use_float64 (a process-wide jax flag in the reference): pass ``use_float64=True`` for that mode."""
+        scripts/train_nmpc.py:431-450 and reloads at src/irbfn_mpc/irbfn_planner.py:46-79).  The reference's card does not
+        record --use_float64 (a process-wide jax flag there): pass ``use_float64=True`` for that mode.  A card written by
+        ``config()`` of a float64 net holds ``use_float64: True`` and keeps the mode."""
         if isinstance(cfg, str):
             import yaml
             with open(cfg, "r") as f:
@@ -127,7 +128,10 @@ class WCRBFNet:
         return cls(**{k: cfg[k] for k in _CFG_FIELDS}, use_float64=use_float64 or bool(cfg.get("use_float64", False)))
 
     def config(self) -> dict:
-        return {k: getattr(self, k) for k in _CFG_FIELDS}
+        cfg = {k: getattr(self, k) for k in _CFG_FIELDS}
+        if self.use_float64:           # float32 cards stay as the reference writes them
+            cfg["use_float64"] = True
+        return cfg
 
     def init(self, seed: int = 0, dtype=np.float32) -> dict:
         """Fresh parameter pytree with the reference initialisers: centers ~ N(0,1), log_sigs = 0
@@ -349,12 +353,18 @@ class WCRBFNet:
         _lib.check(st, "irbfn_f64_forward")
         return like_input(out, x, torch)
 
-    def vjp64(self, params: dict, x, gout) -> dict:
-        """Parameter VJP in float64 (``jax.value_and_grad`` of the reference under --use_float64) -> float64 gradient pytree."""
+    F64_VJP_MAX_O = 16      # irbfn_f64_vjp's limit (include/irbfn_hip.h)
+
+    def vjp64(self, params: dict, x, gout, out: Optional[dict] = None) -> dict:
+        """Parameter VJP in float64 (``jax.value_and_grad`` of the reference under --use_float64) -> float64 gradient pytree.
+        out: caller-provided float64 gradient leaves (e.g. views of the flat buffer of a float64 ``TrainState``)."""
         torch = _lib.require_gpu()
         lib = _lib.load()
         p = _inner(params)
         self._check_shapes(p)
+        R, K, D, O = self.num_regions, self.num_kernels, self.in_features, self.out_features
+        if O > self.F64_VJP_MAX_O:
+            raise ValueError(f"the float64 VJP supports out_features <= {self.F64_VJP_MAX_O}, this net has {O}")
         ent = self._f64_card(torch)
         card = ent[0]
         c, l, k = (self._dev_f64(a, torch) for a in (p["rbf_list"]["centers"], p["rbf_list"]["log_sigs"], p["linear"]["kernel"]))
@@ -362,17 +372,23 @@ class WCRBFNet:
         B = xd.shape[0]
         if tuple(gd.shape) != (B, self.out_features):
             raise ValueError(f"gout must have shape ({B}, {self.out_features}), got {tuple(gd.shape)}")
-        R, K, D, O = self.num_regions, self.num_kernels, self.in_features, self.out_features
-        gc = torch.empty((R, K, D), dtype=torch.float64, device=xd.device)
-        gl = torch.empty((R, K), dtype=torch.float64, device=xd.device)
-        gk = torch.empty((K, O), dtype=torch.float64, device=xd.device)
-        gb = torch.empty((O,), dtype=torch.float64, device=xd.device)
+        if out is not None:
+            o = _inner(out)
+            gc, gl, gk, gb = o["rbf_list"]["centers"], o["rbf_list"]["log_sigs"], o["linear"]["kernel"], o["linear"]["bias"]
+            for t, shp in ((gc, (R, K, D)), (gl, (R, K)), (gk, (K, O)), (gb, (O,))):
+                if tuple(t.shape) != shp or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+                    raise ValueError("vjp64 out= leaves must be contiguous float64 cuda tensors of the parameter shapes")
+        else:
+            gc = torch.empty((R, K, D), dtype=torch.float64, device=xd.device)
+            gl = torch.empty((R, K), dtype=torch.float64, device=xd.device)
+            gk = torch.empty((K, O), dtype=torch.float64, device=xd.device)
+            gb = torch.empty((O,), dtype=torch.float64, device=xd.device)
         nbytes = int(lib.irbfn_f64_workspace_bytes(C.byref(card), B, 1))
         ws = self._f64_ws(torch, ent, nbytes)
         st = lib.irbfn_f64_vjp(C.byref(card), _ptr(c), _ptr(l), _ptr(k), _ptr(xd), _ptr(gd), _ptr(gc), _ptr(gl), _ptr(gk), _ptr(gb),
                                B, _ptr(ws), nbytes, _stream_ptr(torch))
         _lib.check(st, "irbfn_f64_vjp")
-        conv = lambda t: like_input(t, x, torch)
+        conv = (lambda t: t) if out is not None else (lambda t: like_input(t, x, torch))
         return {"params": {"rbf_list": {"centers": conv(gc), "log_sigs": conv(gl)}, "linear": {"kernel": conv(gk), "bias": conv(gb)}}}
 
     def gate(self, x):
@@ -395,6 +411,8 @@ class WCRBFNet:
         if self.use_float64 and out is None:
             return self.vjp64(params, x, gout)
         torch = _lib.require_gpu()
+        if out is not None and _inner(out)["rbf_list"]["centers"].dtype == torch.float64:
+            return self.vjp64(params, x, gout, out=out)      # float64 leaves: the float64 VJP writes into them
         lib = _lib.load()
         self._warn_if_float64(params)
         self.bind(params)
@@ -448,7 +466,9 @@ class DeeperWCRBFNet:
     HIDDEN = 64          # model.py:254-255
 
     def __init__(self, in_features, out_features, num_kernels, basis_func, num_regions, lower_bounds,
-                 upper_bounds, dimension_ranges, activation_idx, delta, **_unused):
+                 upper_bounds, dimension_ranges, activation_idx, delta, use_float64: bool = False, **_unused):
+        if use_float64:
+            raise ValueError("DeeperWCRBFNet has no float64 mode (its MLP head runs in float32); build it with use_float64=False")
         self.out_features = int(out_features)
         self.in_features = int(in_features)
         self.stage = WCRBFNet(in_features=in_features, out_features=self.HIDDEN, num_kernels=num_kernels,
@@ -466,7 +486,7 @@ class DeeperWCRBFNet:
                 cfg = yaml.safe_load(f)
         elif not isinstance(cfg, dict):
             cfg = vars(cfg)
-        return cls(**{k: cfg[k] for k in _CFG_FIELDS})
+        return cls(**{k: cfg[k] for k in _CFG_FIELDS}, use_float64=bool(cfg.get("use_float64", False)))
 
     def apply(self, params: dict, x):
         torch = _lib.require_gpu()
@@ -533,7 +553,9 @@ class ClusterWCRBFNet:
     ``train_step_fullint_withcluster`` differentiates, scripts/train_nmpc_frenet.py:424-453).  No trained checkpoint
     of this variant survives in the reference (.MISSING_LARGE_BLOBS) -> parity against the oracle restatement only."""
 
-    def __init__(self, in_features, out_features, num_kernels, basis_func, num_regions, **_unused):
+    def __init__(self, in_features, out_features, num_kernels, basis_func, num_regions, use_float64: bool = False, **_unused):
+        if use_float64:
+            raise ValueError("ClusterWCRBFNet has no float64 mode (its softmax gate runs in float32); build it with use_float64=False")
         self.in_features, self.out_features = int(in_features), int(out_features)
         self.num_regions = int(num_regions)
         self._gate_ws = {}

@@ -118,12 +118,15 @@ class DeviceTable:
     (train_nmpc.py:456-467 does both on the host).  288 GB of HBM holds any table the reference names
     (the largest, 8x19x19x64x8x6x12 rows x 17 floats, is 7 GB)."""
 
-    def __init__(self, flat_inputs, flat_outputs, device=None, seed: int = 0):
+    def __init__(self, flat_inputs, flat_outputs, device=None, seed: int = 0, dtype=np.float32):
+        """dtype: of the resident rows (NumPy or torch dtype); float64 for the float64 training state of a
+        ``use_float64`` net, whose steps would otherwise cast every batch."""
         from . import _lib
         torch = _lib.require_gpu()
         dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.x = torch.as_tensor(np.ascontiguousarray(flat_inputs, dtype=np.float32)).to(dev)
-        self.y = torch.as_tensor(np.ascontiguousarray(flat_outputs, dtype=np.float32)).to(dev)
+        npd = torch.empty(0, dtype=dtype).numpy().dtype if isinstance(dtype, torch.dtype) else np.dtype(dtype)
+        self.x = torch.as_tensor(np.ascontiguousarray(flat_inputs, dtype=npd)).to(dev)
+        self.y = torch.as_tensor(np.ascontiguousarray(flat_outputs, dtype=npd)).to(dev)
         if self.x.shape[0] != self.y.shape[0]:
             raise ValueError("inputs and outputs differ in row count")
         self.gen = torch.Generator(device=dev)

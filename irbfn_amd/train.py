@@ -7,6 +7,10 @@ gradient buffer when torch.distributed is initialised] -> clip + Adam kernel.  P
 moments and gradients live in ONE flat float32 buffer each (the pytree leaves are views), the step
 count and the loss stay on the device: no host synchronisation per step (the reference does a
 ``jax.device_get`` per step, scripts/train_nmpc.py:477-479).
+
+A ``WCRBFNet(use_float64=True)`` trains in float64, as the reference under --use_float64
+(scripts/train_nmpc.py:41-42): float64 flat buffers, the float64 forward / VJP and the ``*_f64`` seed and
+clip + Adam kernels.
 """
 from __future__ import annotations
 
@@ -33,11 +37,11 @@ class TrainState:
         # gradients + two trailing slots (loss * B_local, B_local) so that ONE all-reduce yields the global-batch
         # mean gradient and loss whatever the shard sizes are (distributed.shard_range hands out sizes that
         # differ by one row)
-        self.gbuf = torch.zeros(flat.numel() + 2, dtype=torch.float32, device=flat.device)
+        self.gbuf = torch.zeros(flat.numel() + 2, dtype=flat.dtype, device=flat.device)
         self.g = self.gbuf[:flat.numel()]
         self.step = torch.zeros(1, dtype=torch.int32, device=flat.device)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=flat.device)
-        self.partials = torch.zeros(_lib.load().irbfn_train_loss_partials(), dtype=torch.float32, device=flat.device)
+        self.loss = torch.zeros(1, dtype=flat.dtype, device=flat.device)
+        self.partials = torch.zeros(_lib.load().irbfn_train_loss_partials(), dtype=flat.dtype, device=flat.device)
         self.lr, self.max_grad_norm, self.b1, self.b2, self.eps = float(lr), float(max_grad_norm), float(b1), float(b2), float(eps)
         self.params = distributed.unflatten_params(net, self.flat)
         self.grads = distributed.unflatten_params(net, self.g)
@@ -46,16 +50,20 @@ class TrainState:
     @classmethod
     def create(cls, net: WCRBFNet, params: dict, lr: float = 1e-3, max_grad_norm: float = 1.0,
                b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8, opt_state=None) -> "TrainState":
-        """opt_state: (mu pytree, nu pytree, count) to resume (``checkpoint.restore_opt_state``)."""
-        _lib.require_gpu()
-        flat = distributed.flatten_params(distributed.params_to_device(params)).clone()
+        """opt_state: (mu pytree, nu pytree, count) to resume (``checkpoint.restore_opt_state``).  A ``use_float64`` net
+        gets a float64 state: parameters, moments, gradient, loss and partials in float64."""
+        torch = _lib.require_gpu()
+        dtype = torch.float64 if getattr(net, "use_float64", False) else torch.float32
+        flat = distributed.flatten_params(distributed.params_to_device(params, dtype=dtype)).clone()
         st = cls(net, flat, lr, max_grad_norm, b1, b2, eps)
-        # a training loop re-binds the parameters every step: the matrix-core kernels' "do the parameters fit" verdict is read back
-        # for the first bind only (the kernels test the device-side verdict themselves; include/irbfn_hip.h, IRBFN_OPT_GRAM_STICKY)
-        net.set_options(gram_sticky=1)
+        if dtype == torch.float32:
+            # a training loop re-binds the parameters every step: the matrix-core kernels' "do the parameters fit" verdict is read
+            # back for the first bind only (the kernels test the device-side verdict themselves; include/irbfn_hip.h,
+            # IRBFN_OPT_GRAM_STICKY).  The float64 mode binds no float32 descriptor.
+            net.set_options(gram_sticky=1)
         if opt_state is not None:
-            st.m.copy_(distributed.flatten_params(distributed.params_to_device(opt_state[0])))
-            st.v.copy_(distributed.flatten_params(distributed.params_to_device(opt_state[1])))
+            st.m.copy_(distributed.flatten_params(distributed.params_to_device(opt_state[0], dtype=dtype)))
+            st.v.copy_(distributed.flatten_params(distributed.params_to_device(opt_state[1], dtype=dtype)))
             st.step.fill_(int(opt_state[2]))
         return st
 
@@ -93,6 +101,8 @@ class ClusterTrainState(TrainState):
                b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8, opt_state=None) -> "ClusterTrainState":
         """opt_state: (mu pytree, nu pytree, count) with the six leaves, to resume (``checkpoint.restore_opt_state``)."""
         torch = _lib.require_gpu()
+        if getattr(net, "use_float64", False) or getattr(getattr(net, "stage", None), "use_float64", False):
+            raise ValueError("ClusterTrainState has no float64 mode: ClusterWCRBFNet runs in float32")
 
         def flat6(tree):
             p = tree["params"] if "params" in tree else tree
@@ -108,6 +118,17 @@ class ClusterTrainState(TrainState):
 
     def opt_state(self):
         return self._views(self.m), self._views(self.v), int(self.step.item())
+
+
+def _is_f64(state: TrainState, torch) -> bool:
+    return state.flat.dtype == torch.float64
+
+
+def _step_inputs(state: TrainState, x, y, torch):
+    """x, y as contiguous device tensors of the state's dtype."""
+    if _is_f64(state, torch):
+        return WCRBFNet._dev_f64(x, torch), WCRBFNet._dev_f64(y, torch)
+    return to_device_f32(x, torch), to_device_f32(y, torch)
 
 
 def _fresh_loss(state: TrainState, torch):
@@ -130,10 +151,10 @@ def _backward_and_update(state: TrainState, x, gy, torch, lib, **vjp_kw):
         torch.distributed.all_reduce(state.gbuf, op=torch.distributed.ReduceOp.SUM)
         state.g.div_(state.gbuf[n + 1])
         loss = (state.gbuf[n:n + 1] / state.gbuf[n + 1]).clone()
-    st = lib.irbfn_adam_clip_step(_ptr(state.flat), _ptr(state.g), _ptr(state.m), _ptr(state.v), state.flat.numel(),
-                                  _ptr(state.step), state.lr, state.b1, state.b2, state.eps, state.max_grad_norm,
-                                  _ptr(state.partials), _stream_ptr(torch))
-    _lib.check(st, "irbfn_adam_clip_step")
+    adam = lib.irbfn_adam_clip_step_f64 if _is_f64(state, torch) else lib.irbfn_adam_clip_step
+    st = adam(_ptr(state.flat), _ptr(state.g), _ptr(state.m), _ptr(state.v), state.flat.numel(), _ptr(state.step), state.lr,
+              state.b1, state.b2, state.eps, state.max_grad_norm, _ptr(state.partials), _stream_ptr(torch))
+    _lib.check(st, adam.__name__)
     # the parameter leaves were updated in place behind torch's back: re-bind on the next apply
     getattr(state.net, "stage", state.net)._bound_fp.pop(torch.cuda.current_device(), None)
     return loss
@@ -143,17 +164,19 @@ def train_step_oneint(state: TrainState, x, y, dyn_params, clip_tie: float = 0.5
     """scripts/train_nmpc.py:258-300.  x [B,7], y [B,O>=2] device tensors -> (state, loss[1] on device)."""
     torch = _lib.require_gpu()
     lib = _lib.load()
-    xd, yd = to_device_f32(x, torch), to_device_f32(y, torch)
+    f64 = _is_f64(state, torch)
+    xd, yd = _step_inputs(state, x, y, torch)
     B, O = yd.shape
     if xd.shape[1] < 7 or O != state.net.out_features or O < 2:
         raise ValueError("train_step_oneint needs x [B,7] and y [B,out_features >= 2]")
     y_pred = state.net.apply(state.params, xd)
     gy = torch.empty_like(y_pred)
-    keep, pp = _dyn(dyn_params)
+    keep, pp = _dyn(dyn_params, np.float64 if f64 else np.float32)
     _fresh_loss(state, torch)
-    st = lib.irbfn_train_seeds_oneint(_ptr(xd), _ptr(y_pred), _ptr(yd), pp, float(clip_tie), _ptr(gy), _ptr(state.loss),
-                                      _ptr(state.partials), B, xd.shape[1], O, _stream_ptr(torch))
-    _lib.check(st, "irbfn_train_seeds_oneint")
+    seeds = lib.irbfn_train_seeds_oneint_f64 if f64 else lib.irbfn_train_seeds_oneint
+    st = seeds(_ptr(xd), _ptr(y_pred), _ptr(yd), pp, float(clip_tie), _ptr(gy), _ptr(state.loss), _ptr(state.partials), B,
+               xd.shape[1], O, _stream_ptr(torch))
+    _lib.check(st, seeds.__name__)
     return state, _backward_and_update(state, xd, gy, torch, lib)
 
 
@@ -161,16 +184,17 @@ def train_step_fullint(state: TrainState, x, y, clip_tie: float = 0.5) -> Tuple[
     """scripts/train_nmpc.py:303-421.  x [B,D], y [B,2T] -> (state, loss[1] on device)."""
     torch = _lib.require_gpu()
     lib = _lib.load()
-    xd, yd = to_device_f32(x, torch), to_device_f32(y, torch)
+    xd, yd = _step_inputs(state, x, y, torch)
     B, O = yd.shape
     if O != state.net.out_features or O % 2:
         raise ValueError("train_step_fullint needs y [B, out_features = 2T]")
     y_pred = state.net.apply(state.params, xd)
     gy = torch.empty_like(y_pred)
     _fresh_loss(state, torch)
-    st = lib.irbfn_train_seeds_fullint(_ptr(xd), _ptr(y_pred), _ptr(yd), float(clip_tie), _ptr(gy), _ptr(state.loss),
-                                       _ptr(state.partials), B, xd.shape[1], O // 2, _stream_ptr(torch))
-    _lib.check(st, "irbfn_train_seeds_fullint")
+    seeds = lib.irbfn_train_seeds_fullint_f64 if _is_f64(state, torch) else lib.irbfn_train_seeds_fullint
+    st = seeds(_ptr(xd), _ptr(y_pred), _ptr(yd), float(clip_tie), _ptr(gy), _ptr(state.loss), _ptr(state.partials), B,
+               xd.shape[1], O // 2, _stream_ptr(torch))
+    _lib.check(st, seeds.__name__)
     return state, _backward_and_update(state, xd, gy, torch, lib)
 
 
@@ -180,17 +204,19 @@ def train_step_frenet_fullint(state: TrainState, x, y, dyn_params, clip_tie: flo
     ``integrate_frenet_mult`` on device (the adjoint of the low-speed Frenet model)."""
     torch = _lib.require_gpu()
     lib = _lib.load()
-    xd, yd = to_device_f32(x, torch), to_device_f32(y, torch)
+    f64 = _is_f64(state, torch)
+    xd, yd = _step_inputs(state, x, y, torch)
     B, O = yd.shape
     if xd.shape[1] != 8 or O != state.net.out_features or O % 2 or O // 2 > 16:
         raise ValueError("train_step_frenet_fullint needs x [B,8] and y [B, out_features = 2T], T <= 16")
     y_pred = state.net.apply(state.params, xd)
     gy = torch.empty_like(y_pred)
-    keep, pp = _dyn(dyn_params)
+    keep, pp = _dyn(dyn_params, np.float64 if f64 else np.float32)
     _fresh_loss(state, torch)
-    st = lib.irbfn_train_seeds_frenet_fullint(_ptr(xd), _ptr(y_pred), _ptr(yd), pp, float(clip_tie), _ptr(gy),
-                                              _ptr(state.loss), _ptr(state.partials), B, 8, O // 2, _stream_ptr(torch))
-    _lib.check(st, "irbfn_train_seeds_frenet_fullint")
+    seeds = lib.irbfn_train_seeds_frenet_fullint_f64 if f64 else lib.irbfn_train_seeds_frenet_fullint
+    st = seeds(_ptr(xd), _ptr(y_pred), _ptr(yd), pp, float(clip_tie), _ptr(gy), _ptr(state.loss), _ptr(state.partials), B, 8,
+               O // 2, _stream_ptr(torch))
+    _lib.check(st, seeds.__name__)
     return state, _backward_and_update(state, xd, gy, torch, lib)
 
 
@@ -231,4 +257,4 @@ def train_epoch(state: TrainState, table, batch_size: int, only_onestep: bool = 
         else:
             state, loss = train_step_fullint(state, bx, by)
         losses.append(loss)
-    return state, (torch.cat(losses) if losses else torch.zeros(0, device=state.flat.device))
+    return state, (torch.cat(losses) if losses else torch.zeros(0, dtype=state.loss.dtype, device=state.flat.device))
