@@ -245,7 +245,7 @@ __device__ __forceinline__ void spiral_coefs(const float (&q)[5], float (&c)[4])
 // <= 1 ulp).  Results move by a few ulp against the float32 restatement; the tests hold them to 1e-5 of the float64 one.
 __device__ __forceinline__ void spiral_step(float (&st)[6], const float (&c)[4], float s, int i, int N, float (&sc)[2]) {
 #pragma clang fp contract(off)   // same mul/add sequence in every kernel that inlines this (fused == stand-alone)
-  const float sk = (i < N - 1) ? s * fdiv_fast((float)i, (float)(N - 1)) : s;   // jnp.linspace(0, s, N) :71
+  const float sk = (i < N - 1) ? s * fdiv_fast((float)i, (float)(N - 1)) : (i > 0 ? s : 0.0f);   // jnp.linspace(0, s, N) :71 (N = 1: [0])
   const float k = (float)(i + 1);                                          // :72
   const float rk = fdiv_fast(1.0f, k);
   const float rj[4] = {1.0f, 0.5f, 1.0f / 3.0f, 0.25f};

@@ -145,8 +145,8 @@ __global__ __launch_bounds__(64) void rollout_vjp_spiral_staged(const RollVjpArg
     for (int tt = G - 1; tt >= 0; --tt) {
       if (tt < n) {
         const int i = i0 + tt;
-        const float tau = (i < N - 1) ? fdiv_fast((float)i, (float)(N - 1)) : 1.0f;    // as spiral_step
-        const float sk = (i < N - 1) ? slen * tau : slen;
+        const float tau = (i < N - 1) ? fdiv_fast((float)i, (float)(N - 1)) : (i > 0 ? 1.0f : 0.0f);    // as spiral_step
+        const float sk = (i < N - 1) ? slen * tau : (i > 0 ? slen : 0.0f);
         const float k = (float)(i + 1);
         const float rk = fdiv_fast(1.0f, k);
         const float dx = pdx[tt], dy = pdy[tt];

@@ -121,7 +121,7 @@ def vjp_spiral(q, gs, N=9):
     gc = np.zeros((B, 4))
     g_s, ldx, ldy, lth = np.zeros(B), np.zeros(B), np.zeros(B), np.zeros(B)
     for i in range(N - 1, -1, -1):
-        tau = i / (N - 1) if i < N - 1 else 1.0
+        tau = i / (N - 1) if i < N - 1 else float(i > 0)      # N = 1: the only sample sits at 0
         sk, k = s * tau, float(i + 1)
         thi = th[:, i]
         thp = th[:, i - 1] if i > 0 else np.zeros(B)

@@ -610,8 +610,8 @@ def integrate_path_mult(params, N: int = SPIRAL_N):
     st = [zero, zero, zero, coefs[:, 0], zero, zero]  # :67-70
     out = []
     for i in range(N):
-        # jnp.linspace(0, s, N)[i] = 0*(1-t) + s*t, t = i/(N-1); endpoint exact.  (:71)
-        sk = s * xp.const(i / (N - 1), params) if i < N - 1 else s
+        # jnp.linspace(0, s, N)[i] = 0*(1-t) + s*t, t = i/(N-1); endpoint exact; N = 1 gives [0].  (:71)
+        sk = s * xp.const(i / (N - 1), params) if i < N - 1 else (s if i > 0 else xp.zeros_like(s))
         k = float(i + 1)                              # :72
         kappa_k, theta_k = get_curvature_theta(coefs, sk)     # :46
         dx = st[4] * (1 - 1 / k) + (xp.cos(theta_k) + xp.cos(st[2])) / 2 / k   # :47-50

@@ -305,7 +305,7 @@ void FN(oracle_integrate_path_mult)(const REAL* params, long B, int N, REAL* sta
     coefs[3] = coefs[3] / (s * s * s);
     REAL st[6] = {0, 0, 0, coefs[0], 0, 0};
     for (int i = 0; i < N; ++i) {
-      REAL sk = (i < N - 1) ? s * (REAL)((double)i / (double)(N - 1)) : s;
+      REAL sk = (i < N - 1) ? s * (REAL)((double)i / (double)(N - 1)) : (i > 0 ? s : (REAL)0);   /* linspace(0, s, 1) = [0] */
       REAL k = (REAL)(i + 1);
       REAL kap = 0, th = 0, pw = 1;
       for (int j = 0; j < 4; ++j) {

@@ -12,7 +12,7 @@ from irbfn_amd.model import WCRBFNet
 from irbfn_amd.planner import plan_batch
 from oracle import c_oracle as co
 from oracle import irbfn_oracle as orc
-from test_gpu_parity import assert_states_close
+from _rollout_util import assert_states_close
 
 import os
 

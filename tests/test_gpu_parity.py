@@ -11,6 +11,9 @@ also required not to exceed the error of a plain float32 CPU evaluation by more 
 import numpy as np
 import pytest
 
+from _rollout_util import assert_states_close
+from _rollout_util import frenet_inputs as _frenet_inputs
+from _rollout_util import st_inputs as _st_inputs
 from conftest import CKPT_RUNS, load_ckpt_fixture, load_deeper_fixture
 from irbfn_amd import _lib, configs
 from irbfn_amd import dynamics as dyn
@@ -27,24 +30,6 @@ DP = np.array(configs.DYN_PARAMS)
 
 def relmax(a, b):
     return float(np.abs(np.asarray(a, np.float64) - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-def assert_states_close(got, ref, ref32=None, rtol=RTOL):
-    """Trajectory states against the float64 oracle.  Pass if |err| <= rtol * (|ref| + scale), scale =
-    max |ref| of that state component along the trajectory -- or, where float32 integration itself is
-    worse conditioned than that (T = 50 steps; the dynamic single-track RHS has a prefactor
-    mu*m/(I*L) = 67 and 1/V terms), if the error is within 4x the error the float32 NumPy restatement
-    of the reference makes on the same trajectory component (the reference itself runs in float32)."""
-    got = np.asarray(got, np.float64)
-    assert got.shape == ref.shape
-    scale = np.maximum(np.abs(ref).max(axis=1, keepdims=True), 1e-3)
-    err = np.abs(got - ref)
-    bound = rtol * (np.abs(ref) + scale)
-    if ref32 is not None:
-        e32 = np.abs(np.asarray(ref32, np.float64) - ref).max(axis=1, keepdims=True)
-        bound = np.maximum(bound, 4.0 * e32 + 1e-7 * scale)
-    bad = err > bound
-    assert not bad.any(), (int(bad.sum()), float(err.max()), float((err / (np.abs(ref) + scale)).max()))
 
 
 F32 = np.float32
@@ -267,22 +252,6 @@ def test_kat1_on_gpu(gpu, kat):
     exp = np.array(k["all_states_row"], np.float32)
     assert got.shape == (10, 5, 7)
     np.testing.assert_allclose(got, np.broadcast_to(exp, got.shape), rtol=1e-6, atol=1e-7)
-
-
-def _st_inputs(B, T, seed, fast=True):
-    rng = np.random.default_rng(seed)
-    st = rng.normal(size=(B, 7)) * [2, 2, .3, 1, 1, .4, .1]
-    st[:, 3] = rng.uniform(0.2, 7.5, B) if fast else rng.uniform(0.0, 2.9, B)
-    u = np.hstack([rng.normal(size=(B, T)) * 5.0, rng.normal(size=(B, T)) * 2.0])
-    return np.hstack([st, u])
-
-
-def _frenet_inputs(B, T, rng):
-    """[s, ey, delta, vx, vy, wz, epsi, cur] + controls; curvature / offsets kept in the range of a
-    race track (|ey*cur| << 1) so that 1/(1 - ey*cur) (dynamics.py:268) stays away from its pole over T steps."""
-    st = rng.normal(size=(B, 8)) * [1, .2, .2, 1, .1, .1, .15, .08] + [0, 0, 0, 4, 0, 0, 0, 0]
-    amp = 1.0 if T <= 10 else 0.25
-    return np.hstack([st, rng.normal(size=(B, T)) * 5 * amp, rng.normal(size=(B, T)) * 2 * amp])
 
 
 @pytest.mark.parametrize("T", [1, 5, 50])
