@@ -162,6 +162,17 @@ int irbfn_net_vjp(irbfn_net* net, const float* x_dev, const float* gout_dev, flo
                   float* g_log_sigs_dev, float* g_kernel_dev, float* g_bias_dev, int64_t B,
                   void* workspace_dev, int64_t workspace_bytes, void* stream);
 
+/* irbfn_net_vjp for the layer classes with frozen leaves (the reference's fixed-centre and fixed-width RBF layers,
+ * src/irbfn_mpc/model.py:131-140): a NULL g_centers_dev / g_log_sigs_dev is a frozen leaf, neither computed nor
+ * written.  Centres NULL runs K2g's no-centres instance, both NULL its Dense-only instance (named
+ * "rbf_vjp_f16gram/no_centres<...>" / "rbf_vjp_f16gram/linear<...>" by irbfn_net_last_launch); live centres with
+ * NULL widths take the full computation and skip the write.  Every other VJP kernel computes what irbfn_net_vjp
+ * computes and writes the live leaves only.  g_kernel_dev and g_bias_dev must be non-NULL; B = 0 zeroes the live
+ * leaves.  irbfn_net_vjp_workspace_bytes(net, B) is a sufficient workspace. */
+int irbfn_net_vjp_frozen(irbfn_net* net, const float* x_dev, const float* gout_dev, float* g_centers_dev,
+                         float* g_log_sigs_dev, float* g_kernel_dev, float* g_bias_dev, int64_t B,
+                         void* workspace_dev, int64_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Roll-outs.  Replace integrate_st_mult (dynamics.py:94-100), dynamic_st_onestep_aux (:103-187),
  * integrate_frenet_mult (:284-290), the inline bicycle of train_step_fullint

@@ -35,6 +35,7 @@ SIGNATURES = {
     "irbfn_net_gate": (_i, [_vp, _fp, _fp, _i64, _vp]),
     "irbfn_net_vjp_workspace_bytes": (_i64, [_vp, _i64]),
     "irbfn_net_vjp": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _vp, _i64, _vp]),
+    "irbfn_net_vjp_frozen": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _vp, _i64, _vp]),
     "irbfn_rollout_state_dim": (_i, [_i]),
     "irbfn_rollout_input_dim": (_i, [_i, _i]),
     "irbfn_rollout_forward": (_i, [_i, _fp, _fp, _fp, _i64, _i, _vp]),

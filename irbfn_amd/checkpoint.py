@@ -82,11 +82,14 @@ def restore_checkpoint(ckpt: str) -> Tuple[dict, int]:
             raise FileNotFoundError(f"no checkpoint_<n> file in {ckpt}")
     tree = load_flax_msgpack(path)
     p = tree["params"]["params"] if "params" in tree["params"] else tree["params"]
-    if "rbf_list" not in p or "linear" not in p or "centers" not in p["rbf_list"]:
+    # a fixed-centre net's tree holds rbf_list.log_sigs alone, a fixed-width net's no rbf_list (model.WCRBFNet: frozen leaves)
+    rbf = p.get("rbf_list")
+    if "linear" not in p or (rbf is None and set(p) != {"linear"}) or (rbf is not None and "log_sigs" not in rbf):
         raise ValueError(f"{path} does not hold a WCRBFNet / DeeperWCRBFNet / ClusterWCRBFNet parameter tree "
                          f"(found {sorted(p)}): the MLP baseline is out of scope")
-    params = {"params": {
-        "rbf_list": {"centers": np.asarray(p["rbf_list"]["centers"]), "log_sigs": np.asarray(p["rbf_list"]["log_sigs"])}}}
+    params = {"params": {}}
+    if rbf is not None:
+        params["params"]["rbf_list"] = {n: np.asarray(rbf[n]) for n in ("centers", "log_sigs") if n in rbf}
     # WCRBFNet holds `linear`; DeeperWCRBFNet adds `linear_pre1`, `linear_pre2` (model.py:254-256); ClusterWCRBFNet
     # adds the gate's Dense `cluster` (model.py:341-414)
     for name in _DENSE_GROUPS:
@@ -106,7 +109,9 @@ def _host_tree(params: dict) -> dict:
 
     def host(a):
         return np.asarray(a.detach().cpu() if hasattr(a, "detach") else a)
-    inner = {"rbf_list": {"centers": host(p["rbf_list"]["centers"]), "log_sigs": host(p["rbf_list"]["log_sigs"])}}
+    inner = {}
+    if "rbf_list" in p:              # a fixed-centre net: log_sigs alone; a fixed-width net: no rbf_list
+        inner["rbf_list"] = {n: host(p["rbf_list"][n]) for n in ("centers", "log_sigs") if n in p["rbf_list"]}
     for name in _DENSE_GROUPS:
         if name in p:
             inner[name] = {"kernel": host(p[name]["kernel"]), "bias": host(p[name]["bias"])}

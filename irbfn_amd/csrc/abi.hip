@@ -211,6 +211,18 @@ int irbfn_net_vjp(irbfn_net* net, const float* x_dev, const float* gout_dev, flo
                     workspace_dev, workspace_bytes, as_stream(stream));
 }
 
+int irbfn_net_vjp_frozen(irbfn_net* net, const float* x_dev, const float* gout_dev, float* g_centers_dev,
+                         float* g_log_sigs_dev, float* g_kernel_dev, float* g_bias_dev, int64_t B,
+                         void* workspace_dev, int64_t workspace_bytes, void* stream) {
+  if (!net || B < 0 || !g_kernel_dev || !g_bias_dev) return IRBFN_ERR_BAD_ARG;
+  if (B > 0 && (!x_dev || !gout_dev)) return IRBFN_ERR_BAD_ARG;
+  if (!net->has_params) return IRBFN_ERR_NO_PARAMS;
+  if (workspace_bytes < vjp_workspace_bytes(net, B) || (!workspace_dev && vjp_workspace_bytes(net, B) > 0))
+    return IRBFN_ERR_BAD_ARG;
+  return launch_vjp_frozen(net, x_dev, gout_dev, g_centers_dev, g_log_sigs_dev, g_kernel_dev, g_bias_dev, B, workspace_dev,
+                           workspace_bytes, as_stream(stream));
+}
+
 int irbfn_net_vjp_gamma(irbfn_net* net, const float* x_dev, const float* gamma_dev, const float* gout_dev,
                         float* g_centers_dev, float* g_log_sigs_dev, float* g_kernel_dev, float* g_bias_dev, float* dgamma_dev,
                         int64_t B, void* workspace_dev, int64_t workspace_bytes, void* stream) {

@@ -210,6 +210,9 @@ int64_t vjp_workspace_bytes(const irbfn_net* net, int64_t B);
 int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs,
                float* g_kernel, float* g_bias, int64_t B, void* ws, int64_t ws_bytes, hipStream_t s,
                const float* gamma_ext = nullptr);
+// irbfn_net_vjp_frozen: a null g_centers / g_log_sigs is a frozen leaf, neither computed (where K2g takes the net) nor written
+int launch_vjp_frozen(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs, float* g_kernel,
+                      float* g_bias, int64_t B, void* ws, int64_t ws_bytes, hipStream_t s);
 int launch_dgamma(irbfn_net* net, const float* x, const float* gout, float* dgamma, int64_t B, hipStream_t s);
 int64_t cluster_gate_vjp_workspace_bytes(int D, int R);
 int launch_cluster_gate_vjp(const float* x, const float* gamma, const float* dgamma, const float* glogits, float* dlogits,

@@ -479,7 +479,9 @@ void record_launch(irbfn_net* net, const LaunchPlan& p) {
     case LK_TICK_K1H: snprintf(n, len, "rbf_tick_f16mfma<D=%d,BC=%d,MODE=%d,S=%d,QG=%d>", D, BC, p.mode, p.S, p.QG); break;
     case LK_TICK_K1G_WIDE: snprintf(n, len, "rbf_tick_f16gram_wide<D=7,BC=%d,NT=7,MODE=%d,SW=%d,QG=%d>", BC, p.mode, p.S, p.QG); break;
     case LK_TICK_K1H_WIDE: snprintf(n, len, "rbf_tick_f16mfma_wide<D=7,BC=%d,NT=7,MODE=%d,SW=%d,QG=%d>", BC, p.mode, p.S, p.QG); break;
-    case LK_K2G: snprintf(n, len, "rbf_vjp_f16gram<D=%d,BC=%d,QSB=%d>", D, BC, p.S); break;
+    case LK_K2G:                 // mode: K2g's live leaves (irbfn_net_vjp_frozen) -- 1 no centres, 2 the Dense leaves only
+      snprintf(n, len, "rbf_vjp_f16gram%s<D=%d,BC=%d,QSB=%d>", p.mode == 1 ? "/no_centres" : (p.mode == 2 ? "/linear" : ""), D, BC, p.S);
+      break;
     default: return;
   }
   net->last_grid = p.grid;

@@ -284,12 +284,66 @@ __global__ __launch_bounds__(64) void vjp_reduce_regions_kernel(const float* __r
   if (lane == 0) g_kernel[(size_t)k * O + o] = s;
 }
 
+// vjp_reduce_kernel for irbfn_net_vjp_frozen; a null g_centers / g_log_sigs is not written.  The slabs hold the rows of K2g's
+// live-leaf mode `mode` (rbf_vjp_gram.hip, VgMode: [d centers (0)] [d log_sigs (0, 1)] d kernel) -- full rows (mode 0) where
+// another kernel wrote them, and where K2g handed this call to K2h: the flag holds `gen` then (K2g returned at once).  V: the
+// full row count, the grid's bias row.  The sums run in the order of vjp_reduce_kernel, whose code the all-live path keeps.
+__global__ __launch_bounds__(256) void vjp_reduce_live_kernel(float* __restrict__ part, float* __restrict__ g_centers,
+                                                              float* __restrict__ g_log_sigs, float* __restrict__ g_kernel, int QSB,
+                                                              int V, int mode, const int* __restrict__ flag, int gen, int Npad, int N,
+                                                              int R, int D, int DC, int O, int OP, const float* __restrict__ bpart,
+                                                              float* __restrict__ g_bias, int bias_blocks) {
+  __shared__ float sm[4][kWave];
+  const int l = threadIdx.x & (kWave - 1), sg = threadIdx.x >> 6;
+  if (blockIdx.y == (unsigned)V) {
+    const int o = blockIdx.x, t = threadIdx.x;
+    if (o >= O || bpart == nullptr) return;
+    float* sb = &sm[0][0];
+    float sacc = 0.0f;
+    for (int b = t; b < bias_blocks; b += 256) sacc += bpart[(size_t)b * O + o];
+    sb[t] = sacc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {             // fixed tree -> deterministic
+      if (t < w) sb[t] += sb[t + w];
+      __syncthreads();
+    }
+    if (t == 0) g_bias[o] = sb[0];
+    return;
+  }
+  const int v = blockIdx.y, n = blockIdx.x * kWave + l;
+  const int m = (flag != nullptr && *flag == gen) ? 0 : mode;
+  const int crows = m == 0 ? DC : 0, lrow = m == 0 ? DC : (m == 1 ? 0 : -1), kb = m == 0 ? DC + 1 : (m == 1 ? 1 : 0);
+  const int Vs = kb + OP;                                    // slab stride of this layout
+  const bool want = v < crows ? (v < D && g_centers != nullptr) : (v == lrow ? g_log_sigs != nullptr : (v >= kb && v < kb + O));
+  if (!want) return;                                        // frozen leaf / padded slot (whole block)
+  float s = 0.0f;
+  if (n < N)
+    for (int q = sg; q < QSB; q += 4) s += part[((size_t)q * Vs + v) * Npad + n];
+  sm[sg][l] = s;
+  __syncthreads();
+  if (sg != 0 || n >= N) return;
+  s = (sm[0][l] + sm[1][l]) + (sm[2][l] + sm[3][l]);
+  if (v < crows) g_centers[(size_t)n * D + v] = s;
+  else if (v == lrow) g_log_sigs[n] = s;
+  else if (R == 1) g_kernel[(size_t)n * O + (v - kb)] = s;
+  else part[(size_t)v * Npad + n] = s;                      // slab 0 (R > 1: full slab rows, kb = DC + 1)
+}
+
+// vg_mode: -1 the all-live path (vjp_reduce_kernel); else vjp_reduce_live_kernel with the slabs' layout (K2g's VgMode; 0 = the
+// full rows of every other kernel) -- and, behind a frozen-leaf K2g, the hand-over flag that says K2h wrote full rows instead
 int launch_vjp_reduce(const irbfn_net* net, float* part, float* g_centers, float* g_log_sigs, float* g_kernel, int QSB, int V,
-                      int Npad, hipStream_t s, const float* bpart, float* g_bias, int bias_blocks) {
+                      int Npad, hipStream_t s, const float* bpart, float* g_bias, int bias_blocks, int vg_mode = -1,
+                      const int* flag = nullptr, int gen = 0) {
   unsigned gx = (unsigned)((net->N + kWave - 1) / kWave);
   if (bpart != nullptr && gx < (unsigned)net->O) gx = (unsigned)net->O;
-  hipLaunchKernelGGL(vjp_reduce_kernel, dim3(gx, V + (bpart != nullptr ? 1 : 0)), dim3(256), 0, s, part, g_centers,
-                     g_log_sigs, g_kernel, QSB, V, Npad, net->N, net->K, net->R, net->D, net->DC, net->O, bpart, g_bias, bias_blocks);
+  if (vg_mode < 0) {
+    hipLaunchKernelGGL(vjp_reduce_kernel, dim3(gx, V + (bpart != nullptr ? 1 : 0)), dim3(256), 0, s, part, g_centers,
+                       g_log_sigs, g_kernel, QSB, V, Npad, net->N, net->K, net->R, net->D, net->DC, net->O, bpart, g_bias, bias_blocks);
+  } else {
+    hipLaunchKernelGGL(vjp_reduce_live_kernel, dim3(gx, V + (bpart != nullptr ? 1 : 0)), dim3(256), 0, s, part, g_centers,
+                       g_log_sigs, g_kernel, QSB, V, vg_mode, flag, gen, Npad, net->N, net->R, net->D, net->DC, net->O, net->OP, bpart,
+                       g_bias, bias_blocks);
+  }
   IRBFN_HIP_CHECK(hipGetLastError());
   if (net->R > 1) {
     hipLaunchKernelGGL(vjp_reduce_regions_kernel, dim3(net->K, net->O), dim3(kWave), 0, s, part, g_kernel, Npad, net->K, net->R,
@@ -373,7 +427,8 @@ struct VjpPlan {
 
 // The VJP's kernel, its slab count and its workspace layout.  The layout depends on the net and B alone
 // (irbfn_net_vjp_workspace_bytes); gamma_ext: caller-provided region weights (ClusterWCRBFNet).
-static VjpPlan make_plan(const irbfn_net* net, int64_t B, const float* gamma_ext = nullptr) {
+// vg_mode: K2g's live-leaf mode (irbfn_net_vjp_frozen; 0 = all leaves): its waves per SIMD set the resident block count
+static VjpPlan make_plan(const irbfn_net* net, int64_t B, const float* gamma_ext = nullptr, int vg_mode = 0) {
   VjpPlan p;
   p.groups = (net->N + kWave - 1) / kWave;
   p.Npad = p.groups * kWave;
@@ -424,7 +479,8 @@ static VjpPlan make_plan(const irbfn_net* net, int64_t B, const float* gamma_ext
     // B = 80000 107 -> 101 us against 1024 blocks)
     const long nqb = (B + 31) / 32;
     const long gb = ((net->N + 31) / 32 + 3) / 4;
-    const long resident = net->O <= 10 ? 1024 : 768;       // rbf_vjp_gram.hip: 4 waves per SIMD where hbar is one MFMA (O <= 10), else 3
+    // rbf_vjp_gram.hip: 4 waves per SIMD where hbar is one MFMA (O <= 10), else 3 (the frozen-leaf modes: more, vjpg_waves)
+    const long resident = vg_mode == 0 ? (net->O <= 10 ? 1024 : 768) : 256L * vjpg_waves(vg_mode, net->O);
     long q2 = (resident + gb - 1) / gb;
     if (q2 > 64) q2 = 64;                                  // small nets: the slab reduce grows with the slices (N = 1000, B = 80000: 64 slices 84 us, 96: 91)
     if (q2 * 8 > nqb) q2 = (nqb + 7) / 8;
@@ -739,19 +795,22 @@ static int launch_vjp_d(const VjpArgs& a, int OP, int bc, bool gated, dim3 grid,
   }
 }
 
-int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs,
-               float* g_kernel, float* g_bias, int64_t B, void* ws, int64_t ws_bytes, hipStream_t s,
-               const float* gamma_ext) {
-  (void)ws_bytes;
+// frozen: irbfn_net_vjp_frozen -- a null g_centers / g_log_sigs is neither written nor, where K2g takes the net, computed
+static int vjp_impl(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs,
+                    float* g_kernel, float* g_bias, int64_t B, void* ws, hipStream_t s, const float* gamma_ext, bool frozen) {
   const long n_c = (long)net->N * net->D, n_l = net->N, n_k = (long)net->K * net->O;
   if (B == 0) {
-    IRBFN_HIP_CHECK(hipMemsetAsync(g_centers, 0, n_c * sizeof(float), s));
-    IRBFN_HIP_CHECK(hipMemsetAsync(g_log_sigs, 0, n_l * sizeof(float), s));
+    if (g_centers) IRBFN_HIP_CHECK(hipMemsetAsync(g_centers, 0, n_c * sizeof(float), s));
+    if (g_log_sigs) IRBFN_HIP_CHECK(hipMemsetAsync(g_log_sigs, 0, n_l * sizeof(float), s));
     IRBFN_HIP_CHECK(hipMemsetAsync(g_kernel, 0, n_k * sizeof(float), s));
     IRBFN_HIP_CHECK(hipMemsetAsync(g_bias, 0, (size_t)net->O * sizeof(float), s));
     return IRBFN_OK;
   }
-  const VjpPlan p = make_plan(net, B, gamma_ext);
+  // K2g's mode: the centres frozen -> NO_CENTRES, the widths too -> LINEAR; live centres with frozen widths take the full
+  // computation (no upstream layer class freezes the widths alone)
+  const int vg_mode = g_centers ? 0 : (g_log_sigs ? 1 : 2);
+  const int red_mode = frozen ? 0 : -1;          // reduce: the live-leaf kernel for every frozen call
+  const VjpPlan p = make_plan(net, B, gamma_ext, frozen ? vg_mode : 0);
   if (p.status != IRBFN_OK) return p.status;
   char* base = static_cast<char*>(ws);
   float* gamma = reinterpret_cast<float*>(base + p.off_gamma);
@@ -777,16 +836,26 @@ int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_cente
       LaunchPlan k;
       k.kind = LK_K2G; k.S = p.QSB;
       k.grid = (int)((((net->N + 31) / 32 + 3) / 4) * p.QSB); k.block = 256;
+      if (frozen && vg_mode != 0) k.mode = vg_mode;
       record_launch(net, k);
-      rch = launch_vjp_gram(net, x, gout, B, reinterpret_cast<unsigned char*>(base + p.off_qblk), bmax, p.bias_blocks, scales, flag,
-                            run_gen, part, p.QSB, p.Npad, s);
+      if (frozen && vg_mode != 0) {
+        // slabs of the live rows only (they fit in the full-row slabs of the plan)
+        rch = launch_vjp_gram_live(net, vg_mode, x, gout, B, reinterpret_cast<unsigned char*>(base + p.off_qblk), bmax, p.bias_blocks,
+                                   scales, flag, run_gen, part, p.QSB, p.Npad, s);
+      } else {
+        rch = launch_vjp_gram(net, x, gout, B, reinterpret_cast<unsigned char*>(base + p.off_qblk), bmax, p.bias_blocks, scales, flag,
+                              run_gen, part, p.QSB, p.Npad, s);
+      }
       if (rch != IRBFN_OK) return rch;
       run_if = flag;
     }
     rch = launch_vjp_f16(net, x, gout, B, reinterpret_cast<unsigned char*>(base + p.off_qblk), bmax, p.bias_blocks,
                          scales, part, p.QSB, p.Npad, s, run_if, run_gen);
     if (rch != IRBFN_OK) return rch;
-    return launch_vjp_reduce(net, part, g_centers, g_log_sigs, g_kernel, p.QSB, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks);
+    if (p.use_g && frozen && vg_mode != 0)       // which of K2g and K2h wrote the slabs is known on the device only: the flag
+      return launch_vjp_reduce(net, part, g_centers, g_log_sigs, g_kernel, p.QSB, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, vg_mode,
+                               run_if, run_gen);
+    return launch_vjp_reduce(net, part, g_centers, g_log_sigs, g_kernel, p.QSB, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, red_mode);
   }
 
   if (p.use_sp) {
@@ -797,7 +866,7 @@ int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_cente
     hipLaunchKernelGGL(colsum_partial_kernel, dim3(p.bias_blocks), dim3(256), 256 * sizeof(float), s, gout, bpart,
                        (long)B, net->O, p.rows_per_block, (float*)nullptr);
     IRBFN_HIP_CHECK(hipGetLastError());
-    return launch_vjp_reduce(net, sp_part, g_centers, g_log_sigs, g_kernel, p.SL, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks);
+    return launch_vjp_reduce(net, sp_part, g_centers, g_log_sigs, g_kernel, p.SL, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, red_mode);
   }
   float* qrec = reinterpret_cast<float*>(base + p.off_qrec);
   {
@@ -826,7 +895,20 @@ int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_cente
   hipLaunchKernelGGL(colsum_partial_kernel, dim3(p.bias_blocks), dim3(256), 256 * sizeof(float), s, gout, bpart,
                      (long)B, net->O, p.rows_per_block, (float*)nullptr);
   IRBFN_HIP_CHECK(hipGetLastError());
-  return launch_vjp_reduce(net, part, g_centers, g_log_sigs, g_kernel, p.QSB, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks);
+  return launch_vjp_reduce(net, part, g_centers, g_log_sigs, g_kernel, p.QSB, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, red_mode);
+}
+
+int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs,
+               float* g_kernel, float* g_bias, int64_t B, void* ws, int64_t ws_bytes, hipStream_t s,
+               const float* gamma_ext) {
+  (void)ws_bytes;
+  return vjp_impl(net, x, gout, g_centers, g_log_sigs, g_kernel, g_bias, B, ws, s, gamma_ext, false);
+}
+
+int launch_vjp_frozen(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs, float* g_kernel,
+                      float* g_bias, int64_t B, void* ws, int64_t ws_bytes, hipStream_t s) {
+  (void)ws_bytes;
+  return vjp_impl(net, x, gout, g_centers, g_log_sigs, g_kernel, g_bias, B, ws, s, nullptr, true);
 }
 
 }  // namespace irbfn

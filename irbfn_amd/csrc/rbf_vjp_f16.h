@@ -27,5 +27,10 @@ bool vjpg_eligible(const irbfn_net* net);
 size_t vjpg_block_bytes();
 int launch_vjp_gram(irbfn_net* net, const float* x, const float* gout, int64_t B, unsigned char* qblk, const float* bmax, int nbmax,
                     float* scales, int* flag, int gen, float* part, int QSB, int Npad, hipStream_t s);
+// K2g's live-leaf modes (irbfn_net_vjp_frozen): 0 all leaves, 1 no centres, 2 the Dense leaves only (rbf_vjp_gram.hip: VgMode)
+int vjpg_waves(int mode, int O);                  // waves per SIMD of a mode's instance
+int vjpg_slab_rows(int mode, int DC, int OP);     // slab rows of a mode: [d centers] [d log_sigs] d kernel
+int launch_vjp_gram_live(irbfn_net* net, int mode, const float* x, const float* gout, int64_t B, unsigned char* qblk, const float* bmax,
+                         int nbmax, float* scales, int* flag, int gen, float* part, int QSB, int Npad, hipStream_t s);
 
 }  // namespace irbfn

@@ -55,7 +55,22 @@ __device__ __forceinline__ float vg_pow2_ceil_scale(float mx) {
 // wave 2 the dW / dC operands -- three dependent chains side by side instead of one long one (one wave per block: 20 us at config 3;
 // now 17-19 us.  Ablation, roles switched off one by one: role 0 alone 8.4 us, role 1 alone 11.7, role 2 alone 9.9, all three 18.6 --
 // 6144 waves of > 64 VGPRs are a round and a half of the chip, so the chains overlap only in part) ----------------------------
-template <int DC>
+// Live-leaf modes (irbfn_net_vjp_frozen): VG_ALL is the full VJP; VG_NO_CENTRES drops the centre gradient (the dC products, the
+// (hi, lo) split of tt that feeds them and x' in the block image); VG_LINEAR keeps d kernel alone (no hbar, tt, dC, d log_sigs: per
+// pair u, the transcendental and the dW products -- and of the block image u's query-side operands and g as dW operand).
+enum VgMode { VG_ALL = 0, VG_NO_CENTRES = 1, VG_LINEAR = 2 };
+// The block image in global memory keeps one layout (kVgBlock per 32 queries); a mode stages only the 1 KiB pieces it reads, packed:
+// ALL 12, NO_CENTRES 10 (x' dropped off the end), LINEAR 7 (u's operands, then gT in place of the hbar operands)
+__host__ __device__ constexpr int vg_pieces(int mode) { return mode == VG_ALL ? kVgPieces : (mode == VG_NO_CENTRES ? 10 : 7); }
+__host__ __device__ constexpr int vg_slot_bytes(int mode) { return vg_pieces(mode) * 1024; }
+__host__ __device__ constexpr int vg_src_piece(int mode, int v) { return mode == VG_LINEAR && v >= kVgDist / 1024 ? v + kVgGA / 1024 : v; }
+__host__ __device__ constexpr int vg_gT_offset(int mode) { return mode == VG_LINEAR ? kVgDist : kVgDist + kVgGA; }
+// slab rows of a mode: [d centers (ALL)] [d log_sigs (not LINEAR)] [d kernel]
+__host__ __device__ constexpr int vg_ls_row(int mode, int dc) { return mode == VG_ALL ? dc : 0; }
+__host__ __device__ constexpr int vg_kernel_row(int mode, int dc) { return mode == VG_ALL ? dc + 1 : (mode == VG_NO_CENTRES ? 1 : 0); }
+
+// MODE: the roles of the pieces a frozen-leaf mode does not read are left out
+template <int DC, int MODE>
 __global__ __launch_bounds__(192) void vjp_pack_blocks_gram_kernel(const float* __restrict__ x, const float* __restrict__ gout,
                                                                   const float* __restrict__ bmax, int nbmax,
                                                                   const float* __restrict__ oscale, const GramHdr* __restrict__ hdr,
@@ -122,6 +137,7 @@ __global__ __launch_bounds__(192) void vjp_pack_blocks_gram_kernel(const float* 
   h4v* gA1 = reinterpret_cast<h4v*>(p + kVgDist);
   h8_t* gA2 = reinterpret_cast<h8_t*>(p + kVgDist + 1024);
   if (role == 1) {
+  if constexpr (MODE != VG_LINEAR)                // LINEAR: no hbar
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     const long q = q0 + 16 * s + n;
@@ -171,7 +187,7 @@ __global__ __launch_bounds__(192) void vjp_pack_blocks_gram_kernel(const float* 
     const float gq = __shfl(gm, ql);
     float v = 0.0f, xv = 0.0f;
     if (q < B && n < O) v = gq * gout[q * O + n] / sg;
-    if (q < B) xv = n < D ? (x[q * D + n] - rn) * xinv : (n == kGramDims ? 1.0f : 0.0f);
+    if (MODE == VG_ALL && q < B) xv = n < D ? (x[q * D + n] - rn) * xinv : (n == kGramDims ? 1.0f : 0.0f);
     _Float16 h, l;
     split_static_f16(v, h, l);
     th[j] = h; tl[j] = l;
@@ -179,7 +195,7 @@ __global__ __launch_bounds__(192) void vjp_pack_blocks_gram_kernel(const float* 
     xh[j] = h; xl[j] = l;
   }
   gT[lane] = th; gT[64 + lane] = tl;
-  xB[lane] = xh; xB[64 + lane] = xl;
+  if constexpr (MODE == VG_ALL) { xB[lane] = xh; xB[64 + lane] = xl; }      // x' only where the centres are live
 }
 
 // ---- main kernel -------------------------------------------------------------------------------------------
@@ -235,12 +251,31 @@ struct VjpGArgs {
 #define IRBFN_K2G_WAVES_OC 4    // O <= 10: fits 128 VGPRs without a spill; config 3: 154 against 158 us (with 1024 blocks per launch, rbf_vjp.hip).
                                 // (Until the head sums went out through gram_heads2 -- rbf_forward_gram.h -- every 4-waves build was WRONG.)
 #endif
+// Waves per SIMD of the frozen-leaf modes: NO_CENTRES drops the dC accumulators and the tt split (a 10 KiB ring slot), LINEAR
+// also hbar, tt and d log_sigs (a 7 KiB slot; hbar's width, OC, plays no part in it: one instance per width and basis class).
+// The ring holds 3 slots per block of 4 waves, so LDS allows 5 (NO_CENTRES) and 7 (LINEAR) blocks per CU.
+#ifndef IRBFN_K2G_WAVES_NC
+#define IRBFN_K2G_WAVES_NC 4
+#endif
+#ifndef IRBFN_K2G_WAVES_NC_OC
+#define IRBFN_K2G_WAVES_NC_OC 5
+#endif
+#ifndef IRBFN_K2G_WAVES_LIN
+#define IRBFN_K2G_WAVES_LIN 6
+#endif
+__host__ __device__ constexpr int vg_waves(int mode, bool oc) {
+  return mode == VG_ALL ? (oc ? IRBFN_K2G_WAVES_OC : IRBFN_K2G_WAVES)
+                        : (mode == VG_NO_CENTRES ? (oc ? IRBFN_K2G_WAVES_NC_OC : IRBFN_K2G_WAVES_NC) : IRBFN_K2G_WAVES_LIN);
+}
 // OC: O <= kVgOC -- hbar's three products (hi x hi, lo x hi, hi x lo over <= 10 outputs: 30 of 32 slots) in ONE 16x16x32 MFMA; the
 // cross terms' B operands carry the 2^-11 of the (hi, lo) scheme, so nothing is left to combine on the VALU (28 instead of 32
 // MFMAs and 16 VALU instructions fewer per 32 x 32 pairs)
-template <int DC, int BC, bool OC>
-__global__ __launch_bounds__(256, OC ? IRBFN_K2G_WAVES_OC : IRBFN_K2G_WAVES) void rbf_vjp_f16gram(const VjpGArgs a) {
+template <int DC, int BC, bool OC, int MODE>
+__global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const VjpGArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  constexpr int SLOT = vg_slot_bytes(MODE);                  // one ring slot: the pieces of a block image this mode reads
+  constexpr bool kHbar = MODE != VG_LINEAR;                  // hbar, tt and d log_sigs
+  constexpr bool kCentres = MODE == VG_ALL;                  // the dC products
   if (*a.flag == a.gen) return;
   // (centre block, query slice) in plain grid order: placing the blocks that stream the same query slice on one XCD -- one L2 --
   // was measured and changes nothing (profiles/r03_vjp_qsb_sweep.txt): the 12 KiB query blocks are not what the kernel waits for
@@ -282,6 +317,7 @@ __global__ __launch_bounds__(256, OC ? IRBFN_K2G_WAVES_OC : IRBFN_K2G_WAVES) voi
       int cid = cb + ct * 16 + n;
       cid = cid < a.N ? cid : a.N - 1;
       const float* rp = a.rec + (size_t)cid * a.S;
+      if constexpr (!kHbar) continue;                      // LINEAR: no hbar operands
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int o = 4 * g + j;
@@ -314,9 +350,9 @@ __global__ __launch_bounds__(256, OC ? IRBFN_K2G_WAVES_OC : IRBFN_K2G_WAVES) voi
   auto stage = [&](int k, int buf) {                         // block qb0 + k -> ring slot buf; the 4 waves share the copy
     if (k >= nb) return;
     const unsigned char* gp = a.qblk + (size_t)(qb0 + k) * kVgBlock + lane * 16;
-    unsigned char* dst = lds + buf * kVgBlock;
-    for (int v = wave; v < kVgPieces; v += 4)
-      __builtin_amdgcn_global_load_lds((gptr_t)(gp + v * 1024), (lptr_t)(dst + v * 1024), 16, 0, 0);
+    unsigned char* dst = lds + buf * SLOT;
+    for (int v = wave; v < vg_pieces(MODE); v += 4)
+      __builtin_amdgcn_global_load_lds((gptr_t)(gp + vg_src_piece(MODE, v) * 1024), (lptr_t)(dst + v * 1024), 16, 0, 0);
   };
   auto step_barrier = [&]() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   stage(0, 0);
@@ -325,7 +361,7 @@ __global__ __launch_bounds__(256, OC ? IRBFN_K2G_WAVES_OC : IRBFN_K2G_WAVES) voi
   stage(2, 2);
   int b0 = 0;
   for (int i = 0; i < nb; ++i) {
-    const unsigned char* cur = lds + b0 * kVgBlock;
+    const unsigned char* cur = lds + b0 * SLOT;
     if (active) {
       float hq[2][8], tq[2][8];                              // P and tts of the lane's 8 queries x 2 centre tiles
 #pragma unroll
@@ -334,15 +370,20 @@ __global__ __launch_bounds__(256, OC ? IRBFN_K2G_WAVES_OC : IRBFN_K2G_WAVES) voi
         const h4_t qh = *reinterpret_cast<const h4_t*>(ps + lane * 8);
         const h8_t qt0 = *reinterpret_cast<const h8_t*>(ps + 512 + lane * 16);
         const h8_t qt1 = *reinterpret_cast<const h8_t*>(ps + 512 + 1024 + lane * 16);
-        const h4v gah = *reinterpret_cast<const h4v*>(cur + kVgDist + (s * 64 + lane) * 8);
-        const h8_t ga2 = *reinterpret_cast<const h8_t*>(cur + kVgDist + 1024 + (s * 64 + lane) * 16);
+        h4v gah;
+        h8_t ga2;
+        if constexpr (kHbar) {
+          gah = *reinterpret_cast<const h4v*>(cur + kVgDist + (s * 64 + lane) * 8);
+          ga2 = *reinterpret_cast<const h8_t*>(cur + kVgDist + 1024 + (s * 64 + lane) * 16);
+        }
         f4_t hb[2], u[2];
         if constexpr (kVgShift) gram_heads2c(qh, cbh, f4_t{-(float)kPhiExp, -(float)kPhiExp, -(float)kPhiExp, -(float)kPhiExp}, u);
         else gram_heads2(qh, cbh, u);                        // exact head sums (rbf_forward_gram.h: why not the builtin)
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
           f4_t hl = f4_t{0, 0, 0, 0};
-          if constexpr (OC) {
+          if constexpr (!kHbar) {
+          } else if constexpr (OC) {
             hb[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ga2, wt2[ct], f4_t{0, 0, 0, 0}, 0, 0, 0);          // all three products
           } else {
             hb[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(gah, wth[ct], f4_t{0, 0, 0, 0}, 0, 0, 0);
@@ -351,7 +392,7 @@ __global__ __launch_bounds__(256, OC ? IRBFN_K2G_WAVES_OC : IRBFN_K2G_WAVES) voi
           u[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qt0, cbt[ct][0], u[ct], 0, 0, 0);
           u[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qt1, cbt[ct][1], u[ct], 0, 0, 0);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
+          for (int r = 0; r < 4 && kHbar; ++r) {
             if (!OC) hb[ct][r] = __builtin_fmaf(hl[r], kLoScale, hb[ct][r]);
             if (ET > kVgExpA + kVgExpB) hb[ct][r] *= cE;
           }
@@ -363,6 +404,10 @@ __global__ __launch_bounds__(256, OC ? IRBFN_K2G_WAVES_OC : IRBFN_K2G_WAVES) voi
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float P = t8[ct * 4 + r];
+            if constexpr (!kHbar) {
+              hq[ct][4 * s + r] = P;
+              continue;
+            }
             float pw = P;
             if constexpr (BC == BC_IQ) pw = P * P;
             if constexpr (BC == BC_IMQ) pw = P * P * P;
@@ -376,20 +421,29 @@ __global__ __launch_bounds__(256, OC ? IRBFN_K2G_WAVES_OC : IRBFN_K2G_WAVES) voi
             tq[ct][4 * s + r] = tts;
           }
       }
-      const h8_t gth = *reinterpret_cast<const h8_t*>(cur + kVgDist + kVgGA + lane * 16);
-      const h8_t gtl = *reinterpret_cast<const h8_t*>(cur + kVgDist + kVgGA + 1024 + lane * 16);
-      const h8_t xbh = *reinterpret_cast<const h8_t*>(cur + kVgDist + kVgGA + 2048 + lane * 16);
-      const h8_t xbl = *reinterpret_cast<const h8_t*>(cur + kVgDist + kVgGA + 2048 + 1024 + lane * 16);
+      const h8_t gth = *reinterpret_cast<const h8_t*>(cur + vg_gT_offset(MODE) + lane * 16);
+      const h8_t gtl = *reinterpret_cast<const h8_t*>(cur + vg_gT_offset(MODE) + 1024 + lane * 16);
+      h8_t xbh, xbl;
+      if constexpr (kCentres) {
+        xbh = *reinterpret_cast<const h8_t*>(cur + kVgDist + kVgGA + 2048 + lane * 16);
+        xbl = *reinterpret_cast<const h8_t*>(cur + kVgDist + kVgGA + 2048 + 1024 + lane * 16);
+      }
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct) {
         unsigned ph[4], pl[4], th[4], tl[4];
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
           split_pair_plain(hq[ct][2 * jj], hq[ct][2 * jj + 1], ph[jj], pl[jj]);
-          split_pair_plain(tq[ct][2 * jj], tq[ct][2 * jj + 1], th[jj], tl[jj]);
+          if constexpr (kCentres) split_pair_plain(tq[ct][2 * jj], tq[ct][2 * jj + 1], th[jj], tl[jj]);
         }
         const h8_t bh = __builtin_bit_cast(h8_t, u4_t{ph[0], ph[1], ph[2], ph[3]});
         const h8_t bl = __builtin_bit_cast(h8_t, u4_t{pl[0], pl[1], pl[2], pl[3]});
+        if constexpr (!kCentres) {
+          dW[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(gth, bh, dW[ct], 0, 0, 0);
+          dWl[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(gtl, bh, dWl[ct], 0, 0, 0);
+          dW[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(gth, bl, dW[ct], 0, 0, 0);
+          continue;
+        }
         const h8_t ah = __builtin_bit_cast(h8_t, u4_t{th[0], th[1], th[2], th[3]});
         const h8_t al = __builtin_bit_cast(h8_t, u4_t{tl[0], tl[1], tl[2], tl[3]});
         // the lo halves of P and tts carry no gain (split_pair_plain): their products join the hi x hi accumulators; the pre-packed
@@ -409,7 +463,8 @@ __global__ __launch_bounds__(256, OC ? IRBFN_K2G_WAVES_OC : IRBFN_K2G_WAVES) voi
   if (!active) return;
 
   // ---- this wave's 32 centres: slab rows (format of rbf_vjp_kernel): d centers [0, DC), d log_sigs DC, d kernel DC + 1 + o
-  const int V = DC + 1 + a.OP;
+  constexpr int LSR = vg_ls_row(MODE, DC), KB = vg_kernel_row(MODE, DC);
+  const int V = KB + a.OP;
   float* dst = a.part + (size_t)by * V * a.Npad;
   const float wscale = sg * (1.0f / (PS * kWScale));         // s_g / (scale of the basis values x 2^15)
   const float xs = __builtin_ldexpf(1.0f, a.hdr->ex - kWExp);   // x' operand: x' 2^-ex 2^15
@@ -420,20 +475,20 @@ __global__ __launch_bounds__(256, OC ? IRBFN_K2G_WAVES_OC : IRBFN_K2G_WAVES) voi
     v += __shfl_xor(v, 16);
     v += __shfl_xor(v, 32);
     const int cid = cb + ct * 16 + n;
-    if (g == 0 && cid < a.Npad) {
+    if (kHbar && g == 0 && cid < a.Npad) {
       const int cc = cid < a.N ? cid : a.N - 1;
       const float scr = a.rec[(size_t)cc * a.S + DC];        // gaussian: alpha = -a log2(e) / sigma^2; others: 1 / sigma^2
-      dst[(size_t)DC * a.Npad + cid] = cid < a.N ? -2.0f * a.sig2[cc] * KT * v / scr : 0.0f;
+      dst[(size_t)LSR * a.Npad + cid] = cid < a.N ? -2.0f * a.sig2[cc] * KT * v / scr : 0.0f;
     }
     // d kernel: D rows = outputs 4 g + r, column = centre n
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int o = 4 * g + r;
-      if (o < a.OP && cid < a.Npad) dst[(size_t)(DC + 1 + o) * a.Npad + cid] = __builtin_fmaf(dWl[ct][r], kLoScale, dW[ct][r]) * wscale;
+      if (o < a.OP && cid < a.Npad) dst[(size_t)(KB + o) * a.Npad + cid] = __builtin_fmaf(dWl[ct][r], kLoScale, dW[ct][r]) * wscale;
     }
     // d centers: D rows = centres 4 g + r, column n = coordinate (n < DC) / the sum of tt (n = 8)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
+    for (int r = 0; r < 4 && kCentres; ++r) {
       const float dv = __builtin_fmaf(dCl[ct][r], kLoScale, dC[ct][r]);
       const float st = __shfl(dv, g * 16 + kGramDims) * (1.0f / kWScale);   // sum of tts over the slice
       const int c2 = cb + ct * 16 + 4 * g + r;
@@ -459,14 +514,14 @@ size_t vjpg_block_bytes() { return kVgBlock; }
 template <int DC>
 static int launch_vjpg_dc(const VjpGArgs& a, int bc, dim3 grid, size_t lds, hipStream_t s) {
   switch (bc) {
-    case BC_GAUSS: if (a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_GAUSS, true>), grid, dim3(256), lds, s, a);
-                   else hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_GAUSS, false>), grid, dim3(256), lds, s, a);
+    case BC_GAUSS: if (a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_GAUSS, true, VG_ALL>), grid, dim3(256), lds, s, a);
+                   else hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_GAUSS, false, VG_ALL>), grid, dim3(256), lds, s, a);
                    break;
-    case BC_IQ: if (a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_IQ, true>), grid, dim3(256), lds, s, a);
-                else hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_IQ, false>), grid, dim3(256), lds, s, a);
+    case BC_IQ: if (a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_IQ, true, VG_ALL>), grid, dim3(256), lds, s, a);
+                else hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_IQ, false, VG_ALL>), grid, dim3(256), lds, s, a);
                 break;
-    case BC_IMQ: if (a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_IMQ, true>), grid, dim3(256), lds, s, a);
-                 else hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_IMQ, false>), grid, dim3(256), lds, s, a);
+    case BC_IMQ: if (a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_IMQ, true, VG_ALL>), grid, dim3(256), lds, s, a);
+                 else hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_IMQ, false, VG_ALL>), grid, dim3(256), lds, s, a);
                  break;
     default: return IRBFN_ERR_UNSUPPORTED;
   }
@@ -481,10 +536,10 @@ int launch_vjp_gram(irbfn_net* net, const float* x, const float* gout, int64_t B
   const GramHdr* hdr = reinterpret_cast<const GramHdr*>(net->gram_hdr);
   const dim3 pg((unsigned)nqb), pb(192);
   switch (net->DC) {
-    case 3: hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<3>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass)); break;
-    case 4: hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<4>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass)); break;
-    case 7: hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<7>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass)); break;
-    case 8: hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<8>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass)); break;
+    case 3: hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<3, VG_ALL>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass)); break;
+    case 4: hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<4, VG_ALL>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass)); break;
+    case 7: hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<7, VG_ALL>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass)); break;
+    case 8: hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<8, VG_ALL>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass)); break;
     default: return IRBFN_ERR_UNSUPPORTED;
   }
   IRBFN_HIP_CHECK(hipGetLastError());
@@ -504,6 +559,76 @@ int launch_vjp_gram(irbfn_net* net, const float* x, const float* gout, int64_t B
     case 7: return launch_vjpg_dc<7>(a, net->bclass, grid, lds, s);
     case 8: return launch_vjpg_dc<8>(a, net->bclass, grid, lds, s);
     default: return IRBFN_ERR_UNSUPPORTED;
+  }
+}
+
+// ---- frozen-leaf modes (irbfn_net_vjp_frozen) ------------------------------------------------------------------
+int vjpg_waves(int mode, int O) { return vg_waves(mode, O <= kVgOC); }
+int vjpg_slab_rows(int mode, int DC, int OP) { return vg_kernel_row(mode, DC) + OP; }
+
+template <int DC, int MODE>
+static int launch_vjpg_live_dc(const VjpGArgs& a, int bc, dim3 grid, hipStream_t s) {
+  const size_t lds = (size_t)3 * vg_slot_bytes(MODE);
+  constexpr bool kOC = MODE == VG_LINEAR;                    // LINEAR has no hbar: one instance serves every O
+#define IRBFN_VG_LIVE(BCV)                                                                                                      \
+  case BCV:                                                                                                                    \
+    if (kOC || a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BCV, true, MODE>), grid, dim3(256), lds, s, a);      \
+    else hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BCV, kOC, MODE>), grid, dim3(256), lds, s, a);                          \
+    break;
+  switch (bc) {
+    IRBFN_VG_LIVE(BC_GAUSS)
+    IRBFN_VG_LIVE(BC_IQ)
+    IRBFN_VG_LIVE(BC_IMQ)
+    default: return IRBFN_ERR_UNSUPPORTED;
+  }
+#undef IRBFN_VG_LIVE
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
+
+template <int MODE>
+static int launch_vjp_gram_mode(irbfn_net* net, const float* x, const float* gout, int64_t B, unsigned char* qblk, const float* bmax,
+                                int nbmax, float* scales, int* flag, int gen, float* part, int QSB, int Npad, hipStream_t s) {
+  const long nqb = (B + 31) / 32;
+  const GramHdr* hdr = reinterpret_cast<const GramHdr*>(net->gram_hdr);
+  const dim3 pg((unsigned)nqb), pb(192);
+#define IRBFN_VG_PRE(DCV)                                                                                                        \
+  case DCV:                                                                                                                     \
+    hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<DCV, MODE>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, \
+                       scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass));                            \
+    break;
+  switch (net->DC) {
+    IRBFN_VG_PRE(3) IRBFN_VG_PRE(4) IRBFN_VG_PRE(7) IRBFN_VG_PRE(8)
+    default: return IRBFN_ERR_UNSUPPORTED;
+  }
+#undef IRBFN_VG_PRE
+  IRBFN_HIP_CHECK(hipGetLastError());
+  VjpGArgs a;
+  a.qblk = qblk; a.scales = scales; a.gimg = net->gram_img; a.hdr = hdr; a.flag = flag; a.gen = gen; a.rec = net->rec; a.sig2 = net->sig2;
+  a.oscale = net->f16_oscale; a.part = part;
+  a.nqb = nqb; a.O = net->O; a.OP = net->OP; a.N = net->N; a.S = net->S; a.Npad = Npad;
+  a.bpb = (int)((nqb + QSB - 1) / QSB);
+  a.cstride = gram_chunk_bytes((net->O + 15) / 16);
+  a.nchunks = (net->N + 31) / 32;
+  a.gscale = gauss_scale(net->basis);
+  const dim3 grid((a.nchunks + 3) / 4, QSB);
+  switch (net->DC) {
+    case 3: return launch_vjpg_live_dc<3, MODE>(a, net->bclass, grid, s);
+    case 4: return launch_vjpg_live_dc<4, MODE>(a, net->bclass, grid, s);
+    case 7: return launch_vjpg_live_dc<7, MODE>(a, net->bclass, grid, s);
+    case 8: return launch_vjpg_live_dc<8, MODE>(a, net->bclass, grid, s);
+    default: return IRBFN_ERR_UNSUPPORTED;
+  }
+}
+
+// launch_vjp_gram for a frozen-leaf mode: slabs part[QSB][vjpg_slab_rows(mode)][Npad] of the live leaves only
+int launch_vjp_gram_live(irbfn_net* net, int mode, const float* x, const float* gout, int64_t B, unsigned char* qblk, const float* bmax,
+                         int nbmax, float* scales, int* flag, int gen, float* part, int QSB, int Npad, hipStream_t s) {
+  switch (mode) {
+    case VG_ALL: return launch_vjp_gram(net, x, gout, B, qblk, bmax, nbmax, scales, flag, gen, part, QSB, Npad, s);
+    case VG_NO_CENTRES: return launch_vjp_gram_mode<VG_NO_CENTRES>(net, x, gout, B, qblk, bmax, nbmax, scales, flag, gen, part, QSB, Npad, s);
+    case VG_LINEAR: return launch_vjp_gram_mode<VG_LINEAR>(net, x, gout, B, qblk, bmax, nbmax, scales, flag, gen, part, QSB, Npad, s);
+    default: return IRBFN_ERR_BAD_ARG;
   }
 }
 

@@ -21,9 +21,20 @@ import torch
 _LEAVES = (("rbf_list", "centers"), ("rbf_list", "log_sigs"), ("linear", "kernel"), ("linear", "bias"))
 
 
+def _leaves(net):
+    """The leaves of ``net`` that train (a fixed-centre / fixed-width WCRBFNet holds fewer; model.WCRBFNet.live_leaves)."""
+    return net.live_leaves() if hasattr(net, "live_leaves") else _LEAVES
+
+
 def _shapes(net):
     R, K, D, O = net.num_regions, net.num_kernels, net.in_features, net.out_features
-    return ((R, K, D), (R, K), (K, O), (O,))
+    full = {"centers": (R, K, D), "log_sigs": (R, K), "kernel": (K, O), "bias": (O,)}
+    return tuple(full[n] for _, n in _leaves(net))
+
+
+def _tree_leaves(p: dict):
+    """The leaves of _LEAVES a pytree holds, in that order (a frozen net's tree lacks its constants)."""
+    return [(g, n) for g, n in _LEAVES if g in p and n in p[g]]
 
 
 def default_device() -> torch.device:
@@ -35,27 +46,27 @@ def params_to_device(params: dict, device: Optional[torch.device] = None, dtype:
     float64 training state of a ``use_float64`` net."""
     device = device or default_device()
     p = params["params"] if "params" in params else params
-    out = {"rbf_list": {}, "linear": {}}
-    for grp, name in _LEAVES:
+    out = {}
+    for grp, name in _tree_leaves(p):
         a = p[grp][name]
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
-        out[grp][name] = t.to(device=device, dtype=dtype).contiguous()
+        out.setdefault(grp, {})[name] = t.to(device=device, dtype=dtype).contiguous()
     return {"params": out}
 
 
 def flatten_params(params: dict) -> torch.Tensor:
     p = params["params"] if "params" in params else params
-    return torch.cat([p[g][n].reshape(-1) for g, n in _LEAVES])
+    return torch.cat([p[g][n].reshape(-1) for g, n in _tree_leaves(p)])
 
 
 def unflatten_params(net, flat: torch.Tensor) -> dict:
     if flat.numel() != flat_param_count(net):
         raise ValueError("flat parameter buffer has the wrong size for this model card")
-    out = {"rbf_list": {}, "linear": {}}
+    out = {}
     off = 0
-    for (g, n), shp in zip(_LEAVES, _shapes(net)):
+    for (g, n), shp in zip(_leaves(net), _shapes(net)):
         cnt = int(np.prod(shp))
-        out[g][n] = flat[off:off + cnt].view(*shp)
+        out.setdefault(g, {})[n] = flat[off:off + cnt].view(*shp)
         off += cnt
     return {"params": out}
 

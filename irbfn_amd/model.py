@@ -69,16 +69,26 @@ class WCRBFNet:
     """Interpolating RBF network (smooth region gate, R vmapped RBF layers, Dense).
 
     Fields as in src/irbfn_mpc/model.py:112-125.  ``centers`` / ``fixed_centers`` / ``fixed_width``
-    select upstream-only layer classes whose source is not in the reference snapshot
-    (model.py:131-140); they all share the forward arithmetic of ``RBFLayer`` and differ in which
-    parameters train, so they are accepted and ignored for ``apply``.
+    select the reference's RBF layer class (model.py:131-140; the upstream classes are not in the reference
+    snapshot: parity unpinned).  They share the forward arithmetic of ``RBFLayer`` and differ in which leaves train:
+
+    * ``centers=C`` alone (warm start): ``init()`` takes the centres from C; the tree is the full one;
+    * ``centers=C, fixed_centers=True``: the centres are constants of the net; the tree is
+      ``{"rbf_list": {"log_sigs"}, "linear": {...}}``;
+    * ``centers=C, fixed_width=True``: centres and widths are constants (widths from ``log_sigs=``, a scalar or
+      [R,K]; default 0, RBFLayer's initial value -- the upstream value is not known); the tree is ``{"linear": {...}}``.
+
+    C is [R,K,D] or [K,D] (the same centres in every region).  The flags without ``centers`` freeze nothing (with a
+    warning).  A frozen net's ``init`` / ``vjp`` use the reduced tree and its ``apply`` / ``bind`` take it; a tree
+    that carries a frozen leaf raises ``ValueError``.
     """
 
     def __init__(self, in_features: int, out_features: int, num_kernels: int, basis_func: Any,
                  num_regions: int, lower_bounds: Sequence[Sequence[float]],
                  upper_bounds: Sequence[Sequence[float]], dimension_ranges: Sequence[Sequence[int]],
                  activation_idx: Sequence[int], delta: Sequence[float], centers=None,
-                 fixed_centers: bool = False, fixed_width: bool = False, use_float64: bool = False, **_unused):
+                 fixed_centers: bool = False, fixed_width: bool = False, use_float64: bool = False, log_sigs=None,
+                 **_unused):
         self.in_features = int(in_features)
         self.out_features = int(out_features)
         self.num_kernels = int(num_kernels)
@@ -107,30 +117,101 @@ class WCRBFNet:
             for d in range(ns):
                 if not (0 <= r[d] < len(self.lower_bounds[d]) and r[d] < len(self.upper_bounds[d])):
                     raise IndexError(f"dimension_ranges[{i}][{d}]={r[d]} indexes outside the bounds of dim {d}")
+        self._init_frozen(centers, log_sigs)
         self._handles: Dict[int, C.c_void_p] = {}
+        self._const_dev: Dict[tuple, tuple] = {}
         self._bound_fp: Dict[int, tuple] = {}
         self._keepalive: Dict[int, tuple] = {}
         self._vjp_ws: Dict[int, Any] = {}
 
+    def _init_frozen(self, centers, log_sigs):
+        """The layer class: which leaves are constants of the net (``frozen``) and their values."""
+        R, K, D = self.num_regions, self.num_kernels, self.in_features
+        self.centers = None
+        if centers is not None:
+            c = np.asarray(centers.detach().cpu() if hasattr(centers, "detach") else centers)
+            if c.shape == (K, D):
+                c = np.broadcast_to(c, (R, K, D))
+            if c.shape != (R, K, D):
+                raise ValueError(f"centers has shape {c.shape}, the model card implies ({R}, {K}, {D}) or ({K}, {D})")
+            self.centers = np.ascontiguousarray(c, dtype=np.float64 if c.dtype == np.float64 else np.float32)
+        elif self.fixed_centers or self.fixed_width:
+            import warnings
+            warnings.warn("WCRBFNet: fixed_centers / fixed_width without centers= freeze nothing (the reference loads the "
+                          "centres from a file); every leaf trains", stacklevel=3)
+        frozen = ()
+        if self.centers is not None and self.fixed_width:
+            frozen = ("centers", "log_sigs")
+        elif self.centers is not None and self.fixed_centers:
+            frozen = ("centers",)
+        self.frozen = frozen
+        self.log_sigs = None
+        if "log_sigs" in frozen:
+            ls = np.asarray(0.0 if log_sigs is None else log_sigs, dtype=np.float64)
+            if ls.ndim == 0:
+                ls = np.full((R, K), float(ls))
+            if ls.shape != (R, K):
+                raise ValueError(f"log_sigs has shape {ls.shape}, expected a scalar or ({R}, {K})")
+            self.log_sigs = np.ascontiguousarray(ls)
+        elif log_sigs is not None:
+            raise ValueError("log_sigs= is the constant width of a fixed_width net (with centers=)")
+
+    def live_leaves(self) -> tuple:
+        """(group, name) of the leaves that train, in checkpoint order."""
+        return tuple((g, n) for g, n in (("rbf_list", "centers"), ("rbf_list", "log_sigs"), ("linear", "kernel"), ("linear", "bias"))
+                     if n not in self.frozen)
+
+    def leaf_shapes(self) -> dict:
+        R, K, D, O = self.num_regions, self.num_kernels, self.in_features, self.out_features
+        return {"centers": (R, K, D), "log_sigs": (R, K), "kernel": (K, O), "bias": (O,)}
+
+    def _const(self, torch, dtype):
+        """The frozen leaves as device tensors, uploaded once per device and dtype."""
+        key = (torch.cuda.current_device(), str(dtype))
+        ent = self._const_dev.get(key)
+        if ent is None:
+            dev = torch.device("cuda", key[0])
+            ent = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dtype) if a is not None else None
+                        for a in (self.centers if "centers" in self.frozen else None, self.log_sigs))
+            self._const_dev[key] = ent
+        return ent
+
+    def _leaves(self, p: dict, torch, dtype=None) -> list:
+        """[centers, log_sigs, kernel, bias] of a (checked) tree, the frozen ones from the net."""
+        c = p["rbf_list"]["centers"] if "centers" not in self.frozen else self._const(torch, dtype or torch.float32)[0]
+        ls = p["rbf_list"]["log_sigs"] if "log_sigs" not in self.frozen else self._const(torch, dtype or torch.float32)[1]
+        return [c, ls, p["linear"]["kernel"], p["linear"]["bias"]]
+
     # ------------------------------------------------------------------ construction helpers
     @classmethod
-    def from_config(cls, cfg, use_float64: bool = False) -> "WCRBFNet":
+    def from_config(cls, cfg, use_float64: bool = False, centers=None) -> "WCRBFNet":
         """cfg: dict, argparse.Namespace or path of a YAML model card (the file the reference writes at
         scripts/train_nmpc.py:431-450 and reloads at src/irbfn_mpc/irbfn_planner.py:46-79).  The reference's card does not
         record --use_float64 (a process-wide jax flag there): pass ``use_float64=True`` for that mode.  A card written by
-        ``config()`` of a float64 net holds ``use_float64: True`` and keeps the mode."""
+        ``config()`` of a float64 net holds ``use_float64: True`` and keeps the mode.  centers: the centres file's array,
+        which the card does not hold (as in the reference); with it the card's ``fixed_centers`` / ``fixed_width`` (and
+        ``log_sigs``) restore the layer class."""
         if isinstance(cfg, str):
             import yaml
             with open(cfg, "r") as f:
                 cfg = yaml.safe_load(f)
         elif not isinstance(cfg, dict):
             cfg = vars(cfg)
-        return cls(**{k: cfg[k] for k in _CFG_FIELDS}, use_float64=use_float64 or bool(cfg.get("use_float64", False)))
+        extra = {k: cfg[k] for k in ("fixed_centers", "fixed_width", "log_sigs") if cfg.get(k) is not None}
+        return cls(**{k: cfg[k] for k in _CFG_FIELDS}, use_float64=use_float64 or bool(cfg.get("use_float64", False)),
+                   centers=centers, **extra)
 
     def config(self) -> dict:
         cfg = {k: getattr(self, k) for k in _CFG_FIELDS}
         if self.use_float64:           # float32 cards stay as the reference writes them
             cfg["use_float64"] = True
+        if self.fixed_centers:
+            cfg["fixed_centers"] = True
+        if self.fixed_width:
+            cfg["fixed_width"] = True
+            if self.log_sigs is not None:
+                ls = self.log_sigs
+                cfg["log_sigs"] = float(ls.flat[0]) if np.all(ls == ls.flat[0]) else ls.tolist()
         return cfg
 
     def init(self, seed: int = 0, dtype=np.float32) -> dict:
@@ -140,10 +221,16 @@ class WCRBFNet:
         R, K, D, O = self.num_regions, self.num_kernels, self.in_features, self.out_features
         std = 1.0 / np.sqrt(K) / 0.87962566103423978   # truncated-normal correction of lecun_normal
         kern = np.clip(rng.normal(size=(K, O)), -2, 2) * std
-        return {"params": {
-            "rbf_list": {"centers": rng.normal(size=(R, K, D)).astype(dtype),
-                         "log_sigs": np.zeros((R, K), dtype)},
-            "linear": {"kernel": kern.astype(dtype), "bias": np.zeros((O,), dtype)}}}
+        centers = rng.normal(size=(R, K, D)).astype(dtype)
+        if self.centers is not None:           # warm start / the net's constant centres
+            centers = self.centers.astype(dtype)
+        p = {"rbf_list": {"centers": centers, "log_sigs": np.zeros((R, K), dtype)},
+             "linear": {"kernel": kern.astype(dtype), "bias": np.zeros((O,), dtype)}}
+        for name in self.frozen:               # a frozen net's tree holds the live leaves only
+            del p["rbf_list"][name]
+        if not p["rbf_list"]:
+            del p["rbf_list"]
+        return {"params": p}
 
     # ------------------------------------------------------------------ descriptor management
     def _gate_tables(self):
@@ -197,13 +284,18 @@ class WCRBFNet:
 
     # ------------------------------------------------------------------ parameters
     def _check_shapes(self, p: dict):
-        R, K, D, O = self.num_regions, self.num_kernels, self.in_features, self.out_features
-        want = {"centers": (R, K, D), "log_sigs": (R, K), "kernel": (K, O), "bias": (O,)}
-        got = {"centers": tuple(p["rbf_list"]["centers"].shape), "log_sigs": tuple(p["rbf_list"]["log_sigs"].shape),
-               "kernel": tuple(p["linear"]["kernel"].shape), "bias": tuple(p["linear"]["bias"].shape)}
-        for k in want:
-            if want[k] != got[k]:
-                raise ValueError(f"params {k} has shape {got[k]}, the model card implies {want[k]}")
+        want = self.leaf_shapes()
+        rbf = p.get("rbf_list", {})
+        for name in self.frozen:
+            if name in rbf:
+                raise ValueError(f"params carry rbf_list.{name}, a constant of this net (fixed_centers={self.fixed_centers}, "
+                                 f"fixed_width={self.fixed_width}): pass the tree of the live leaves {self.live_leaves()}")
+        for g, n in self.live_leaves():
+            if g not in p or n not in p[g]:
+                raise ValueError(f"params lack {g}.{n}")
+            got = tuple(p[g][n].shape)
+            if want[n] != got:
+                raise ValueError(f"params {n} has shape {got}, the model card implies {want[n]}")
 
     @staticmethod
     def _fingerprint(leaves, torch) -> tuple:
@@ -243,7 +335,7 @@ class WCRBFNet:
         lib = _lib.load()
         p = _inner(params)
         self._check_shapes(p)
-        leaves = [p["rbf_list"]["centers"], p["rbf_list"]["log_sigs"], p["linear"]["kernel"], p["linear"]["bias"]]
+        leaves = self._leaves(p, torch)
         dev = torch.cuda.current_device()
         fp = self._fingerprint(leaves, torch)
         if self._same_fingerprint(self._bound_fp.get(dev), fp):
@@ -289,8 +381,7 @@ class WCRBFNet:
         if self._warned_f64:
             return
         p = _inner(params)
-        dts = {str(getattr(p[g][n], "dtype", "")) for g, n in (("rbf_list", "centers"), ("rbf_list", "log_sigs"),
-                                                                 ("linear", "kernel"), ("linear", "bias"))}
+        dts = {str(getattr(p[g][n], "dtype", "")) for g, n in self.live_leaves() if g in p and n in p[g]}
         if any("float64" in d for d in dts):
             import warnings
             warnings.warn("WCRBFNet: float64 parameter leaves are evaluated in float32 (within 1e-5 of a float64 run); construct "
@@ -339,8 +430,7 @@ class WCRBFNet:
         self._check_shapes(p)
         ent = self._f64_card(torch)
         card = ent[0]
-        c, l, k, b = (self._dev_f64(a, torch) for a in (p["rbf_list"]["centers"], p["rbf_list"]["log_sigs"], p["linear"]["kernel"],
-                                                        p["linear"]["bias"]))
+        c, l, k, b = (self._dev_f64(a, torch) for a in self._leaves(p, torch, torch.float64))
         xd = self._dev_f64(x, torch)
         if xd.dim() != 2 or xd.shape[1] != self.in_features:
             raise ValueError(f"x must have shape (B, {self.in_features}), got {tuple(xd.shape)}")
@@ -367,29 +457,35 @@ class WCRBFNet:
             raise ValueError(f"the float64 VJP supports out_features <= {self.F64_VJP_MAX_O}, this net has {O}")
         ent = self._f64_card(torch)
         card = ent[0]
-        c, l, k = (self._dev_f64(a, torch) for a in (p["rbf_list"]["centers"], p["rbf_list"]["log_sigs"], p["linear"]["kernel"]))
+        c, l, k = (self._dev_f64(a, torch) for a in self._leaves(p, torch, torch.float64)[:3])
         xd, gd = self._dev_f64(x, torch), self._dev_f64(gout, torch)
         B = xd.shape[0]
         if tuple(gd.shape) != (B, self.out_features):
             raise ValueError(f"gout must have shape ({B}, {self.out_features}), got {tuple(gd.shape)}")
+        # a frozen net: the full float64 VJP into scratch for the frozen leaves, the live ones returned
+        full = {n: torch.empty(shp, dtype=torch.float64, device=xd.device) for n, shp in self.leaf_shapes().items()}
         if out is not None:
             o = _inner(out)
-            gc, gl, gk, gb = o["rbf_list"]["centers"], o["rbf_list"]["log_sigs"], o["linear"]["kernel"], o["linear"]["bias"]
-            for t, shp in ((gc, (R, K, D)), (gl, (R, K)), (gk, (K, O)), (gb, (O,))):
-                if tuple(t.shape) != shp or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+            for g, n in self.live_leaves():
+                t = o[g][n]
+                if tuple(t.shape) != full[n].shape or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
                     raise ValueError("vjp64 out= leaves must be contiguous float64 cuda tensors of the parameter shapes")
-        else:
-            gc = torch.empty((R, K, D), dtype=torch.float64, device=xd.device)
-            gl = torch.empty((R, K), dtype=torch.float64, device=xd.device)
-            gk = torch.empty((K, O), dtype=torch.float64, device=xd.device)
-            gb = torch.empty((O,), dtype=torch.float64, device=xd.device)
+                full[n] = t
+        gc, gl, gk, gb = full["centers"], full["log_sigs"], full["kernel"], full["bias"]
         nbytes = int(lib.irbfn_f64_workspace_bytes(C.byref(card), B, 1))
         ws = self._f64_ws(torch, ent, nbytes)
         st = lib.irbfn_f64_vjp(C.byref(card), _ptr(c), _ptr(l), _ptr(k), _ptr(xd), _ptr(gd), _ptr(gc), _ptr(gl), _ptr(gk), _ptr(gb),
                                B, _ptr(ws), nbytes, _stream_ptr(torch))
         _lib.check(st, "irbfn_f64_vjp")
         conv = (lambda t: t) if out is not None else (lambda t: like_input(t, x, torch))
-        return {"params": {"rbf_list": {"centers": conv(gc), "log_sigs": conv(gl)}, "linear": {"kernel": conv(gk), "bias": conv(gb)}}}
+        return self._grad_tree(full, conv)
+
+    def _grad_tree(self, leaves: dict, conv) -> dict:
+        """The gradient pytree of the live leaves."""
+        g = {}
+        for grp, n in self.live_leaves():
+            g.setdefault(grp, {})[n] = conv(leaves[n])
+        return {"params": g}
 
     def gate(self, x):
         """``_region_activation`` (model.py:42-95): x[B,D] -> gamma[B,R]."""
@@ -411,7 +507,7 @@ class WCRBFNet:
         if self.use_float64 and out is None:
             return self.vjp64(params, x, gout)
         torch = _lib.require_gpu()
-        if out is not None and _inner(out)["rbf_list"]["centers"].dtype == torch.float64:
+        if out is not None and _inner(out)["linear"]["kernel"].dtype == torch.float64:
             return self.vjp64(params, x, gout, out=out)      # float64 leaves: the float64 VJP writes into them
         lib = _lib.load()
         self._warn_if_float64(params)
@@ -422,29 +518,36 @@ class WCRBFNet:
             raise ValueError(f"gout must have shape ({B}, {self.out_features}), got {tuple(gd.shape)}")
         R, K, D, O = self.num_regions, self.num_kernels, self.in_features, self.out_features
         dev = xd.device
+        shapes = self.leaf_shapes()
+        full = {}
         if out is not None:      # caller-provided gradient leaves (e.g. views of one flat buffer)
             o = _inner(out)
-            gc, gl, gk, gb = o["rbf_list"]["centers"], o["rbf_list"]["log_sigs"], o["linear"]["kernel"], o["linear"]["bias"]
-            for t, shp in ((gc, (R, K, D)), (gl, (R, K)), (gk, (K, O)), (gb, (O,))):
-                if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            for g, n in self.live_leaves():
+                t = o[g][n]
+                if tuple(t.shape) != shapes[n] or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
                     raise ValueError("vjp out= leaves must be contiguous float32 cuda tensors of the parameter shapes")
+                full[n] = t
         else:
-            gc = torch.empty((R, K, D), dtype=torch.float32, device=dev)
-            gl = torch.empty((R, K), dtype=torch.float32, device=dev)
-            gk = torch.empty((K, O), dtype=torch.float32, device=dev)
-            gb = torch.empty((O,), dtype=torch.float32, device=dev)
+            for g, n in self.live_leaves():
+                full[n] = torch.empty(shapes[n], dtype=torch.float32, device=dev)
+        gc, gl, gk, gb = (full.get(n) for n in ("centers", "log_sigs", "kernel", "bias"))
         h = self._handle(torch)
         nbytes = int(lib.irbfn_net_vjp_workspace_bytes(h, B))
         ws = self._vjp_ws.get(dev.index)
         if ws is None or ws.numel() < nbytes:        # grown on demand, reused across steps
             ws = torch.empty((max(nbytes, 4),), dtype=torch.uint8, device=dev)
             self._vjp_ws[dev.index] = ws
-        st = lib.irbfn_net_vjp(h, _ptr(xd), _ptr(gd), _ptr(gc), _ptr(gl), _ptr(gk), _ptr(gb), B, _ptr(ws), nbytes,
-                               _stream_ptr(torch))
-        _lib.check(st, "irbfn_net_vjp")
+        if self.frozen:          # the frozen leaves are neither computed (K2g) nor written
+            st = lib.irbfn_net_vjp_frozen(h, _ptr(xd), _ptr(gd), _ptr(gc) if gc is not None else None,
+                                          _ptr(gl) if gl is not None else None, _ptr(gk), _ptr(gb), B, _ptr(ws), nbytes,
+                                          _stream_ptr(torch))
+            _lib.check(st, "irbfn_net_vjp_frozen")
+        else:
+            st = lib.irbfn_net_vjp(h, _ptr(xd), _ptr(gd), _ptr(gc), _ptr(gl), _ptr(gk), _ptr(gb), B, _ptr(ws), nbytes,
+                                   _stream_ptr(torch))
+            _lib.check(st, "irbfn_net_vjp")
         conv = (lambda t: t) if out is not None else (lambda t: like_input(t, x, torch))
-        return {"params": {"rbf_list": {"centers": conv(gc), "log_sigs": conv(gl)},
-                           "linear": {"kernel": conv(gk), "bias": conv(gb)}}}
+        return self._grad_tree(full, conv)
 
     def last_launch(self) -> dict:
         torch = _lib.require_gpu()
@@ -453,6 +556,11 @@ class WCRBFNet:
         g, b = C.c_int(0), C.c_int(0)
         lib.irbfn_net_last_launch(self._handle(torch), buf, 128, C.byref(g), C.byref(b))
         return {"kernel": buf.value.decode(), "grid": g.value, "block": b.value}
+
+
+def _no_frozen(cls_name: str, kw: dict):
+    if kw.get("centers") is not None and (kw.get("fixed_centers") or kw.get("fixed_width")):
+        raise NotImplementedError(f"{cls_name} with fixed centres / widths is not supported (WCRBFNet is)")
 
 
 class DeeperWCRBFNet:
@@ -467,6 +575,7 @@ class DeeperWCRBFNet:
 
     def __init__(self, in_features, out_features, num_kernels, basis_func, num_regions, lower_bounds,
                  upper_bounds, dimension_ranges, activation_idx, delta, use_float64: bool = False, **_unused):
+        _no_frozen("DeeperWCRBFNet", _unused)
         if use_float64:
             raise ValueError("DeeperWCRBFNet has no float64 mode (its MLP head runs in float32); build it with use_float64=False")
         self.out_features = int(out_features)
@@ -554,6 +663,7 @@ class ClusterWCRBFNet:
     of this variant survives in the reference (.MISSING_LARGE_BLOBS) -> parity against the oracle restatement only."""
 
     def __init__(self, in_features, out_features, num_kernels, basis_func, num_regions, use_float64: bool = False, **_unused):
+        _no_frozen("ClusterWCRBFNet", _unused)
         if use_float64:
             raise ValueError("ClusterWCRBFNet has no float64 mode (its softmax gate runs in float32); build it with use_float64=False")
         self.in_features, self.out_features = int(in_features), int(out_features)

@@ -26,7 +26,8 @@ from .model import ClusterWCRBFNet, WCRBFNet, _ptr, _stream_ptr, to_device_f32
 
 class TrainState:
     """Stand-in of ``flax.training.train_state.TrainState`` for the hot path: ``params`` (pytree of views
-    into a flat buffer), Adam moments, device-resident step count."""
+    into a flat buffer), Adam moments, device-resident step count.  A fixed-centre / fixed-width net's buffers hold its
+    live leaves only, so the clip by global norm runs over them (what optax does on the reduced tree)."""
 
     def __init__(self, net: WCRBFNet, flat, lr, max_grad_norm, b1, b2, eps):
         import torch
@@ -54,6 +55,8 @@ class TrainState:
         gets a float64 state: parameters, moments, gradient, loss and partials in float64."""
         torch = _lib.require_gpu()
         dtype = torch.float64 if getattr(net, "use_float64", False) else torch.float32
+        if isinstance(net, WCRBFNet):
+            net._check_shapes(params["params"] if "params" in params else params)    # a frozen net: its live leaves only
         flat = distributed.flatten_params(distributed.params_to_device(params, dtype=dtype)).clone()
         st = cls(net, flat, lr, max_grad_norm, b1, b2, eps)
         if dtype == torch.float32:
