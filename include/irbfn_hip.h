@@ -135,9 +135,12 @@ typedef enum irbfn_fwd_kernel {
                          on the f16 matrix cores in front of K1h's Phi x W; IRBFN_ERR_UNSUPPORTED when the bound parameters
                          do not fit the expansion (widths of 1e-3 of the centres' spread, non-finite values) */
 } irbfn_fwd_kernel;
-typedef enum irbfn_vjp_kernel { IRBFN_VJP_AUTO = 0, IRBFN_VJP_K2 = 1, IRBFN_VJP_K2H = 2, IRBFN_VJP_K2R = 3, IRBFN_VJP_K2G = 4 } irbfn_vjp_kernel;
+typedef enum irbfn_vjp_kernel { IRBFN_VJP_AUTO = 0, IRBFN_VJP_K2 = 1, IRBFN_VJP_K2H = 2, IRBFN_VJP_K2R = 3, IRBFN_VJP_K2G = 4,
+                                IRBFN_VJP_K2M = 5 } irbfn_vjp_kernel;
 /* K2: all-float32 VALU; K2H: hbar and dW on the f16 matrix cores; K2R: region-sparse pair lists; K2G: the squared distances (K1g's
- * expansion) and the centre gradients on the matrix cores as well -- automatic from 16384 queries where K1g's expansion fits.
+ * expansion) and the centre gradients on the matrix cores as well -- automatic from 16384 queries where K1g's expansion fits;
+ * K2M: hbar and dW on the f32 matrix cores (full f32 operands), one region, gaussian / inverse quadratic / inverse multiquadric,
+ * padded d in {3, 4, 7, 8}, 16 < O <= 128 -- forced only, IRBFN_VJP_AUTO never selects it.
  * A forced kernel that cannot take the net answers IRBFN_ERR_UNSUPPORTED at the call that would launch it. */
 int irbfn_net_set_option(irbfn_net* net, int option, int value);
 int irbfn_net_get_option(const irbfn_net* net, int option, int* value_out);
@@ -208,6 +211,9 @@ int irbfn_net_forward_rollout(irbfn_net* net, int mode, const float* x_dev, cons
  * controls buffer for this net, mode, batch and horizon (wide outputs need it, narrow ones on the matrix-core kernel are
  * faster with it), 0 if the tick is one launch and controls_dev may be NULL, < 0 on a bad argument. */
 int irbfn_net_tick_needs_controls(irbfn_net* net, int mode, int64_t B, int T);
+/* 1 if irbfn_net_vjp with IRBFN_OPT_VJP_KERNEL = `kernel` (irbfn_vjp_kernel) runs for this net and batch, 0 if it would answer
+ * IRBFN_ERR_UNSUPPORTED, < 0 on a bad argument.  Lets a caller ask before it forces a kernel; changes nothing. */
+int irbfn_net_vjp_kernel_supported(irbfn_net* net, int kernel, int64_t B);
 
 /* ---------------------------------------------------------------------------------------------
  * Training-step pieces: the loss compositions that define the VJP seeds, and the

@@ -21,7 +21,7 @@ ROLLOUT_ST_SELECT, ROLLOUT_ST_KS, ROLLOUT_FULLINT, ROLLOUT_FRENET_LS, ROLLOUT_SP
 # irbfn_option / irbfn_fwd_kernel / irbfn_vjp_kernel (include/irbfn_hip.h; the missing option numbers are retired)
 OPTIONS = {"fwd_kernel": 0, "fwd_f16_terms": 2, "fwd_f16_s": 7, "fwd_f16_qg": 8, "vjp_kernel": 9, "tick_fused": 13, "gram_sticky": 14}
 FWD_AUTO, FWD_K1, FWD_K1M, FWD_K1H, FWD_K1R, FWD_K1G = 0, 1, 2, 3, 4, 5
-VJP_AUTO, VJP_K2, VJP_K2H, VJP_K2R, VJP_K2G = 0, 1, 2, 3, 4
+VJP_AUTO, VJP_K2, VJP_K2H, VJP_K2R, VJP_K2G, VJP_K2M = 0, 1, 2, 3, 4, 5
 
 # every symbol include/irbfn_hip.h declares: (name, restype, argtypes)
 _vp, _fp, _ip, _i, _i64, _f, _d = C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
@@ -60,6 +60,7 @@ SIGNATURES = {
     "irbfn_intersect_point": (_i, [_fp, _fp, _fp, _f, _i, _fp, _ip, _fp, _ip, _i64, _i, _vp]),
     "irbfn_cluster_gate": (_i, [_fp, _fp, _fp, _fp, _fp, _i64, _i, _i, _vp]),
     "irbfn_net_tick_needs_controls": (_i, [_vp, _i, _i64, _i]),
+    "irbfn_net_vjp_kernel_supported": (_i, [_vp, _i, _i64]),
     "irbfn_net_forward_gamma": (_i, [_vp, _fp, _fp, _fp, _i64, _vp]),
     "irbfn_net_vjp_gamma": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _vp, _i64, _vp]),
     "irbfn_cluster_gate_vjp_workspace_bytes": (_i64, [_i, _i]),

@@ -161,7 +161,7 @@ int irbfn_net_set_option(irbfn_net* net, int option, int value) {
   if (!net || !option_known(option) || value < 0) return IRBFN_ERR_BAD_ARG;
   switch (option) {
     case IRBFN_OPT_FWD_KERNEL: if (value > IRBFN_FWD_K1G) return IRBFN_ERR_BAD_ARG; break;
-    case IRBFN_OPT_VJP_KERNEL: if (value > IRBFN_VJP_K2G) return IRBFN_ERR_BAD_ARG; break;
+    case IRBFN_OPT_VJP_KERNEL: if (value > IRBFN_VJP_K2M) return IRBFN_ERR_BAD_ARG; break;
     case IRBFN_OPT_FWD_F16_TERMS: if (value != 1 && value != 2 && value != 3) return IRBFN_ERR_BAD_ARG; break;
     case IRBFN_OPT_FWD_F16_S:
     case IRBFN_OPT_FWD_F16_QG: if (value > 16) return IRBFN_ERR_BAD_ARG; break;
@@ -313,6 +313,11 @@ int irbfn_net_forward_rollout(irbfn_net* net, int mode, const float* x_dev, cons
   if (rc != IRBFN_OK) return rc;
   return launch_forward_rollout(net, mode, x_dev, nullptr, state0_dev, dp, controls_dev, states_dev, B, T,
                                 as_stream(stream));
+}
+
+int irbfn_net_vjp_kernel_supported(irbfn_net* net, int kernel, int64_t B) {
+  if (!net || kernel < IRBFN_VJP_AUTO || kernel > IRBFN_VJP_K2M || B < 0) return IRBFN_ERR_BAD_ARG;
+  return vjp_kernel_supported(net, kernel, B);
 }
 
 int irbfn_net_tick_needs_controls(irbfn_net* net, int mode, int64_t B, int T) {

@@ -132,7 +132,9 @@ enum LaunchKind : int {
   LK_TICK_K1H,       // rbf_tick_f16mfma
   LK_TICK_K1G_WIDE,  // rbf_tick_f16gram_wide
   LK_TICK_K1H_WIDE,  // rbf_tick_f16mfma_wide
-  LK_K2G             // rbf_vjp_f16gram (the VJP plan, rbf_vjp.hip, launches it; named here with the others)
+  LK_K2G,            // rbf_vjp_f16gram (the VJP plan, rbf_vjp.hip, launches it; named here with the others)
+  LK_K2,             // rbf_vjp_kernel (`gated`: region weights per lane)
+  LK_K2M             // rbf_vjp_mfma (rbf_vjp_mfma.hip; Q: padded width OW, nw: centre tiles per wave, S: query slabs)
 };
 
 struct F16Geom {           // K1h's block geometry where the dispatch reached K1h (forced AUTO / K1H, its image, B >= 65)
@@ -213,6 +215,16 @@ int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_cente
 // irbfn_net_vjp_frozen: a null g_centers / g_log_sigs is a frozen leaf, neither computed (where K2g takes the net) nor written
 int launch_vjp_frozen(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs, float* g_kernel,
                       float* g_bias, int64_t B, void* ws, int64_t ws_bytes, hipStream_t s);
+// K2m (rbf_vjp_mfma.hip): one region, fast basis, padded d in {3, 4, 7, 8}, 16 < O <= 128
+bool vjpm_eligible(const irbfn_net* net);
+size_t vjpm_qrec_bytes(const irbfn_net* net, int64_t B);
+int vjpm_groups(const irbfn_net* net);
+int vjpm_slices(const irbfn_net* net, int64_t B, int max_qsb);
+void vjpm_names(const irbfn_net* net, int* OW, int* CT);
+int launch_vjp_mfma(irbfn_net* net, const float* x, const float* gout, int64_t B, float* qm, float* part, int QSB, int Npad,
+                    hipStream_t s);
+// irbfn_net_vjp_kernel_supported: 1 if `kernel` forced on this net takes a batch of B, else 0
+int vjp_kernel_supported(const irbfn_net* net, int kernel, int64_t B);
 int launch_dgamma(irbfn_net* net, const float* x, const float* gout, float* dgamma, int64_t B, hipStream_t s);
 int64_t cluster_gate_vjp_workspace_bytes(int D, int R);
 int launch_cluster_gate_vjp(const float* x, const float* gamma, const float* dgamma, const float* glogits, float* dlogits,

@@ -420,8 +420,10 @@ struct VjpPlan {
   bool use_h;      // K2h (matrix-core VJP) instead of K2
   bool use_g;      // K2g (u and the centre gradients on the matrix cores too) in front of K2h
   bool use_sp;     // K2r (region-sparse VJP, rbf_sparse.hip) instead of K2
+  bool use_m;      // K2m (hbar and dW on the f32 matrix cores, rbf_vjp_mfma.hip): forced only, never automatic
   int SL;          // K2r: slices per region (<= QSB slabs are allocated)
   size_t off_sp, off_sp_part;   // K2r: pair lists, slabs
+  size_t off_qm;                // K2m: its query records
   int status;      // IRBFN_OK, or why nothing runs (a forced kernel that cannot take the net, LDS)
 };
 
@@ -495,9 +497,19 @@ static VjpPlan make_plan(const irbfn_net* net, int64_t B, const float* gamma_ext
     if (q2 < 1) q2 = 1;
     if (q2 < p.QSB) p.QSB = (int)q2;          // never more slabs than were allocated above
   }
+  p.off_qm = off;
+  if (vjpm_eligible(net)) off += al(vjpm_qrec_bytes(net, B));
   p.total = off;
   // the kernel
   p.status = IRBFN_OK;
+  p.use_m = false;
+  if (vk == IRBFN_VJP_K2M) {                    // IRBFN_VJP_AUTO never takes K2m: every net keeps the kernel (and the bits) it had
+    p.use_h = p.use_g = p.use_sp = false;
+    p.use_m = vjpm_eligible(net) && gamma_ext == nullptr;
+    if (!p.use_m) p.status = IRBFN_ERR_UNSUPPORTED;
+    else p.QSB = vjpm_slices(net, B, p.QSB);    // never more slabs than were allocated above
+    return p;
+  }
   if (gamma_ext) p.use_h = false;                // the gated K2 (with the slab count chosen above)
   if (vk == IRBFN_VJP_K2G && !(p.use_h && p.use_g)) p.status = IRBFN_ERR_UNSUPPORTED;   // a forced kernel that cannot take the net
   if (p.use_h && vjph_lds_bytes(net) > 64 * 1024) p.status = IRBFN_ERR_UNSUPPORTED;
@@ -740,6 +752,12 @@ int launch_softmax_xent(const float* logits, const float* labels, float* glogits
   return IRBFN_OK;
 }
 
+int vjp_kernel_supported(const irbfn_net* net, int kernel, int64_t B) {
+  irbfn_net probe = *net;                        // the plan reads the option from the descriptor: ask a copy
+  probe.opt[IRBFN_OPT_VJP_KERNEL] = kernel;
+  return make_plan(&probe, B > 0 ? B : 1).status == IRBFN_OK ? 1 : 0;
+}
+
 int64_t vjp_workspace_bytes(const irbfn_net* net, int64_t B) {
   if (B <= 0) return 0;
   return (int64_t)make_plan(net, B).total;
@@ -858,6 +876,20 @@ static int vjp_impl(irbfn_net* net, const float* x, const float* gout, float* g_
     return launch_vjp_reduce(net, part, g_centers, g_log_sigs, g_kernel, p.QSB, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, red_mode);
   }
 
+  if (p.use_m) {
+    LaunchPlan k;
+    k.kind = LK_K2M; k.S = p.QSB;
+    vjpm_names(net, &k.Q, &k.nw);
+    k.grid = vjpm_groups(net) * p.QSB; k.block = 256;
+    record_launch(net, k);
+    const int rcm = launch_vjp_mfma(net, x, gout, B, reinterpret_cast<float*>(base + p.off_qm), part, p.QSB, p.Npad, s);
+    if (rcm != IRBFN_OK) return rcm;
+    hipLaunchKernelGGL(colsum_partial_kernel, dim3(p.bias_blocks), dim3(256), 256 * sizeof(float), s, gout, bpart,
+                       (long)B, net->O, p.rows_per_block, (float*)nullptr);
+    IRBFN_HIP_CHECK(hipGetLastError());
+    return launch_vjp_reduce(net, part, g_centers, g_log_sigs, g_kernel, p.QSB, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, red_mode);
+  }
+
   if (p.use_sp) {
     // K2r: pair lists per region -> one wave per (region, slice) -> the same fixed-order slab reduce; no query packing
     float* sp_part = reinterpret_cast<float*>(base + p.off_sp_part);
@@ -883,6 +915,12 @@ static int vjp_impl(irbfn_net* net, const float* x, const float* gout, float* g_
   a.basis = net->basis; a.Npad = p.Npad; a.per_wave = p.per_wave; a.gscale = gauss_scale(net->basis);
   const dim3 grid(p.groups, p.QSB);
   const bool gated = net->R > 1 || gamma_ext != nullptr;
+  {
+    LaunchPlan k;
+    k.kind = LK_K2; k.gated = gated;
+    k.grid = (int)(grid.x * grid.y); k.block = 256;
+    record_launch(net, k);
+  }
   switch (net->DC) {
     case 3: rc = launch_vjp_d<3>(a, net->OP, net->bclass, gated, grid, s); break;
     case 4: rc = launch_vjp_d<4>(a, net->OP, net->bclass, gated, grid, s); break;

@@ -19,6 +19,9 @@ import numpy as np
 import torch
 
 _LEAVES = (("rbf_list", "centers"), ("rbf_list", "log_sigs"), ("linear", "kernel"), ("linear", "bias"))
+# DeeperWCRBFNet (model.DeeperWCRBFNet.LEAVES): the RBF stage, its 64-wide Dense, then the head's two Dense layers
+_DEEPER_LEAVES = (("rbf_list", "centers"), ("rbf_list", "log_sigs"), ("linear_pre1", "kernel"), ("linear_pre1", "bias"),
+                  ("linear_pre2", "kernel"), ("linear_pre2", "bias"), ("linear", "kernel"), ("linear", "bias"))
 
 
 def _leaves(net):
@@ -27,14 +30,19 @@ def _leaves(net):
 
 
 def _shapes(net):
+    if hasattr(net, "group_leaf_shapes"):          # DeeperWCRBFNet: three groups hold a "kernel"
+        full = net.group_leaf_shapes()
+        return tuple(full[leaf] for leaf in _leaves(net))
     R, K, D, O = net.num_regions, net.num_kernels, net.in_features, net.out_features
     full = {"centers": (R, K, D), "log_sigs": (R, K), "kernel": (K, O), "bias": (O,)}
     return tuple(full[n] for _, n in _leaves(net))
 
 
 def _tree_leaves(p: dict):
-    """The leaves of _LEAVES a pytree holds, in that order (a frozen net's tree lacks its constants)."""
-    return [(g, n) for g, n in _LEAVES if g in p and n in p[g]]
+    """The leaves of _LEAVES a pytree holds, in that order (a frozen net's tree lacks its constants); a DeeperWCRBFNet tree
+    (it has linear_pre1) in the order of _DEEPER_LEAVES."""
+    order = _DEEPER_LEAVES if "linear_pre1" in p else _LEAVES
+    return [(g, n) for g, n in order if g in p and n in p[g]]
 
 
 def default_device() -> torch.device:

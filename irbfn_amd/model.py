@@ -597,16 +597,35 @@ class DeeperWCRBFNet:
             cfg = vars(cfg)
         return cls(**{k: cfg[k] for k in _CFG_FIELDS}, use_float64=bool(cfg.get("use_float64", False)))
 
-    def apply(self, params: dict, x):
-        torch = _lib.require_gpu()
-        lib = _lib.load()
+    LEAVES = (("rbf_list", "centers"), ("rbf_list", "log_sigs"), ("linear_pre1", "kernel"), ("linear_pre1", "bias"),
+              ("linear_pre2", "kernel"), ("linear_pre2", "bias"), ("linear", "kernel"), ("linear", "bias"))
+
+    def live_leaves(self) -> tuple:
+        """(group, name) of the eight leaves, in the order of the flat training buffers (distributed.flatten_params)."""
+        return self.LEAVES
+
+    def group_leaf_shapes(self) -> dict:
+        """{(group, name): shape} of the parameter pytree."""
+        R, K, D, H, O = self.stage.num_regions, self.stage.num_kernels, self.in_features, self.HIDDEN, self.out_features
+        return {("rbf_list", "centers"): (R, K, D), ("rbf_list", "log_sigs"): (R, K), ("linear_pre1", "kernel"): (K, H),
+                ("linear_pre1", "bias"): (H,), ("linear_pre2", "kernel"): (H, H), ("linear_pre2", "bias"): (H,),
+                ("linear", "kernel"): (H, O), ("linear", "bias"): (O,)}
+
+    def _check_shapes(self, p: dict):
+        for (g, n), shp in self.group_leaf_shapes().items():
+            if g not in p or n not in p[g]:
+                raise ValueError(f"params lack {g}.{n}")
+            if tuple(p[g][n].shape) != shp:
+                raise ValueError(f"params {g}.{n} has shape {tuple(p[g][n].shape)}, the model card implies {shp}")
+
+    def _forward(self, params: dict, xd, torch, lib):
+        """(out, h1) as device tensors: h1 = linear_pre1(rbf_out) [B, 64] (model.py:283), out the head's output."""
         p = _inner(params)
         H, O = self.HIDDEN, self.out_features
         for name, shp in (("linear_pre2", (H, H)), ("linear", (H, O))):
             if tuple(p[name]["kernel"].shape) != shp:
                 raise ValueError(f"params {name}.kernel has shape {tuple(p[name]['kernel'].shape)}, expected {shp}")
         stage_params = {"rbf_list": p["rbf_list"], "linear": p["linear_pre1"]}
-        xd = to_device_f32(x, torch)
         h1 = self.stage.apply(stage_params, xd)                     # linear_pre1(rbf_out)   model.py:283
         head = [to_device_f32(a, torch) for a in (p["linear_pre2"]["kernel"], p["linear_pre2"]["bias"],
                                                   p["linear"]["kernel"], p["linear"]["bias"])]
@@ -615,10 +634,21 @@ class DeeperWCRBFNet:
         st = lib.irbfn_mlp_head_forward(_ptr(h1), _ptr(head[0]), _ptr(head[1]), _ptr(head[2]), _ptr(head[3]), _ptr(out),
                                         B, H, H, O, _stream_ptr(torch))
         _lib.check(st, "irbfn_mlp_head_forward")
+        return out, h1
+
+    def apply(self, params: dict, x):
+        torch = _lib.require_gpu()
+        out, _ = self._forward(params, to_device_f32(x, torch), torch, _lib.load())
         return like_input(out, x, torch)
 
+    def apply_with_hidden(self, params: dict, x):
+        """``apply`` that also returns the stage output h1 [B, 64] (linear_pre1's output), which ``vjp(h1=)`` reuses instead
+        of running the RBF stage a second time.  -> (out [B, O], h1 [B, 64]), in the flavour of x."""
+        torch = _lib.require_gpu()
+        out, h1 = self._forward(params, to_device_f32(x, torch), torch, _lib.load())
+        return like_input(out, x, torch), like_input(h1, x, torch)
 
-    def _vjp_impl(self, params: dict, x, gout):
+    def _vjp_impl(self, params: dict, x, gout, out=None, h1=None, stage_vjp_kernel=None):
         torch = _lib.require_gpu()
         lib = _lib.load()
         p = _inner(params)
@@ -628,12 +658,27 @@ class DeeperWCRBFNet:
         B = xd.shape[0]
         if tuple(gd.shape) != (B, O):
             raise ValueError(f"gout must have shape ({B}, {O})")
-        h1 = self.stage.apply(stage_params, xd)
+        if h1 is None:
+            h1 = self.stage.apply(stage_params, xd)
+        else:
+            if not isinstance(h1, torch.Tensor) or tuple(h1.shape) != (B, H) or h1.dtype != torch.float32 or not h1.is_cuda \
+                    or not h1.is_contiguous():
+                raise ValueError(f"vjp h1= must be the contiguous float32 cuda stage output [{B}, {H}] of apply_with_hidden")
         w2, b2, w3 = (to_device_f32(a, torch) for a in (p["linear_pre2"]["kernel"], p["linear_pre2"]["bias"], p["linear"]["kernel"]))
         dev = xd.device
+        if out is not None:      # caller-provided gradient leaves (e.g. views of one flat buffer)
+            o = _inner(out)
+            for (g, n), shp in self.group_leaf_shapes().items():
+                t = o[g][n]
+                if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                    raise ValueError("vjp out= leaves must be contiguous float32 cuda tensors of the parameter shapes")
+            gw2, gb2, gw3, gb3 = o["linear_pre2"]["kernel"], o["linear_pre2"]["bias"], o["linear"]["kernel"], o["linear"]["bias"]
+            stage_out = {"rbf_list": o["rbf_list"], "linear": o["linear_pre1"]}
+        else:
+            gw2, gb2 = torch.empty((H, H), dtype=torch.float32, device=dev), torch.empty((H,), dtype=torch.float32, device=dev)
+            gw3, gb3 = torch.empty((H, O), dtype=torch.float32, device=dev), torch.empty((O,), dtype=torch.float32, device=dev)
+            stage_out = None
         gh1 = torch.empty((B, H), dtype=torch.float32, device=dev)
-        gw2, gb2 = torch.empty((H, H), dtype=torch.float32, device=dev), torch.empty((H,), dtype=torch.float32, device=dev)
-        gw3, gb3 = torch.empty((H, O), dtype=torch.float32, device=dev), torch.empty((O,), dtype=torch.float32, device=dev)
         nbytes = int(lib.irbfn_mlp_head_vjp_workspace_bytes(H, H, O))
         if nbytes < 0:
             _lib.check(nbytes, "irbfn_mlp_head_vjp_workspace_bytes")
@@ -641,17 +686,32 @@ class DeeperWCRBFNet:
         st = lib.irbfn_mlp_head_vjp(_ptr(h1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(gd), _ptr(gh1), _ptr(gw2), _ptr(gb2),
                                     _ptr(gw3), _ptr(gb3), B, H, H, O, _ptr(ws), nbytes, _stream_ptr(torch))
         _lib.check(st, "irbfn_mlp_head_vjp")
-        gs = self.stage.vjp(stage_params, xd, gh1)["params"]
-        conv = lambda t: like_input(t, x, torch)
+        if stage_vjp_kernel is None:
+            gs = self.stage.vjp(stage_params, xd, gh1, out=stage_out)["params"]
+        else:                    # this call only: the descriptor's own choice is put back whatever happens
+            h = self.stage._handle(torch)
+            prev = C.c_int(0)
+            _lib.check(lib.irbfn_net_get_option(h, _lib.OPTIONS["vjp_kernel"], C.byref(prev)), "irbfn_net_get_option")
+            _lib.check(lib.irbfn_net_set_option(h, _lib.OPTIONS["vjp_kernel"], int(stage_vjp_kernel)),
+                       f"irbfn_net_set_option(vjp_kernel={stage_vjp_kernel})")
+            try:
+                gs = self.stage.vjp(stage_params, xd, gh1, out=stage_out)["params"]
+            finally:
+                lib.irbfn_net_set_option(h, _lib.OPTIONS["vjp_kernel"], prev.value)
+        conv = (lambda t: t) if out is not None else (lambda t: like_input(t, x, torch))
         return {"params": {"rbf_list": {k: conv(v) for k, v in gs["rbf_list"].items()},
                            "linear_pre1": {k: conv(v) for k, v in gs["linear"].items()},
                            "linear_pre2": {"kernel": conv(gw2), "bias": conv(gb2)},
                            "linear": {"kernel": conv(gw3), "bias": conv(gb3)}}}
 
-    def vjp(self, params: dict, x, gout) -> dict:
+    def vjp(self, params: dict, x, gout, out: Optional[dict] = None, h1=None, stage_vjp_kernel: Optional[int] = None) -> dict:
         """Parameter VJP of the whole model: cotangent gout[B,O] -> gradient pytree with the structure of ``params``
-        (what ``jax.value_and_grad`` returns for a DeeperWCRBFNet, scripts/train_nmpc_frenet.py:388-389,416-417)."""
-        return self._vjp_impl(params, x, gout)
+        (what ``jax.value_and_grad`` returns for a DeeperWCRBFNet, scripts/train_nmpc_frenet.py:388-389,416-417).
+
+        out: caller-provided contiguous float32 cuda leaves (e.g. views of a flat buffer), written and returned.
+        h1: the stage output of ``apply_with_hidden`` for these params and x: the RBF stage is not run again.
+        stage_vjp_kernel: ``_lib.VJP_*`` for the stage VJP of this call only; the stage's option is restored afterwards."""
+        return self._vjp_impl(params, x, gout, out=out, h1=h1, stage_vjp_kernel=stage_vjp_kernel)
 
 
 class ClusterWCRBFNet:

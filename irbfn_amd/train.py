@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib, distributed
 from .dynamics import _dyn
-from .model import ClusterWCRBFNet, WCRBFNet, _ptr, _stream_ptr, to_device_f32
+from .model import ClusterWCRBFNet, DeeperWCRBFNet, WCRBFNet, _ptr, _stream_ptr, to_device_f32
 
 
 class TrainState:
@@ -123,6 +123,44 @@ class ClusterTrainState(TrainState):
         return self._views(self.m), self._views(self.v), int(self.step.item())
 
 
+class DeeperTrainState(TrainState):
+    """TrainState of a ``DeeperWCRBFNet`` (scripts/train_nmpc_frenet.py:388-417), float32 only: the flat buffers hold the eight
+    leaves in ``DeeperWCRBFNet.LEAVES`` order.  A step keeps the stage output h1 of its forward for the VJP (the RBF stage
+    runs once) and runs the stage VJP on K2m where the stage descriptor supports it (``stage_vjp_kernel``)."""
+
+    @classmethod
+    def create(cls, net: DeeperWCRBFNet, params: dict, lr: float = 1e-3, max_grad_norm: float = 1.0,
+               b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8, opt_state=None) -> "DeeperTrainState":
+        """opt_state: (mu pytree, nu pytree, count) with the eight leaves, to resume (``checkpoint.restore_opt_state``)."""
+        torch = _lib.require_gpu()
+        if not isinstance(net, DeeperWCRBFNet):
+            raise TypeError("DeeperTrainState trains a DeeperWCRBFNet (TrainState: WCRBFNet, ClusterTrainState: ClusterWCRBFNet)")
+        net._check_shapes(params["params"] if "params" in params else params)
+        flat = distributed.flatten_params(distributed.params_to_device(params)).clone()
+        st = cls(net, flat, lr, max_grad_norm, b1, b2, eps)
+        net.stage.set_options(gram_sticky=1)        # as TrainState.create: no read-back of the pack's verdict per re-bind
+        if opt_state is not None:
+            st.m.copy_(distributed.flatten_params(distributed.params_to_device(opt_state[0])))
+            st.v.copy_(distributed.flatten_params(distributed.params_to_device(opt_state[1])))
+            st.step.fill_(int(opt_state[2]))
+        return st
+
+    def stage_vjp_kernel(self, B: int) -> int:
+        """The stage VJP's kernel for a batch of B: K2m where the descriptor takes it, else the automatic choice."""
+        lib = _lib.load()
+        import torch
+        h = self.net.stage._handle(torch)
+        return _lib.VJP_K2M if lib.irbfn_net_vjp_kernel_supported(h, _lib.VJP_K2M, int(B)) == 1 else _lib.VJP_AUTO
+
+
+def _forward(state: TrainState, xd):
+    """The step's forward -> (prediction, the keywords of its VJP): a DeeperTrainState keeps h1 for the stage VJP."""
+    if isinstance(state, DeeperTrainState):
+        y_pred, h1 = state.net.apply_with_hidden(state.params, xd)
+        return y_pred, {"h1": h1, "stage_vjp_kernel": state.stage_vjp_kernel(xd.shape[0])}
+    return state.net.apply(state.params, xd), {}
+
+
 def _is_f64(state: TrainState, torch) -> bool:
     return state.flat.dtype == torch.float64
 
@@ -172,7 +210,7 @@ def train_step_oneint(state: TrainState, x, y, dyn_params, clip_tie: float = 0.5
     B, O = yd.shape
     if xd.shape[1] < 7 or O != state.net.out_features or O < 2:
         raise ValueError("train_step_oneint needs x [B,7] and y [B,out_features >= 2]")
-    y_pred = state.net.apply(state.params, xd)
+    y_pred, vjp_kw = _forward(state, xd)
     gy = torch.empty_like(y_pred)
     keep, pp = _dyn(dyn_params, np.float64 if f64 else np.float32)
     _fresh_loss(state, torch)
@@ -180,7 +218,7 @@ def train_step_oneint(state: TrainState, x, y, dyn_params, clip_tie: float = 0.5
     st = seeds(_ptr(xd), _ptr(y_pred), _ptr(yd), pp, float(clip_tie), _ptr(gy), _ptr(state.loss), _ptr(state.partials), B,
                xd.shape[1], O, _stream_ptr(torch))
     _lib.check(st, seeds.__name__)
-    return state, _backward_and_update(state, xd, gy, torch, lib)
+    return state, _backward_and_update(state, xd, gy, torch, lib, **vjp_kw)
 
 
 def train_step_fullint(state: TrainState, x, y, clip_tie: float = 0.5) -> Tuple[TrainState, "object"]:
@@ -191,14 +229,14 @@ def train_step_fullint(state: TrainState, x, y, clip_tie: float = 0.5) -> Tuple[
     B, O = yd.shape
     if O != state.net.out_features or O % 2:
         raise ValueError("train_step_fullint needs y [B, out_features = 2T]")
-    y_pred = state.net.apply(state.params, xd)
+    y_pred, vjp_kw = _forward(state, xd)
     gy = torch.empty_like(y_pred)
     _fresh_loss(state, torch)
     seeds = lib.irbfn_train_seeds_fullint_f64 if _is_f64(state, torch) else lib.irbfn_train_seeds_fullint
     st = seeds(_ptr(xd), _ptr(y_pred), _ptr(yd), float(clip_tie), _ptr(gy), _ptr(state.loss), _ptr(state.partials), B,
                xd.shape[1], O // 2, _stream_ptr(torch))
     _lib.check(st, seeds.__name__)
-    return state, _backward_and_update(state, xd, gy, torch, lib)
+    return state, _backward_and_update(state, xd, gy, torch, lib, **vjp_kw)
 
 
 def train_step_frenet_fullint(state: TrainState, x, y, dyn_params, clip_tie: float = 0.5) -> Tuple[TrainState, "object"]:
@@ -212,7 +250,7 @@ def train_step_frenet_fullint(state: TrainState, x, y, dyn_params, clip_tie: flo
     B, O = yd.shape
     if xd.shape[1] != 8 or O != state.net.out_features or O % 2 or O // 2 > 16:
         raise ValueError("train_step_frenet_fullint needs x [B,8] and y [B, out_features = 2T], T <= 16")
-    y_pred = state.net.apply(state.params, xd)
+    y_pred, vjp_kw = _forward(state, xd)
     gy = torch.empty_like(y_pred)
     keep, pp = _dyn(dyn_params, np.float64 if f64 else np.float32)
     _fresh_loss(state, torch)
@@ -220,7 +258,7 @@ def train_step_frenet_fullint(state: TrainState, x, y, dyn_params, clip_tie: flo
     st = seeds(_ptr(xd), _ptr(y_pred), _ptr(yd), pp, float(clip_tie), _ptr(gy), _ptr(state.loss), _ptr(state.partials), B, 8,
                O // 2, _stream_ptr(torch))
     _lib.check(st, seeds.__name__)
-    return state, _backward_and_update(state, xd, gy, torch, lib)
+    return state, _backward_and_update(state, xd, gy, torch, lib, **vjp_kw)
 
 
 def train_step_fullint_withcluster(state: ClusterTrainState, x, y, cluster_ids, dyn_params, clip_tie: float = 0.5):
