@@ -332,7 +332,9 @@ int irbfn_net_forward_gamma(irbfn_net* net, const float* x_dev, const float* gam
  * irbfn_cluster_gate_vjp: softmax + Dense backward of the gate (model.py:402-404): dlogits = gamma * (dgamma -
  *   <gamma, dgamma>) [+ glogits_dev, the direct cotangent of the logits; may be NULL] -> g_wc [D,R], g_bc [R];
  *   dlogits_dev [B,R] is scratch / output; workspace_dev: irbfn_cluster_gate_vjp_workspace_bytes(D, R) bytes (per-block
- *   partial sums, added in block order: deterministic).
+ *   partial sums, added in block order: deterministic).  Supported: 1 <= D <= 16 (as irbfn_cluster_gate) and any R >= 1
+ *   with (D + 1) * R < 2^31; R is otherwise limited by memory only (the workspace is 256 (D + 1) R floats, 4.6 MB at
+ *   D = 8, R = 500).  Outside it: IRBFN_ERR_UNSUPPORTED.
  * irbfn_softmax_xent: optax.softmax_cross_entropy(logits, labels).mean() (train_nmpc_frenet.py:431) -> loss (added to
  *   *loss_dev if accumulate != 0) and glogits = d loss / d logits; partials_dev: irbfn_train_loss_partials() floats. */
 int irbfn_net_vjp_gamma(irbfn_net* net, const float* x_dev, const float* gamma_dev, const float* gout_dev,

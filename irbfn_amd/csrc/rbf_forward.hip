@@ -131,9 +131,10 @@ static LaunchPlan plan_qlane(const irbfn_net* net, int64_t B, bool gated, bool r
   const int OP = net->OP;
   // --- Q: two queries per lane halve the scalar-stream traffic per pair, but the kernel is VALU-issue
   // bound and more resident waves hide the scalar-load latency better (measured: Q=1,NW=16 152 us vs
-  // Q=2,NW=16 175 us at cfg-2), so Q = 2 only once Q = 1 alone over-subscribes the chip.
+  // Q=2,NW=16 175 us at cfg-2), so Q = 2 only once Q = 1 alone over-subscribes the chip.  The Q = 2 instances exist for
+  // the fast bases only (launch_bc, rbf_forward_kernels.hip): generic bases stay at Q = 1 at every B.
   int Q = 1;
-  const bool q2_compiled = (OP == 2 || OP == 5 || OP == 10);
+  const bool q2_compiled = (OP == 2 || OP == 5 || OP == 10) && net->bclass != BC_GENERIC;
   if (q2_compiled && B >= (int64_t)kWave * 32768) Q = 2;
   const int ROWS = kWave * Q;
   const long tiles = (B + ROWS - 1) / ROWS;

@@ -18,6 +18,8 @@
 #include "rbf_forward.h"
 #include "rbf_vjp_f16.h"
 
+#include <climits>
+
 
 namespace irbfn {
 
@@ -612,24 +614,35 @@ __global__ __launch_bounds__(256) void cluster_dlogits_kernel(const float* __res
   }
 }
 
-// d Wc[d,r] = sum_b x[b,d] dlogits[b,r] (d < D), d bc[r] = sum_b dlogits[b,r] (d == D).  kGateBwdBlocks blocks walk the
-// batch in 64-row tiles (coalesced copies into LDS), thread t owns outputs t, t + 256, ... and adds the tile's rows in
-// order; the per-block partial sums are added in block order by cluster_dense_final_kernel: deterministic.  (The first
-// version gave one block to an output and let it stride over the whole batch: 99 blocks, uncoalesced -- 102 us at 80000 rows.)
+// d Wc[d,r] = sum_b x[b,d] dlogits[b,r] (d < D), d bc[r] = sum_b dlogits[b,r] (d == D).  Grid (region chunk, batch block):
+// each of kGateBwdBlocks batch blocks walks the batch in 64-row tiles (coalesced copies into LDS) for one chunk of at most
+// RC = gate_bwd_chunk(D) regions, whose (D + 1) * RC outputs fit in 256 threads x kGateBwdOut registers and whose
+// xs[64][D + 1] + dl[64][RC] stage fits in 48 KiB of LDS, whatever R is.  Thread t owns the chunk's outputs t, t + 256, ...
+// and adds the tile's rows in order; the per-block partial sums are added in block order by cluster_dense_final_kernel:
+// deterministic, and each output's order does not depend on the chunking.  (The first version gave one block to an output
+// and let it stride over the whole batch: 99 blocks, uncoalesced -- 102 us at 80000 rows.)
 constexpr int kGateBwdBlocks = 256;
+constexpr int kGateBwdOut = 8;                   // outputs per thread
+constexpr int kGateBwdLdsFloats = 48 * 1024 / 4;
+static int gate_bwd_chunk(int D) {
+  const int by_regs = 256 * kGateBwdOut / (D + 1);
+  const int by_lds = kGateBwdLdsFloats / kWave - (D + 1);
+  return by_regs < by_lds ? by_regs : by_lds;
+}
 __global__ __launch_bounds__(256) void cluster_dense_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dlogits,
-                                                                float* __restrict__ part, long B, int D, int R) {
-  extern __shared__ float lds[];                 // xs[64][D + 1] (last column = 1), dl[64][R]
+                                                                float* __restrict__ part, long B, int D, int R, int RC) {
+  extern __shared__ float lds[];                 // xs[64][D + 1] (last column = 1), dl[64][nr]
   float* xs = lds;
   float* dl = lds + kWave * (D + 1);
   const int tid = threadIdx.x;
-  const int nout = (D + 1) * R;
-  constexpr int MAXO = 8;                        // outputs per thread: (D + 1) * R <= 2048
-  float acc[MAXO];
+  const int r0 = blockIdx.x * RC;
+  const int nr = R - r0 < RC ? R - r0 : RC;      // regions of this chunk
+  const int nout = (D + 1) * nr;
+  float acc[kGateBwdOut];
 #pragma unroll
-  for (int k = 0; k < MAXO; ++k) acc[k] = 0.0f;
+  for (int k = 0; k < kGateBwdOut; ++k) acc[k] = 0.0f;
   const long ntiles = (B + kWave - 1) / kWave;
-  for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+  for (long tile = blockIdx.y; tile < ntiles; tile += gridDim.y) {
     const long b0 = tile * kWave;
     const long left = B - b0;
     const int nv = left < kWave ? (int)left : kWave;
@@ -637,24 +650,31 @@ __global__ __launch_bounds__(256) void cluster_dense_bwd_kernel(const float* __r
       const int row = i / (D + 1), d = i - row * (D + 1);
       xs[i] = row < nv ? (d < D ? x[(b0 + row) * D + d] : 1.0f) : 0.0f;
     }
-    for (int i = tid; i < kWave * R; i += 256) dl[i] = i < nv * R ? dlogits[b0 * R + i] : 0.0f;
+    for (int i = tid; i < kWave * nr; i += 256) {
+      const int row = i / nr, r = i - row * nr;
+      dl[i] = row < nv ? dlogits[(b0 + row) * R + r0 + r] : 0.0f;
+    }
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < MAXO; ++k) {
+    for (int k = 0; k < kGateBwdOut; ++k) {
       const int t = tid + k * 256;
       if (t < nout) {
-        const int d = t / R, r = t - d * R;
+        const int d = t / nr, r = t - d * nr;
         float s = acc[k];
-        for (int row = 0; row < kWave; ++row) s = __builtin_fmaf(xs[row * (D + 1) + d], dl[row * R + r], s);
+        for (int row = 0; row < kWave; ++row) s = __builtin_fmaf(xs[row * (D + 1) + d], dl[row * nr + r], s);
         acc[k] = s;
       }
     }
     __syncthreads();
   }
+  const size_t nall = (size_t)(D + 1) * R;
 #pragma unroll
-  for (int k = 0; k < MAXO; ++k) {
+  for (int k = 0; k < kGateBwdOut; ++k) {
     const int t = tid + k * 256;
-    if (t < nout) part[(size_t)blockIdx.x * nout + t] = acc[k];
+    if (t < nout) {
+      const int d = t / nr, r = t - d * nr;
+      part[(size_t)blockIdx.y * nall + (size_t)d * R + r0 + r] = acc[k];
+    }
   }
 }
 
@@ -687,14 +707,17 @@ int launch_cluster_gate_vjp(const float* x, const float* gamma, const float* dga
     IRBFN_HIP_CHECK(hipMemsetAsync(g_bc, 0, (size_t)R * sizeof(float), s));
     return IRBFN_OK;
   }
-  if ((D + 1) * R > 2048) return IRBFN_ERR_UNSUPPORTED;
+  if (D < 1 || D > 16 || R < 1 || (int64_t)(D + 1) * R > INT_MAX) return IRBFN_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(cluster_dlogits_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, gamma, dgamma, glogits, dlogits,
                      (long)B, R);
   IRBFN_HIP_CHECK(hipGetLastError());
-  const size_t lds = (size_t)kWave * (D + 1 + R) * sizeof(float);
+  const int RC = gate_bwd_chunk(D);
+  const int nchunk = (R + RC - 1) / RC;
+  const size_t lds = (size_t)kWave * (D + 1 + (R < RC ? R : RC)) * sizeof(float);
   const long ntiles = (B + kWave - 1) / kWave;
   const int nblk = ntiles < kGateBwdBlocks ? (int)ntiles : kGateBwdBlocks;
-  hipLaunchKernelGGL(cluster_dense_bwd_kernel, dim3(nblk), dim3(256), lds, s, x, dlogits, ws, (long)B, D, R);
+  hipLaunchKernelGGL(cluster_dense_bwd_kernel, dim3((unsigned)nchunk, (unsigned)nblk), dim3(256), lds, s, x, dlogits, ws,
+                     (long)B, D, R, RC);
   IRBFN_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(cluster_dense_final_kernel, dim3(((D + 1) * R + 15) / 16), dim3(256), 0, s, ws, g_wc, g_bc, nblk, D, R);
   IRBFN_HIP_CHECK(hipGetLastError());

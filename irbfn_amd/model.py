@@ -719,8 +719,10 @@ class ClusterWCRBFNet:
     softmax gate ``softmax(Dense(R)(x))`` instead of the tanh indicator.  Parameter pytree: ``{"rbf_list":
     {centers[R,K,D], log_sigs[R,K]}, "linear": {kernel[K,O], bias[O]}, "cluster": {kernel[D,R], bias[R]}}``.
     ``apply`` returns ``(out, logits)`` like the reference module; ``vjp`` is the parameter VJP of both outputs (what
-    ``train_step_fullint_withcluster`` differentiates, scripts/train_nmpc_frenet.py:424-453).  No trained checkpoint
-    of this variant survives in the reference (.MISSING_LARGE_BLOBS) -> parity against the oracle restatement only."""
+    ``train_step_fullint_withcluster`` differentiates, scripts/train_nmpc_frenet.py:424-453).  The reference trains it at
+    R = 500, D = 8, O = 10 (scripts/ckpts/dnmpc_500_clusters/checkpoint_0, K = 10;
+    dnmpc_500_clusters_numk50/checkpoint_100, K = 50); those checkpoints are not in this repository, so parity is
+    against the oracle restatement on synthetic parameters at their shapes (tests/test_gpu_cluster_scale.py)."""
 
     def __init__(self, in_features, out_features, num_kernels, basis_func, num_regions, use_float64: bool = False, **_unused):
         _no_frozen("ClusterWCRBFNet", _unused)

@@ -599,7 +599,8 @@ def test_deeper_wcrbfnet_forward(gpu, B):
 @pytest.mark.parametrize("R,K,O,B", [(11, 20, 10, 500), (2, 64, 2, 70), (1, 33, 5, 130), (64, 8, 10, 3000)])
 def test_cluster_wcrbfnet_forward(gpu, R, K, O, B):
     """ClusterWCRBFNet (model.py:341-414): softmax gate kernel + fused forward with external region
-    weights, against the float64 restatement.  No trained checkpoint of this variant survives in the reference."""
+    weights, against the float64 restatement.  The reference's R = 500 checkpoints are not in this repository; their
+    shapes are tested on synthetic parameters in test_gpu_cluster_scale.py."""
     from irbfn_amd.model import ClusterWCRBFNet
     rng = np.random.default_rng(R * 7 + K)
     D = 8

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from _cluster_util import CLEAVES, cluster_case as _cluster_case, t64 as _t64
 from conftest import load_ckpt_fixture
 from irbfn_amd import configs, distributed, train
 from irbfn_amd.model import WCRBFNet
@@ -201,26 +202,6 @@ def test_deeper_wcrbfnet_vjp_on_the_reference_checkpoint(gpu):
             assert torch.equal(a[grp][name], a2[grp][name])
             e = np.abs(got - ref).max() / (np.abs(ref).max() + 1e-300)
             assert e <= 2e-4, (grp, name, e)
-
-
-def _cluster_case(seed, R=11, K=20, O=10, B=400, D=8):
-    rng = np.random.default_rng(seed)
-    cfg = {"in_features": D, "out_features": O, "num_kernels": K, "basis_func": "gaussian", "num_regions": R}
-    params = {"params": {
-        "rbf_list": {"centers": rng.uniform(-2, 2, size=(R, K, D)).astype(np.float32),
-                     "log_sigs": rng.uniform(0.5, 1.5, size=(R, K)).astype(np.float32)},
-        "linear": {"kernel": (rng.normal(size=(K, O)) * 0.3).astype(np.float32), "bias": (rng.normal(size=(O,)) * 0.1).astype(np.float32)},
-        "cluster": {"kernel": rng.normal(size=(D, R)).astype(np.float32), "bias": rng.normal(size=(R,)).astype(np.float32)}}}
-    x = rng.uniform(-2, 2, size=(B, D)).astype(np.float32)
-    return rng, cfg, params, x
-
-
-CLEAVES = LEAVES + (("cluster", "kernel"), ("cluster", "bias"))
-
-
-def _t64(params, requires_grad=True):
-    return {"params": {k: {n: torch.tensor(np.asarray(v, np.float64), requires_grad=requires_grad) for n, v in d.items()}
-                       for k, d in params["params"].items()}}
 
 
 @pytest.mark.parametrize("R,K,O,B", [(11, 20, 10, 400), (2, 64, 2, 70), (1, 33, 5, 130), (16, 8, 16, 1500)])
