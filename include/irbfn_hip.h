@@ -122,7 +122,8 @@ typedef enum irbfn_option {
                                   1: only the first one does and later calls keep its verdict -- for training loops, which re-bind every step.
                                   The kernels test the device-side verdict themselves and fall back to the VALU distances / to K2h, so a stale
                                   host verdict costs speed, never correctness */
-  IRBFN_OPT_COUNT = 16
+  IRBFN_OPT_VJPX_KERNEL = 16,  /* irbfn_vjpx_kernel below; default IRBFN_VJPX_AUTO (15 is a retired number) */
+  IRBFN_OPT_COUNT = 17
 } irbfn_option;
 typedef enum irbfn_fwd_kernel {
   IRBFN_FWD_AUTO = 0, /* B <= 64: K1s; sparse multi-region gate: K1r; one region + fast basis: K1g (d <= 8, parameters inside its budget; O <= 16:
@@ -142,6 +143,12 @@ typedef enum irbfn_vjp_kernel { IRBFN_VJP_AUTO = 0, IRBFN_VJP_K2 = 1, IRBFN_VJP_
  * K2M: hbar and dW on the f32 matrix cores (full f32 operands), one region, gaussian / inverse quadratic / inverse multiquadric,
  * padded d in {3, 4, 7, 8}, 16 < O <= 128 -- forced only, IRBFN_VJP_AUTO never selects it.
  * A forced kernel that cannot take the net answers IRBFN_ERR_UNSUPPORTED at the call that would launch it. */
+typedef enum irbfn_vjpx_kernel { IRBFN_VJPX_AUTO = 0, IRBFN_VJPX_K5 = 1, IRBFN_VJPX_K5M = 2 } irbfn_vjpx_kernel;
+/* Kernels of irbfn_net_vjp_x.  K5 (rbf_vjpx_qlane): all-float32 VALU, every net the forward's K1 takes.  K5M (rbf_vjpx_mfma):
+ * hbar = gout W^T on the f32 matrix cores (full f32 operands); one region, gaussian family / inverse quadratic / inverse
+ * multiquadric, d = 2..8, O <= 128, the net's own gate (not irbfn_net_vjp_x_gamma); IRBFN_VJPX_AUTO selects it for O > 16,
+ * where it was measured ahead of K5 (profiles/vjp_x.txt), otherwise K5.  A forced K5M on a net it does not take answers
+ * IRBFN_ERR_UNSUPPORTED at the call. */
 int irbfn_net_set_option(irbfn_net* net, int option, int value);
 int irbfn_net_get_option(const irbfn_net* net, int option, int* value_out);
 
@@ -159,8 +166,7 @@ int64_t irbfn_net_vjp_workspace_bytes(const irbfn_net* net, int64_t B);
 /* Parameter VJP: replaces `jax.value_and_grad(loss_fn)(state.params)` restricted to the network
  * (scripts/train_nmpc.py:297-298, scripts/train_nmpc_frenet.py:388-389,416-417).
  * Cotangent gout_dev[B,O] -> g_centers[R,K,D], g_log_sigs[R,K], g_kernel[K,O], g_bias[O]
- * (overwritten, not accumulated).  Gradients w.r.t. x are never taken by the reference and are
- * not produced.  Deterministic (no float atomics). */
+ * (overwritten, not accumulated).  The gradient w.r.t. x is irbfn_net_vjp_x below.  Deterministic (no float atomics). */
 int irbfn_net_vjp(irbfn_net* net, const float* x_dev, const float* gout_dev, float* g_centers_dev,
                   float* g_log_sigs_dev, float* g_kernel_dev, float* g_bias_dev, int64_t B,
                   void* workspace_dev, int64_t workspace_bytes, void* stream);
@@ -175,6 +181,16 @@ int irbfn_net_vjp(irbfn_net* net, const float* x_dev, const float* gout_dev, flo
 int irbfn_net_vjp_frozen(irbfn_net* net, const float* x_dev, const float* gout_dev, float* g_centers_dev,
                          float* g_log_sigs_dev, float* g_kernel_dev, float* g_bias_dev, int64_t B,
                          void* workspace_dev, int64_t workspace_bytes, void* stream);
+
+/* Query VJP: `jax.vjp(lambda x: WCRBFNet.apply(params, x), x)[1](gout)` -- nothing in the reference takes this gradient
+ * (its losses differentiate the parameters only); it is what the sensitivity d u / d state of the predicted controls,
+ * gradient-based refinement of a query through net + roll-out (irbfn_rollout_vjp returns the gradient of the whole input row)
+ * and composition under an autodiff framework need.  Cotangent gout_dev[B,O] -> gx_dev[B,D] (overwritten), RBF term and the
+ * term through the smooth region gate (model.py:42-95).  No workspace, deterministic, B = 0 is a no-op; rows are independent
+ * (NaN / Inf in one query or cotangent row stay in that row).  A query exactly on a centre: that pair contributes 0 -- the
+ * limit for every basis but linear / poisson_one / poisson_two, whose derivative in d^2 diverges there (jax.grad: NaN).
+ * Kernel: IRBFN_OPT_VJPX_KERNEL. */
+int irbfn_net_vjp_x(irbfn_net* net, const float* x_dev, const float* gout_dev, float* gx_dev, int64_t B, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Roll-outs.  Replace integrate_st_mult (dynamics.py:94-100), dynamic_st_onestep_aux (:103-187),
@@ -340,6 +356,12 @@ int irbfn_net_forward_gamma(irbfn_net* net, const float* x_dev, const float* gam
 int irbfn_net_vjp_gamma(irbfn_net* net, const float* x_dev, const float* gamma_dev, const float* gout_dev,
                         float* g_centers_dev, float* g_log_sigs_dev, float* g_kernel_dev, float* g_bias_dev, float* dgamma_dev,
                         int64_t B, void* workspace_dev, int64_t workspace_bytes, void* stream);
+/* irbfn_net_vjp_x with caller-provided region weights gamma_dev [B,R] (`jax.vjp` of ClusterWCRBFNet's fused stage,
+ * model.py:405-412, w.r.t. x at fixed gamma; nothing in the reference takes it): gx_dev [B,D] holds the RBF term only; if
+ * dgamma_dev is not NULL it receives the cotangent of the weights, dgamma[b,r] = sum_k (gout W^T)[b,k] phi[b,r,k] (any O).
+ * The softmax / Dense chain of the gate back to x is the caller's (a [B,R] x [R,D] product).  Always K5. */
+int irbfn_net_vjp_x_gamma(irbfn_net* net, const float* x_dev, const float* gamma_dev, const float* gout_dev,
+                          float* gx_dev, float* dgamma_dev, int64_t B, void* stream);
 int64_t irbfn_cluster_gate_vjp_workspace_bytes(int D, int R);
 int irbfn_cluster_gate_vjp(const float* x_dev, const float* gamma_dev, const float* dgamma_dev, const float* glogits_dev,
                            float* dlogits_dev, float* g_wc_dev, float* g_bc_dev, int64_t B, int D, int R,
@@ -387,6 +409,12 @@ int irbfn_f64_vjp(const irbfn_f64_card* card, const double* centers_dev, const d
                   const double* x_dev, const double* gout_dev, double* g_centers_dev, double* g_log_sigs_dev,
                   double* g_kernel_dev, double* g_bias_dev, int64_t B, void* workspace_dev, int64_t workspace_bytes,
                   void* stream);
+/* irbfn_net_vjp_x in float64 (`jax.vjp` of apply w.r.t. x under jax_enable_x64; nothing in the reference takes it):
+ * gout [B,O] -> gx [B,D] (overwritten), RBF and gate term, the gate from the float64 card; any O, all 13 bases (the same
+ * convention for a query on a centre).  One lane per query; needs no workspace: workspace_dev may be NULL. */
+int irbfn_f64_vjp_x(const irbfn_f64_card* card, const double* centers_dev, const double* log_sigs_dev,
+                    const double* kernel_dev, const double* x_dev, const double* gout_dev, double* gx_dev, int64_t B,
+                    void* workspace_dev, int64_t workspace_bytes, void* stream);
 
 /* Diagnostics */
 int irbfn_abi_version(void);

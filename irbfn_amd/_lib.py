@@ -19,9 +19,11 @@ BASIS_ENUM = {"gaussian": 0, "gaussian_wide": 1, "gaussian_wider": 2, "inverse_q
 ROLLOUT_ST_SELECT, ROLLOUT_ST_KS, ROLLOUT_FULLINT, ROLLOUT_FRENET_LS, ROLLOUT_SPIRAL = 0, 1, 2, 3, 4
 
 # irbfn_option / irbfn_fwd_kernel / irbfn_vjp_kernel (include/irbfn_hip.h; the missing option numbers are retired)
-OPTIONS = {"fwd_kernel": 0, "fwd_f16_terms": 2, "fwd_f16_s": 7, "fwd_f16_qg": 8, "vjp_kernel": 9, "tick_fused": 13, "gram_sticky": 14}
+OPTIONS = {"fwd_kernel": 0, "fwd_f16_terms": 2, "fwd_f16_s": 7, "fwd_f16_qg": 8, "vjp_kernel": 9, "tick_fused": 13, "gram_sticky": 14,
+           "vjpx_kernel": 16}
 FWD_AUTO, FWD_K1, FWD_K1M, FWD_K1H, FWD_K1R, FWD_K1G = 0, 1, 2, 3, 4, 5
 VJP_AUTO, VJP_K2, VJP_K2H, VJP_K2R, VJP_K2G, VJP_K2M = 0, 1, 2, 3, 4, 5
+VJPX_AUTO, VJPX_K5, VJPX_K5M = 0, 1, 2
 
 # every symbol include/irbfn_hip.h declares: (name, restype, argtypes)
 _vp, _fp, _ip, _i, _i64, _f, _d = C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
@@ -36,6 +38,8 @@ SIGNATURES = {
     "irbfn_net_vjp_workspace_bytes": (_i64, [_vp, _i64]),
     "irbfn_net_vjp": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _vp, _i64, _vp]),
     "irbfn_net_vjp_frozen": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _vp, _i64, _vp]),
+    "irbfn_net_vjp_x": (_i, [_vp, _fp, _fp, _fp, _i64, _vp]),
+    "irbfn_net_vjp_x_gamma": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i64, _vp]),
     "irbfn_rollout_state_dim": (_i, [_i]),
     "irbfn_rollout_input_dim": (_i, [_i, _i]),
     "irbfn_rollout_forward": (_i, [_i, _fp, _fp, _fp, _i64, _i, _vp]),
@@ -72,6 +76,7 @@ SIGNATURES = {
     "irbfn_f64_workspace_bytes": (_i64, [_vp, _i64, _i]),
     "irbfn_f64_forward": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _vp, _i64, _vp]),
     "irbfn_f64_vjp": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _vp, _i64, _vp]),
+    "irbfn_f64_vjp_x": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _vp, _i64, _vp]),
     "irbfn_abi_version": (_i, []),
     "irbfn_device_count": (_i, []),
     "irbfn_last_hip_error": (_i, []),

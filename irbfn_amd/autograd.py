@@ -1,8 +1,10 @@
 """``torch.autograd`` surface -- the counterpart of ``jax.grad`` over the reference hot path.
 
 ``wcrbf_apply(net, centers, log_sigs, kernel, bias, x)`` is differentiable w.r.t. the four parameter
-leaves (never w.r.t. x: the reference never takes that gradient); the roll-outs are
-differentiable w.r.t. their input rows.  Backward passes call the hand-written VJP kernels.
+leaves and w.r.t. the query x (``net.vjp_x``: the reference never takes that gradient, SURVEY 8 a-5, but
+whatever sits in front of the net under autograd needs it; it is computed only when x requires grad); the
+roll-outs are differentiable w.r.t. their input rows, so query -> net -> roll-out is differentiable end to
+end.  Backward passes call the hand-written VJP kernels.
 """
 from __future__ import annotations
 
@@ -23,9 +25,11 @@ class _WCRBFApply(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         (x,) = ctx.saved_tensors
-        g = ctx.net.vjp(ctx.params, x, gout.contiguous())["params"]
+        gout = gout.contiguous()
+        g = ctx.net.vjp(ctx.params, x, gout)["params"]
+        gx = ctx.net.vjp_x(ctx.params, x, gout) if ctx.needs_input_grad[5] else None
         return (None, g["rbf_list"]["centers"], g["rbf_list"]["log_sigs"], g["linear"]["kernel"],
-                g["linear"]["bias"], None)
+                g["linear"]["bias"], gx)
 
 
 def wcrbf_apply(net, params: dict, x: torch.Tensor) -> torch.Tensor:

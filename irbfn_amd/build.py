@@ -45,6 +45,13 @@ UNITS = [
     ("rbf_vjp_f16.hip", "rbf_vjp_f16.o", ["-fno-slp-vectorize"]),
     ("rbf_vjp_gram.hip", "rbf_vjp_gram.o", ["-fno-slp-vectorize"]),
     ("rbf_vjp_mfma.hip", "rbf_vjp_mfma.o", []),        # K2m: hbar and dW on the f32 matrix cores   # VGPR operands: plain FMAs (2.4 cyc) beat packed (4.7) + pairing moves
+    # x-VJP: plan + launchers, K5 per compiled D (as K1), K5m
+    ("rbf_vjpx.hip", "rbf_vjpx.o", []),
+    ("rbf_vjpx_kernels.hip", "rbf_vjpx_d3.o", ["-DIRBFN_INST_D=3"] + _SLP),
+    ("rbf_vjpx_kernels.hip", "rbf_vjpx_d4.o", ["-DIRBFN_INST_D=4"] + _SLP),
+    ("rbf_vjpx_kernels.hip", "rbf_vjpx_d7.o", ["-DIRBFN_INST_D=7"] + _SLP),
+    ("rbf_vjpx_kernels.hip", "rbf_vjpx_d8.o", ["-DIRBFN_INST_D=8"] + _SLP),
+    ("rbf_vjpx_mfma.hip", "rbf_vjpx_mfma.o", []),
     # 12-step unrolled groups of the roll-out; no SLP: v_pk_* cost more than the two plain VALU instructions they replace
     ("rollout.hip", "rollout.o", ["-mllvm", "-pragma-unroll-threshold=100000", "-fno-slp-vectorize"]),
     # the fused planning tick: wide K1h forward + K3p roll-out core in one kernel (the roll-out's flags: 50-knot register arrays)

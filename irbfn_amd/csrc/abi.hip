@@ -152,7 +152,8 @@ static bool option_known(int option) {
     case IRBFN_OPT_FWD_F16_QG:
     case IRBFN_OPT_VJP_KERNEL:
     case IRBFN_OPT_TICK_FUSED:
-    case IRBFN_OPT_GRAM_STICKY: return true;
+    case IRBFN_OPT_GRAM_STICKY:
+    case IRBFN_OPT_VJPX_KERNEL: return true;
     default: return false;
   }
 }
@@ -162,6 +163,7 @@ int irbfn_net_set_option(irbfn_net* net, int option, int value) {
   switch (option) {
     case IRBFN_OPT_FWD_KERNEL: if (value > IRBFN_FWD_K1G) return IRBFN_ERR_BAD_ARG; break;
     case IRBFN_OPT_VJP_KERNEL: if (value > IRBFN_VJP_K2M) return IRBFN_ERR_BAD_ARG; break;
+    case IRBFN_OPT_VJPX_KERNEL: if (value > IRBFN_VJPX_K5M) return IRBFN_ERR_BAD_ARG; break;
     case IRBFN_OPT_FWD_F16_TERMS: if (value != 1 && value != 2 && value != 3) return IRBFN_ERR_BAD_ARG; break;
     case IRBFN_OPT_FWD_F16_S:
     case IRBFN_OPT_FWD_F16_QG: if (value > 16) return IRBFN_ERR_BAD_ARG; break;
@@ -235,6 +237,23 @@ int irbfn_net_vjp_gamma(irbfn_net* net, const float* x_dev, const float* gamma_d
                       workspace_bytes, as_stream(stream), B > 0 ? gamma_dev : nullptr);
   if (rc == IRBFN_OK && dgamma_dev) rc = launch_dgamma(net, x_dev, gout_dev, dgamma_dev, B, as_stream(stream));
   return rc;
+}
+
+int irbfn_net_vjp_x(irbfn_net* net, const float* x_dev, const float* gout_dev, float* gx_dev, int64_t B, void* stream) {
+  if (!net || B < 0) return IRBFN_ERR_BAD_ARG;
+  if (B == 0) return IRBFN_OK;
+  if (!x_dev || !gout_dev || !gx_dev) return IRBFN_ERR_BAD_ARG;
+  if (!net->has_params) return IRBFN_ERR_NO_PARAMS;
+  return launch_vjp_x(net, x_dev, nullptr, gout_dev, gx_dev, nullptr, B, as_stream(stream));
+}
+
+int irbfn_net_vjp_x_gamma(irbfn_net* net, const float* x_dev, const float* gamma_dev, const float* gout_dev,
+                          float* gx_dev, float* dgamma_dev, int64_t B, void* stream) {
+  if (!net || B < 0) return IRBFN_ERR_BAD_ARG;
+  if (B == 0) return IRBFN_OK;
+  if (!x_dev || !gamma_dev || !gout_dev || !gx_dev) return IRBFN_ERR_BAD_ARG;
+  if (!net->has_params) return IRBFN_ERR_NO_PARAMS;
+  return launch_vjp_x(net, x_dev, gamma_dev, gout_dev, gx_dev, dgamma_dev, B, as_stream(stream));
 }
 
 int64_t irbfn_cluster_gate_vjp_workspace_bytes(int D, int R) {

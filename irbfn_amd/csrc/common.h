@@ -225,6 +225,10 @@ int launch_vjp_mfma(irbfn_net* net, const float* x, const float* gout, int64_t B
                     hipStream_t s);
 // irbfn_net_vjp_kernel_supported: 1 if `kernel` forced on this net takes a batch of B, else 0
 int vjp_kernel_supported(const irbfn_net* net, int kernel, int64_t B);
+// x-VJP (rbf_vjpx.hip): gamma null = the net's tanh gate (gate term included); else caller-provided region weights, the RBF term
+// only and, if dgamma is not null, q[b,r]
+int launch_vjp_x(irbfn_net* net, const float* x, const float* gamma, const float* gout, float* gx, float* dgamma, int64_t B,
+                 hipStream_t s);
 int launch_dgamma(irbfn_net* net, const float* x, const float* gout, float* dgamma, int64_t B, hipStream_t s);
 int64_t cluster_gate_vjp_workspace_bytes(int D, int R);
 int launch_cluster_gate_vjp(const float* x, const float* gamma, const float* dgamma, const float* glogits, float* dlogits,

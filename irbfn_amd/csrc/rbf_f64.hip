@@ -144,6 +144,102 @@ __global__ __launch_bounds__(64) void f64_forward_kernel(const F64Card c, const 
   }
 }
 
+// d phi / d(d^2) for the x-VJP, in the forms that stay finite where the limit is; linear / poisson_one / poisson_two diverge at
+// d = 0 and return 0 there (the convention of the float32 kernels, rbf_vjpx.h)
+__device__ __forceinline__ double dphi_dd2_x_f64(double phi, double d2, int basis) {
+  const double d = sqrt(d2);
+  switch (basis) {
+    case IRBFN_GAUSSIAN: return -phi;
+    case IRBFN_GAUSSIAN_WIDE: return -0.1 * phi;
+    case IRBFN_GAUSSIAN_WIDER: return -0.01 * phi;
+    case IRBFN_INVERSE_QUADRATIC: return -(phi * phi);
+    case IRBFN_INVERSE_MULTIQUADRIC: return -0.5 * phi * phi * phi;
+    case IRBFN_MULTIQUADRIC: return 0.5 / phi;
+    case IRBFN_QUADRATIC: return 1.0;
+    case IRBFN_LINEAR: return d > 0.0 ? 0.5 / d : (d == 0.0 ? 0.0 : d);
+    case IRBFN_SPLINE: return log(d + 1.0) + 0.5 * d / (d + 1.0);
+    case IRBFN_POISSON_ONE: return d > 0.0 ? (2.0 - d) * exp(-d) * (0.5 / d) : (d == 0.0 ? 0.0 : d);
+    case IRBFN_POISSON_TWO: return d > 0.0 ? (2.0 * d - 1.0 - 0.5 * d2) * exp(-d) * (0.5 / d) : (d == 0.0 ? 0.0 : d);
+    case IRBFN_MATERN32: return -1.5 * exp(-1.7320508075688772 * d);
+    case IRBFN_MATERN52: return -(5.0 / 6.0) * (1.0 + 2.23606797749979 * d) * exp(-2.23606797749979 * d);
+    default: return 0.0;
+  }
+}
+
+// x-VJP (rbf_vjpx.h for the formula): one lane per query, centres / widths / weights wave-uniform; the gate and its logarithmic
+// derivative are evaluated per region in the tanh form of the reference (model.py:83-85)
+__global__ __launch_bounds__(64) void vjpx_f64(const F64Card c, const double* __restrict__ centers, const double* __restrict__ log_sigs,
+                                               const double* __restrict__ kernel, const double* __restrict__ x,
+                                               const double* __restrict__ g, double* __restrict__ gx, long B) {
+  const int lane = threadIdx.x;
+  const long b = (long)blockIdx.x * kWave + lane;
+  const long bb = b < B ? b : B - 1;
+  double xq[kMaxD], acc[kMaxD], gq[kF64OT];
+#pragma unroll
+  for (int j = 0; j < kMaxD; ++j) {
+    xq[j] = j < c.D ? x[bb * c.D + j] : 0.0;
+    acc[j] = 0.0;
+  }
+  const bool greg = c.O <= kF64OT;               // the cotangent row in registers; wider rows are read per centre
+#pragma unroll
+  for (int o = 0; o < kF64OT; ++o) gq[o] = (greg && o < c.O) ? g[bb * c.O + o] : 0.0;
+  const double* grow = g + bb * c.O;
+  for (int r = 0; r < c.R; ++r) {
+    double gam = 0.0, dl[kMaxD];                 // regions without a range stay 0 (model.py:70)
+#pragma unroll
+    for (int d = 0; d < kMaxD; ++d) dl[d] = 0.0;
+    if (r < c.n_ranges) {
+      gam = 1.0;
+#pragma unroll
+      for (int d = 0; d < kMaxD; ++d) {
+        if (d < c.nsplit) {
+          const int e = d * c.max_ranges + c.dim_ranges[r * c.nsplit + d];
+          const double t1 = tanh(c.delta[d] * (xq[d] - c.lo[e])), t2 = tanh(c.delta[d] * (c.hi[e] - xq[d]));
+          gam *= ((t1 + 1.0) / 2.0) * ((t2 + 1.0) / 2.0);
+          dl[d] = c.delta[d] * (t2 - t1);        // d log gamma_r / d x_d
+        }
+      }
+    }
+    double q = 0.0, racc[kMaxD];
+#pragma unroll
+    for (int j = 0; j < kMaxD; ++j) racc[j] = 0.0;
+    for (int k = 0; k < c.K; ++k) {
+      const int n = r * c.K + k;
+      const double* cp = centers + (size_t)n * c.D;
+      double df[kMaxD], r2 = 0.0;
+#pragma unroll
+      for (int j = 0; j < kMaxD; ++j) {
+        df[j] = j < c.D ? xq[j] - cp[j] : 0.0;
+        r2 = fma(df[j], df[j], r2);
+      }
+      const double s2 = exp(-2.0 * log_sigs[n]);
+      const double d2 = r2 * s2;
+      const double phi = basis_f64(d2, c.basis);
+      const double* wr = kernel + (size_t)k * c.O;
+      double hb = 0.0;
+      if (greg) {
+#pragma unroll
+        for (int o = 0; o < kF64OT; ++o)
+          if (o < c.O) hb = fma(gq[o], wr[o], hb);
+      } else {
+        for (int o = 0; o < c.O; ++o) hb = fma(grow[o], wr[o], hb);
+      }
+      q = fma(hb, phi, q);
+      const double s = 2.0 * hb * dphi_dd2_x_f64(phi, d2, c.basis) * s2;
+#pragma unroll
+      for (int j = 0; j < kMaxD; ++j) racc[j] = fma(s, df[j], racc[j]);
+    }
+    const double gq_r = gam * q;
+#pragma unroll
+    for (int j = 0; j < kMaxD; ++j) acc[j] += gam * racc[j] + gq_r * dl[j];
+  }
+  if (b < B) {
+#pragma unroll
+    for (int j = 0; j < kMaxD; ++j)
+      if (j < c.D) gx[b * c.D + j] = acc[j];
+  }
+}
+
 // parameter VJP: one lane per centre, the block's query slice streams past it (wave-uniform rows); O <= 16
 struct F64VjpArgs {
   const double* centers; const double* log_sigs; const double* kernel;
@@ -356,6 +452,21 @@ int irbfn_f64_vjp(const irbfn_f64_card* card, const double* centers_dev, const d
                      g_centers_dev, g_log_sigs_dev, g_kernel_dev);
   IRBFN_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(f64_colsum_kernel, dim3(c.O), dim3(256), 0, s, gout_dev, g_bias_dev, (long)B, c.O);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
+
+int irbfn_f64_vjp_x(const irbfn_f64_card* card, const double* centers_dev, const double* log_sigs_dev, const double* kernel_dev,
+                    const double* x_dev, const double* gout_dev, double* gx_dev, int64_t B, void* workspace_dev,
+                    int64_t workspace_bytes, void* stream) {
+  (void)workspace_dev; (void)workspace_bytes;
+  if (!f64_card_ok(card) || B < 0) return IRBFN_ERR_BAD_ARG;
+  if (B == 0) return IRBFN_OK;
+  if (!centers_dev || !log_sigs_dev || !kernel_dev || !x_dev || !gout_dev || !gx_dev) return IRBFN_ERR_BAD_ARG;
+  const F64Card c = f64_card(card);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(vjpx_f64, dim3((unsigned)((B + kWave - 1) / kWave)), dim3(kWave), 0, s, c, centers_dev, log_sigs_dev, kernel_dev,
+                     x_dev, gout_dev, gx_dev, (long)B);
   IRBFN_HIP_CHECK(hipGetLastError());
   return IRBFN_OK;
 }

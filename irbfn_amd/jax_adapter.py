@@ -2,7 +2,7 @@
 ``state.apply_fn(state.params, x)`` inside jitted train / predict steps, src/irbfn_mpc/irbfn_planner.py:29-32,
 scripts/train_nmpc.py:268-299).
 
-The forward and the parameter VJP run in the HIP kernels behind ``WCRBFNet``; JAX sees one primitive with a custom VJP that
+The forward, the parameter VJP and the query VJP run in the HIP kernels behind ``WCRBFNet``; JAX sees one primitive with a custom VJP that
 calls out through ``jax.pure_callback``.  JAX is NOT part of the build image (nothing here can be exercised there:
 ``tests/test_jax_adapter_cpu.py`` skips without it), so this module is the written-out form of INTEGRATION.md section 3 and
 imports JAX only when used."""
@@ -13,7 +13,8 @@ import numpy as np
 
 def make_irbfn(net):
     """net: ``irbfn_amd.model.WCRBFNet``.  Returns ``irbfn(params, x) -> out[B, O]`` usable under ``jax.jit`` and ``jax.grad``
-    (gradients w.r.t. ``params``; the reference never differentiates w.r.t. ``x`` -- zeros are returned for it)."""
+    (gradients w.r.t. ``params`` and, from a second callback into ``net.vjp_x``, w.r.t. ``x``; like the rest of this module
+    the x-cotangent has not been executed: JAX is absent from the build image)."""
     try:
         import jax
         import jax.numpy as jnp
@@ -41,7 +42,9 @@ def make_irbfn(net):
             out = grads if "params" in p else inner
             return jax.tree_util.tree_map(lambda a: np.asarray(a, dtype), out)
         grads = jax.pure_callback(cb, shapes, params, x, g)
-        return grads, jnp.zeros_like(x)
+        gx = jax.pure_callback(lambda p, xx, gg: np.asarray(net.vjp_x(host(p), np.asarray(xx), np.asarray(gg)), dtype),
+                               jax.ShapeDtypeStruct(x.shape, dtype), params, x, g)
+        return grads, gx
 
     irbfn.defvjp(fwd, bwd)
     return irbfn

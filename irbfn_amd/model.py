@@ -503,7 +503,7 @@ class WCRBFNet:
     def vjp(self, params: dict, x, gout, out: Optional[dict] = None) -> dict:
         """Parameter VJP: cotangent gout[B,O] -> gradient pytree (same structure as ``params``).
         Replaces ``jax.value_and_grad(loss_fn)(params)`` restricted to the network
-        (scripts/train_nmpc.py:297-298).  Gradients w.r.t. x are never taken by the reference."""
+        (scripts/train_nmpc.py:297-298).  The gradient w.r.t. x is ``vjp_x``."""
         if self.use_float64 and out is None:
             return self.vjp64(params, x, gout)
         torch = _lib.require_gpu()
@@ -548,6 +548,65 @@ class WCRBFNet:
             _lib.check(st, "irbfn_net_vjp")
         conv = (lambda t: t) if out is not None else (lambda t: like_input(t, x, torch))
         return self._grad_tree(full, conv)
+
+    # ------------------------------------------------------------------ query VJP
+    def _check_xg(self, xd, gd):
+        B = xd.shape[0]
+        if xd.dim() != 2 or xd.shape[1] != self.in_features:
+            raise ValueError(f"x must have shape (B, {self.in_features}), got {tuple(xd.shape)}")
+        if tuple(gd.shape) != (B, self.out_features):
+            raise ValueError(f"gout must have shape ({B}, {self.out_features}), got {tuple(gd.shape)}")
+        return B
+
+    def vjp_x(self, params: dict, x, gout):
+        """Query VJP: cotangent gout[B,O] -> gx[B,D] = ``jax.vjp(lambda x: apply(params, x), x)[1](gout)``, the RBF term and
+        the term through the smooth region gate (``irbfn_net_vjp_x``; nothing in the reference takes this gradient).  Numpy in,
+        numpy out; cuda in, cuda out.  ``use_float64=True``: evaluated in float64 (``vjp_x64``).  Frozen-leaf nets need
+        nothing special: the kernel reads the bound images."""
+        if self.use_float64:
+            return self.vjp_x64(params, x, gout)
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        self._warn_if_float64(params)
+        self.bind(params)
+        xd, gd = to_device_f32(x, torch), to_device_f32(gout, torch)
+        B = self._check_xg(xd, gd)
+        gx = torch.empty((B, self.in_features), dtype=torch.float32, device=xd.device)
+        if B:
+            st = lib.irbfn_net_vjp_x(self._handle(torch), _ptr(xd), _ptr(gd), _ptr(gx), B, _stream_ptr(torch))
+            _lib.check(st, "irbfn_net_vjp_x")
+        return like_input(gx, x, torch)
+
+    def vjp_x64(self, params: dict, x, gout):
+        """``vjp_x`` in float64 (``irbfn_f64_vjp_x``) -> float64 [B,D]; any out_features."""
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        p = _inner(params)
+        self._check_shapes(p)
+        card = self._f64_card(torch)[0]
+        c, l, k = (self._dev_f64(a, torch) for a in self._leaves(p, torch, torch.float64)[:3])
+        xd, gd = self._dev_f64(x, torch), self._dev_f64(gout, torch)
+        B = self._check_xg(xd, gd)
+        gx = torch.empty((B, self.in_features), dtype=torch.float64, device=xd.device)
+        st = lib.irbfn_f64_vjp_x(C.byref(card), _ptr(c), _ptr(l), _ptr(k), _ptr(xd), _ptr(gd), _ptr(gx), B, None, 0,
+                                 _stream_ptr(torch))
+        _lib.check(st, "irbfn_f64_vjp_x")
+        return like_input(gx, x, torch)
+
+    def input_jacobian(self, params: dict, x):
+        """d apply(params, x)[b, o] / d x[b, d] -> [B, O, D]: the sensitivity of every output to the query.  Built from
+        ``out_features`` one-hot cotangents, i.e. O launches of ``vjp_x`` (fine for the reference's O <= 10)."""
+        torch = _lib.require_gpu()
+        f64 = self.use_float64
+        xd = self._dev_f64(x, torch) if f64 else to_device_f32(x, torch)
+        B, O = xd.shape[0], self.out_features
+        jac = torch.empty((B, O, self.in_features), dtype=xd.dtype, device=xd.device)
+        g = torch.zeros((B, O), dtype=xd.dtype, device=xd.device)
+        for o in range(O):
+            g[:, o] = 1.0
+            jac[:, o, :] = self.vjp_x(params, xd, g)
+            g[:, o] = 0.0
+        return like_input(jac, x, torch)
 
     def last_launch(self) -> dict:
         torch = _lib.require_gpu()
@@ -704,6 +763,37 @@ class DeeperWCRBFNet:
                            "linear_pre2": {"kernel": conv(gw2), "bias": conv(gb2)},
                            "linear": {"kernel": conv(gw3), "bias": conv(gb3)}}}
 
+    def vjp_x(self, params: dict, x, gout, h1=None):
+        """Query VJP of the whole model: gout[B,O] -> gx[B,D].  The head backward gives the cotangent of linear_pre1's output
+        (``irbfn_mlp_head_vjp``; its parameter gradients are by-products here), the stage's ``vjp_x`` takes it to x.
+        h1: the stage output of ``apply_with_hidden``, as for ``vjp``."""
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        p = _inner(params)
+        H, O = self.HIDDEN, self.out_features
+        stage_params = {"rbf_list": p["rbf_list"], "linear": p["linear_pre1"]}
+        xd, gd = to_device_f32(x, torch), to_device_f32(gout, torch)
+        B = xd.shape[0]
+        if tuple(gd.shape) != (B, O):
+            raise ValueError(f"gout must have shape ({B}, {O})")
+        if h1 is None:
+            h1 = self.stage.apply(stage_params, xd)
+        elif not isinstance(h1, torch.Tensor) or tuple(h1.shape) != (B, H) or h1.dtype != torch.float32 or not h1.is_cuda \
+                or not h1.is_contiguous():
+            raise ValueError(f"vjp_x h1= must be the contiguous float32 cuda stage output [{B}, {H}] of apply_with_hidden")
+        w2, b2, w3 = (to_device_f32(a, torch) for a in (p["linear_pre2"]["kernel"], p["linear_pre2"]["bias"], p["linear"]["kernel"]))
+        dev = xd.device
+        new = lambda *shp: torch.empty(shp, dtype=torch.float32, device=dev)
+        gh1, gw2, gb2, gw3, gb3 = new(B, H), new(H, H), new(H), new(H, O), new(O)
+        nbytes = int(lib.irbfn_mlp_head_vjp_workspace_bytes(H, H, O))
+        if nbytes < 0:
+            _lib.check(nbytes, "irbfn_mlp_head_vjp_workspace_bytes")
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        st = lib.irbfn_mlp_head_vjp(_ptr(h1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(gd), _ptr(gh1), _ptr(gw2), _ptr(gb2),
+                                    _ptr(gw3), _ptr(gb3), B, H, H, O, _ptr(ws), nbytes, _stream_ptr(torch))
+        _lib.check(st, "irbfn_mlp_head_vjp")
+        return like_input(self.stage.vjp_x(stage_params, xd, gh1), x, torch)
+
     def vjp(self, params: dict, x, gout, out: Optional[dict] = None, h1=None, stage_vjp_kernel: Optional[int] = None) -> dict:
         """Parameter VJP of the whole model: cotangent gout[B,O] -> gradient pytree with the structure of ``params``
         (what ``jax.value_and_grad`` returns for a DeeperWCRBFNet, scripts/train_nmpc_frenet.py:388-389,416-417).
@@ -757,6 +847,44 @@ class ClusterWCRBFNet:
         st = lib.irbfn_net_forward_gamma(self.stage._handle(torch), _ptr(xd), _ptr(gamma), _ptr(out), B, _stream_ptr(torch))
         _lib.check(st, "irbfn_net_forward_gamma")
         return like_input(out, x, torch), like_input(logits, x, torch)
+
+    def vjp_x(self, params: dict, x, gout, glogits=None):
+        """Query VJP of ``apply``: cotangents gout[B,O] of ``out`` and (optionally) glogits[B,R] of ``logits`` -> gx[B,D].
+        ``irbfn_net_vjp_x_gamma`` gives the RBF term at fixed region weights and the cotangent of those weights; the softmax
+        backward and the [B,R] x [R,D] product with the gate's kernel run in torch on the device."""
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        p = _inner(params)
+        D, R, O = self.in_features, self.num_regions, self.out_features
+        self.stage.bind({"rbf_list": p["rbf_list"], "linear": p["linear"]})
+        xd, gd = to_device_f32(x, torch), to_device_f32(gout, torch)
+        B = xd.shape[0]
+        if tuple(xd.shape) != (B, D) or tuple(gd.shape) != (B, O):
+            raise ValueError(f"x must be [B, {D}] and gout [B, {O}]")
+        wc, bc = to_device_f32(p["cluster"]["kernel"], torch), to_device_f32(p["cluster"]["bias"], torch)
+        if tuple(wc.shape) != (D, R) or tuple(bc.shape) != (R,):
+            raise ValueError(f"params cluster.kernel / bias must be [{D},{R}] / [{R}]")
+        dev = xd.device
+        logits = torch.empty((B, R), dtype=torch.float32, device=dev)
+        gamma = torch.empty((B, R), dtype=torch.float32, device=dev)
+        dgamma = torch.empty((B, R), dtype=torch.float32, device=dev)
+        gx = torch.empty((B, D), dtype=torch.float32, device=dev)
+        if B:
+            stream = _stream_ptr(torch)
+            _lib.check(lib.irbfn_cluster_gate(_ptr(xd), _ptr(wc), _ptr(bc), _ptr(logits), _ptr(gamma), B, D, R, stream),
+                       "irbfn_cluster_gate")
+            st = lib.irbfn_net_vjp_x_gamma(self.stage._handle(torch), _ptr(xd), _ptr(gamma), _ptr(gd), _ptr(gx), _ptr(dgamma), B,
+                                           stream)
+            _lib.check(st, "irbfn_net_vjp_x_gamma")
+            # softmax backward (model.py:402-404), then logits = x Wc + bc
+            dlogits = gamma * (dgamma - (gamma * dgamma).sum(dim=1, keepdim=True))
+            if glogits is not None:
+                gl_in = to_device_f32(glogits, torch)
+                if tuple(gl_in.shape) != (B, R):
+                    raise ValueError(f"glogits must be [B, {R}]")
+                dlogits = dlogits + gl_in
+            gx = gx + dlogits @ wc.t()
+        return like_input(gx, x, torch)
 
     def vjp(self, params: dict, x, gout, glogits=None, out: Optional[dict] = None) -> dict:
         """Parameter VJP of ``apply``: cotangents gout[B,O] of ``out`` and (optionally) glogits[B,R] of ``logits`` ->
