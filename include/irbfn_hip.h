@@ -341,6 +341,15 @@ int irbfn_cluster_gate(const float* x_dev, const float* wc_dev, const float* bc_
 int irbfn_net_forward_gamma(irbfn_net* net, const float* x_dev, const float* gamma_dev, float* out_dev, int64_t B,
                             void* stream);
 
+/* irbfn_plan_tick with caller-provided region weights gamma_dev [B,R]: the planning tick (pred_step -> sign flip of the
+ * mirrored rows -> roll-out, src/irbfn_mpc/irbfn_planner.py:203-212, :487-488) of a ClusterWCRBFNet (model.py:393-412) behind
+ * irbfn_cluster_gate.  One launch of the fused kernel with the roll-out in its epilogue (fast bases, T * S <= 64; controls_dev
+ * may then be NULL); otherwise irbfn_net_forward_gamma -> flip -> split-row roll-out through controls_dev (NULL there:
+ * IRBFN_ERR_BAD_ARG).  mirror_dev / states_dev may be NULL as for irbfn_plan_tick. */
+int irbfn_plan_tick_gamma(irbfn_net* net, int mode, const float* x_dev, const float* gamma_dev,
+                          const int32_t* mirror_dev, const float* state0_dev, const float* dyn_params_host,
+                          float* controls_dev, float* states_dev, int64_t B, int T, void* stream);
+
 /* VJP of ClusterWCRBFNet (the reference trains it: scripts/train_nmpc_frenet.py:424-453).
  * irbfn_net_vjp_gamma: irbfn_net_vjp with caller-provided region weights gamma_dev [B,R] (the softmax gate) instead of
  *   the tanh tables, plus -- if dgamma_dev is not NULL -- the cotangent of those weights,
@@ -376,6 +385,23 @@ int irbfn_softmax_xent(const float* logits_dev, const float* labels_dev, float* 
  * reference).  The VJP of the head is irbfn_mlp_head_vjp below. */
 int irbfn_mlp_head_forward(const float* h1_dev, const float* w2_dev, const float* b2_dev, const float* w3_dev,
                            const float* b3_dev, float* out_dev, int64_t B, int H1, int H2, int O, void* stream);
+
+/* One planning tick of the Deeper planner behind its RBF stage: the head above -> negate the steer-velocity controls [T, 2T)
+ * of mirrored rows (src/irbfn_mpc/irbfn_planner.py:203-204, :487-488) -> roll-out from state0 (:205-212), the chain
+ * IRBFNFrenetPlanner(deeper=True) (:286-298) runs per pose, for B rows in ONE launch where O = 2T <= 16 (the reference's
+ * cards: O = 2 and O = 10): the controls go from the output MFMAs through LDS to the wave's own roll-out, bit-equal to
+ * irbfn_mlp_head_forward -> flip -> irbfn_rollout_forward.  Arguments as for irbfn_plan_tick: mirror_dev may be NULL (no
+ * flip); states_dev may be NULL (controls only, with the flip; state0 / dyn unused; controls_dev required); controls_dev may
+ * be NULL where irbfn_mlp_head_tick_needs_controls is 0.  Modes ST_SELECT, ST_KS, FULLINT, FRENET_LS; H1 = H2 = 64.
+ * O > 16 runs head forward -> flip -> split-row roll-out through controls_dev, which is then required.
+ * irbfn_mlp_head_tick_needs_controls: 1 if the tick goes through the caller's controls buffer (O > 16), 0 if it is one launch,
+ * < 0 on a bad argument (no roll-out mode, T < 1, O != 2T): the counterpart of irbfn_net_tick_needs_controls. */
+int irbfn_mlp_head_tick(const float* h1_dev, const float* w2_dev, const float* b2_dev, const float* w3_dev,
+                        const float* b3_dev, int mode, const int32_t* mirror_dev /* or NULL */,
+                        const float* state0_dev, const float* dyn_params_host,
+                        float* controls_dev /* or NULL */, float* states_dev /* or NULL */,
+                        int64_t B, int H1, int H2, int O, int T, void* stream);
+int irbfn_mlp_head_tick_needs_controls(int mode, int O, int T);
 
 /* VJP of that head (the reference trains the model: scripts/train_nmpc_frenet.py:339-421): gout [B,O] ->
  * gh1 [B,H1] (cotangent of linear_pre1's output = the seed of irbfn_net_vjp on the stage descriptor) and the

@@ -57,6 +57,9 @@ SIGNATURES = {
     "irbfn_plan_queries_cartesian": (_i, [_fp, _fp, _fp, _fp, _ip, _i64, _vp]),
     "irbfn_plan_queries_frenet": (_i, [_fp, _fp, _fp, _fp, _ip, _i64, _vp]),
     "irbfn_plan_tick": (_i, [_vp, _i, _fp, _ip, _fp, _fp, _fp, _fp, _i64, _i, _vp]),
+    "irbfn_mlp_head_tick": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _ip, _fp, _fp, _fp, _fp, _i64, _i, _i, _i, _i, _vp]),
+    "irbfn_mlp_head_tick_needs_controls": (_i, [_i, _i, _i]),
+    "irbfn_plan_tick_gamma": (_i, [_vp, _i, _fp, _fp, _ip, _fp, _fp, _fp, _fp, _i64, _i, _vp]),
     "irbfn_lut_grid_lookup": (_i, [_fp, _ip, _ip, _fp, _fp, _ip, _fp, _i64, _i, _i, _vp]),
     "irbfn_lut_nearest_workspace_bytes": (_i64, [_i64, _i64]),
     "irbfn_lut_nearest": (_i, [_fp, _fp, _fp, _ip, _fp, _fp, _i64, _i64, _i, _i, _vp, _i64, _vp]),

@@ -377,6 +377,46 @@ int irbfn_plan_tick(irbfn_net* net, int mode, const float* x_dev, const int32_t*
                                 as_stream(stream));
 }
 
+int irbfn_mlp_head_tick(const float* h1_dev, const float* w2_dev, const float* b2_dev, const float* w3_dev, const float* b3_dev,
+                        int mode, const int32_t* mirror_dev, const float* state0_dev, const float* dyn_params_host,
+                        float* controls_dev, float* states_dev, int64_t B, int H1, int H2, int O, int T, void* stream) {
+  if (rollout_state_dim(mode) < 0 || B < 0 || T < 1) return IRBFN_ERR_BAD_ARG;
+  if (B == 0) return IRBFN_OK;
+  if (!h1_dev || !w2_dev || !b2_dev || !w3_dev || !b3_dev || (states_dev && !state0_dev) || (!states_dev && !controls_dev))
+    return IRBFN_ERR_BAD_ARG;
+  if (O != 2 * T) return IRBFN_ERR_BAD_ARG;
+  if (H1 != 64 || H2 != 64) return IRBFN_ERR_UNSUPPORTED;      // the reference hard-codes Dense(64), Dense(64)
+  if (states_dev && mode == IRBFN_ROLLOUT_SPIRAL) return IRBFN_ERR_UNSUPPORTED;
+  if (mlp_head_tick_needs_controls(O) && !controls_dev) return IRBFN_ERR_BAD_ARG;
+  DynParams dp;
+  memset(&dp, 0, sizeof(dp));
+  int rc = states_dev ? load_dyn(mode, dyn_params_host, &dp) : IRBFN_OK;
+  if (rc != IRBFN_OK) return rc;
+  return launch_mlp_head_tick(h1_dev, w2_dev, b2_dev, w3_dev, b3_dev, mode, mirror_dev, state0_dev, dp, controls_dev, states_dev, B,
+                              O, T, as_stream(stream));
+}
+
+int irbfn_mlp_head_tick_needs_controls(int mode, int O, int T) {
+  if (rollout_state_dim(mode) < 0 || T < 1 || O != 2 * T) return IRBFN_ERR_BAD_ARG;
+  return mlp_head_tick_needs_controls(O);
+}
+
+int irbfn_plan_tick_gamma(irbfn_net* net, int mode, const float* x_dev, const float* gamma_dev, const int32_t* mirror_dev,
+                          const float* state0_dev, const float* dyn_params_host, float* controls_dev, float* states_dev,
+                          int64_t B, int T, void* stream) {
+  if (!net || rollout_state_dim(mode) < 0 || B < 0 || T < 1) return IRBFN_ERR_BAD_ARG;
+  if (B == 0) return IRBFN_OK;
+  if (!x_dev || !gamma_dev || (states_dev && !state0_dev) || (!states_dev && !controls_dev)) return IRBFN_ERR_BAD_ARG;
+  if (!net->has_params) return IRBFN_ERR_NO_PARAMS;
+  if (net->O != 2 * T) return IRBFN_ERR_BAD_ARG;
+  DynParams dp;
+  memset(&dp, 0, sizeof(dp));
+  int rc = states_dev ? load_dyn(mode, dyn_params_host, &dp) : IRBFN_OK;
+  if (rc != IRBFN_OK) return rc;
+  return launch_forward_rollout_gamma(net, mode, x_dev, gamma_dev, mirror_dev, state0_dev, dp, controls_dev, states_dev, B, T,
+                                      as_stream(stream));
+}
+
 int irbfn_net_last_launch(const irbfn_net* net, char* name_buf, int name_len, int* grid, int* block) {
   if (!net) return IRBFN_ERR_BAD_ARG;
   if (name_buf && name_len > 0) {

@@ -5,6 +5,7 @@
 // the H2 hidden accumulators live in VGPRs; the weights are wave-uniform and stream through the scalar
 // cache.  H1 = H2 = 64 in the reference; the work is ~5 kFLOP per row, negligible next to the RBF stage.
 #include "common.h"
+#include "rollout_step.h"
 
 namespace irbfn {
 
@@ -513,6 +514,191 @@ __global__ __launch_bounds__(256) void mlp_head_fwd_mfma_kernel(const float* __r
   }
 }
 
+// ---- the planning tick of the head in one launch (IRBFNFrenetPlanner(deeper=True): pred_step -> sign flip of the mirrored
+// rows -> roll-out, irbfn_planner.py:203-212, :487-488): the body of mlp_head_fwd_mfma_kernel with the narrow tick's epilogue
+// behind the output MFMAs of each tile.  The lanes n < O negate columns >= T of mirrored rows, store the controls (if asked for)
+// and park them in a wave-private 32 x 17 tile; lane l < 32 then integrates row l with the step functions of the stand-alone
+// roll-out kernels (rollout_step.h: same bits), reading its two controls per step from that tile; the T x S states are staged
+// at pitch 65 in the wave's Hs tile (free once the output MFMAs have their operands) and leave as coalesced dwords.  These are
+// the lines of narrow_epilogue<ROLL> (rbf_forward_f16_narrow.h) in a copy of their own: sharing them through one inlined
+// function moved the instruction streams of rbf_tick_f16mfma / rbf_tick_f16gram.  No block barrier in the tile loop.
+// O = 2T <= 16, T * S <= 64; states == nullptr: controls only.
+constexpr int kHeadTickT = 8;                    // horizons: O = 2T <= 16
+constexpr int kHeadTickWave = kHeadTR * kHeadP + kHeadTR * kHeadGP;   // floats of LDS per wave: Hs, Ct
+
+template <int H1, int H2>
+__global__ __launch_bounds__(256) void mlp_head_tick_kernel(const float* __restrict__ h1, const float* __restrict__ W2,
+                                                            const float* __restrict__ b2, const float* __restrict__ W3,
+                                                            const float* __restrict__ b3, const int* __restrict__ mirror,
+                                                            const float* __restrict__ state0, const DynParams dp,
+                                                            float* __restrict__ controls, float* __restrict__ states, long B, int O,
+                                                            int T, int mode) {
+  static_assert(H1 == 64 && H2 == 64, "the reference hard-codes Dense(64), Dense(64)");
+  extern __shared__ float lds[];
+  constexpr int P = kHeadP, GP = kHeadGP, TR = kHeadTR, MB = TR / 16;
+  float* W2s = lds;                              // [64][P]
+  float* W3s = W2s + 64 * P;                     // [64][GP]  W3[j][o], o padded to 16 with zeros
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = lane & 15, g = lane >> 4;
+  float* Hs = W3s + 64 * GP + wave * kHeadTickWave;   // [TR][P]: relu(h1) rows, then relu(z2) rows, then the states of the tile
+  float* Ct = Hs + TR * P;                       // [TR][GP]: the controls of the tile
+  {                                              // block-shared copies of the weights (loads first, then the LDS writes)
+    float wv[16], w3v[4];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) wv[k] = W2[tid + 256 * k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = tid + 256 * k, j = i >> 4, o = i & 15;
+      w3v[k] = o < O ? W3[j * O + o] : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int i = tid + 256 * k;
+      W2s[(i >> 6) * P + (i & 63)] = wv[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = tid + 256 * k;
+      W3s[(i >> 4) * GP + (i & 15)] = w3v[k];
+    }
+  }
+  __syncthreads();
+  auto wave_sync = [&]() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+  };
+  float b2n[4];
+#pragma unroll
+  for (int nj = 0; nj < 4; ++nj) b2n[nj] = b2[nj * 16 + n];
+  const float b3n = n < O ? b3[n] : 0.0f;
+  const int S = (mode == IRBFN_ROLLOUT_FULLINT) ? 5 : (mode == IRBFN_ROLLOUT_FRENET_LS ? 8 : 7);
+  const long ntiles = (B + TR - 1) / TR;
+  // a tile's h1 rows: 8 x 16-byte loads per lane (row 4k + lane / 16, columns 4 (lane % 16) ..), requested one tile ahead
+  hf4 hv[TR / 4];
+  auto fetch = [&](long tile) {
+    const long b0 = tile * TR;
+#pragma unroll
+    for (int k = 0; k < TR / 4; ++k) {
+      const long row = b0 + 4 * k + (lane >> 4);
+      hv[k] = (tile < ntiles && row < B) ? *reinterpret_cast<const hf4*>(h1 + row * 64 + 4 * (lane & 15)) : hf4{0, 0, 0, 0};
+    }
+  };
+  fetch((long)blockIdx.x * 4 + wave);
+  for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
+    const long b0 = tile * TR;
+    const long left = B - b0;
+    const int nvalid = left < TR ? (int)left : TR;
+#pragma unroll
+    for (int k = 0; k < TR / 4; ++k) {
+      float* d = Hs + (4 * k + (lane >> 4)) * P + 4 * (lane & 15);
+      d[0] = fmaxf(hv[k].x, 0.0f); d[1] = fmaxf(hv[k].y, 0.0f); d[2] = fmaxf(hv[k].z, 0.0f); d[3] = fmaxf(hv[k].w, 0.0f);   // nn.relu(out_pre1)
+    }
+    fetch(tile + (long)gridDim.x * 4);           // the next tile's rows travel while this one is computed
+    wave_sync();
+    hf4 z2[MB][4];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+      for (int nj = 0; nj < 4; ++nj) z2[mb][nj] = hf4{b2n[nj], b2n[nj], b2n[nj], b2n[nj]};
+#pragma unroll 4
+    for (int ks = 0; ks < 16; ++ks) {
+      float av[MB], bv[4];
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb) av[mb] = Hs[(mb * 16 + n) * P + ks * 4 + g];
+#pragma unroll
+      for (int nj = 0; nj < 4; ++nj) bv[nj] = W2s[(ks * 4 + g) * P + nj * 16 + n];
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int nj = 0; nj < 4; ++nj) z2[mb][nj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mb], bv[nj], z2[mb][nj], 0, 0, 0);
+    }
+    wave_sync();                                 // every read of relu(h1) is done: the tile takes relu(z2)
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+      for (int nj = 0; nj < 4; ++nj)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Hs[(mb * 16 + 4 * g + r) * P + nj * 16 + n] = fmaxf(z2[mb][nj][r], 0.0f);   // nn.relu(out_pre2)
+    // the mirror flags of the lane's eight rows (D layout: row = 16 mb + 4 g + r) travel under the output MFMAs
+    int mf[MB][4];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = mb * 16 + 4 * g + r;
+        mf[mb][r] = (mirror != nullptr && n >= T && n < O && row < nvalid) ? mirror[b0 + row] : 0;
+      }
+    wave_sync();
+    hf4 oacc[MB];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) oacc[mb] = hf4{b3n, b3n, b3n, b3n};
+#pragma unroll 4
+    for (int ks = 0; ks < 16; ++ks) {
+      const float bv = W3s[(ks * 4 + g) * GP + n];
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb)
+        oacc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(Hs[(mb * 16 + n) * P + ks * 4 + g], bv, oacc[mb], 0, 0, 0);
+    }
+    if (n < O) {
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = mb * 16 + 4 * g + r;
+          float y = oacc[mb][r];
+          if (mf[mb][r] != 0) y = -y;                                                          // irbfn_planner.py:203-204
+          Ct[row * GP + n] = y;
+          if (row < nvalid && controls != nullptr) controls[(b0 + row) * O + n] = y;
+        }
+    }
+    wave_sync();                                 // the controls tile is complete; Hs has been read for the last time
+    if (states != nullptr) {
+      // ---- the wave that produced the 32 rows rolls them out: lane l < 32 integrates row l
+      if (lane < nvalid) {
+        const long b = b0 + lane;
+        const float* u = Ct + lane * GP;         // a_0..a_{T-1}, sv_0..sv_{T-1}
+        float* o = Hs + lane * P;
+        if (mode == IRBFN_ROLLOUT_ST_SELECT || mode == IRBFN_ROLLOUT_ST_KS) {
+          float st[7];
+#pragma unroll
+          for (int i = 0; i < 7; ++i) st[i] = state0[b * 7 + i];
+          for (int t = 0; t < T; ++t) {
+            if (mode == IRBFN_ROLLOUT_ST_SELECT) st_step<true>(st, u[t], u[T + t], dp);
+            else st_step<false>(st, u[t], u[T + t], dp);
+#pragma unroll
+            for (int i = 0; i < 7; ++i) o[t * 7 + i] = st[i];
+          }
+        } else if (mode == IRBFN_ROLLOUT_FRENET_LS) {
+          float st[8];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) st[i] = state0[b * 8 + i];
+          for (int t = 0; t < T; ++t) {
+            frenet_step(st, u[t], u[T + t], dp);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) o[t * 8 + i] = st[i];
+          }
+        } else {
+          float st[5] = {0.0f, 0.0f, 0.0f, clipf(state0[b], 0.0f, 7.0f), 0.0f};                // train_nmpc.py:319
+          for (int t = 0; t < T; ++t) {
+            fullint_step(st, u[t], u[T + t]);
+#pragma unroll
+            for (int i = 0; i < 5; ++i) o[t * 5 + i] = st[i];
+          }
+        }
+      }
+      wave_sync();
+      const int rowf = T * S;                    // floats per trajectory (<= 64)
+      float* gout = states + b0 * (long)rowf;    // the tile's states: one contiguous block of HBM
+      for (int idx = lane; idx < nvalid * rowf; idx += 64) {
+        const int r = idx / rowf, c = idx - r * rowf;
+        gout[idx] = Hs[r * P + c];
+      }
+      wave_sync();                               // Hs / Ct are free for the next tile
+    }
+  }
+}
+
 // 64 consecutive values per block; thread (sg, v) sums slabs sg, sg + 4, ... in order, the four partial sums are added in
 // a fixed order: deterministic, coalesced, no single thread walks all the slabs
 __global__ __launch_bounds__(256) void mlp_head_bwd_reduce_kernel(const float* __restrict__ part, int nblk, int n,
@@ -565,6 +751,34 @@ extern "C" int irbfn_mlp_head_forward(const float* h1_dev, const float* w2_dev, 
   IRBFN_HIP_CHECK(hipGetLastError());
   return IRBFN_OK;
 }
+
+// irbfn_mlp_head_tick behind its argument checks (abi.hip): O <= 16 one launch of mlp_head_tick_kernel; wider heads through the
+// caller's controls buffer: head forward -> sign flip -> split-row roll-out
+int irbfn::launch_mlp_head_tick(const float* h1, const float* w2, const float* b2, const float* w3, const float* b3, int mode,
+                                const int* mirror, const float* state0, const DynParams& dp, float* controls, float* states,
+                                int64_t B, int O, int T, hipStream_t s) {
+  if (B == 0) return IRBFN_OK;
+  if (O > 2 * kHeadTickT) {
+    if (!controls) return IRBFN_ERR_BAD_ARG;
+    int rc = irbfn_mlp_head_forward(h1, w2, b2, w3, b3, controls, B, 64, 64, O, s);
+    if (rc == IRBFN_OK && mirror) rc = launch_unmirror(controls, mirror, B, O, T, s);
+    if (rc != IRBFN_OK || !states) return rc;
+    return launch_rollout_forward_split(mode, state0, controls, dp, states, B, T, s);
+  }
+  if (states && T * rollout_state_dim(mode) > kHeadP - 1) return IRBFN_ERR_UNSUPPORTED;   // the staging tile: 64 floats per row
+  const size_t lds = ((size_t)64 * kHeadP + 64 * kHeadGP + 4 * (size_t)kHeadTickWave) * sizeof(float);
+  auto k = mlp_head_tick_kernel<64, 64>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }
+  const long tiles = (B + kHeadTR - 1) / kHeadTR;
+  const long blocks = (tiles + 3) / 4;
+  hipLaunchKernelGGL(k, dim3((unsigned)(blocks < 512 ? blocks : 512)), dim3(256), lds, s, h1, w2, b2, w3, b3, mirror, state0, dp,
+                     controls, states, (long)B, O, T, mode);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
+
+int irbfn::mlp_head_tick_needs_controls(int O) { return O > 2 * kHeadTickT ? 1 : 0; }
 
 extern "C" int64_t irbfn_mlp_head_vjp_workspace_bytes(int H1, int H2, int O) {
   if (H1 != 64 || H2 != 64 || O < 1 || O > 16) return IRBFN_ERR_UNSUPPORTED;

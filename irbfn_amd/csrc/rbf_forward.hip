@@ -607,4 +607,46 @@ int launch_forward_rollout(irbfn_net* net, int mode, const float* x, const int* 
   return rc;
 }
 
+// the tick with caller-provided region weights gamma[B][R] (ClusterWCRBFNet, model.py:393-412): the gated K1 with the roll-out
+// in its epilogue; where that plan cannot roll (generic basis, T x S > 64 floats of staging, LDS), forward -> sign flip ->
+// split-row roll-out through the caller's controls buffer
+int launch_forward_rollout_gamma(irbfn_net* net, int mode, const float* x, const float* gamma, const int* mirror,
+                                 const float* state0, const DynParams& dp, float* controls, float* states, int64_t B, int T,
+                                 hipStream_t s) {
+  if (B == 0) return IRBFN_OK;
+  if (states == nullptr) {                       // controls only: the forward, then the sign flip
+    if (!controls) return IRBFN_ERR_BAD_ARG;
+    int rc = launch_forward_gamma(net, x, gamma, controls, B, s);
+    if (rc != IRBFN_OK || !mirror) return rc;
+    return launch_unmirror(controls, mirror, B, net->O, net->O / 2, s);
+  }
+  if (mode != IRBFN_ROLLOUT_ST_SELECT && mode != IRBFN_ROLLOUT_ST_KS && mode != IRBFN_ROLLOUT_FULLINT &&
+      mode != IRBFN_ROLLOUT_FRENET_LS)
+    return IRBFN_ERR_UNSUPPORTED;
+  if (net->O != 2 * T) return IRBFN_ERR_BAD_ARG;
+  if (net->bclass != BC_GENERIC && T * rollout_state_dim(mode) <= 64) {
+    const LaunchPlan p = plan_qlane(net, B, true, true);
+    if (p.kind == LK_K1) {
+      FwdArgs a;
+      fill_args(net, a, x, controls, B);
+      a.gamma_ext = gamma;
+      a.state0 = state0;
+      a.states = states;
+      a.T = T;
+      a.mode = mode;
+      a.dp = dp;
+      a.mirror = mirror;
+      a.sv0 = T;
+      const int rc = launch_qlane(net, p, a, s);
+      if (rc == IRBFN_OK) record_launch(net, p);
+      return rc;
+    }
+  }
+  if (!controls) return IRBFN_ERR_BAD_ARG;
+  int rc = launch_forward_gamma(net, x, gamma, controls, B, s);
+  if (rc == IRBFN_OK && mirror) rc = launch_unmirror(controls, mirror, B, net->O, T, s);
+  if (rc != IRBFN_OK) return rc;
+  return launch_rollout_forward_split(mode, state0, controls, dp, states, B, T, s);
+}
+
 }  // namespace irbfn

@@ -677,8 +677,9 @@ class DeeperWCRBFNet:
             if tuple(p[g][n].shape) != shp:
                 raise ValueError(f"params {g}.{n} has shape {tuple(p[g][n].shape)}, the model card implies {shp}")
 
-    def _forward(self, params: dict, xd, torch, lib):
-        """(out, h1) as device tensors: h1 = linear_pre1(rbf_out) [B, 64] (model.py:283), out the head's output."""
+    def _stage_and_head(self, params: dict, xd, torch):
+        """(h1, [w2, b2, w3, b3]) as device tensors: the stage output linear_pre1(rbf_out) [B, 64] (model.py:283) and the
+        head's leaves, shapes checked."""
         p = _inner(params)
         H, O = self.HIDDEN, self.out_features
         for name, shp in (("linear_pre2", (H, H)), ("linear", (H, O))):
@@ -688,6 +689,12 @@ class DeeperWCRBFNet:
         h1 = self.stage.apply(stage_params, xd)                     # linear_pre1(rbf_out)   model.py:283
         head = [to_device_f32(a, torch) for a in (p["linear_pre2"]["kernel"], p["linear_pre2"]["bias"],
                                                   p["linear"]["kernel"], p["linear"]["bias"])]
+        return h1, head
+
+    def _forward(self, params: dict, xd, torch, lib):
+        """(out, h1) as device tensors: h1 = linear_pre1(rbf_out) [B, 64] (model.py:283), out the head's output."""
+        H, O = self.HIDDEN, self.out_features
+        h1, head = self._stage_and_head(params, xd, torch)
         B = xd.shape[0]
         out = torch.empty((B, O), dtype=torch.float32, device=xd.device)
         st = lib.irbfn_mlp_head_forward(_ptr(h1), _ptr(head[0]), _ptr(head[1]), _ptr(head[2]), _ptr(head[3]), _ptr(out),
@@ -826,24 +833,30 @@ class ClusterWCRBFNet:
                               basis_func=basis_func, num_regions=num_regions, lower_bounds=[], upper_bounds=[],
                               dimension_ranges=[], activation_idx=[], delta=[])
 
-    def apply(self, params: dict, x):
-        torch = _lib.require_gpu()
-        lib = _lib.load()
+    def _bind_and_gate(self, params: dict, xd, torch, lib):
+        """Binds the stage to the RBF leaves and runs the softmax gate (model.py:402-404) -> (logits, gamma), [B, R] each."""
         p = _inner(params)
-        D, R, O = self.in_features, self.num_regions, self.out_features
+        D, R = self.in_features, self.num_regions
         if tuple(p["cluster"]["kernel"].shape) != (D, R) or tuple(p["cluster"]["bias"].shape) != (R,):
             raise ValueError(f"params cluster.kernel / bias must be [{D},{R}] / [{R}]")
         self.stage.bind({"rbf_list": p["rbf_list"], "linear": p["linear"]})
-        xd = to_device_f32(x, torch)
         B = xd.shape[0]
         if tuple(xd.shape) != (B, D):
             raise ValueError(f"x must be [B, {D}]")
         wc, bc = to_device_f32(p["cluster"]["kernel"], torch), to_device_f32(p["cluster"]["bias"], torch)
         logits = torch.empty((B, R), dtype=torch.float32, device=xd.device)
         gamma = torch.empty((B, R), dtype=torch.float32, device=xd.device)
-        out = torch.empty((B, O), dtype=torch.float32, device=xd.device)
         st = lib.irbfn_cluster_gate(_ptr(xd), _ptr(wc), _ptr(bc), _ptr(logits), _ptr(gamma), B, D, R, _stream_ptr(torch))
         _lib.check(st, "irbfn_cluster_gate")
+        return logits, gamma
+
+    def apply(self, params: dict, x):
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        xd = to_device_f32(x, torch)
+        logits, gamma = self._bind_and_gate(params, xd, torch, lib)
+        B, O = xd.shape[0], self.out_features
+        out = torch.empty((B, O), dtype=torch.float32, device=xd.device)
         st = lib.irbfn_net_forward_gamma(self.stage._handle(torch), _ptr(xd), _ptr(gamma), _ptr(out), B, _stream_ptr(torch))
         _lib.check(st, "irbfn_net_forward_gamma")
         return like_input(out, x, torch), like_input(logits, x, torch)
