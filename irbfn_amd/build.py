@@ -76,14 +76,21 @@ def _newest_header() -> float:
     return max(os.path.getmtime(h) for h in hs)
 
 
+def compile_cmd(src, extra, emit, out, root=os.path.dirname(HERE), hipcc=None):
+    """The hipcc line of one unit of the tree at `root`: `emit` says what to write to `out` (["-c"] for the object).
+    tools/isa_diff.py compiles two checkouts with it, so that it compares what ships."""
+    csrc = os.path.join(root, "irbfn_amd", "csrc")
+    return [hipcc or _hipcc(), "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-I", os.path.join(root, "include"),
+            "-I", csrc, *extra, *emit, os.path.join(csrc, src), "-o", out]
+
+
 def _compile(unit, hipcc, hdr_mtime, force):
     src, obj, extra = unit
     srcp, objp = os.path.join(CSRC, src), os.path.join(OBJ, obj)
     if (not force and os.path.exists(objp)
             and os.path.getmtime(objp) >= max(os.path.getmtime(srcp), hdr_mtime)):
         return objp, False
-    cmd = [hipcc, "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-I", INCLUDE, "-I", CSRC,
-           *extra, "-c", srcp, "-o", objp]
+    cmd = compile_cmd(src, extra, ["-c"], objp, hipcc=hipcc)
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src} {extra}:\n{r.stderr[-4000:]}")

@@ -523,6 +523,11 @@ __global__ __launch_bounds__(256) void mlp_head_fwd_mfma_kernel(const float* __r
 // the lines of narrow_epilogue<ROLL> (rbf_forward_f16_narrow.h) in a copy of their own: sharing them through one inlined
 // function moved the instruction streams of rbf_tick_f16mfma / rbf_tick_f16gram.  No block barrier in the tile loop.
 // O = 2T <= 16, T * S <= 64; states == nullptr: controls only.
+// The tile pieces (weight staging, fetch, the two MFMA loops, the relu stores) stay written out here and in
+// mlp_head_fwd_mfma_kernel.  As shared __forceinline__ functions they gave the same bits (array_equal at B = 1 / 8192 / 65 536 /
+// 80 000), fewer instructions (forward 1134 -> 1015, this kernel 2708 -> 2574, 145 -> 143 VGPRs), and a slower tick on the MI355X:
+// 11.30 -> 11.57 us at B = 8192 and 17.48 -> 17.70 us at B = 65 536, medians of three runs per library against a spread of the
+// parent's runs of 0.20 / 0.07 us (profiles/fold_twins.txt).  Every piece but wave_sync moves both instruction streams on its own.
 constexpr int kHeadTickT = 8;                    // horizons: O = 2T <= 16
 constexpr int kHeadTickWave = kHeadTR * kHeadP + kHeadTR * kHeadGP;   // floats of LDS per wave: Hs, Ct
 
@@ -725,6 +730,23 @@ __global__ __launch_bounds__(256) void mlp_head_bwd_reduce_kernel(const float* _
 
 using namespace irbfn;
 
+// Launch a 256-thread head kernel with `lds` bytes of dynamic LDS (more than the default limit: raise the kernel's own first).
+template <typename K, typename... A>
+static int launch_head(K k, unsigned blocks, size_t lds, hipStream_t s, A... args) {
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, s, args...);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
+
+// blocks of the two forward kernels: four 32-row tiles (one per wave) at a time, at most 512 blocks
+static unsigned head_tile_blocks(int64_t B) {
+  const long tiles = (B + kHeadTR - 1) / kHeadTR;
+  const long blocks = (tiles + 3) / 4;
+  return (unsigned)(blocks < 512 ? blocks : 512);
+}
+
 extern "C" int irbfn_mlp_head_forward(const float* h1_dev, const float* w2_dev, const float* b2_dev,
                                       const float* w3_dev, const float* b3_dev, float* out_dev, int64_t B, int H1,
                                       int H2, int O, void* stream) {
@@ -735,15 +757,8 @@ extern "C" int irbfn_mlp_head_forward(const float* h1_dev, const float* w2_dev, 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (O <= 16) {                                               // matrix-core head (every model card of the reference: O = 2 or 10)
     const size_t lds = ((size_t)64 * kHeadP + 64 * kHeadGP + 4 * (size_t)kHeadTR * kHeadP) * sizeof(float);
-    auto k = mlp_head_fwd_mfma_kernel<64, 64>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }
-    const long tiles = (B + kHeadTR - 1) / kHeadTR;
-    const long blocks = (tiles + 3) / 4;
-    hipLaunchKernelGGL(k, dim3((unsigned)(blocks < 512 ? blocks : 512)), dim3(256), lds, s, h1_dev, w2_dev, b2_dev, w3_dev,
-                       b3_dev, out_dev, (long)B, O);
-    IRBFN_HIP_CHECK(hipGetLastError());
-    return IRBFN_OK;
+    return launch_head(mlp_head_fwd_mfma_kernel<64, 64>, head_tile_blocks(B), lds, s, h1_dev, w2_dev, b2_dev, w3_dev, b3_dev, out_dev,
+                       (long)B, O);
   }
   const size_t lds = (size_t)kWave * (64 + 1) * sizeof(float);
   hipLaunchKernelGGL((mlp_head_kernel<64, 64>), dim3((unsigned)((B + kWave - 1) / kWave)), dim3(kWave), lds, s, h1_dev,
@@ -767,15 +782,8 @@ int irbfn::launch_mlp_head_tick(const float* h1, const float* w2, const float* b
   }
   if (states && T * rollout_state_dim(mode) > kHeadP - 1) return IRBFN_ERR_UNSUPPORTED;   // the staging tile: 64 floats per row
   const size_t lds = ((size_t)64 * kHeadP + 64 * kHeadGP + 4 * (size_t)kHeadTickWave) * sizeof(float);
-  auto k = mlp_head_tick_kernel<64, 64>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }
-  const long tiles = (B + kHeadTR - 1) / kHeadTR;
-  const long blocks = (tiles + 3) / 4;
-  hipLaunchKernelGGL(k, dim3((unsigned)(blocks < 512 ? blocks : 512)), dim3(256), lds, s, h1, w2, b2, w3, b3, mirror, state0, dp,
-                     controls, states, (long)B, O, T, mode);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
+  return launch_head(mlp_head_tick_kernel<64, 64>, head_tile_blocks(B), lds, s, h1, w2, b2, w3, b3, mirror, state0, dp, controls,
+                     states, (long)B, O, T, mode);
 }
 
 int irbfn::mlp_head_tick_needs_controls(int O) { return O > 2 * kHeadTickT ? 1 : 0; }
@@ -796,19 +804,13 @@ extern "C" int irbfn_mlp_head_vjp(const float* h1_dev, const float* w2_dev, cons
   const int n = H1 * H2 + H2 + H2 * O + O;
   if (ws_bytes < (int64_t)kHeadBwdBlocks * n * (int64_t)sizeof(float)) return IRBFN_ERR_BAD_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  {
-    // working set: W2 / W3 copies + four wave tile sets; the slab combine (4 x 5200 floats) reuses it
-    size_t lf = 64 * kHeadP + 64 * kHeadGP + 4 * (size_t)(2 * kHeadTR * kHeadP + kHeadTR * kHeadGP);
-    const size_t cf = 4 * (size_t)(64 * 64 + 64 + 64 * 16 + 16);
-    lf = lf > cf ? lf : cf;
-    const size_t lds = lf * sizeof(float);
-    auto k = mlp_head_bwd_mfma_kernel<64, 64>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }
-    hipLaunchKernelGGL(k, dim3(kHeadBwdBlocks), dim3(256), lds, s, h1_dev, w2_dev, b2_dev, w3_dev, gout_dev, gh1_dev,
-                       static_cast<float*>(ws_dev), (long)B, O);
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
+  // working set: W2 / W3 copies + four wave tile sets; the slab combine (4 x 5200 floats) reuses it
+  size_t lf = 64 * kHeadP + 64 * kHeadGP + 4 * (size_t)(2 * kHeadTR * kHeadP + kHeadTR * kHeadGP);
+  const size_t cf = 4 * (size_t)(64 * 64 + 64 + 64 * 16 + 16);
+  lf = lf > cf ? lf : cf;
+  const int rc = launch_head(mlp_head_bwd_mfma_kernel<64, 64>, kHeadBwdBlocks, lf * sizeof(float), s, h1_dev, w2_dev, b2_dev, w3_dev,
+                             gout_dev, gh1_dev, static_cast<float*>(ws_dev), (long)B, O);
+  if (rc != IRBFN_OK) return rc;
   hipLaunchKernelGGL(mlp_head_bwd_reduce_kernel, dim3((n + 63) / 64), dim3(256), 0, s, static_cast<const float*>(ws_dev),
                      kHeadBwdBlocks, n, gw2_dev, gb2_dev, gw3_dev, gb3_dev, H1 * H2, H2, H2 * O);
   IRBFN_HIP_CHECK(hipGetLastError());

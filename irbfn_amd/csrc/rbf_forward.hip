@@ -560,20 +560,46 @@ int launch_forward_gamma(irbfn_net* net, const float* x, const float* gamma, flo
   return rc;
 }
 
+// ---- pieces both ticks below share (gamma: the caller's region weights, null for the net's own gate) ----------------------
+// controls only (no states asked for): any forward kernel, then the sign flip
+static int forward_controls_only(irbfn_net* net, const float* x, const float* gamma, const int* mirror, float* controls, int64_t B,
+                                 hipStream_t s) {
+  if (!controls) return IRBFN_ERR_BAD_ARG;
+  const int rc = gamma ? launch_forward_gamma(net, x, gamma, controls, B, s) : launch_forward(net, x, controls, B, s);
+  if (rc != IRBFN_OK || !mirror) return rc;
+  return launch_unmirror(controls, mirror, B, net->O, net->O / 2, s);
+}
+
+static int check_tick(const irbfn_net* net, int mode, int T) {
+  if (mode != IRBFN_ROLLOUT_ST_SELECT && mode != IRBFN_ROLLOUT_ST_KS && mode != IRBFN_ROLLOUT_FULLINT &&
+      mode != IRBFN_ROLLOUT_FRENET_LS)
+    return IRBFN_ERR_UNSUPPORTED;
+  return net->O != 2 * T ? IRBFN_ERR_BAD_ARG : IRBFN_OK;
+}
+
+// K1 with the roll-out in its epilogue
+static int launch_qlane_tick(irbfn_net* net, const LaunchPlan& p, int mode, const float* x, const float* gamma, const int* mirror,
+                             const float* state0, const DynParams& dp, float* controls, float* states, int64_t B, int T,
+                             hipStream_t s) {
+  FwdArgs a;
+  fill_args(net, a, x, controls, B);
+  a.gamma_ext = gamma;
+  a.state0 = state0;
+  a.states = states;
+  a.T = T;
+  a.mode = mode;
+  a.dp = dp;
+  a.mirror = mirror;
+  a.sv0 = T;
+  return launch_qlane(net, p, a, s);
+}
+
 int launch_forward_rollout(irbfn_net* net, int mode, const float* x, const int* mirror, const float* state0,
                            const DynParams& dp, float* controls, float* states, int64_t B, int T,
                            hipStream_t s) {
   if (B == 0) return IRBFN_OK;
-  if (states == nullptr) {                       // controls only: any forward kernel, then the sign flip
-    if (!controls) return IRBFN_ERR_BAD_ARG;
-    int rc = launch_forward(net, x, controls, B, s);
-    if (rc != IRBFN_OK || !mirror) return rc;
-    return launch_unmirror(controls, mirror, B, net->O, net->O / 2, s);
-  }
-  if (mode != IRBFN_ROLLOUT_ST_SELECT && mode != IRBFN_ROLLOUT_ST_KS && mode != IRBFN_ROLLOUT_FULLINT &&
-      mode != IRBFN_ROLLOUT_FRENET_LS)
-    return IRBFN_ERR_UNSUPPORTED;
-  if (net->O != 2 * T) return IRBFN_ERR_BAD_ARG;
+  if (states == nullptr) return forward_controls_only(net, x, nullptr, mirror, controls, B, s);
+  if (const int rc = check_tick(net, mode, T); rc != IRBFN_OK) return rc;
   const LaunchPlan p = plan_tick(net, mode, B, T, controls != nullptr);
   if (p.split) {
     int rc = launch_planned(net, p, x, controls, B, s);
@@ -588,19 +614,7 @@ int launch_forward_rollout(irbfn_net* net, int mode, const float* x, const int* 
     case LK_TICK_K1G: rc = launch_tick_gram_narrow(net, p, x, mirror, state0, dp, controls, states, B, T, s); break;
     case LK_TICK_K1H: rc = launch_tick_f16_narrow(net, p, x, mirror, state0, dp, controls, states, B, T, s); break;
     case LK_K1R: rc = launch_forward_sparse(net, p, x, controls, B, mirror, T, mode, state0, &dp, states, T, s); break;
-    case LK_K1: {
-      FwdArgs a;
-      fill_args(net, a, x, controls, B);
-      a.state0 = state0;
-      a.states = states;
-      a.T = T;
-      a.mode = mode;
-      a.dp = dp;
-      a.mirror = mirror;
-      a.sv0 = T;
-      rc = launch_qlane(net, p, a, s);
-      break;
-    }
+    case LK_K1: rc = launch_qlane_tick(net, p, mode, x, nullptr, mirror, state0, dp, controls, states, B, T, s); break;
     default: return p.status;
   }
   if (rc == IRBFN_OK) record_launch(net, p);
@@ -614,30 +628,12 @@ int launch_forward_rollout_gamma(irbfn_net* net, int mode, const float* x, const
                                  const float* state0, const DynParams& dp, float* controls, float* states, int64_t B, int T,
                                  hipStream_t s) {
   if (B == 0) return IRBFN_OK;
-  if (states == nullptr) {                       // controls only: the forward, then the sign flip
-    if (!controls) return IRBFN_ERR_BAD_ARG;
-    int rc = launch_forward_gamma(net, x, gamma, controls, B, s);
-    if (rc != IRBFN_OK || !mirror) return rc;
-    return launch_unmirror(controls, mirror, B, net->O, net->O / 2, s);
-  }
-  if (mode != IRBFN_ROLLOUT_ST_SELECT && mode != IRBFN_ROLLOUT_ST_KS && mode != IRBFN_ROLLOUT_FULLINT &&
-      mode != IRBFN_ROLLOUT_FRENET_LS)
-    return IRBFN_ERR_UNSUPPORTED;
-  if (net->O != 2 * T) return IRBFN_ERR_BAD_ARG;
+  if (states == nullptr) return forward_controls_only(net, x, gamma, mirror, controls, B, s);
+  if (const int rc = check_tick(net, mode, T); rc != IRBFN_OK) return rc;
   if (net->bclass != BC_GENERIC && T * rollout_state_dim(mode) <= 64) {
     const LaunchPlan p = plan_qlane(net, B, true, true);
     if (p.kind == LK_K1) {
-      FwdArgs a;
-      fill_args(net, a, x, controls, B);
-      a.gamma_ext = gamma;
-      a.state0 = state0;
-      a.states = states;
-      a.T = T;
-      a.mode = mode;
-      a.dp = dp;
-      a.mirror = mirror;
-      a.sv0 = T;
-      const int rc = launch_qlane(net, p, a, s);
+      const int rc = launch_qlane_tick(net, p, mode, x, gamma, mirror, state0, dp, controls, states, B, T, s);
       if (rc == IRBFN_OK) record_launch(net, p);
       return rc;
     }

@@ -237,7 +237,10 @@ __global__ __launch_bounds__(256) void rbf_vjp_kernel(const VjpArgs a) {
 // output value in ONE thread: 100 threads x 128 regions x 24 slices of dependent loads = 2.2 ms of the 2.6 ms training
 // step of the reference's 128-region net at its batch size of 80000.)
 // Row V of the grid (blockIdx.y == V) is the second stage of the bias gradient: block o sums the per-block column sums of g
-// (colsum_partial_kernel) -- a launch of its own until round 3.
+// (colsum_partial_kernel) -- a launch of its own until round 3.  vjp_reduce_live_kernel repeats that row: as one
+// __forceinline__ device function (three spellings tried) the last tree step of both kernels compiles to two ds_read_b32
+// instead of one ds_read2_b32 (275 -> 277 and 341 -> 343 instructions; registers, LDS, scratch equal).  The folded form was not timed
+// on the device, so it is not taken on an instruction count alone: the 12 lines stay written twice.
 __global__ __launch_bounds__(256) void vjp_reduce_kernel(float* __restrict__ part, float* __restrict__ g_centers,
                                                          float* __restrict__ g_log_sigs, float* __restrict__ g_kernel, int QSB,
                                                          int V, int Npad, int N, int K, int R, int D, int DC, int O,
@@ -289,7 +292,7 @@ __global__ __launch_bounds__(64) void vjp_reduce_regions_kernel(const float* __r
 // vjp_reduce_kernel for irbfn_net_vjp_frozen; a null g_centers / g_log_sigs is not written.  The slabs hold the rows of K2g's
 // live-leaf mode `mode` (rbf_vjp_gram.hip, VgMode: [d centers (0)] [d log_sigs (0, 1)] d kernel) -- full rows (mode 0) where
 // another kernel wrote them, and where K2g handed this call to K2h: the flag holds `gen` then (K2g returned at once).  V: the
-// full row count, the grid's bias row.  The sums run in the order of vjp_reduce_kernel, whose code the all-live path keeps.
+// full row count, the grid's bias row.  The sums run in the order of vjp_reduce_kernel, which the all-live path keeps.
 __global__ __launch_bounds__(256) void vjp_reduce_live_kernel(float* __restrict__ part, float* __restrict__ g_centers,
                                                               float* __restrict__ g_log_sigs, float* __restrict__ g_kernel, int QSB,
                                                               int V, int mode, const int* __restrict__ flag, int gen, int Npad, int N,
@@ -790,23 +793,15 @@ template <int D, int OP>
 static int launch_vjp_bc(const VjpArgs& a, int bc, bool gated, dim3 grid, hipStream_t s) {
   constexpr int V = D + 1 + OP;
   const size_t lds = (size_t)4 * V * (kWave + 1) * sizeof(float);
-#define IRBFN_VCASE(BCV)                                                                                  \
-  case BCV: {                                                                                             \
-    if (gated) {                                                                                          \
-      auto k = rbf_vjp_kernel<D, OP, BCV, true>;                                                          \
-      if (lds > 48 * 1024)                                                                                \
-        IRBFN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k),                             \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
-      hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a);                                                  \
-    } else {                                                                                              \
-      auto k = rbf_vjp_kernel<D, OP, BCV, false>;                                                         \
-      if (lds > 48 * 1024)                                                                                \
-        IRBFN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k),                             \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
-      hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a);                                                  \
-    }                                                                                                     \
-    break;                                                                                                \
-  }
+  auto launch = [&](auto k) -> int {
+    if (lds > 48 * 1024)
+      IRBFN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a);
+    IRBFN_HIP_CHECK(hipGetLastError());
+    return IRBFN_OK;
+  };
+#define IRBFN_VCASE(BCV) \
+  case BCV: return gated ? launch(rbf_vjp_kernel<D, OP, BCV, true>) : launch(rbf_vjp_kernel<D, OP, BCV, false>);
   switch (bc) {
     IRBFN_VCASE(BC_GAUSS)
     IRBFN_VCASE(BC_IQ)
@@ -815,8 +810,6 @@ static int launch_vjp_bc(const VjpArgs& a, int bc, bool gated, dim3 grid, hipStr
     default: return IRBFN_ERR_UNSUPPORTED;
   }
 #undef IRBFN_VCASE
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
 }
 
 template <int D>
@@ -857,6 +850,13 @@ static int vjp_impl(irbfn_net* net, const float* x, const float* gout, float* g_
   float* gamma = reinterpret_cast<float*>(base + p.off_gamma);
   float* part = reinterpret_cast<float*>(base + p.off_part);
   float* bpart = reinterpret_cast<float*>(base + p.off_bias);
+  // the tail of K2m, K2r and K2: the bias column sums (no block maxima: nobody packs g to f16 there), then the slab reduce
+  auto bias_and_reduce = [&](float* slabs, int slices) -> int {
+    hipLaunchKernelGGL(colsum_partial_kernel, dim3(p.bias_blocks), dim3(256), 256 * sizeof(float), s, gout, bpart,
+                       (long)B, net->O, p.rows_per_block, (float*)nullptr);
+    IRBFN_HIP_CHECK(hipGetLastError());
+    return launch_vjp_reduce(net, slabs, g_centers, g_log_sigs, g_kernel, slices, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, red_mode);
+  };
   if (p.use_h) {
     float* bmax = reinterpret_cast<float*>(base + p.off_misc);           // [bias_blocks] max |g| per block
     float* scales = bmax + p.bias_blocks;                                // [2]
@@ -907,10 +907,7 @@ static int vjp_impl(irbfn_net* net, const float* x, const float* gout, float* g_
     record_launch(net, k);
     const int rcm = launch_vjp_mfma(net, x, gout, B, reinterpret_cast<float*>(base + p.off_qm), part, p.QSB, p.Npad, s);
     if (rcm != IRBFN_OK) return rcm;
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(p.bias_blocks), dim3(256), 256 * sizeof(float), s, gout, bpart,
-                       (long)B, net->O, p.rows_per_block, (float*)nullptr);
-    IRBFN_HIP_CHECK(hipGetLastError());
-    return launch_vjp_reduce(net, part, g_centers, g_log_sigs, g_kernel, p.QSB, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, red_mode);
+    return bias_and_reduce(part, p.QSB);
   }
 
   if (p.use_sp) {
@@ -918,10 +915,7 @@ static int vjp_impl(irbfn_net* net, const float* x, const float* gout, float* g_
     float* sp_part = reinterpret_cast<float*>(base + p.off_sp_part);
     const int rcs = launch_vjp_sparse(net, x, gout, B, base + p.off_sp, sp_part, p.SL, p.Npad, s);
     if (rcs != IRBFN_OK) return rcs;
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(p.bias_blocks), dim3(256), 256 * sizeof(float), s, gout, bpart,
-                       (long)B, net->O, p.rows_per_block, (float*)nullptr);
-    IRBFN_HIP_CHECK(hipGetLastError());
-    return launch_vjp_reduce(net, sp_part, g_centers, g_log_sigs, g_kernel, p.SL, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, red_mode);
+    return bias_and_reduce(sp_part, p.SL);
   }
   float* qrec = reinterpret_cast<float*>(base + p.off_qrec);
   {
@@ -953,10 +947,7 @@ static int vjp_impl(irbfn_net* net, const float* x, const float* gout, float* g_
   }
   if (rc != IRBFN_OK) return rc;
 
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3(p.bias_blocks), dim3(256), 256 * sizeof(float), s, gout, bpart,
-                     (long)B, net->O, p.rows_per_block, (float*)nullptr);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return launch_vjp_reduce(net, part, g_centers, g_log_sigs, g_kernel, p.QSB, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, red_mode);
+  return bias_and_reduce(part, p.QSB);
 }
 
 int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs,

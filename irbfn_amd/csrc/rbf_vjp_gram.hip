@@ -511,60 +511,11 @@ bool vjpg_eligible(const irbfn_net* net) {
 
 size_t vjpg_block_bytes() { return kVgBlock; }
 
-template <int DC>
-static int launch_vjpg_dc(const VjpGArgs& a, int bc, dim3 grid, size_t lds, hipStream_t s) {
-  switch (bc) {
-    case BC_GAUSS: if (a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_GAUSS, true, VG_ALL>), grid, dim3(256), lds, s, a);
-                   else hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_GAUSS, false, VG_ALL>), grid, dim3(256), lds, s, a);
-                   break;
-    case BC_IQ: if (a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_IQ, true, VG_ALL>), grid, dim3(256), lds, s, a);
-                else hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_IQ, false, VG_ALL>), grid, dim3(256), lds, s, a);
-                break;
-    case BC_IMQ: if (a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_IMQ, true, VG_ALL>), grid, dim3(256), lds, s, a);
-                 else hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BC_IMQ, false, VG_ALL>), grid, dim3(256), lds, s, a);
-                 break;
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-// x, gout -> slabs part[QSB][V][Npad].  qblk / scales / flag: workspace; bmax: per-block max |g| written by colsum_partial_kernel
-int launch_vjp_gram(irbfn_net* net, const float* x, const float* gout, int64_t B, unsigned char* qblk, const float* bmax, int nbmax,
-                    float* scales, int* flag, int gen, float* part, int QSB, int Npad, hipStream_t s) {
-  const long nqb = (B + 31) / 32;
-  const GramHdr* hdr = reinterpret_cast<const GramHdr*>(net->gram_hdr);
-  const dim3 pg((unsigned)nqb), pb(192);
-  switch (net->DC) {
-    case 3: hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<3, VG_ALL>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass)); break;
-    case 4: hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<4, VG_ALL>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass)); break;
-    case 7: hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<7, VG_ALL>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass)); break;
-    case 8: hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<8, VG_ALL>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass)); break;
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
-  VjpGArgs a;
-  a.qblk = qblk; a.scales = scales; a.gimg = net->gram_img; a.hdr = hdr; a.flag = flag; a.gen = gen; a.rec = net->rec; a.sig2 = net->sig2;
-  a.oscale = net->f16_oscale; a.part = part;
-  a.nqb = nqb; a.O = net->O; a.OP = net->OP; a.N = net->N; a.S = net->S; a.Npad = Npad;
-  a.bpb = (int)((nqb + QSB - 1) / QSB);
-  a.cstride = gram_chunk_bytes((net->O + 15) / 16);
-  a.nchunks = (net->N + 31) / 32;
-  a.gscale = gauss_scale(net->basis);
-  const dim3 grid((a.nchunks + 3) / 4, QSB);
-  const size_t lds = (size_t)3 * kVgBlock;
-  switch (net->DC) {
-    case 3: return launch_vjpg_dc<3>(a, net->bclass, grid, lds, s);
-    case 4: return launch_vjpg_dc<4>(a, net->bclass, grid, lds, s);
-    case 7: return launch_vjpg_dc<7>(a, net->bclass, grid, lds, s);
-    case 8: return launch_vjpg_dc<8>(a, net->bclass, grid, lds, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
-// ---- frozen-leaf modes (irbfn_net_vjp_frozen) ------------------------------------------------------------------
+// ---- one launcher per leaf mode: VG_ALL and the frozen-leaf modes (irbfn_net_vjp_frozen) ------------------------
 int vjpg_waves(int mode, int O) { return vg_waves(mode, O <= kVgOC); }
 int vjpg_slab_rows(int mode, int DC, int OP) { return vg_kernel_row(mode, DC) + OP; }
+
+static_assert(vg_slot_bytes(VG_ALL) == kVgBlock, "the all-live ring slot is the whole block image");
 
 template <int DC, int MODE>
 static int launch_vjpg_live_dc(const VjpGArgs& a, int bc, dim3 grid, hipStream_t s) {
@@ -619,6 +570,12 @@ static int launch_vjp_gram_mode(irbfn_net* net, const float* x, const float* gou
     case 8: return launch_vjpg_live_dc<8, MODE>(a, net->bclass, grid, s);
     default: return IRBFN_ERR_UNSUPPORTED;
   }
+}
+
+// x, gout -> slabs part[QSB][V][Npad].  qblk / scales / flag: workspace; bmax: per-block max |g| written by colsum_partial_kernel
+int launch_vjp_gram(irbfn_net* net, const float* x, const float* gout, int64_t B, unsigned char* qblk, const float* bmax, int nbmax,
+                    float* scales, int* flag, int gen, float* part, int QSB, int Npad, hipStream_t s) {
+  return launch_vjp_gram_mode<VG_ALL>(net, x, gout, B, qblk, bmax, nbmax, scales, flag, gen, part, QSB, Npad, s);
 }
 
 // launch_vjp_gram for a frozen-leaf mode: slabs part[QSB][vjpg_slab_rows(mode)][Npad] of the live leaves only

@@ -10,9 +10,9 @@
 //                   (scripts/train_nmpc.py:231-233, :299)
 // All reductions are two-stage with a fixed order (deterministic).
 //
-// The float64 twins (*_f64) are the same compositions for a net trained under the reference's --use_float64
-// (scripts/train_nmpc.py:41-42): the one-step maps and adjoints of rollout_step.h / rollout_adjoint.h with S = double and
-// ocml's double trigonometry.  They are plain loops of their own: the float32 kernels keep their register-resident forms.
+// Every kernel and launcher is a template over the scalar S.  S = double is a net trained under the reference's --use_float64
+// (scripts/train_nmpc.py:41-42): the one-step maps and adjoints of rollout_step.h / rollout_adjoint.h with DynParams64 and
+// ocml's double trigonometry (TrigOf<S>).  Only seeds_fullint has one form per type, see there.
 #include <string.h>
 
 #include "common.h"
@@ -20,6 +20,12 @@
 #include "rollout_step.h"
 
 namespace irbfn {
+
+template <typename S> struct TrigOf { using type = TrigDirect; };
+template <> struct TrigOf<double> { using type = TrigF64; };
+
+template <typename S>
+__device__ __forceinline__ S sgn(S d) { return d > S(0) ? S(1) : (d < S(0) ? S(-1) : S(0)); }   // d|.| = sign
 
 template <typename S>
 __device__ __forceinline__ S block_sum_256(S v, S* sm) {
@@ -40,42 +46,44 @@ __device__ __forceinline__ S block_sum_256(S v, S* sm) {
 // initial_state = [0,0,0, x[:,0], 0, x[:,6], x[:,5]]                       (train_nmpc.py:260-266)
 // loss = mean(0.5 (y_pred - y)^2) + mean(0.5 (s_pred - s_act)[:, [0,1,3,4]]^2)   (:286-292)
 // gy = d loss / d y_pred (through dynamic_st_onestep_aux, dynamics.py:103-187).
-__global__ __launch_bounds__(256) void seeds_oneint_kernel(const float* __restrict__ x, const float* __restrict__ yp,
-                                                           const float* __restrict__ y, float* __restrict__ gy,
-                                                           float* __restrict__ loss_part, long B, int D, int O,
-                                                           DynParams dp, float tie) {
-  __shared__ float sm[256];
-  float lsum = 0.0f;
-  const float inv_y = 1.0f / ((float)B * (float)O), inv_s = 1.0f / ((float)B * 4.0f);
+template <typename S>
+__global__ __launch_bounds__(256) void seeds_oneint_kernel(const S* __restrict__ x, const S* __restrict__ yp,
+                                                           const S* __restrict__ y, S* __restrict__ gy,
+                                                           S* __restrict__ loss_part, long B, int D, int O,
+                                                           typename DynOf<S>::type dp, S tie) {
+  using Trig = typename TrigOf<S>::type;
+  __shared__ S sm[256];
+  S lsum = S(0);
+  const S inv_y = S(1) / ((S)B * (S)O), inv_s = S(1) / ((S)B * S(4));
   for (long b = (long)blockIdx.x * 256 + threadIdx.x; b < B; b += (long)gridDim.x * 256) {
-    const float* xb = x + b * D;
-    float sp[7] = {0.0f, 0.0f, 0.0f, xb[0], 0.0f, xb[6], xb[5]};
-    float sa[7] = {0.0f, 0.0f, 0.0f, xb[0], 0.0f, xb[6], xb[5]};
-    float pk[ModeTraits<IRBFN_ROLLOUT_ST_KS>::NP];
+    const S* xb = x + b * D;
+    S sp[7] = {S(0), S(0), S(0), xb[0], S(0), xb[6], xb[5]};
+    S sa[7] = {S(0), S(0), S(0), xb[0], S(0), xb[6], xb[5]};
+    S pk[ModeTraits<IRBFN_ROLLOUT_ST_KS>::NP];
     vjp_park<IRBFN_ROLLOUT_ST_KS>(sp, pk);
-    const float ap = yp[b * O + 0], svp = yp[b * O + 1];
-    st_step<false>(sp, ap, svp, dp);                       // predicted_integrated_states  (:276)
-    st_step<false>(sa, y[b * O + 0], y[b * O + 1], dp);    // actual_integrated_states     (:275)
-    float lam[7] = {0, 0, 0, 0, 0, 0, 0};
+    const S ap = yp[b * O + 0], svp = yp[b * O + 1];
+    st_step<false, Trig>(sp, ap, svp, dp);                       // predicted_integrated_states  (:276)
+    st_step<false, Trig>(sa, y[b * O + 0], y[b * O + 1], dp);    // actual_integrated_states     (:275)
+    S lam[7] = {0, 0, 0, 0, 0, 0, 0};
     const int idx[4] = {0, 1, 3, 4};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float d = sp[idx[k]] - sa[idx[k]];
-      lsum += 0.5f * d * d * inv_s;
+      const S d = sp[idx[k]] - sa[idx[k]];
+      lsum += S(0.5) * d * d * inv_s;
       lam[idx[k]] = d * inv_s;
     }
     for (int o = 0; o < O; ++o) {
-      const float d = yp[b * O + o] - y[b * O + o];
-      lsum += 0.5f * d * d * inv_y;
+      const S d = yp[b * O + o] - y[b * O + o];
+      lsum += S(0.5) * d * d * inv_y;
       gy[b * O + o] = d * inv_y;
     }
     // adjoint of the kinematic step w.r.t. its controls (oracle/hand_vjp.py: vjp_st_ks, T = 1)
-    float ga, gsv;
-    vjp_back_step<IRBFN_ROLLOUT_ST_KS>(pk, ap, svp, lam, 0.0f, tie, dp, ga, gsv);
+    S ga, gsv;
+    vjp_back_step<IRBFN_ROLLOUT_ST_KS, Trig>(pk, ap, svp, lam, S(0), tie, dp, ga, gsv);
     gy[b * O + 0] += ga;
     gy[b * O + 1] += gsv;
   }
-  const float tot = block_sum_256(lsum, sm);
+  const S tot = block_sum_256(lsum, sm);
   if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
 }
 
@@ -151,7 +159,7 @@ __global__ __launch_bounds__(256) void seeds_fullint_kernel(const float* __restr
     for (int i = 0; i < 5; ++i) {
       const float d = sp[i] - sa[i];
       lsum += fabsf(d) * inv_s;
-      lam[i] = (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f)) * inv_s;    // d|.| = sign
+      lam[i] = sgn(d) * inv_s;    // d|.| = sign
     }
     if constexpr (!REGS)
       for (int o = 0; o < O; ++o) gy[b * O + o] = 0.0f;
@@ -190,12 +198,12 @@ __global__ __launch_bounds__(256) void seeds_fullint_kernel(const float* __restr
     for (int k = 0; k < 2; ++k) {
       const float d = prd(0, k) - lab(0, k);                  // column k * T
       lsum += fabsf(d) * inv_y;
-      const float sgn = (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f)) * inv_y;
+      const float sg = sgn(d) * inv_y;
       if constexpr (REGS) {
 #pragma unroll
-        for (int o = 0; o < 2 * TMAX; ++o) gr[o] += (o == cols[k]) ? sgn : 0.0f;
+        for (int o = 0; o < 2 * TMAX; ++o) gr[o] += (o == cols[k]) ? sg : 0.0f;
       } else {
-        gy[b * O + cols[k]] += sgn;
+        gy[b * O + cols[k]] += sg;
       }
     }
     if constexpr (REGS) {
@@ -208,151 +216,9 @@ __global__ __launch_bounds__(256) void seeds_fullint_kernel(const float* __restr
   if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
 }
 
-// ---- Frenet train_step_fullint (scripts/train_nmpc_frenet.py:394-421) -------------------------------------------
-// x[B,8] = [ey, delta, vx_car, vy_car, vx_goal, wz, epsi, curv]; initial_state = x[:, [0,0,1,2,3,5,6,7]] (:398);
-// loss = mean|y_pred - y| + mean|integrate_frenet_mult([init, y_pred]) - integrate_frenet_mult([init, y])|
-// (:402-412; all T states, all 8 components).  gy = d loss / d y_pred through the T-step Frenet roll-out
-// (rollout_adjoint.h: the adjoint of dynamics.py:190-290, low-speed RHS).  O = 2T.
-template <int TMAX>
-__global__ __launch_bounds__(256) void seeds_frenet_fullint_kernel(const float* __restrict__ x, const float* __restrict__ yp,
-                                                                   const float* __restrict__ y, float* __restrict__ gy,
-                                                                   float* __restrict__ loss_part, long B, int D, int T,
-                                                                   DynParams dp, float tie) {
-  __shared__ float sm[256];
-  const int O = 2 * T;
-  const float inv_y = 1.0f / ((float)B * (float)O), inv_s = 1.0f / ((float)B * (float)T * 8.0f);
-  float lsum = 0.0f;
-  for (long b = (long)blockIdx.x * 256 + threadIdx.x; b < B; b += (long)gridDim.x * 256) {
-    const float* xb = x + b * D;
-    float sa[8] = {xb[0], xb[0], xb[1], xb[2], xb[3], xb[5], xb[6], xb[7]};
-    float sp[8] = {xb[0], xb[0], xb[1], xb[2], xb[3], xb[5], xb[6], xb[7]};
-    const float cur = sp[7];
-    float park[TMAX][4], seed[TMAX][8];
-#pragma unroll
-    for (int t = 0; t < TMAX; ++t) {
-      if (t < T) {
-        frenet_step(sa, y[b * O + t], y[b * O + T + t], dp);        // actual_states (:407)
-        vjp_park<IRBFN_ROLLOUT_FRENET_LS>(sp, park[t]);
-        frenet_step(sp, yp[b * O + t], yp[b * O + T + t], dp);      // pred_states   (:408)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float d = sp[i] - sa[i];
-          lsum += fabsf(d) * inv_s;
-          seed[t][i] = (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f)) * inv_s;      // d|.| = sign
-        }
-      }
-    }
-    float lam[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int t = TMAX - 1; t >= 0; --t) {
-      if (t < T) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) lam[i] += seed[t][i];
-        float ga, gsv;
-        vjp_back_step<IRBFN_ROLLOUT_FRENET_LS>(park[t], yp[b * O + t], yp[b * O + T + t], lam, cur, tie, dp, ga, gsv);
-        gy[b * O + t] = ga;
-        gy[b * O + T + t] = gsv;
-      }
-    }
-    for (int o = 0; o < O; ++o) {                             // pred_loss = |y_pred - y|.mean()  (:401)
-      const float d = yp[b * O + o] - y[b * O + o];
-      lsum += fabsf(d) * inv_y;
-      gy[b * O + o] += (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f)) * inv_y;
-    }
-  }
-  const float tot = block_sum_256(lsum, sm);
-  if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(256) void final_sum_kernel(const float* __restrict__ part, int n, float* __restrict__ out) {
-  __shared__ float sm[256];
-  float v = 0.0f;
-  for (int i = threadIdx.x; i < n; i += 256) v += part[i];
-  const float tot = block_sum_256(v, sm);
-  if (threadIdx.x == 0) out[0] = tot;
-}
-
-// ---- optimiser: clip_by_global_norm + adam ----------------------------------------------------------
-// Also hands the incremented step count to adam_clip_kernel through part[kRedBlocks] (the buffer holds kSeedBlocksMax
-// floats): every block of the Adam kernel reads THAT word, its thread (0, 0) stores it back to step[0] -- no block reads
-// step[0] there, so no separate "bump" launch is needed.
-__global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __restrict__ g, long n, float* __restrict__ part,
-                                                             const int* __restrict__ step) {
-  __shared__ float sm[256];
-  if (blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<int*>(part)[kRedBlocks] = step[0] + 1;
-  float v = 0.0f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) v += g[i] * g[i];
-  const float tot = block_sum_256(v, sm);
-  if (threadIdx.x == 0) part[blockIdx.x] = tot;
-}
-
-// optax.clip_by_global_norm: g <- g if ||g|| < max_norm else g / ||g|| * max_norm.
-// optax.adam (scale_by_adam, eps_root = 0): m <- b1 m + (1-b1) g ; v <- b2 v + (1-b2) g^2 ;
-//   update = -lr * (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) ; t is the incremented count.
-__global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                        float* __restrict__ m, float* __restrict__ v, long n,
-                                                        int* __restrict__ step, const float* __restrict__ part,
-                                                        float lr, float b1, float b2, float eps, float max_norm) {
-  __shared__ float sm[256];
-  const float sq = block_sum_256(threadIdx.x < kRedBlocks ? part[threadIdx.x] : 0.0f, sm);   // same in every block
-  const float gn = sqrtf(sq);
-  const float scale = (max_norm > 0.0f && !(gn < max_norm)) ? max_norm / gn : 1.0f;
-  const int t = reinterpret_cast<const int*>(part)[kRedBlocks];   // step[0] + 1, written by sqnorm_partial_kernel
-  if (blockIdx.x == 0 && threadIdx.x == 0) step[0] = t;
-  const float c1 = 1.0f - powf(b1, (float)t), c2 = 1.0f - powf(b2, (float)t);
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const float gi = g[i] * scale;
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = p[i] - lr * (mi / c1) / (sqrtf(vi / c2) + eps);
-  }
-}
-
-// ---- float64 twins ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double sgn64(double d) { return d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0); }   // d|.| = sign
-
-// train_step_oneint in float64 (scripts/train_nmpc.py:268-295): as seeds_oneint_kernel
-__global__ __launch_bounds__(256) void seeds_oneint_f64_kernel(const double* __restrict__ x, const double* __restrict__ yp,
-                                                               const double* __restrict__ y, double* __restrict__ gy,
-                                                               double* __restrict__ loss_part, long B, int D, int O,
-                                                               DynParams64 dp, double tie) {
-  __shared__ double sm[256];
-  double lsum = 0.0;
-  const double inv_y = 1.0 / ((double)B * (double)O), inv_s = 1.0 / ((double)B * 4.0);
-  for (long b = (long)blockIdx.x * 256 + threadIdx.x; b < B; b += (long)gridDim.x * 256) {
-    const double* xb = x + b * D;
-    double sp[7] = {0.0, 0.0, 0.0, xb[0], 0.0, xb[6], xb[5]};
-    double sa[7] = {0.0, 0.0, 0.0, xb[0], 0.0, xb[6], xb[5]};
-    double pk[ModeTraits<IRBFN_ROLLOUT_ST_KS>::NP];
-    vjp_park<IRBFN_ROLLOUT_ST_KS>(sp, pk);
-    const double ap = yp[b * O + 0], svp = yp[b * O + 1];
-    st_step<false, TrigF64>(sp, ap, svp, dp);                       // predicted_integrated_states  (:276)
-    st_step<false, TrigF64>(sa, y[b * O + 0], y[b * O + 1], dp);    // actual_integrated_states     (:275)
-    double lam[7] = {0, 0, 0, 0, 0, 0, 0};
-    const int idx[4] = {0, 1, 3, 4};
-    for (int k = 0; k < 4; ++k) {
-      const double d = sp[idx[k]] - sa[idx[k]];
-      lsum += 0.5 * d * d * inv_s;
-      lam[idx[k]] = d * inv_s;
-    }
-    for (int o = 0; o < O; ++o) {
-      const double d = yp[b * O + o] - y[b * O + o];
-      lsum += 0.5 * d * d * inv_y;
-      gy[b * O + o] = d * inv_y;
-    }
-    double ga, gsv;
-    vjp_back_step<IRBFN_ROLLOUT_ST_KS, TrigF64>(pk, ap, svp, lam, 0.0, tie, dp, ga, gsv);
-    gy[b * O + 0] += ga;
-    gy[b * O + 1] += gsv;
-  }
-  const double tot = block_sum_256(lsum, sm);
-  if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
-}
-
-// train_step_fullint in float64 (scripts/train_nmpc.py:306-390): as seeds_fullint_kernel, the reverse sweep is
-// vjp_back_step<FULLINT>.  O = 2T, T <= TMAX.
+// The same loss in float64: vjp_park / fullint_step / vjp_back_step<FULLINT> in a plain loop over T <= TMAX.  The float32
+// form above is a different algorithm (register-resident rows, static indices, a written-out reverse sweep whose contraction
+// the T = 5 gradients depend on), so the two stay side by side.
 template <int TMAX>
 __global__ __launch_bounds__(256) void seeds_fullint_f64_kernel(const double* __restrict__ x, const double* __restrict__ yp,
                                                                 const double* __restrict__ y, double* __restrict__ gy,
@@ -380,7 +246,7 @@ __global__ __launch_bounds__(256) void seeds_fullint_f64_kernel(const double* __
     for (int i = 0; i < 5; ++i) {
       const double d = sp[i] - sa[i];
       lsum += fabs(d) * inv_s;
-      lam[i] = sgn64(d) * inv_s;
+      lam[i] = sgn(d) * inv_s;
     }
     for (int t = T - 1; t >= 0; --t) {
       double ga, gsv;
@@ -391,95 +257,212 @@ __global__ __launch_bounds__(256) void seeds_fullint_f64_kernel(const double* __
     for (int k = 0; k < 2; ++k) {                            // y_predictions[:, [0, T]]  (:387)
       const double d = pr[k * T] - yr[k * T];
       lsum += fabs(d) * inv_y;
-      gr[k * T] += sgn64(d) * inv_y;
+      gr[k * T] += sgn(d) * inv_y;
     }
   }
   const double tot = block_sum_256(lsum, sm);
   if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
 }
 
-// Frenet train_step_fullint in float64 (scripts/train_nmpc_frenet.py:394-421): as seeds_frenet_fullint_kernel
-template <int TMAX>
-__global__ __launch_bounds__(256) void seeds_frenet_fullint_f64_kernel(const double* __restrict__ x, const double* __restrict__ yp,
-                                                                       const double* __restrict__ y, double* __restrict__ gy,
-                                                                       double* __restrict__ loss_part, long B, int D, int T,
-                                                                       DynParams64 dp, double tie) {
-  __shared__ double sm[256];
-  const int O = 2 * T;
-  const double inv_y = 1.0 / ((double)B * (double)O), inv_s = 1.0 / ((double)B * (double)T * 8.0);
-  double lsum = 0.0;
+// ---- Frenet train_step_fullint (scripts/train_nmpc_frenet.py:394-421) -------------------------------------------
+// x[B,8] = [ey, delta, vx_car, vy_car, vx_goal, wz, epsi, curv]; initial_state = x[:, [0,0,1,2,3,5,6,7]] (:398);
+// loss = mean|y_pred - y| + mean|integrate_frenet_mult([init, y_pred]) - integrate_frenet_mult([init, y])|
+// (:402-412; all T states, all 8 components).  gy = d loss / d y_pred through the T-step Frenet roll-out
+// (rollout_adjoint.h: the adjoint of dynamics.py:190-290, low-speed RHS).  O = 2T.
+// The loop shape follows S.  float: both sweeps unrolled to TMAX under a t < T guard, so park / seed stay in registers.
+// double: rolled loops over T (ROLLED); unrolled, that kernel grows from 1768 to 6719 instructions at TMAX = 5 (22 364 at 16).
+template <int TMAX, typename S>
+__global__ __launch_bounds__(256) void seeds_frenet_fullint_kernel(const S* __restrict__ x, const S* __restrict__ yp,
+                                                                   const S* __restrict__ y, S* __restrict__ gy,
+                                                                   S* __restrict__ loss_part, long B, int D, int T,
+                                                                   typename DynOf<S>::type dp, S tie) {
+  using Trig = typename TrigOf<S>::type;
+  constexpr bool ROLLED = std::is_same<S, double>::value;
+  constexpr int UNROLL = ROLLED ? 1 : TMAX;
+  __shared__ S sm[256];
+  const int O = 2 * T, TN = ROLLED ? T : TMAX;                                // trip count of the two sweeps
+  const S inv_y = S(1) / ((S)B * (S)O), inv_s = S(1) / ((S)B * (S)T * S(8));
+  S lsum = S(0);
   for (long b = (long)blockIdx.x * 256 + threadIdx.x; b < B; b += (long)gridDim.x * 256) {
-    const double* xb = x + b * D;
-    double sa[8] = {xb[0], xb[0], xb[1], xb[2], xb[3], xb[5], xb[6], xb[7]};
-    double sp[8] = {xb[0], xb[0], xb[1], xb[2], xb[3], xb[5], xb[6], xb[7]};
-    const double cur = sp[7];
-    double park[TMAX][ModeTraits<IRBFN_ROLLOUT_FRENET_LS>::NP], seed[TMAX][8];
-    for (int t = 0; t < T; ++t) {
-      frenet_step<TrigF64>(sa, y[b * O + t], y[b * O + T + t], dp);       // actual_states (:407)
-      vjp_park<IRBFN_ROLLOUT_FRENET_LS>(sp, park[t]);
-      frenet_step<TrigF64>(sp, yp[b * O + t], yp[b * O + T + t], dp);     // pred_states   (:408)
-      for (int i = 0; i < 8; ++i) {
-        const double d = sp[i] - sa[i];
-        lsum += fabs(d) * inv_s;
-        seed[t][i] = sgn64(d) * inv_s;
+    const S* xb = x + b * D;
+    S sa[8] = {xb[0], xb[0], xb[1], xb[2], xb[3], xb[5], xb[6], xb[7]};
+    S sp[8] = {xb[0], xb[0], xb[1], xb[2], xb[3], xb[5], xb[6], xb[7]};
+    const S cur = sp[7];
+    S park[TMAX][ModeTraits<IRBFN_ROLLOUT_FRENET_LS>::NP], seed[TMAX][8];
+#pragma unroll UNROLL
+    for (int t = 0; t < TN; ++t) {
+      if (ROLLED || t < T) {
+        frenet_step<Trig>(sa, y[b * O + t], y[b * O + T + t], dp);        // actual_states (:407)
+        vjp_park<IRBFN_ROLLOUT_FRENET_LS>(sp, park[t]);
+        frenet_step<Trig>(sp, yp[b * O + t], yp[b * O + T + t], dp);      // pred_states   (:408)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const S d = sp[i] - sa[i];
+          lsum += fabs(d) * inv_s;
+          seed[t][i] = sgn(d) * inv_s;
+        }
       }
     }
-    double lam[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int t = T - 1; t >= 0; --t) {
-      for (int i = 0; i < 8; ++i) lam[i] += seed[t][i];
-      double ga, gsv;
-      vjp_back_step<IRBFN_ROLLOUT_FRENET_LS, TrigF64>(park[t], yp[b * O + t], yp[b * O + T + t], lam, cur, tie, dp, ga, gsv);
-      gy[b * O + t] = ga;
-      gy[b * O + T + t] = gsv;
+    S lam[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll UNROLL
+    for (int t = TN - 1; t >= 0; --t) {
+      if (ROLLED || t < T) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) lam[i] += seed[t][i];
+        S ga, gsv;
+        vjp_back_step<IRBFN_ROLLOUT_FRENET_LS, Trig>(park[t], yp[b * O + t], yp[b * O + T + t], lam, cur, tie, dp, ga, gsv);
+        gy[b * O + t] = ga;
+        gy[b * O + T + t] = gsv;
+      }
     }
-    for (int o = 0; o < O; ++o) {                            // pred_loss = |y_pred - y|.mean()  (:401)
-      const double d = yp[b * O + o] - y[b * O + o];
+    for (int o = 0; o < O; ++o) {                             // pred_loss = |y_pred - y|.mean()  (:401)
+      const S d = yp[b * O + o] - y[b * O + o];
       lsum += fabs(d) * inv_y;
-      gy[b * O + o] += sgn64(d) * inv_y;
+      gy[b * O + o] += sgn(d) * inv_y;
     }
   }
-  const double tot = block_sum_256(lsum, sm);
+  const S tot = block_sum_256(lsum, sm);
   if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
 }
 
-__global__ __launch_bounds__(256) void final_sum_f64_kernel(const double* __restrict__ part, int n, double* __restrict__ out) {
-  __shared__ double sm[256];
-  double v = 0.0;
+template <typename S>
+__global__ __launch_bounds__(256) void final_sum_kernel(const S* __restrict__ part, int n, S* __restrict__ out) {
+  __shared__ S sm[256];
+  S v = S(0);
   for (int i = threadIdx.x; i < n; i += 256) v += part[i];
-  const double tot = block_sum_256(v, sm);
+  const S tot = block_sum_256(v, sm);
   if (threadIdx.x == 0) out[0] = tot;
 }
 
-// the step count travels in the int at the start of the double part[kRedBlocks], as in sqnorm_partial_kernel
-__global__ __launch_bounds__(256) void sqnorm_partial_f64_kernel(const double* __restrict__ g, long n, double* __restrict__ part,
-                                                                 const int* __restrict__ step) {
-  __shared__ double sm[256];
+// ---- optimiser: clip_by_global_norm + adam ----------------------------------------------------------
+// Also hands the incremented step count to adam_clip_kernel through the int at the start of part[kRedBlocks] (the buffer
+// holds kSeedBlocksMax scalars): every block of the Adam kernel reads THAT word, its thread (0, 0) stores it back to
+// step[0] -- no block reads step[0] there, so no separate "bump" launch is needed.
+template <typename S>
+__global__ __launch_bounds__(256) void sqnorm_partial_kernel(const S* __restrict__ g, long n, S* __restrict__ part,
+                                                             const int* __restrict__ step) {
+  __shared__ S sm[256];
   if (blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<int*>(part + kRedBlocks)[0] = step[0] + 1;
-  double v = 0.0;
+  S v = S(0);
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) v += g[i] * g[i];
-  const double tot = block_sum_256(v, sm);
+  const S tot = block_sum_256(v, sm);
   if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
-__global__ __launch_bounds__(256) void adam_clip_f64_kernel(double* __restrict__ p, const double* __restrict__ g,
-                                                            double* __restrict__ m, double* __restrict__ v, long n,
-                                                            int* __restrict__ step, const double* __restrict__ part,
-                                                            double lr, double b1, double b2, double eps, double max_norm) {
-  __shared__ double sm[256];
-  const double sq = block_sum_256(threadIdx.x < kRedBlocks ? part[threadIdx.x] : 0.0, sm);
-  const double gn = sqrt(sq);
-  const double scale = (max_norm > 0.0 && !(gn < max_norm)) ? max_norm / gn : 1.0;
-  const int t = reinterpret_cast<const int*>(part + kRedBlocks)[0];
+// optax.clip_by_global_norm: g <- g if ||g|| < max_norm else g / ||g|| * max_norm.
+// optax.adam (scale_by_adam, eps_root = 0): m <- b1 m + (1-b1) g ; v <- b2 v + (1-b2) g^2 ;
+//   update = -lr * (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) ; t is the incremented count.
+template <typename S>
+__global__ __launch_bounds__(256) void adam_clip_kernel(S* __restrict__ p, const S* __restrict__ g,
+                                                        S* __restrict__ m, S* __restrict__ v, long n,
+                                                        int* __restrict__ step, const S* __restrict__ part,
+                                                        S lr, S b1, S b2, S eps, S max_norm) {
+  __shared__ S sm[256];
+  const S sq = block_sum_256(threadIdx.x < kRedBlocks ? part[threadIdx.x] : S(0), sm);   // same in every block
+  const S gn = sqrt(sq);
+  const S scale = (max_norm > S(0) && !(gn < max_norm)) ? max_norm / gn : S(1);
+  const int t = reinterpret_cast<const int*>(part + kRedBlocks)[0];   // step[0] + 1, written by sqnorm_partial_kernel
   if (blockIdx.x == 0 && threadIdx.x == 0) step[0] = t;
-  const double c1 = 1.0 - pow(b1, (double)t), c2 = 1.0 - pow(b2, (double)t);
+  const S c1 = S(1) - pow(b1, (S)t), c2 = S(1) - pow(b2, (S)t);
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const double gi = g[i] * scale;
-    const double mi = b1 * m[i] + (1.0 - b1) * gi;
-    const double vi = b2 * v[i] + (1.0 - b2) * gi * gi;
+    const S gi = g[i] * scale;
+    const S mi = b1 * m[i] + (S(1) - b1) * gi;
+    const S vi = b2 * v[i] + (S(1) - b2) * gi * gi;
     m[i] = mi;
     v[i] = vi;
     p[i] = p[i] - lr * (mi / c1) / (sqrt(vi / c2) + eps);
   }
+}
+
+// ---- launchers: one per step, S = float / double (the argument rules and status codes of both entry points) -----------------
+
+// blocks of the loss / seed kernels: one row per thread (a second pass over the rows doubled the kernel: 18 -> 9 us at the
+// reference's batch of 80000), grid-stride beyond kSeedBlocksMax * 256 rows
+static int seed_blocks(int64_t B) {
+  const int64_t nb = (B + 255) / 256;
+  return nb < 1 ? 1 : (nb > kSeedBlocksMax ? kSeedBlocksMax : (int)nb);
+}
+
+// the shared tail of the three seed launchers: the launch status of the seed kernel, then the loss from its partials
+template <typename S>
+static int finish_loss(S* partials_dev, S* loss_dev, int64_t B, hipStream_t s) {
+  IRBFN_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(final_sum_kernel<S>, dim3(1), dim3(256), 0, s, partials_dev, seed_blocks(B), loss_dev);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
+
+template <typename S>
+static int train_seeds_oneint(const S* x_dev, const S* y_pred_dev, const S* y_dev, const S* dyn_params_host, S clip_tie,
+                              S* gy_dev, S* loss_dev, S* partials_dev, int64_t B, int D, int O, void* stream) {
+  if (B < 0 || D < 7 || O < 2 || !dyn_params_host) return IRBFN_ERR_BAD_ARG;
+  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
+  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
+  typename DynOf<S>::type dp;
+  memcpy(dp.p, dyn_params_host, sizeof(dp.p));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(seeds_oneint_kernel<S>, dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
+                     partials_dev, (long)B, D, O, dp, clip_tie);
+  return finish_loss(partials_dev, loss_dev, B, s);
+}
+
+template <typename S>
+static int train_seeds_fullint(const S* x_dev, const S* y_pred_dev, const S* y_dev, S clip_tie, S* gy_dev, S* loss_dev,
+                               S* partials_dev, int64_t B, int D, int T, void* stream) {
+  if (B < 0 || D < 1 || T < 1) return IRBFN_ERR_BAD_ARG;
+  if (T > 64) return IRBFN_ERR_UNSUPPORTED;
+  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
+  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid(seed_blocks(B)), block(256);
+#define IRBFN_SEEDS_FULLINT(KERNEL) \
+  hipLaunchKernelGGL(KERNEL, grid, block, 0, s, x_dev, y_pred_dev, y_dev, gy_dev, partials_dev, (long)B, D, T, clip_tie)
+  if constexpr (std::is_same<S, float>::value) {
+    if (T == 5) IRBFN_SEEDS_FULLINT((seeds_fullint_kernel<8, 5>));    // the reference's horizon (train_nmpc.py:306-374)
+    else if (T <= 8) IRBFN_SEEDS_FULLINT((seeds_fullint_kernel<8>));
+    else IRBFN_SEEDS_FULLINT((seeds_fullint_kernel<64>));
+  } else {
+    if (T <= 8) IRBFN_SEEDS_FULLINT((seeds_fullint_f64_kernel<8>));
+    else IRBFN_SEEDS_FULLINT((seeds_fullint_f64_kernel<64>));
+  }
+#undef IRBFN_SEEDS_FULLINT
+  return finish_loss(partials_dev, loss_dev, B, s);
+}
+
+template <typename S>
+static int train_seeds_frenet_fullint(const S* x_dev, const S* y_pred_dev, const S* y_dev, const S* dyn_params_host,
+                                      S clip_tie, S* gy_dev, S* loss_dev, S* partials_dev, int64_t B, int D, int T,
+                                      void* stream) {
+  if (B < 0 || D < 8 || T < 1 || T > 16 || !dyn_params_host) return IRBFN_ERR_BAD_ARG;
+  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
+  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
+  typename DynOf<S>::type dp;
+  memcpy(dp.p, dyn_params_host, sizeof(dp.p));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (T <= 5)
+    hipLaunchKernelGGL((seeds_frenet_fullint_kernel<5, S>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev,
+                       gy_dev, partials_dev, (long)B, D, T, dp, clip_tie);
+  else
+    hipLaunchKernelGGL((seeds_frenet_fullint_kernel<16, S>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev,
+                       gy_dev, partials_dev, (long)B, D, T, dp, clip_tie);
+  return finish_loss(partials_dev, loss_dev, B, s);
+}
+
+template <typename S>
+static int adam_clip_step(S* params_dev, const S* grads_dev, S* m_dev, S* v_dev, int64_t n, int* step_dev, S lr, S beta1,
+                          S beta2, S eps, S max_grad_norm, S* partials_dev, void* stream) {
+  if (n < 0 || !step_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
+  if (n > 0 && (!params_dev || !grads_dev || !m_dev || !v_dev)) return IRBFN_ERR_BAD_ARG;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(sqnorm_partial_kernel<S>, dim3(kRedBlocks), dim3(256), 0, s, grads_dev, (long)n, partials_dev, step_dev);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  long blocks = (n + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adam_clip_kernel<S>, dim3((unsigned)blocks), dim3(256), 0, s, params_dev, grads_dev, m_dev, v_dev,
+                     (long)n, step_dev, partials_dev, lr, beta1, beta2, eps, max_grad_norm);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
 }
 
 }  // namespace irbfn
@@ -490,166 +473,56 @@ extern "C" {
 
 int irbfn_train_loss_partials(void) { return kSeedBlocksMax; }
 
-// blocks of the loss / seed kernels: one row per thread (a second pass over the rows doubled the kernel: 18 -> 9 us at the
-// reference's batch of 80000), grid-stride beyond kSeedBlocksMax * 256 rows
-static int seed_blocks(int64_t B) {
-  const int64_t nb = (B + 255) / 256;
-  return nb < 1 ? 1 : (nb > kSeedBlocksMax ? kSeedBlocksMax : (int)nb);
-}
-
 int irbfn_train_seeds_oneint(const float* x_dev, const float* y_pred_dev, const float* y_dev,
                              const float* dyn_params_host, float clip_tie, float* gy_dev, float* loss_dev,
                              float* partials_dev, int64_t B, int D, int O, void* stream) {
-  if (B < 0 || D < 7 || O < 2 || !dyn_params_host) return IRBFN_ERR_BAD_ARG;
-  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
-  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
-  DynParams dp;
-  memcpy(dp.p, dyn_params_host, sizeof(dp.p));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(seeds_oneint_kernel, dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
-                     partials_dev, (long)B, D, O, dp, clip_tie);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, s, partials_dev, seed_blocks(B), loss_dev);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
+  return train_seeds_oneint(x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev, partials_dev, B, D, O, stream);
 }
 
 int irbfn_train_seeds_fullint(const float* x_dev, const float* y_pred_dev, const float* y_dev, float clip_tie,
                               float* gy_dev, float* loss_dev, float* partials_dev, int64_t B, int D, int T,
                               void* stream) {
-  if (B < 0 || D < 1 || T < 1) return IRBFN_ERR_BAD_ARG;
-  if (T > 64) return IRBFN_ERR_UNSUPPORTED;
-  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
-  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (T == 5)                                                // the reference's horizon (train_nmpc.py:306-374)
-    hipLaunchKernelGGL((seeds_fullint_kernel<8, 5>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
-                       partials_dev, (long)B, D, T, clip_tie);
-  else if (T <= 8)
-    hipLaunchKernelGGL((seeds_fullint_kernel<8>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
-                       partials_dev, (long)B, D, T, clip_tie);
-  else
-    hipLaunchKernelGGL((seeds_fullint_kernel<64>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
-                       partials_dev, (long)B, D, T, clip_tie);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, s, partials_dev, seed_blocks(B), loss_dev);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
+  return train_seeds_fullint(x_dev, y_pred_dev, y_dev, clip_tie, gy_dev, loss_dev, partials_dev, B, D, T, stream);
 }
 
 int irbfn_train_seeds_frenet_fullint(const float* x_dev, const float* y_pred_dev, const float* y_dev,
                                      const float* dyn_params_host, float clip_tie, float* gy_dev, float* loss_dev,
                                      float* partials_dev, int64_t B, int D, int T, void* stream) {
-  if (B < 0 || D < 8 || T < 1 || T > 16 || !dyn_params_host) return IRBFN_ERR_BAD_ARG;
-  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
-  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
-  DynParams dp;
-  memcpy(dp.p, dyn_params_host, sizeof(dp.p));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (T <= 5)
-    hipLaunchKernelGGL((seeds_frenet_fullint_kernel<5>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
-                       partials_dev, (long)B, D, T, dp, clip_tie);
-  else
-    hipLaunchKernelGGL((seeds_frenet_fullint_kernel<16>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
-                       partials_dev, (long)B, D, T, dp, clip_tie);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, s, partials_dev, seed_blocks(B), loss_dev);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
+  return train_seeds_frenet_fullint(x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev, partials_dev, B, D, T,
+                                    stream);
 }
 
 int irbfn_adam_clip_step(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev, int64_t n,
                          int* step_dev, float lr, float beta1, float beta2, float eps, float max_grad_norm,
                          float* partials_dev, void* stream) {
-  if (n < 0 || !step_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
-  if (n > 0 && (!params_dev || !grads_dev || !m_dev || !v_dev)) return IRBFN_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(kRedBlocks), dim3(256), 0, s, grads_dev, (long)n, partials_dev, step_dev);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  long blocks = (n + 255) / 256;
-  if (blocks > 1024) blocks = 1024;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, s, params_dev, grads_dev, m_dev, v_dev,
-                     (long)n, step_dev, partials_dev, lr, beta1, beta2, eps, max_grad_norm);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
+  return adam_clip_step(params_dev, grads_dev, m_dev, v_dev, n, step_dev, lr, beta1, beta2, eps, max_grad_norm, partials_dev,
+                        stream);
 }
-
-// ---- float64 entry points: the argument rules and status codes of their float32 twins above -------------------------------
 
 int irbfn_train_seeds_oneint_f64(const double* x_dev, const double* y_pred_dev, const double* y_dev,
                                  const double* dyn_params_host, double clip_tie, double* gy_dev, double* loss_dev,
                                  double* partials_dev, int64_t B, int D, int O, void* stream) {
-  if (B < 0 || D < 7 || O < 2 || !dyn_params_host) return IRBFN_ERR_BAD_ARG;
-  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
-  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
-  DynParams64 dp;
-  memcpy(dp.p, dyn_params_host, sizeof(dp.p));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(seeds_oneint_f64_kernel, dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
-                     partials_dev, (long)B, D, O, dp, clip_tie);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(final_sum_f64_kernel, dim3(1), dim3(256), 0, s, partials_dev, seed_blocks(B), loss_dev);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
+  return train_seeds_oneint(x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev, partials_dev, B, D, O, stream);
 }
 
 int irbfn_train_seeds_fullint_f64(const double* x_dev, const double* y_pred_dev, const double* y_dev, double clip_tie,
                                   double* gy_dev, double* loss_dev, double* partials_dev, int64_t B, int D, int T,
                                   void* stream) {
-  if (B < 0 || D < 1 || T < 1) return IRBFN_ERR_BAD_ARG;
-  if (T > 64) return IRBFN_ERR_UNSUPPORTED;
-  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
-  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (T <= 8)
-    hipLaunchKernelGGL((seeds_fullint_f64_kernel<8>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
-                       partials_dev, (long)B, D, T, clip_tie);
-  else
-    hipLaunchKernelGGL((seeds_fullint_f64_kernel<64>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev,
-                       partials_dev, (long)B, D, T, clip_tie);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(final_sum_f64_kernel, dim3(1), dim3(256), 0, s, partials_dev, seed_blocks(B), loss_dev);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
+  return train_seeds_fullint(x_dev, y_pred_dev, y_dev, clip_tie, gy_dev, loss_dev, partials_dev, B, D, T, stream);
 }
 
 int irbfn_train_seeds_frenet_fullint_f64(const double* x_dev, const double* y_pred_dev, const double* y_dev,
                                          const double* dyn_params_host, double clip_tie, double* gy_dev, double* loss_dev,
                                          double* partials_dev, int64_t B, int D, int T, void* stream) {
-  if (B < 0 || D < 8 || T < 1 || T > 16 || !dyn_params_host) return IRBFN_ERR_BAD_ARG;
-  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
-  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
-  DynParams64 dp;
-  memcpy(dp.p, dyn_params_host, sizeof(dp.p));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (T <= 5)
-    hipLaunchKernelGGL((seeds_frenet_fullint_f64_kernel<5>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev,
-                       gy_dev, partials_dev, (long)B, D, T, dp, clip_tie);
-  else
-    hipLaunchKernelGGL((seeds_frenet_fullint_f64_kernel<16>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev,
-                       gy_dev, partials_dev, (long)B, D, T, dp, clip_tie);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(final_sum_f64_kernel, dim3(1), dim3(256), 0, s, partials_dev, seed_blocks(B), loss_dev);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
+  return train_seeds_frenet_fullint(x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev, partials_dev, B, D, T,
+                                    stream);
 }
 
 int irbfn_adam_clip_step_f64(double* params_dev, const double* grads_dev, double* m_dev, double* v_dev, int64_t n,
                              int* step_dev, double lr, double beta1, double beta2, double eps, double max_grad_norm,
                              double* partials_dev, void* stream) {
-  if (n < 0 || !step_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
-  if (n > 0 && (!params_dev || !grads_dev || !m_dev || !v_dev)) return IRBFN_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(sqnorm_partial_f64_kernel, dim3(kRedBlocks), dim3(256), 0, s, grads_dev, (long)n, partials_dev, step_dev);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  long blocks = (n + 255) / 256;
-  if (blocks > 1024) blocks = 1024;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adam_clip_f64_kernel, dim3((unsigned)blocks), dim3(256), 0, s, params_dev, grads_dev, m_dev, v_dev,
-                     (long)n, step_dev, partials_dev, lr, beta1, beta2, eps, max_grad_norm);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
+  return adam_clip_step(params_dev, grads_dev, m_dev, v_dev, n, step_dev, lr, beta1, beta2, eps, max_grad_norm, partials_dev,
+                        stream);
 }
 
 }  // extern "C"

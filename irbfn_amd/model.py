@@ -65,6 +65,30 @@ def like_input(out_t, ref, torch):
     return out_t.cpu().numpy()
 
 
+def _load_card(cfg) -> dict:
+    """A model card as a dict: cfg is a dict, an argparse.Namespace or the path of a YAML card."""
+    if isinstance(cfg, str):
+        import yaml
+        with open(cfg, "r") as f:
+            return yaml.safe_load(f)
+    return cfg if isinstance(cfg, dict) else vars(cfg)
+
+
+def _grown_ws(cache: dict, key, nbytes: int, torch, dev):
+    """The byte workspace kept in cache[key], grown on demand and reused across steps."""
+    ws = cache.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty((max(int(nbytes), 8),), dtype=torch.uint8, device=dev)
+        cache[key] = ws
+    return ws
+
+
+def _check_out_leaf(t, shape, dtype, torch, what="vjp"):
+    """A caller-provided gradient leaf (``out=``, e.g. a view of one flat buffer) must be what the kernels write."""
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{what} out= leaves must be contiguous {str(dtype).split('.')[-1]} cuda tensors of the parameter shapes")
+
+
 class WCRBFNet:
     """Interpolating RBF network (smooth region gate, R vmapped RBF layers, Dense).
 
@@ -191,12 +215,7 @@ class WCRBFNet:
         ``config()`` of a float64 net holds ``use_float64: True`` and keeps the mode.  centers: the centres file's array,
         which the card does not hold (as in the reference); with it the card's ``fixed_centers`` / ``fixed_width`` (and
         ``log_sigs``) restore the layer class."""
-        if isinstance(cfg, str):
-            import yaml
-            with open(cfg, "r") as f:
-                cfg = yaml.safe_load(f)
-        elif not isinstance(cfg, dict):
-            cfg = vars(cfg)
+        cfg = _load_card(cfg)
         extra = {k: cfg[k] for k in ("fixed_centers", "fixed_width", "log_sigs") if cfg.get(k) is not None}
         return cls(**{k: cfg[k] for k in _CFG_FIELDS}, use_float64=use_float64 or bool(cfg.get("use_float64", False)),
                    centers=centers, **extra)
@@ -233,15 +252,15 @@ class WCRBFNet:
         return {"params": p}
 
     # ------------------------------------------------------------------ descriptor management
-    def _gate_tables(self):
+    def _gate_tables(self, dtype=np.float32):
         ns = self.num_split_dimensions
         mr = max([1] + [max(len(self.lower_bounds[d]), len(self.upper_bounds[d])) for d in range(ns)])
-        lo = np.zeros((max(ns, 1), mr), np.float32)
-        hi = np.zeros((max(ns, 1), mr), np.float32)
+        lo = np.zeros((max(ns, 1), mr), dtype)
+        hi = np.zeros((max(ns, 1), mr), dtype)
         for d in range(ns):
             lo[d, :len(self.lower_bounds[d])] = self.lower_bounds[d]
             hi[d, :len(self.upper_bounds[d])] = self.upper_bounds[d]
-        delta = np.asarray(self.delta[:ns] if ns else [0.0], np.float32)
+        delta = np.asarray(self.delta[:ns] if ns else [0.0], dtype)
         nr = min(len(self.dimension_ranges), self.num_regions)   # .at[:, i].set past R is dropped
         dr = np.asarray([r[:ns] for r in self.dimension_ranges[:nr]], np.int32).reshape(nr, ns)
         return ns, mr, lo, hi, delta, np.ascontiguousarray(dr), nr
@@ -392,17 +411,8 @@ class WCRBFNet:
         dev = torch.cuda.current_device()
         ent = self._f64.get(dev)
         if ent is None:
-            ns = self.num_split_dimensions
-            mr = max([1] + [max(len(self.lower_bounds[d]), len(self.upper_bounds[d])) for d in range(ns)])
-            lo = np.zeros((max(ns, 1), mr), np.float64)
-            hi = np.zeros((max(ns, 1), mr), np.float64)
-            for d in range(ns):
-                lo[d, :len(self.lower_bounds[d])] = self.lower_bounds[d]
-                hi[d, :len(self.upper_bounds[d])] = self.upper_bounds[d]
-            nr = min(len(self.dimension_ranges), self.num_regions)
-            dr = np.asarray([r[:ns] for r in self.dimension_ranges[:nr]], np.int32).reshape(nr, max(ns, 0))
-            tens = [torch.from_numpy(a).cuda() for a in (lo, hi, np.asarray(self.delta[:ns] if ns else [0.0], np.float64),
-                                                         np.ascontiguousarray(dr if dr.size else np.zeros((1, 1), np.int32)))]
+            ns, mr, lo, hi, delta, dr, nr = self._gate_tables(np.float64)
+            tens = [torch.from_numpy(a).cuda() for a in (lo, hi, delta, dr if dr.size else np.zeros((1, 1), np.int32))]
             card = _lib.F64Card(self.in_features, self.num_regions, self.num_kernels, self.out_features,
                                 _lib.BASIS_ENUM[self.basis_func], ns, mr, nr, tens[0].data_ptr(), tens[1].data_ptr(),
                                 tens[2].data_ptr(), tens[3].data_ptr())
@@ -414,13 +424,6 @@ class WCRBFNet:
     def _dev_f64(a, torch):
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
         return t.to(device=torch.device("cuda", torch.cuda.current_device()), dtype=torch.float64).contiguous()
-
-    def _f64_ws(self, torch, ent, nbytes):
-        ws = ent[2].get("ws")
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.empty((max(int(nbytes), 8),), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
-            ent[2]["ws"] = ws
-        return ws
 
     def apply64(self, params: dict, x):
         """``apply`` in float64 (the reference under --use_float64, scripts/train_nmpc.py:41-42) -> float64 [B,O]."""
@@ -437,7 +440,7 @@ class WCRBFNet:
         B = xd.shape[0]
         out = torch.empty((B, self.out_features), dtype=torch.float64, device=xd.device)
         nbytes = int(lib.irbfn_f64_workspace_bytes(C.byref(card), B, 0))
-        ws = self._f64_ws(torch, ent, nbytes)
+        ws = _grown_ws(ent[2], "ws", nbytes, torch, xd.device)
         st = lib.irbfn_f64_forward(C.byref(card), _ptr(c), _ptr(l), _ptr(k), _ptr(b), _ptr(xd), _ptr(out), B, _ptr(ws), nbytes,
                                    _stream_ptr(torch))
         _lib.check(st, "irbfn_f64_forward")
@@ -467,13 +470,11 @@ class WCRBFNet:
         if out is not None:
             o = _inner(out)
             for g, n in self.live_leaves():
-                t = o[g][n]
-                if tuple(t.shape) != full[n].shape or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
-                    raise ValueError("vjp64 out= leaves must be contiguous float64 cuda tensors of the parameter shapes")
-                full[n] = t
+                _check_out_leaf(o[g][n], full[n].shape, torch.float64, torch, "vjp64")
+                full[n] = o[g][n]
         gc, gl, gk, gb = full["centers"], full["log_sigs"], full["kernel"], full["bias"]
         nbytes = int(lib.irbfn_f64_workspace_bytes(C.byref(card), B, 1))
-        ws = self._f64_ws(torch, ent, nbytes)
+        ws = _grown_ws(ent[2], "ws", nbytes, torch, xd.device)
         st = lib.irbfn_f64_vjp(C.byref(card), _ptr(c), _ptr(l), _ptr(k), _ptr(xd), _ptr(gd), _ptr(gc), _ptr(gl), _ptr(gk), _ptr(gb),
                                B, _ptr(ws), nbytes, _stream_ptr(torch))
         _lib.check(st, "irbfn_f64_vjp")
@@ -523,20 +524,15 @@ class WCRBFNet:
         if out is not None:      # caller-provided gradient leaves (e.g. views of one flat buffer)
             o = _inner(out)
             for g, n in self.live_leaves():
-                t = o[g][n]
-                if tuple(t.shape) != shapes[n] or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-                    raise ValueError("vjp out= leaves must be contiguous float32 cuda tensors of the parameter shapes")
-                full[n] = t
+                _check_out_leaf(o[g][n], shapes[n], torch.float32, torch)
+                full[n] = o[g][n]
         else:
             for g, n in self.live_leaves():
                 full[n] = torch.empty(shapes[n], dtype=torch.float32, device=dev)
         gc, gl, gk, gb = (full.get(n) for n in ("centers", "log_sigs", "kernel", "bias"))
         h = self._handle(torch)
         nbytes = int(lib.irbfn_net_vjp_workspace_bytes(h, B))
-        ws = self._vjp_ws.get(dev.index)
-        if ws is None or ws.numel() < nbytes:        # grown on demand, reused across steps
-            ws = torch.empty((max(nbytes, 4),), dtype=torch.uint8, device=dev)
-            self._vjp_ws[dev.index] = ws
+        ws = _grown_ws(self._vjp_ws, dev.index, nbytes, torch, dev)
         if self.frozen:          # the frozen leaves are neither computed (K2g) nor written
             st = lib.irbfn_net_vjp_frozen(h, _ptr(xd), _ptr(gd), _ptr(gc) if gc is not None else None,
                                           _ptr(gl) if gl is not None else None, _ptr(gk), _ptr(gb), B, _ptr(ws), nbytes,
@@ -648,12 +644,7 @@ class DeeperWCRBFNet:
 
     @classmethod
     def from_config(cls, cfg) -> "DeeperWCRBFNet":
-        if isinstance(cfg, str):
-            import yaml
-            with open(cfg, "r") as f:
-                cfg = yaml.safe_load(f)
-        elif not isinstance(cfg, dict):
-            cfg = vars(cfg)
+        cfg = _load_card(cfg)
         return cls(**{k: cfg[k] for k in _CFG_FIELDS}, use_float64=bool(cfg.get("use_float64", False)))
 
     LEAVES = (("rbf_list", "centers"), ("rbf_list", "log_sigs"), ("linear_pre1", "kernel"), ("linear_pre1", "bias"),
@@ -714,7 +705,10 @@ class DeeperWCRBFNet:
         out, h1 = self._forward(params, to_device_f32(x, torch), torch, _lib.load())
         return like_input(out, x, torch), like_input(h1, x, torch)
 
-    def _vjp_impl(self, params: dict, x, gout, out=None, h1=None, stage_vjp_kernel=None):
+    def _head_backward(self, params: dict, x, gout, h1, what: str, head_out=None):
+        """The head's backward (``irbfn_mlp_head_vjp``) -> (stage_params, xd, gh1, (gw2, gb2, gw3, gb3)): gh1 [B, 64] is the
+        cotangent of linear_pre1's output, the seed of the stage's VJPs.  h1: the stage output, computed here if None.
+        head_out: the caller's four gradient leaves of the head; fresh tensors otherwise."""
         torch = _lib.require_gpu()
         lib = _lib.load()
         p = _inner(params)
@@ -726,25 +720,14 @@ class DeeperWCRBFNet:
             raise ValueError(f"gout must have shape ({B}, {O})")
         if h1 is None:
             h1 = self.stage.apply(stage_params, xd)
-        else:
-            if not isinstance(h1, torch.Tensor) or tuple(h1.shape) != (B, H) or h1.dtype != torch.float32 or not h1.is_cuda \
-                    or not h1.is_contiguous():
-                raise ValueError(f"vjp h1= must be the contiguous float32 cuda stage output [{B}, {H}] of apply_with_hidden")
+        elif not isinstance(h1, torch.Tensor) or tuple(h1.shape) != (B, H) or h1.dtype != torch.float32 or not h1.is_cuda \
+                or not h1.is_contiguous():
+            raise ValueError(f"{what} h1= must be the contiguous float32 cuda stage output [{B}, {H}] of apply_with_hidden")
         w2, b2, w3 = (to_device_f32(a, torch) for a in (p["linear_pre2"]["kernel"], p["linear_pre2"]["bias"], p["linear"]["kernel"]))
         dev = xd.device
-        if out is not None:      # caller-provided gradient leaves (e.g. views of one flat buffer)
-            o = _inner(out)
-            for (g, n), shp in self.group_leaf_shapes().items():
-                t = o[g][n]
-                if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-                    raise ValueError("vjp out= leaves must be contiguous float32 cuda tensors of the parameter shapes")
-            gw2, gb2, gw3, gb3 = o["linear_pre2"]["kernel"], o["linear_pre2"]["bias"], o["linear"]["kernel"], o["linear"]["bias"]
-            stage_out = {"rbf_list": o["rbf_list"], "linear": o["linear_pre1"]}
-        else:
-            gw2, gb2 = torch.empty((H, H), dtype=torch.float32, device=dev), torch.empty((H,), dtype=torch.float32, device=dev)
-            gw3, gb3 = torch.empty((H, O), dtype=torch.float32, device=dev), torch.empty((O,), dtype=torch.float32, device=dev)
-            stage_out = None
-        gh1 = torch.empty((B, H), dtype=torch.float32, device=dev)
+        new = lambda *shp: torch.empty(shp, dtype=torch.float32, device=dev)
+        gw2, gb2, gw3, gb3 = head_out if head_out is not None else (new(H, H), new(H), new(H, O), new(O))
+        gh1 = new(B, H)
         nbytes = int(lib.irbfn_mlp_head_vjp_workspace_bytes(H, H, O))
         if nbytes < 0:
             _lib.check(nbytes, "irbfn_mlp_head_vjp_workspace_bytes")
@@ -752,6 +735,33 @@ class DeeperWCRBFNet:
         st = lib.irbfn_mlp_head_vjp(_ptr(h1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(gd), _ptr(gh1), _ptr(gw2), _ptr(gb2),
                                     _ptr(gw3), _ptr(gb3), B, H, H, O, _ptr(ws), nbytes, _stream_ptr(torch))
         _lib.check(st, "irbfn_mlp_head_vjp")
+        return stage_params, xd, gh1, (gw2, gb2, gw3, gb3)
+
+    def vjp_x(self, params: dict, x, gout, h1=None):
+        """Query VJP of the whole model: gout[B,O] -> gx[B,D].  The head backward gives the cotangent of linear_pre1's output
+        (``irbfn_mlp_head_vjp``; its parameter gradients are by-products here), the stage's ``vjp_x`` takes it to x.
+        h1: the stage output of ``apply_with_hidden``, as for ``vjp``."""
+        torch = _lib.require_gpu()
+        stage_params, xd, gh1, _ = self._head_backward(params, x, gout, h1, "vjp_x")
+        return like_input(self.stage.vjp_x(stage_params, xd, gh1), x, torch)
+
+    def vjp(self, params: dict, x, gout, out: Optional[dict] = None, h1=None, stage_vjp_kernel: Optional[int] = None) -> dict:
+        """Parameter VJP of the whole model: cotangent gout[B,O] -> gradient pytree with the structure of ``params``
+        (what ``jax.value_and_grad`` returns for a DeeperWCRBFNet, scripts/train_nmpc_frenet.py:388-389,416-417).
+
+        out: caller-provided contiguous float32 cuda leaves (e.g. views of a flat buffer), written and returned.
+        h1: the stage output of ``apply_with_hidden`` for these params and x: the RBF stage is not run again.
+        stage_vjp_kernel: ``_lib.VJP_*`` for the stage VJP of this call only; the stage's option is restored afterwards."""
+        torch = _lib.require_gpu()
+        lib = _lib.load()
+        head_out = stage_out = None
+        if out is not None:
+            o = _inner(out)
+            for (g, n), shp in self.group_leaf_shapes().items():
+                _check_out_leaf(o[g][n], shp, torch.float32, torch)
+            head_out = (o["linear_pre2"]["kernel"], o["linear_pre2"]["bias"], o["linear"]["kernel"], o["linear"]["bias"])
+            stage_out = {"rbf_list": o["rbf_list"], "linear": o["linear_pre1"]}
+        stage_params, xd, gh1, (gw2, gb2, gw3, gb3) = self._head_backward(params, x, gout, h1, "vjp", head_out)
         if stage_vjp_kernel is None:
             gs = self.stage.vjp(stage_params, xd, gh1, out=stage_out)["params"]
         else:                    # this call only: the descriptor's own choice is put back whatever happens
@@ -769,46 +779,6 @@ class DeeperWCRBFNet:
                            "linear_pre1": {k: conv(v) for k, v in gs["linear"].items()},
                            "linear_pre2": {"kernel": conv(gw2), "bias": conv(gb2)},
                            "linear": {"kernel": conv(gw3), "bias": conv(gb3)}}}
-
-    def vjp_x(self, params: dict, x, gout, h1=None):
-        """Query VJP of the whole model: gout[B,O] -> gx[B,D].  The head backward gives the cotangent of linear_pre1's output
-        (``irbfn_mlp_head_vjp``; its parameter gradients are by-products here), the stage's ``vjp_x`` takes it to x.
-        h1: the stage output of ``apply_with_hidden``, as for ``vjp``."""
-        torch = _lib.require_gpu()
-        lib = _lib.load()
-        p = _inner(params)
-        H, O = self.HIDDEN, self.out_features
-        stage_params = {"rbf_list": p["rbf_list"], "linear": p["linear_pre1"]}
-        xd, gd = to_device_f32(x, torch), to_device_f32(gout, torch)
-        B = xd.shape[0]
-        if tuple(gd.shape) != (B, O):
-            raise ValueError(f"gout must have shape ({B}, {O})")
-        if h1 is None:
-            h1 = self.stage.apply(stage_params, xd)
-        elif not isinstance(h1, torch.Tensor) or tuple(h1.shape) != (B, H) or h1.dtype != torch.float32 or not h1.is_cuda \
-                or not h1.is_contiguous():
-            raise ValueError(f"vjp_x h1= must be the contiguous float32 cuda stage output [{B}, {H}] of apply_with_hidden")
-        w2, b2, w3 = (to_device_f32(a, torch) for a in (p["linear_pre2"]["kernel"], p["linear_pre2"]["bias"], p["linear"]["kernel"]))
-        dev = xd.device
-        new = lambda *shp: torch.empty(shp, dtype=torch.float32, device=dev)
-        gh1, gw2, gb2, gw3, gb3 = new(B, H), new(H, H), new(H), new(H, O), new(O)
-        nbytes = int(lib.irbfn_mlp_head_vjp_workspace_bytes(H, H, O))
-        if nbytes < 0:
-            _lib.check(nbytes, "irbfn_mlp_head_vjp_workspace_bytes")
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        st = lib.irbfn_mlp_head_vjp(_ptr(h1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(gd), _ptr(gh1), _ptr(gw2), _ptr(gb2),
-                                    _ptr(gw3), _ptr(gb3), B, H, H, O, _ptr(ws), nbytes, _stream_ptr(torch))
-        _lib.check(st, "irbfn_mlp_head_vjp")
-        return like_input(self.stage.vjp_x(stage_params, xd, gh1), x, torch)
-
-    def vjp(self, params: dict, x, gout, out: Optional[dict] = None, h1=None, stage_vjp_kernel: Optional[int] = None) -> dict:
-        """Parameter VJP of the whole model: cotangent gout[B,O] -> gradient pytree with the structure of ``params``
-        (what ``jax.value_and_grad`` returns for a DeeperWCRBFNet, scripts/train_nmpc_frenet.py:388-389,416-417).
-
-        out: caller-provided contiguous float32 cuda leaves (e.g. views of a flat buffer), written and returned.
-        h1: the stage output of ``apply_with_hidden`` for these params and x: the RBF stage is not run again.
-        stage_vjp_kernel: ``_lib.VJP_*`` for the stage VJP of this call only; the stage's option is restored afterwards."""
-        return self._vjp_impl(params, x, gout, out=out, h1=h1, stage_vjp_kernel=stage_vjp_kernel)
 
 
 class ClusterWCRBFNet:
@@ -835,6 +805,10 @@ class ClusterWCRBFNet:
 
     def _bind_and_gate(self, params: dict, xd, torch, lib):
         """Binds the stage to the RBF leaves and runs the softmax gate (model.py:402-404) -> (logits, gamma), [B, R] each."""
+        return self._gate(params, xd, torch, lib)[:2]
+
+    def _gate(self, params: dict, xd, torch, lib):
+        """``_bind_and_gate`` that also returns the gate's kernel on the device -> (logits, gamma, wc)."""
         p = _inner(params)
         D, R = self.in_features, self.num_regions
         if tuple(p["cluster"]["kernel"].shape) != (D, R) or tuple(p["cluster"]["bias"].shape) != (R,):
@@ -848,7 +822,7 @@ class ClusterWCRBFNet:
         gamma = torch.empty((B, R), dtype=torch.float32, device=xd.device)
         st = lib.irbfn_cluster_gate(_ptr(xd), _ptr(wc), _ptr(bc), _ptr(logits), _ptr(gamma), B, D, R, _stream_ptr(torch))
         _lib.check(st, "irbfn_cluster_gate")
-        return logits, gamma
+        return logits, gamma, wc
 
     def apply(self, params: dict, x):
         torch = _lib.require_gpu()
@@ -867,25 +841,16 @@ class ClusterWCRBFNet:
         backward and the [B,R] x [R,D] product with the gate's kernel run in torch on the device."""
         torch = _lib.require_gpu()
         lib = _lib.load()
-        p = _inner(params)
         D, R, O = self.in_features, self.num_regions, self.out_features
-        self.stage.bind({"rbf_list": p["rbf_list"], "linear": p["linear"]})
         xd, gd = to_device_f32(x, torch), to_device_f32(gout, torch)
         B = xd.shape[0]
         if tuple(xd.shape) != (B, D) or tuple(gd.shape) != (B, O):
             raise ValueError(f"x must be [B, {D}] and gout [B, {O}]")
-        wc, bc = to_device_f32(p["cluster"]["kernel"], torch), to_device_f32(p["cluster"]["bias"], torch)
-        if tuple(wc.shape) != (D, R) or tuple(bc.shape) != (R,):
-            raise ValueError(f"params cluster.kernel / bias must be [{D},{R}] / [{R}]")
-        dev = xd.device
-        logits = torch.empty((B, R), dtype=torch.float32, device=dev)
-        gamma = torch.empty((B, R), dtype=torch.float32, device=dev)
-        dgamma = torch.empty((B, R), dtype=torch.float32, device=dev)
-        gx = torch.empty((B, D), dtype=torch.float32, device=dev)
+        logits, gamma, wc = self._gate(params, xd, torch, lib)
+        dgamma = torch.empty((B, R), dtype=torch.float32, device=xd.device)
+        gx = torch.empty((B, D), dtype=torch.float32, device=xd.device)
         if B:
             stream = _stream_ptr(torch)
-            _lib.check(lib.irbfn_cluster_gate(_ptr(xd), _ptr(wc), _ptr(bc), _ptr(logits), _ptr(gamma), B, D, R, stream),
-                       "irbfn_cluster_gate")
             st = lib.irbfn_net_vjp_x_gamma(self.stage._handle(torch), _ptr(xd), _ptr(gamma), _ptr(gd), _ptr(gx), _ptr(dgamma), B,
                                            stream)
             _lib.check(st, "irbfn_net_vjp_x_gamma")
@@ -906,11 +871,9 @@ class ClusterWCRBFNet:
         ``irbfn_net_vjp_gamma`` and goes back through softmax + Dense in ``irbfn_cluster_gate_vjp``."""
         torch = _lib.require_gpu()
         lib = _lib.load()
-        p = _inner(params)
         D, R, O, K = self.in_features, self.num_regions, self.out_features, self.stage.num_kernels
         if O > 16:
             raise ValueError("ClusterWCRBFNet.vjp supports out_features <= 16 (the reference trains it with 10)")
-        self.stage.bind({"rbf_list": p["rbf_list"], "linear": p["linear"]})
         xd, gd = to_device_f32(x, torch), to_device_f32(gout, torch)
         B = xd.shape[0]
         if tuple(xd.shape) != (B, D) or tuple(gd.shape) != (B, O):
@@ -927,31 +890,20 @@ class ClusterWCRBFNet:
             leaves = {"centers": o["rbf_list"]["centers"], "log_sigs": o["rbf_list"]["log_sigs"], "kernel": o["linear"]["kernel"],
                       "bias": o["linear"]["bias"], "ckernel": o["cluster"]["kernel"], "cbias": o["cluster"]["bias"]}
             for n, t in leaves.items():
-                if tuple(t.shape) != shapes[n] or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-                    raise ValueError("vjp out= leaves must be contiguous float32 cuda tensors of the parameter shapes")
+                _check_out_leaf(t, shapes[n], torch.float32, torch)
         else:
             leaves = {n: torch.empty(shp, dtype=torch.float32, device=dev) for n, shp in shapes.items()}
-        wc, bc = to_device_f32(p["cluster"]["kernel"], torch), to_device_f32(p["cluster"]["bias"], torch)
-        logits = torch.empty((B, R), dtype=torch.float32, device=dev)
-        gamma = torch.empty((B, R), dtype=torch.float32, device=dev)
+        logits, gamma = self._bind_and_gate(params, xd, torch, lib)         # after every check of the arguments
         dgamma = torch.empty((B, R), dtype=torch.float32, device=dev)
         stream = _stream_ptr(torch)
-        _lib.check(lib.irbfn_cluster_gate(_ptr(xd), _ptr(wc), _ptr(bc), _ptr(logits), _ptr(gamma), B, D, R, stream),
-                   "irbfn_cluster_gate")
         h = self.stage._handle(torch)
         nbytes = int(lib.irbfn_net_vjp_workspace_bytes(h, B))
-        ws = self.stage._vjp_ws.get(dev.index)
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.empty((max(nbytes, 4),), dtype=torch.uint8, device=dev)
-            self.stage._vjp_ws[dev.index] = ws
+        ws = _grown_ws(self.stage._vjp_ws, dev.index, nbytes, torch, dev)
         st = lib.irbfn_net_vjp_gamma(h, _ptr(xd), _ptr(gamma), _ptr(gd), _ptr(leaves["centers"]), _ptr(leaves["log_sigs"]),
                                      _ptr(leaves["kernel"]), _ptr(leaves["bias"]), _ptr(dgamma), B, _ptr(ws), nbytes, stream)
         _lib.check(st, "irbfn_net_vjp_gamma")
         gbytes = int(lib.irbfn_cluster_gate_vjp_workspace_bytes(D, R))
-        gws = self._gate_ws.get(dev.index)
-        if gws is None or gws.numel() < gbytes:
-            gws = torch.empty((max(gbytes, 4),), dtype=torch.uint8, device=dev)
-            self._gate_ws[dev.index] = gws
+        gws = _grown_ws(self._gate_ws, dev.index, gbytes, torch, dev)
         st = lib.irbfn_cluster_gate_vjp(_ptr(xd), _ptr(gamma), _ptr(dgamma), _ptr(gl_in) if gl_in is not None else None,
                                         _ptr(logits), _ptr(leaves["ckernel"]), _ptr(leaves["cbias"]), B, D, R, _ptr(gws), gbytes,
                                         stream)
