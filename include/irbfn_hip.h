@@ -382,7 +382,14 @@ int irbfn_softmax_xent(const float* logits_dev, const float* labels_dev, float* 
  * deeper=True, src/irbfn_mpc/irbfn_planner.py:286-298):  out = linear(relu(linear_pre2(relu(h1)))) with
  * h1 = linear_pre1(rbf_out) [B,H1] produced by irbfn_net_forward on a descriptor whose Dense layer is
  * linear_pre1.  w2[H1,H2], b2[H2], w3[H2,O], b3[O] device pointers; H1 = H2 = 64 (hard-coded in the
- * reference).  The VJP of the head is irbfn_mlp_head_vjp below. */
+ * reference).  The VJP of the head is irbfn_mlp_head_vjp below.
+ * For the three head entry points (irbfn_mlp_head_forward, irbfn_mlp_head_tick, irbfn_mlp_head_vjp):
+ *   - h1_dev must be 16-byte aligned (its rows are read with 16-byte vector loads): IRBFN_ERR_BAD_ARG otherwise, for B > 0
+ *     (irbfn_mlp_head_tick checks the address behind its shape checks: an unsupported shape stays IRBFN_ERR_UNSUPPORTED).  The
+ *     other pointers need float alignment only (gradients may be views of a flat buffer at any float offset).
+ *   - relu is max(v, 0) that propagates NaN, as jnp.maximum does: a NaN in a row of h1 gives a NaN output row (NaN controls
+ *     from the tick) and NaN in the weight gradients it reaches; +Inf / -Inf follow IEEE arithmetic.
+ *   - relu'(0) = 0 (jax.nn.relu): the VJP masks with h1 > 0 and z2 > 0; a NaN pre-activation masks to 0. */
 int irbfn_mlp_head_forward(const float* h1_dev, const float* w2_dev, const float* b2_dev, const float* w3_dev,
                            const float* b3_dev, float* out_dev, int64_t B, int H1, int H2, int O, void* stream);
 

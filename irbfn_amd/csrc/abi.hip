@@ -388,6 +388,8 @@ int irbfn_mlp_head_tick(const float* h1_dev, const float* w2_dev, const float* b
   if (H1 != 64 || H2 != 64) return IRBFN_ERR_UNSUPPORTED;      // the reference hard-codes Dense(64), Dense(64)
   if (states_dev && mode == IRBFN_ROLLOUT_SPIRAL) return IRBFN_ERR_UNSUPPORTED;
   if (mlp_head_tick_needs_controls(O) && !controls_dev) return IRBFN_ERR_BAD_ARG;
+  // h1 rows are read with 16-byte loads; checked behind the shape checks: an unsupported shape keeps its status whatever the address
+  if (!aligned16(h1_dev)) return IRBFN_ERR_BAD_ARG;
   DynParams dp;
   memset(&dp, 0, sizeof(dp));
   int rc = states_dev ? load_dyn(mode, dyn_params_host, &dp) : IRBFN_OK;

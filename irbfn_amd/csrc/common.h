@@ -242,6 +242,8 @@ int launch_rollout_forward_split(int mode, const float* state0, const float* con
 int launch_rollout_vjp(int mode, const float* x0u, const DynParams& dp, const float* gstates,
                        float* g_x0u, int64_t B, int T, float clip_tie, hipStream_t s);
 int launch_unmirror(float* controls, const int* mirror, int64_t B, int O, int sv0, hipStream_t s);
+// the head kernels read h1 rows with 16-byte vector loads: the three head entry points refuse any other h1_dev
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // the tick of DeeperWCRBFNet's Dense head (mlp_head.hip): H1 = H2 = 64, O = 2T; states null = controls only
 int launch_mlp_head_tick(const float* h1, const float* w2, const float* b2, const float* w3, const float* b3, int mode,
                          const int* mirror, const float* state0, const DynParams& dp, float* controls, float* states, int64_t B,

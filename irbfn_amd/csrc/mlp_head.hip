@@ -9,6 +9,11 @@
 
 namespace irbfn {
 
+// nn.relu of the head, in every kernel below: max(v, 0) that propagates NaN, as jnp.maximum does (one v_maximum3_f32 on gfx950).
+// fmaxf(v, 0.0f) returns 0 for a NaN (v_max_f32 v, v, v; v_max_f32 v, 0, v): a NaN row of h1 gave finite controls and acted as
+// a zero row in training.  The derivative masks stay `> 0.0f`: relu'(0) = 0 (jax.nn.relu) and a NaN pre-activation masks to 0.
+__device__ __forceinline__ float relu(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
+
 template <int H1, int H2>
 __global__ __launch_bounds__(64) void mlp_head_kernel(const float* __restrict__ h1, const float* __restrict__ W2,
                                                       const float* __restrict__ b2, const float* __restrict__ W3,
@@ -25,7 +30,7 @@ __global__ __launch_bounds__(64) void mlp_head_kernel(const float* __restrict__ 
   const int rr = lane < nvalid ? lane : nvalid - 1;
   float z[H1];
 #pragma unroll
-  for (int i = 0; i < H1; ++i) z[i] = fmaxf(tile[rr * (H1 + 1) + i], 0.0f);      // nn.relu(out_pre1)
+  for (int i = 0; i < H1; ++i) z[i] = relu(tile[rr * (H1 + 1) + i]);      // nn.relu(out_pre1)
   float a2[H2];
 #pragma unroll
   for (int j = 0; j < H2; ++j) a2[j] = b2[j];
@@ -36,7 +41,7 @@ __global__ __launch_bounds__(64) void mlp_head_kernel(const float* __restrict__ 
     for (int j = 0; j < H2; ++j) a2[j] = __builtin_fmaf(z[i], wrow[j], a2[j]);
   }
 #pragma unroll
-  for (int j = 0; j < H2; ++j) a2[j] = fmaxf(a2[j], 0.0f);                         // nn.relu(out_pre2)
+  for (int j = 0; j < H2; ++j) a2[j] = relu(a2[j]);                         // nn.relu(out_pre2)
   __syncthreads();
   // final Dense (H2 -> O): stage through the tile for a coalesced store
   float* orow = tile + lane * (H1 + 1);
@@ -101,7 +106,7 @@ __global__ __launch_bounds__(64) void mlp_head_bwd_kernel(const float* __restric
     for (int j = 0; j < H2; ++j) a2[j] = b2[j];
 #pragma unroll
     for (int i = 0; i < H1; ++i) {
-      const float zi = fmaxf(z[i], 0.0f);
+      const float zi = relu(z[i]);
       const float* wrow = W2 + i * H2;
 #pragma unroll
       for (int j = 0; j < H2; ++j) a2[j] = __builtin_fmaf(zi, wrow[j], a2[j]);   // z2 = relu(h1) W2 + b2
@@ -121,13 +126,13 @@ __global__ __launch_bounds__(64) void mlp_head_bwd_kernel(const float* __restric
 #pragma unroll
       for (int j = 0; j < H2; ++j) acc = __builtin_fmaf(dz[j], wrow[j], acc);       // d a1 = d z2 W2^T
       const float gi = z[i] > 0.0f ? acc : 0.0f;
-      z1t[lane * P1 + i] = live ? fmaxf(z[i], 0.0f) : 0.0f;                        // park relu(h1)
+      z1t[lane * P1 + i] = live ? relu(z[i]) : 0.0f;                        // park relu(h1)
       z[i] = gi;
     }
 #pragma unroll
     for (int j = 0; j < H2; ++j) {
       dzt[lane * P2 + j] = live ? dz[j] : 0.0f;
-      a2t[lane * P2 + j] = live ? fmaxf(a2[j], 0.0f) : 0.0f;
+      a2t[lane * P2 + j] = live ? relu(a2[j]) : 0.0f;
     }
     if (!live)
       for (int o = 0; o < O; ++o) gt[lane * PO + o] = 0.0f;
@@ -271,7 +276,7 @@ __global__ __launch_bounds__(256) void mlp_head_bwd_mfma_kernel(const float* __r
     for (int ks = 0; ks < 16; ++ks) {
       float av[MB], bv[4];
 #pragma unroll
-      for (int mb = 0; mb < MB; ++mb) av[mb] = fmaxf(Hs[(mb * 16 + n) * P + ks * 4 + g], 0.0f);
+      for (int mb = 0; mb < MB; ++mb) av[mb] = relu(Hs[(mb * 16 + n) * P + ks * 4 + g]);
 #pragma unroll
       for (int nj = 0; nj < 4; ++nj) bv[nj] = W2s[(ks * 4 + g) * P + nj * 16 + n];
 #pragma unroll
@@ -304,7 +309,7 @@ __global__ __launch_bounds__(256) void mlp_head_bwd_mfma_kernel(const float* __r
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           dz[mb][nj][r] = z2[mb][nj][r] > 0.0f ? dz[mb][nj][r] : 0.0f;          // relu'
-          z2[mb][nj][r] = fmaxf(z2[mb][nj][r], 0.0f);                            // a2 = relu(z2)
+          z2[mb][nj][r] = relu(z2[mb][nj][r]);                            // a2 = relu(z2)
           db2p[nj] += dz[mb][nj][r];
           Dz[(mb * 16 + 4 * g + r) * P + nj * 16 + n] = dz[mb][nj][r];
         }
@@ -320,7 +325,7 @@ __global__ __launch_bounds__(256) void mlp_head_bwd_mfma_kernel(const float* __r
         for (int mj = 0; mj < 4; ++mj) dW3[mj] = __builtin_amdgcn_mfma_f32_16x16x4f32(z2[mb][mj][r], gq, dW3[mj], 0, 0, 0);
         float av[4];
 #pragma unroll
-        for (int mi = 0; mi < 4; ++mi) av[mi] = fmaxf(Hs[row * P + mi * 16 + n], 0.0f);
+        for (int mi = 0; mi < 4; ++mi) av[mi] = relu(Hs[row * P + mi * 16 + n]);
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
@@ -462,7 +467,7 @@ __global__ __launch_bounds__(256) void mlp_head_fwd_mfma_kernel(const float* __r
 #pragma unroll
     for (int k = 0; k < TR / 4; ++k) {
       float* d = Hs + (4 * k + (lane >> 4)) * P + 4 * (lane & 15);
-      d[0] = fmaxf(hv[k].x, 0.0f); d[1] = fmaxf(hv[k].y, 0.0f); d[2] = fmaxf(hv[k].z, 0.0f); d[3] = fmaxf(hv[k].w, 0.0f);   // nn.relu(out_pre1)
+      d[0] = relu(hv[k].x); d[1] = relu(hv[k].y); d[2] = relu(hv[k].z); d[3] = relu(hv[k].w);   // nn.relu(out_pre1)
     }
     fetch(tile + (long)gridDim.x * 4);           // the next tile's rows travel while this one is computed
     wave_sync();
@@ -489,7 +494,7 @@ __global__ __launch_bounds__(256) void mlp_head_fwd_mfma_kernel(const float* __r
 #pragma unroll
       for (int nj = 0; nj < 4; ++nj)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) Hs[(mb * 16 + 4 * g + r) * P + nj * 16 + n] = fmaxf(z2[mb][nj][r], 0.0f);   // nn.relu(out_pre2)
+        for (int r = 0; r < 4; ++r) Hs[(mb * 16 + 4 * g + r) * P + nj * 16 + n] = relu(z2[mb][nj][r]);   // nn.relu(out_pre2)
     wave_sync();
     hf4 oacc[MB];
 #pragma unroll
@@ -597,7 +602,7 @@ __global__ __launch_bounds__(256) void mlp_head_tick_kernel(const float* __restr
 #pragma unroll
     for (int k = 0; k < TR / 4; ++k) {
       float* d = Hs + (4 * k + (lane >> 4)) * P + 4 * (lane & 15);
-      d[0] = fmaxf(hv[k].x, 0.0f); d[1] = fmaxf(hv[k].y, 0.0f); d[2] = fmaxf(hv[k].z, 0.0f); d[3] = fmaxf(hv[k].w, 0.0f);   // nn.relu(out_pre1)
+      d[0] = relu(hv[k].x); d[1] = relu(hv[k].y); d[2] = relu(hv[k].z); d[3] = relu(hv[k].w);   // nn.relu(out_pre1)
     }
     fetch(tile + (long)gridDim.x * 4);           // the next tile's rows travel while this one is computed
     wave_sync();
@@ -624,7 +629,7 @@ __global__ __launch_bounds__(256) void mlp_head_tick_kernel(const float* __restr
 #pragma unroll
       for (int nj = 0; nj < 4; ++nj)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) Hs[(mb * 16 + 4 * g + r) * P + nj * 16 + n] = fmaxf(z2[mb][nj][r], 0.0f);   // nn.relu(out_pre2)
+        for (int r = 0; r < 4; ++r) Hs[(mb * 16 + 4 * g + r) * P + nj * 16 + n] = relu(z2[mb][nj][r]);   // nn.relu(out_pre2)
     // the mirror flags of the lane's eight rows (D layout: row = 16 mb + 4 g + r) travel under the output MFMAs
     int mf[MB][4];
 #pragma unroll
@@ -752,7 +757,7 @@ extern "C" int irbfn_mlp_head_forward(const float* h1_dev, const float* w2_dev, 
                                       int H2, int O, void* stream) {
   if (B < 0 || O < 1) return IRBFN_ERR_BAD_ARG;
   if (B == 0) return IRBFN_OK;
-  if (!h1_dev || !w2_dev || !b2_dev || !w3_dev || !b3_dev || !out_dev) return IRBFN_ERR_BAD_ARG;
+  if (!h1_dev || !w2_dev || !b2_dev || !w3_dev || !b3_dev || !out_dev || !aligned16(h1_dev)) return IRBFN_ERR_BAD_ARG;
   if (H1 != 64 || H2 != 64) return IRBFN_ERR_UNSUPPORTED;      // the reference hard-codes Dense(64), Dense(64)
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (O <= 16) {                                               // matrix-core head (every model card of the reference: O = 2 or 10)
@@ -800,7 +805,7 @@ extern "C" int irbfn_mlp_head_vjp(const float* h1_dev, const float* w2_dev, cons
   if (B < 0 || O < 1) return IRBFN_ERR_BAD_ARG;
   if (H1 != 64 || H2 != 64 || O > 16) return IRBFN_ERR_UNSUPPORTED;
   if (!w2_dev || !b2_dev || !w3_dev || !gw2_dev || !gb2_dev || !gw3_dev || !gb3_dev || !ws_dev) return IRBFN_ERR_BAD_ARG;
-  if (B > 0 && (!h1_dev || !gout_dev || !gh1_dev)) return IRBFN_ERR_BAD_ARG;
+  if (B > 0 && (!h1_dev || !gout_dev || !gh1_dev || !aligned16(h1_dev))) return IRBFN_ERR_BAD_ARG;
   const int n = H1 * H2 + H2 + H2 * O + O;
   if (ws_bytes < (int64_t)kHeadBwdBlocks * n * (int64_t)sizeof(float)) return IRBFN_ERR_BAD_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);

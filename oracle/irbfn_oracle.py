@@ -268,7 +268,8 @@ def deeper_wcrbfnet_apply(cfg: dict, params: dict, x):
     stage = {"rbf_list": p["rbf_list"], "linear": p["linear_pre1"]}
     stage_cfg = dict(cfg, out_features=p["linear_pre1"]["kernel"].shape[1])
     out_pre1 = wcrbfnet_apply(stage_cfg, stage, x)                               # :283
-    relu = (lambda t: np.maximum(t, 0)) if xp is _NP else (lambda t: t.clamp(min=0))
+    # torch.relu, not clamp(min=0): the gradient of clamp at exactly 0 is 1, jax.nn.relu's (and the kernels') is 0
+    relu = (lambda t: np.maximum(t, 0)) if xp is _NP else (lambda t: t.relu())
     out_pre2 = relu(out_pre1) @ p["linear_pre2"]["kernel"] + p["linear_pre2"]["bias"]   # :284
     return relu(out_pre2) @ p["linear"]["kernel"] + p["linear"]["bias"]                 # :285
 

@@ -254,8 +254,8 @@ def test_deeper_train_step_fullint_and_oneint(gpu, kind, monkeypatch):
     def deeper(c, p, xx, **kw):          # the oracle's losses with the Deeper net in place of the WCRBFNet
         q = p["params"]
         h = stage_apply(dict(c, out_features=64), {"rbf_list": q["rbf_list"], "linear": q["linear_pre1"]}, xx)
-        h2 = h.clamp(min=0) @ q["linear_pre2"]["kernel"] + q["linear_pre2"]["bias"]
-        return h2.clamp(min=0) @ q["linear"]["kernel"] + q["linear"]["bias"]
+        h2 = torch.relu(h) @ q["linear_pre2"]["kernel"] + q["linear_pre2"]["bias"]
+        return torch.relu(h2) @ q["linear"]["kernel"] + q["linear"]["bias"]
     xt, yt = torch.tensor(x, dtype=torch.float64), torch.tensor(y, dtype=torch.float64)
     monkeypatch.setattr(orc, "wcrbfnet_apply", deeper)
     if kind == "fullint":

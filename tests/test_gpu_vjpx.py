@@ -241,7 +241,7 @@ def test_deeper_vjp_x(gpu):
     stage = {"params": {"rbf_list": p["rbf_list"], "linear": p["linear_pre1"]}}
     h1 = torch.tensor(orc.wcrbfnet_apply(stage_cfg, {"params": {"rbf_list": tp["rbf_list"], "linear": tp["linear_pre1"]}},
                                          torch.tensor(np.asarray(x, np.float64))).numpy(), requires_grad=True)
-    out = (h1.clamp(min=0) @ tp["linear_pre2"]["kernel"] + tp["linear_pre2"]["bias"]).clamp(min=0) @ tp["linear"]["kernel"]
+    out = torch.relu(torch.relu(h1) @ tp["linear_pre2"]["kernel"] + tp["linear_pre2"]["bias"]) @ tp["linear"]["kernel"]
     (gh1,) = torch.autograd.grad((out * torch.tensor(np.asarray(g, np.float64))).sum(), h1)
     _, S = vx.hand_gx(stage_cfg, stage, x, gh1.numpy(), np.float64)
     ok, worst = vx.within(gx, ref, S)

@@ -60,6 +60,32 @@ def test_head_tick_status_table_without_gpu():
     assert call(H1=32, O=9) == BAD_ARG and call(H1=32, h1=None) == BAD_ARG
 
 
+def test_head_entry_points_refuse_a_misaligned_h1_without_gpu():
+    """h1_dev is read with 16-byte vector loads: the three head entry points return BAD_ARG for an address that is not a
+    multiple of 16, before any HIP call (every other argument below is acceptable, so alignment alone decides; the aligned
+    counterpart runs in tests/test_gpu_mlp_head.py::test_refusals).  No call reaches a launch: the fake pointers are never
+    dereferenced.  The tick checks the address behind its shape checks: an unsupported shape keeps its status."""
+    lib = _lib.load()
+    ok = C.c_void_p(64)
+    dyn = (C.c_float * 16)()
+    FR = _lib.ROLLOUT_FRENET_LS
+    nb = lib.irbfn_mlp_head_vjp_workspace_bytes(64, 64, 10)
+    assert nb > 0
+    for addr in (4, 8, 12, 20, 60, 68):
+        bad = C.c_void_p(addr)
+        tick = lambda h1, H1=64: _head_tick(lib, h1, ok, ok, ok, ok, FR, ok, ok, dyn, ok, ok, 4, H1, 64, 10, 5)
+        assert tick(bad) == BAD_ARG, addr
+        assert tick(bad, H1=32) == UNSUPPORTED and tick(ok, H1=32) == UNSUPPORTED
+        fwd = lambda h1, H1=64, O=10: lib.irbfn_mlp_head_forward(h1, ok, ok, ok, ok, ok, 4, H1, 64, O, None)
+        assert fwd(bad) == BAD_ARG and fwd(bad, O=20) == BAD_ARG, addr               # both forward kernels
+        assert fwd(bad, H1=32) == BAD_ARG and fwd(ok, H1=32) == UNSUPPORTED          # here the bad argument wins
+        for B in (1, 4, 80000):
+            assert lib.irbfn_mlp_head_vjp(bad, ok, ok, ok, ok, ok, ok, ok, ok, ok, B, 64, 64, 10, ok, nb, None) == BAD_ARG, (addr, B)
+    # an empty batch reads no h1: a no-op whatever the pointer (the VJP's, which still zeroes its leaves: on the GPU)
+    assert lib.irbfn_mlp_head_forward(C.c_void_p(4), ok, ok, ok, ok, ok, 0, 64, 64, 10, None) == OK
+    assert _head_tick(lib, C.c_void_p(4), ok, ok, ok, ok, FR, ok, ok, dyn, ok, ok, 0, 64, 64, 10, 5) == OK
+
+
 def test_plan_tick_gamma_status_table_without_gpu():
     lib = _lib.load()
     one = C.c_void_p(8)
