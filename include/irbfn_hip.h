@@ -123,7 +123,10 @@ typedef enum irbfn_option {
                                   The kernels test the device-side verdict themselves and fall back to the VALU distances / to K2h, so a stale
                                   host verdict costs speed, never correctness */
   IRBFN_OPT_VJPX_KERNEL = 16,  /* irbfn_vjpx_kernel below; default IRBFN_VJPX_AUTO (15 is a retired number) */
-  IRBFN_OPT_COUNT = 17
+  IRBFN_OPT_FWD_GAMMA_KERNEL = 17, /* irbfn_fwd_gamma_kernel below: the kernel of irbfn_net_forward_gamma / irbfn_plan_tick_gamma; default
+                                      IRBFN_FWDG_AUTO.  Selecting IRBFN_FWDG_K1G allocates the kernel's images on a net of several regions;
+                                      the next irbfn_net_set_params fills them (until then the two calls answer IRBFN_ERR_NO_PARAMS) */
+  IRBFN_OPT_COUNT = 18
 } irbfn_option;
 typedef enum irbfn_fwd_kernel {
   IRBFN_FWD_AUTO = 0, /* B <= 64: K1s; sparse multi-region gate: K1r; one region + fast basis: K1g (d <= 8, parameters inside its budget; O <= 16:
@@ -136,6 +139,17 @@ typedef enum irbfn_fwd_kernel {
                          on the f16 matrix cores in front of K1h's Phi x W; IRBFN_ERR_UNSUPPORTED when the bound parameters
                          do not fit the expansion (widths of 1e-3 of the centres' spread, non-finite values) */
 } irbfn_fwd_kernel;
+typedef enum irbfn_fwd_gamma_kernel {
+  IRBFN_FWDG_AUTO = 0, /* the gated K1 (rbf_fwd_qlane, GATED = 1); never selects K1g */
+  IRBFN_FWDG_K1 = 1,   /* the same, forced */
+  IRBFN_FWDG_K1G = 2   /* rbf_fwd_f16gram_gamma / rbf_tick_f16gram_gamma: K1g's chunk loop over the R regions, each padded to whole chunks of 32
+                          centres, gamma[b][region] multiplied onto the basis values in front of their f16 hi/lo split.  Gaussian family /
+                          inverse quadratic / inverse multiquadric, d <= 8, O <= 16, any R, K, B; one-launch tick for d = 7 / 8 as
+                          IRBFN_OPT_TICK_FUSED describes.  Every finite gamma with |gamma| <= 1 (what irbfn_cluster_gate and irbfn_net_gate
+                          produce; larger values leave the f16 range of the split); a product |gamma| phi below 2^-28 is flushed towards 0,
+                          which is 2^-38 of a full term.  A NaN in a gamma row gives NaN in that output row only.  IRBFN_ERR_UNSUPPORTED at the
+                          call for a net outside these shapes or parameters outside K1g's expansion; nothing else is launched in its place */
+} irbfn_fwd_gamma_kernel;
 typedef enum irbfn_vjp_kernel { IRBFN_VJP_AUTO = 0, IRBFN_VJP_K2 = 1, IRBFN_VJP_K2H = 2, IRBFN_VJP_K2R = 3, IRBFN_VJP_K2G = 4,
                                 IRBFN_VJP_K2M = 5 } irbfn_vjp_kernel;
 /* K2: all-float32 VALU; K2H: hbar and dW on the f16 matrix cores; K2R: region-sparse pair lists; K2G: the squared distances (K1g's

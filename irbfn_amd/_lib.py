@@ -20,8 +20,9 @@ ROLLOUT_ST_SELECT, ROLLOUT_ST_KS, ROLLOUT_FULLINT, ROLLOUT_FRENET_LS, ROLLOUT_SP
 
 # irbfn_option / irbfn_fwd_kernel / irbfn_vjp_kernel (include/irbfn_hip.h; the missing option numbers are retired)
 OPTIONS = {"fwd_kernel": 0, "fwd_f16_terms": 2, "fwd_f16_s": 7, "fwd_f16_qg": 8, "vjp_kernel": 9, "tick_fused": 13, "gram_sticky": 14,
-           "vjpx_kernel": 16}
+           "vjpx_kernel": 16, "fwd_gamma_kernel": 17}
 FWD_AUTO, FWD_K1, FWD_K1M, FWD_K1H, FWD_K1R, FWD_K1G = 0, 1, 2, 3, 4, 5
+FWDG_AUTO, FWDG_K1, FWDG_K1G = 0, 1, 2          # irbfn_fwd_gamma_kernel (OPTIONS["fwd_gamma_kernel"])
 VJP_AUTO, VJP_K2, VJP_K2H, VJP_K2R, VJP_K2G, VJP_K2M = 0, 1, 2, 3, 4, 5
 VJPX_AUTO, VJPX_K5, VJPX_K5M = 0, 1, 2
 

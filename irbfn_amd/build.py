@@ -41,6 +41,7 @@ UNITS = [
     ("rbf_f64.hip", "rbf_f64.o", []),
     ("rbf_forward_gram.hip", "rbf_forward_gram.o", []),
     ("rbf_forward_gram_wide.hip", "rbf_forward_gram_wide.o", []),
+    ("rbf_forward_gram_gamma.hip", "rbf_forward_gram_gamma.o", []),    # K1g over padded regions, caller-provided region weights
     ("rbf_vjp.hip", "rbf_vjp.o", [] + _SLP),
     ("rbf_vjp_f16.hip", "rbf_vjp_f16.o", ["-fno-slp-vectorize"]),
     ("rbf_vjp_gram.hip", "rbf_vjp_gram.o", ["-fno-slp-vectorize"]),

@@ -153,7 +153,8 @@ static bool option_known(int option) {
     case IRBFN_OPT_VJP_KERNEL:
     case IRBFN_OPT_TICK_FUSED:
     case IRBFN_OPT_GRAM_STICKY:
-    case IRBFN_OPT_VJPX_KERNEL: return true;
+    case IRBFN_OPT_VJPX_KERNEL:
+    case IRBFN_OPT_FWD_GAMMA_KERNEL: return true;
     default: return false;
   }
 }
@@ -168,6 +169,11 @@ int irbfn_net_set_option(irbfn_net* net, int option, int value) {
     case IRBFN_OPT_FWD_F16_S:
     case IRBFN_OPT_FWD_F16_QG: if (value > 16) return IRBFN_ERR_BAD_ARG; break;
     case IRBFN_OPT_GRAM_STICKY: if (value > 1) return IRBFN_ERR_BAD_ARG; break;
+    case IRBFN_OPT_FWD_GAMMA_KERNEL:
+      if (value > IRBFN_FWDG_K1G) return IRBFN_ERR_BAD_ARG;
+      if (value == IRBFN_FWDG_K1G)
+        if (const int rc = gram_gamma_select(net); rc != IRBFN_OK) return rc;
+      break;
     default: break;
   }
   net->opt[option] = value;

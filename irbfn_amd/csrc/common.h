@@ -90,6 +90,7 @@ struct irbfn_net {
   int gram_exp[5];          // K1g: exponents ex, ec, eq, ea, e2 (diagnostics)
   int gram_checked;         // K1g: gram_ok has been read back at least once (IRBFN_OPT_GRAM_STICKY)
   float* pack_part;         // K1g: partial statistics of the pack, one row per 1024 centres (pack_all.hip)
+  int gamma_packed;         // K1g with region weights (rbf_forward_gram_gamma.hip): the images hold the parameters last bound
   int* vjp_flags;           // K2g: ring of 64 hand-over words (rbf_vjp.hip); zero at creation, never reset
   int vjp_gen;              // K2g: generation number of the last VJP call
   float* small_part;            // K1s workspace part[NB][B][OP] (small-batch latency kernel)
@@ -134,7 +135,9 @@ enum LaunchKind : int {
   LK_TICK_K1H_WIDE,  // rbf_tick_f16mfma_wide
   LK_K2G,            // rbf_vjp_f16gram (the VJP plan, rbf_vjp.hip, launches it; named here with the others)
   LK_K2,             // rbf_vjp_kernel (`gated`: region weights per lane)
-  LK_K2M             // rbf_vjp_mfma (rbf_vjp_mfma.hip; Q: padded width OW, nw: centre tiles per wave, S: query slabs)
+  LK_K2M,            // rbf_vjp_mfma (rbf_vjp_mfma.hip; Q: padded width OW, nw: centre tiles per wave, S: query slabs)
+  LK_K1G_GAMMA,      // rbf_fwd_f16gram_gamma (caller-provided region weights)
+  LK_TICK_K1G_GAMMA  // rbf_tick_f16gram_gamma
 };
 
 struct F16Geom {           // K1h's block geometry where the dispatch reached K1h (forced AUTO / K1H, its image, B >= 65)
@@ -186,10 +189,18 @@ int launch_forward_f16(irbfn_net* net, const LaunchPlan& p, const float* x, floa
 bool gram_eligible(const irbfn_net* net);
 size_t gram_image_bytes(const irbfn_net* net);
 size_t gram_header_bytes();
-size_t gram_lds_bytes(int S, int QG, bool tick);
+size_t gram_lds_bytes(int S, int QG, bool tick, bool gamma = false);   // gamma: rbf_forward_gram_gamma.hip
 size_t gram_wide_ring_bytes(const irbfn_net* net, int SW);
 size_t gram_wide_lds_bytes(const irbfn_net* net, int SW, int QG, size_t extra_red_floats);
 int launch_forward_gram(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s);
+// K1g with caller-provided region weights (rbf_forward_gram_gamma.hip): regions padded to cpr chunks; select allocates the images
+int gram_gamma_cpr(const irbfn_net* net);
+bool gram_gamma_eligible(const irbfn_net* net);
+int gram_gamma_select(irbfn_net* net);
+int launch_forward_gram_gamma(irbfn_net* net, const LaunchPlan& p, const float* x, const float* gamma, float* out, int64_t B,
+                              hipStream_t s);
+int launch_tick_gram_gamma(irbfn_net* net, const LaunchPlan& p, const float* x, const float* gamma, const int* mirror,
+                           const float* state0, const DynParams& dp, float* controls, float* states, int64_t B, int T, hipStream_t s);
 // the one-launch planning ticks: is an instance compiled for this net, mode and horizon; their LDS; the launchers
 bool tick_narrow_compiled(const irbfn_net* net, int mode, int T);
 bool tick_wide_compiled(const irbfn_net* net, int mode, int T);

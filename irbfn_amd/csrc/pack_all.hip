@@ -45,6 +45,7 @@ struct PackArgs {
   float gscale;
   int CW, OW;                                                // K1m record: centre words, weight words
   int RF, NT, nchunks;                                       // K1h / K1g chunk images
+  int cpr, KR;                                               // ... chunk c = region c / cpr, centres 32 (c % cpr) + kk < KR of it
   int nbR, nbM, nbC, nbS, nbP, nbF, nbG;
   float* __restrict__ sp_ctab;                               // K1r / K2r: [n_ranges][RS] centre table, [K][WP] weight rows
   float* __restrict__ sp_wtab;
@@ -201,12 +202,14 @@ __device__ __forceinline__ void f16_image_body(const PackArgs& a, int vb) {
   const int idx = vb * kPackBlock + threadIdx.x;
   if (idx >= a.nchunks * kF16Chunk) return;
   const int c = idx / kF16Chunk, kk = idx % kF16Chunk;
-  const int n = idx;                                         // centre index (R == 1: n == k)
+  // one region: n = idx.  Several (K1g with region weights): every region padded to cpr whole chunks
+  const int reg = c / a.cpr, kr = (c - reg * a.cpr) * kF16Chunk + kk;
+  const int n = reg * a.KR + kr;
   const int RF = a.RF, NT = a.NT;
   const size_t cb = (size_t)kF16Chunk * RF * 4 + (size_t)NT * 2 * kF16WBytes + (NT == 1 ? kF16WBytes : 0);
   unsigned char* p = a.f16_img + (size_t)c * cb;
   float* rec = reinterpret_cast<float*>(p) + kk * RF;
-  const bool real = n < a.N;
+  const bool real = kr < a.KR;
   for (int j = 0; j < RF - 1; ++j) rec[j] = (real && j < a.D) ? a.centers[(size_t)n * a.D + j] : 0.0f;
   float sc = 0.0f;                                           // padding centre: P = 2^kPhiExp exactly, W = 0
   if (real) {
@@ -329,8 +332,9 @@ __device__ __forceinline__ void gram_image_body(const PackArgs& a, int c, unsign
   unsigned char* p = simg;
   for (int it = tid; it < kF16Chunk * 16; it += kPackBlock) {
     const int part = it >> 5, kk = it & 31;                  // a wave = two parts x 32 centres: (nearly) one path per wave
-    const int n = c * kF16Chunk + kk;
-    const bool real = n < a.N;
+    const int reg = c / a.cpr, kr = (c - reg * a.cpr) * kF16Chunk + kk;      // as f16_image_body
+    const int n = reg * a.KR + kr;
+    const bool real = kr < a.KR;
     const int ct = kk >> 4, row = kk & 15;                   // centre tile, A-operand row
     _Float16* head = reinterpret_cast<_Float16*>(p + ct * 512);                // lane (g, row): k = 4 g + j
     auto put_head = [&](int s, double v, int T) { head[((s >> 2) * 16 + row) * 4 + (s & 3)] = (_Float16)(float)(v * gram_pow2(T - gram_ax(T))); };
@@ -417,20 +421,32 @@ int launch_pack_all(irbfn_net* net, const float* centers, const float* log_sigs,
   PackArgs a{};
   a.centers = centers; a.log_sigs = log_sigs; a.kernel = kernel; a.bias = bias;
   a.rec = net->rec; a.bias_out = net->bias; a.sig2 = net->sig2; a.recm = net->recm; a.oscale = net->f16_oscale;
-  a.f16_img = net->f16_img; a.gram_img = net->gram_img; a.hdr = reinterpret_cast<GramHdr*>(net->gram_hdr);
+  // A net of several regions has the images only once it selected K1g for its region-weighted forward (gram_gamma_select),
+  // in the padded chunk order; while the option is off they are not packed (and say so)
+  const bool gam = net->R > 1 && net->f16_img != nullptr;
+  const bool gam_on = gam && net->opt[IRBFN_OPT_FWD_GAMMA_KERNEL] == IRBFN_FWDG_K1G;
+  unsigned char* const f16_img = (gam && !gam_on) ? nullptr : net->f16_img;
+  unsigned char* const gram_img = (gam && !gam_on) ? nullptr : net->gram_img;
+  if (gam) net->gamma_packed = gam_on ? 1 : 0;
+  a.f16_img = f16_img; a.gram_img = gram_img; a.hdr = reinterpret_cast<GramHdr*>(net->gram_hdr);
   a.part = net->pack_part;
   a.N = net->N; a.Npad = net->Npad; a.K = net->K; a.D = net->D; a.DC = net->DC; a.O = net->O; a.OP = net->OP; a.S = net->S;
   a.bclass = net->bclass; a.gscale = gauss_scale(net->basis);
   a.CW = mfma_cw(net->D); a.OW = 16 * ((net->O + 15) / 16);
   a.RF = f16_rf(net->DC); a.NT = (net->O + 15) / 16;
   a.nchunks = (net->N + kF16Chunk - 1) / kF16Chunk;
+  a.cpr = a.nchunks; a.KR = net->N;
+  if (gam_on) {
+    a.cpr = gram_gamma_cpr(net); a.KR = net->K;
+    a.nchunks = net->R * a.cpr;
+  }
   const int nrec = net->N > net->OP ? net->N : net->OP;
   a.nbR = (nrec + kPackBlock - 1) / kPackBlock;
   a.nbM = net->recm ? (net->Npad + kPackBlock - 1) / kPackBlock : 0;
-  a.nbC = net->f16_img ? 16 * a.NT : 0;
-  const bool gram = net->gram_img && net->f16_img && net->pack_part;
+  a.nbC = f16_img ? 16 * a.NT : 0;
+  const bool gram = gram_img && f16_img && net->pack_part;
   a.nbS = gram ? (net->N + kStatsCentres - 1) / kStatsCentres : 0;
-  a.nbF = net->f16_img ? (a.nchunks * kF16Chunk + kPackBlock - 1) / kPackBlock : 0;
+  a.nbF = f16_img ? (a.nchunks * kF16Chunk + kPackBlock - 1) / kPackBlock : 0;
   a.nbG = gram ? a.nchunks : 0;
   a.nbP = 0;
   if (net->sp_ok) {

@@ -285,9 +285,8 @@ static bool gram_wide_preferred(const irbfn_net* net, int64_t B) {
 // second, thin round of blocks costs a wave's whole latency-bound pass over its slice; blocks of FOUR waves with all the centres
 // (S = 1, QG = 4: four resident per CU, 4096 groups at once) spread the same work over the chip in one round
 // (profiles/r03_gram_geometry_sweep.txt: N = 1000, B = 80000: 40.7 vs 47.4 us; N = 2048: 67 vs 73; N = 4096: 121 vs 122).
-static void gram_geometry(const irbfn_net* net, int64_t B, int* S_out, int* QG_out) {
+static void gram_geometry(const irbfn_net* net, int64_t B, int nchunks, int* S_out, int* QG_out) {
   const long groups = (B + 31) / 32;
-  const int nchunks = (net->N + 31) / 32;
   int S = groups <= 512 ? 4 : (groups <= 2048 ? 2 : 1);
   while (S > 1 && nchunks / (2 * S) < 4) S /= 2;            // at least 8 chunks per wave
   S = opt_or(net, IRBFN_OPT_FWD_F16_S, S);
@@ -326,7 +325,7 @@ static bool plan_gram(const irbfn_net* net, int64_t B, LaunchPlan* p) {
     lds = gram_wide_lds_bytes(net, S, QG, 0);
     p->kind = LK_K1G_WIDE;
   } else {
-    gram_geometry(net, B, &S, &QG);
+    gram_geometry(net, B, (net->N + 31) / 32, &S, &QG);
     lds = gram_lds_bytes(S, QG, false);
     p->kind = LK_K1G;
   }
@@ -480,6 +479,8 @@ void record_launch(irbfn_net* net, const LaunchPlan& p) {
     case LK_TICK_K1H: snprintf(n, len, "rbf_tick_f16mfma<D=%d,BC=%d,MODE=%d,S=%d,QG=%d>", D, BC, p.mode, p.S, p.QG); break;
     case LK_TICK_K1G_WIDE: snprintf(n, len, "rbf_tick_f16gram_wide<D=7,BC=%d,NT=7,MODE=%d,SW=%d,QG=%d>", BC, p.mode, p.S, p.QG); break;
     case LK_TICK_K1H_WIDE: snprintf(n, len, "rbf_tick_f16mfma_wide<D=7,BC=%d,NT=7,MODE=%d,SW=%d,QG=%d>", BC, p.mode, p.S, p.QG); break;
+    case LK_K1G_GAMMA: snprintf(n, len, "rbf_fwd_f16gram_gamma<D=%d,BC=%d,S=%d,QG=%d>", D, BC, p.S, p.QG); break;
+    case LK_TICK_K1G_GAMMA: snprintf(n, len, "rbf_tick_f16gram_gamma<D=%d,BC=%d,MODE=%d,S=%d,QG=%d>", D, BC, p.mode, p.S, p.QG); break;
     case LK_K2G:                 // mode: K2g's live leaves (irbfn_net_vjp_frozen) -- 1 no centres, 2 the Dense leaves only
       snprintf(n, len, "rbf_vjp_f16gram%s<D=%d,BC=%d,QSB=%d>", p.mode == 1 ? "/no_centres" : (p.mode == 2 ? "/linear" : ""), D, BC, p.S);
       break;
@@ -547,9 +548,43 @@ int launch_forward(irbfn_net* net, const float* x, float* out, int64_t B, hipStr
   return launch_planned(net, plan_forward(net, B), x, out, B, s);
 }
 
-// forward with caller-provided region weights gamma[B][R] (ClusterWCRBFNet): always the gated K1
+// K1g with caller-provided region weights (rbf_forward_gram_gamma.hip), selected by IRBFN_OPT_FWD_GAMMA_KERNEL = IRBFN_FWDG_K1G only.
+// status: IRBFN_ERR_UNSUPPORTED for a net outside its instances or parameters outside the expansion's budget (the pack's verdict),
+// IRBFN_ERR_NO_PARAMS while the images have not been packed since the option was set.  K1g's geometry over the R x cpr chunks of
+// the padded regions; a forced S stands even where slices stay empty.
+static LaunchPlan plan_gram_gamma(const irbfn_net* net, int64_t B, bool tick, int mode) {
+  LaunchPlan p;
+  if (!gram_gamma_eligible(net)) return p;
+  const bool packed = net->gram_img && net->f16_img && (net->R == 1 || net->gamma_packed);
+  if (!packed) { p.status = IRBFN_ERR_NO_PARAMS; return p; }
+  if (!net->gram_ok) return p;
+  const int nchunks = net->R * gram_gamma_cpr(net);
+  int S, QG;
+  gram_geometry(net, B, nchunks, &S, &QG);
+  const int fs = net->opt[IRBFN_OPT_FWD_F16_S];
+  if (fs > 0 && fs <= 7 && S != fs) {
+    S = fs;
+    QG = opt_or(net, IRBFN_OPT_FWD_F16_QG, 8 / S > 0 ? 8 / S : 1);
+    if (S * QG > 16) QG = 1;
+  }
+  p.lds = gram_lds_bytes(S, QG, tick, true);
+  if (p.lds > 160 * 1024) return p;
+  p.kind = tick ? LK_TICK_K1G_GAMMA : LK_K1G_GAMMA; p.status = IRBFN_OK; p.mode = mode;
+  p.S = S; p.QG = QG;
+  p.grid = (int)(((B + 31) / 32 + QG - 1) / QG); p.block = S * QG * 64;
+  return p;
+}
+
+// forward with caller-provided region weights gamma[B][R] (ClusterWCRBFNet): the gated K1 unless the descriptor selects K1g
 int launch_forward_gamma(irbfn_net* net, const float* x, const float* gamma, float* out, int64_t B, hipStream_t s) {
   if (B == 0) return IRBFN_OK;
+  if (net->opt[IRBFN_OPT_FWD_GAMMA_KERNEL] == IRBFN_FWDG_K1G) {
+    const LaunchPlan g = plan_gram_gamma(net, B, false, -1);
+    if (g.kind == LK_NONE) return g.status;
+    const int rc = launch_forward_gram_gamma(net, g, x, gamma, out, B, s);
+    if (rc == IRBFN_OK) record_launch(net, g);
+    return rc;
+  }
   const LaunchPlan p = plan_qlane(net, B, true, false);
   if (p.kind == LK_NONE) return p.status;
   FwdArgs a;
@@ -630,7 +665,18 @@ int launch_forward_rollout_gamma(irbfn_net* net, int mode, const float* x, const
   if (B == 0) return IRBFN_OK;
   if (states == nullptr) return forward_controls_only(net, x, gamma, mirror, controls, B, s);
   if (const int rc = check_tick(net, mode, T); rc != IRBFN_OK) return rc;
-  if (net->bclass != BC_GENERIC && T * rollout_state_dim(mode) <= 64) {
+  if (net->opt[IRBFN_OPT_FWD_GAMMA_KERNEL] == IRBFN_FWDG_K1G) {
+    // K1g: one launch where the ROLL instance exists and its tiles fit, else its forward through the controls buffer below
+    if (const LaunchPlan f = plan_gram_gamma(net, B, false, -1); f.kind == LK_NONE) return f.status;
+    if (net->opt[IRBFN_OPT_TICK_FUSED] != 0 && tick_narrow_compiled(net, mode, T)) {
+      const LaunchPlan g = plan_gram_gamma(net, B, true, mode);
+      if (g.kind != LK_NONE) {
+        const int rc = launch_tick_gram_gamma(net, g, x, gamma, mirror, state0, dp, controls, states, B, T, s);
+        if (rc == IRBFN_OK) record_launch(net, g);
+        return rc;
+      }
+    }
+  } else if (net->bclass != BC_GENERIC && T * rollout_state_dim(mode) <= 64) {
     const LaunchPlan p = plan_qlane(net, B, true, true);
     if (p.kind == LK_K1) {
       const int rc = launch_qlane_tick(net, p, mode, x, gamma, mirror, state0, dp, controls, states, B, T, s);

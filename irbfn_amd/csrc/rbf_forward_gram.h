@@ -272,8 +272,10 @@ __device__ __forceinline__ void gram_distances(const unsigned char* buf, int lan
 }
 
 // The same arguments on the VALU from K1h's centre records `recs` of the chunk (a wave with a query outside the box): t16[t * 8 + j] for
-// centre 16 (j >> 2) + 4 g + (j & 3) -- the k order of the Phi x W product here
-template <int DC, int BC>
+// centre 16 (j >> 2) + 4 g + (j & 3) -- the k order of the Phi x W product here.  FINITE_R2: an infinite squared distance (a query
+// with an Inf coordinate) enters as 3e38, so that a padding centre (scale 0) gives its finite P and not Inf x 0 -- the kernels
+// whose regions all end in padding centres (rbf_forward_gram_gamma.hip) answer such a row as K1 does, with phi = 0
+template <int DC, int BC, bool FINITE_R2 = false>
 __device__ __forceinline__ void gram_valu_args(const F16Args& a, const long (&qrow)[2], int g, const float* recs, float (&t16)[16]) {
   constexpr int RF = f16_rf(DC);
 #pragma unroll
@@ -290,6 +292,7 @@ __device__ __forceinline__ void gram_valu_args(const F16Args& a, const long (&qr
         const float df = xq[d] - rp[d];                      // flax_rbf.py:280
         r2 = __builtin_fmaf(df, df, r2);
       }
+      if constexpr (FINITE_R2) r2 = r2 == __builtin_inff() ? 3.0e38f : r2;
       float arg = f16_arg<BC>(r2, rp[RF - 1]);
       if constexpr (BC == BC_IMQ) arg *= kPhiScale;          // 2^7 phi here (gram_phi_scale), K1h's records are scaled for 2^14 phi
       t16[t * 8 + j] = arg;

@@ -30,174 +30,16 @@
 // which become k-slots 8 g + 4 ct + r of the Phi x W product (the W rows of the image are permuted to match).
 // Chunk image (32 centres, 7 KiB): head operands [ct][lane] 8 B, tail operands [ct][half][lane] 16 B, W hi, W lo (1 KiB each);
 // the QG waves of a centre slice share an LDS ring of five images filled by LDS-DMA, one barrier per two chunks.
+// The kernel body is gram_body (rbf_forward_gram_body.h); rbf_forward_gram_gamma.hip instantiates it for nets of several regions
+// evaluated with caller-provided region weights.
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "rbf_forward_gram.h"
+#include "rbf_forward_gram_body.h"
 
 namespace irbfn {
-
-// ---- kernel ----------------------------------------------------------------------------------------------
-template <int DC, int BC, bool ROLL>
-__device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl, int mode, unsigned char* lds) {
-  static_assert(DC <= kGramDims, "eight coordinate slots");
-  const F16Args& a = ga.f;
-  constexpr int CBL = f16_chunk_bytes(DC);                   // K1h's chunk image (the VALU path reads its records)
-  constexpr int CB = kGramChunkBytes;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int S = a.S, QG = a.QG;
-  const int slice = wave / QG, qg = wave % QG;               // the QG waves of a slice are adjacent and share its ring
-  const int g = lane >> 4, n = lane & 15;
-  const long q0 = ((long)blockIdx.x * QG + qg) * 32;
-  const GramHdr* hp = ga.hdr;
-  long qrow[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    long q = q0 + t * 16 + n;
-    q = q < a.B ? q : a.B - 1;
-    qrow[t] = q < 0 ? 0 : q;
-  }
-  // ---- query-side operands: B[k = slot][column = query]
-  h4_t bhd[2];
-  h8_t btl[2][2];
-  const bool bad = gram_query_operands<DC>(a, hp, qrow, g, bhd, btl);
-  const bool wave_bad = __builtin_amdgcn_ballot_w64(bad) != 0ull;     // wave-uniform: the VALU distances for these 32 queries
-
-  const int c0 = (int)((long)a.nchunks * slice / S), c1 = (int)((long)a.nchunks * (slice + 1) / S);
-  const int na = c1 - c0;
-  int nsteps = 0;                                            // every wave of the block walks the longest slice (barriers)
-  for (int s2 = 0; s2 < S; ++s2) {
-    const int m = (int)((long)a.nchunks * (s2 + 1) / S) - (int)((long)a.nchunks * s2 / S);
-    nsteps = m > nsteps ? m : nsteps;
-  }
-  // Ring of kGramRing chunk images per slice: during step i the waves read the distance operands of chunk i + 1 and the W
-  // operands of chunk i while later chunks land (end_of_step below).
-  unsigned char* ring = lds + (size_t)slice * kGramRing * CB;
-  constexpr int NVI = CB / 1024;                             // 7 wave-instructions per chunk image
-  auto stage = [&](int k, int buf) {                         // chunk c0 + k of the slice -> ring slot buf; the QG waves share the copy
-    if (k >= na) return;
-    const unsigned char* gp = ga.gimg + (size_t)(c0 + k) * CB + lane * 16;
-    unsigned char* dst = ring + buf * CB;
-    for (int v = qg; v < NVI; v += QG)
-      __builtin_amdgcn_global_load_lds((gptr_t)(gp + v * 1024), (lptr_t)(dst + v * 1024), 16, 0, 0);
-  };
-  auto step_barrier = [&]() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-  auto next3 = [&](int b3) { return b3 == kGramRing - 1 ? 0 : b3 + 1; };
-  // A step touches chunks i (W) and i + 1 (distance operands).  One barrier per kGramPer = (kGramRing - 1) / 2 steps: behind it chunks
-  // i + 1 .. i + kGramPer + 1 are resident and the next kGramPer are requested into the slots of the chunks everybody has left
-  // (kGramRing = 3: a barrier per chunk; 5: one per two chunks).
-  constexpr int kGramPer = (kGramRing - 1) / 2;
-  static_assert(kGramRing == 2 * kGramPer + 1 && kGramPer >= 1, "ring = 2 x (steps per barrier) + 1");
-  auto end_of_step = [&](int i, int b0) {
-    if ((i % kGramPer) != kGramPer - 1) return;
-    step_barrier();
-#pragma unroll
-    for (int j = 0; j < kGramPer; ++j) {
-      int slot = b0 - (kGramPer - 1) + j;                    // slot of chunk i - (kGramPer - 1) + j
-      slot = slot < 0 ? slot + kGramRing : slot;
-      stage(i + kGramPer + 2 + j, slot);
-    }
-  };
-
-  f4_t acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};                // A1: ph * wh
-  f4_t acl[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};                // A2: pls * wh + ph * wls
-  auto distances = [&](const unsigned char* buf, f4_t (&u)[2][2]) { gram_distances(buf, lane, bhd, btl, u); };
-  // transcendental, hi / lo split and Phi x W of the 16 pairs in t16 with the W operands of chunk `buf`
-  auto products = [&](float (&t16)[16], const unsigned char* buf, auto pre) {
-    const h8_t bh = *reinterpret_cast<const h8_t*>(buf + kGramOpBytes + lane * 16);
-    const h8_t bl = *reinterpret_cast<const h8_t*>(buf + kGramOpBytes + kF16WBytes + lane * 16);
-    pre(t16);                                                // P = 2^kPhiExp * phi for the step's 16 pairs
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      unsigned wh[4], wl[4];
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) split_pair_mix(t16[t * 8 + 2 * jj], t16[t * 8 + 2 * jj + 1], wh[jj], wl[jj]);
-      const h8_t ah = __builtin_bit_cast(h8_t, u4_t{wh[0], wh[1], wh[2], wh[3]});
-      const h8_t al = __builtin_bit_cast(h8_t, u4_t{wl[0], wl[1], wl[2], wl[3]});
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[t], 0, 0, 0);
-      acl[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acl[t], 0, 0, 0);
-      acl[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acl[t], 0, 0, 0);
-    }
-  };
-
-#pragma unroll
-  for (int k = 0; k <= kGramPer; ++k) stage(k, k);
-  step_barrier();                                            // the first kGramPer + 1 chunks are there
-#pragma unroll
-  for (int k = kGramPer + 1; k < kGramRing; ++k) stage(k, k);
-  if (!wave_bad) {
-    // two steps per trip: the distances of chunk i + 1 are issued in front of the VALU work on chunk i
-    f4_t ua[2][2], ub[2][2];
-    if (na > 0) distances(ring, ua);
-    // trans16 is inline asm: the hazard recogniser does not see it read MFMA results.  In the loop the 12 distance MFMAs of the
-    // next chunk lie in front of it; a slice of ONE chunk reads them right away: explicit wait states, once
-    asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-    int b0 = 0;                                              // ring slot of chunk i
-    [[maybe_unused]] unsigned long long tph[5] = {0, 0, 0, 0, 0};
-    auto one_step = [&](int i, f4_t (&ucur)[2][2], f4_t (&unxt)[2][2]) {
-      const int b1 = next3(b0);
-      [[maybe_unused]] const unsigned long long t0 = IRBFN_GRAM_T();
-      if (i + 1 < na) distances(ring + b1 * CB, unxt);       // issued in front of the VALU work on chunk i
-      if (i < na) {
-        float t16[16];
-        products(t16, ring + b0 * CB, [&](float (&o)[16]) { trans16<BC>(ucur, o); });
-      }
-      [[maybe_unused]] const unsigned long long t2 = IRBFN_GRAM_T();
-      end_of_step(i, b0);
-      [[maybe_unused]] const unsigned long long t4 = IRBFN_GRAM_T();
-#ifdef IRBFN_GRAM_STAMPS
-      tph[1] += t2 - t0; tph[2] += t4 - t2; tph[4] += 1;
-#endif
-      b0 = b1;
-    };
-    for (int i = 0; i < nsteps; i += 2) {
-      one_step(i, ua, ub);
-      if (i + 1 < nsteps) one_step(i + 1, ub, ua);
-    }
-#ifdef IRBFN_GRAM_STAMPS
-    if (blockIdx.x < 2 && tid == 0)
-      for (int k = 0; k < 5; ++k) g_gram_stamps[blockIdx.x * 8 + k] = tph[k];
-#endif
-  } else {
-    // a query of this wave lies outside the representable box (or is not finite): K1h's distances for its 32 queries,
-    // same barriers and the same share of the copies
-    int b0 = 0;
-    for (int i = 0; i < nsteps; ++i) {
-      if (i < na) {
-        float t16[16];
-        gram_valu_args<DC, BC>(a, qrow, g, reinterpret_cast<const float*>(a.img + (size_t)(c0 + i) * CBL), t16);
-        products(t16, ring + b0 * CB, [&](float (&o)[16]) { trans_block<BC, 16>(o); });
-      }
-      end_of_step(i, b0);
-      b0 = next3(b0);
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[t][r] = __builtin_fmaf(acl[t][r], kLoScale, acc[t][r]);   // A1 + 2^-11 A2
-
-  // ---- smooth region gate of the single region (model.py:42-95), one value per query
-  const GateTables gt = a.gate;
-  float gam[2] = {0.0f, 0.0f};
-  if (slice == 0) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      float gv = gt.n_ranges > 0 ? 1.0f : 0.0f;              // model.py:70
-#pragma unroll
-      for (int d = 0; d < DC; ++d)
-        if (d < gt.nsplit && gt.n_ranges > 0) {
-          const int e = d * gt.max_ranges + gt.dim_ranges[d];
-          gv *= gate_factor(a.x[qrow[t] * a.Dreal + d], gt.lo[e], gt.hi[e], gt.delta[d]);
-        }
-      gam[t] = gv;
-    }
-  }
-  narrow_epilogue<ROLL>(a, rl, mode, lds, acc, gam, S, slice, qg, q0, 1.0f / (gram_phi_scale<BC>() * kWScale));
-}
 
 template <int DC, int BC>
 __global__ __launch_bounds__(1024, IRBFN_GRAM_WAVES) void rbf_fwd_f16gram(const GramArgs ga) {
@@ -257,8 +99,9 @@ static int launch_gram_bc(const GramArgs& a, int bc, int grid, int block, size_t
 }
 
 // S centre slices x QG query groups of 32 per block (tick: the one-launch tick's control and state tiles on top)
-size_t gram_lds_bytes(int S, int QG, bool tick) {
-  const size_t ring = (size_t)S * kGramRing * kGramChunkBytes;
+size_t gram_lds_bytes(int S, int QG, bool tick, bool gamma) {
+  size_t ring = (size_t)S * kGramRing * kGramChunkBytes;
+  if (gamma) ring += (size_t)S * QG * 128 * sizeof(float);   // a double-buffered tile of region weights per wave
   size_t red = (size_t)S * QG * 2 * 4 * 64 + (size_t)QG * 32;
   if (tick) red += (size_t)QG * 32 * (kTickNarrowCP + kTickNarrowSP);
   red *= sizeof(float);

@@ -1,0 +1,230 @@
+// K1g's narrow kernel body (rbf_forward_gram.hip: the description of the scheme), shared by the one-region instances
+// (rbf_fwd_f16gram / rbf_tick_f16gram, GAMMA = false) and the instances for nets evaluated with caller-provided region weights
+// gamma[B][R] (rbf_forward_gram_gamma.hip, GAMMA = true).
+#pragma once
+
+#include "rbf_forward_gram.h"
+
+namespace irbfn {
+
+// GAMMA: the region weights of the call.  The chunk range is R regions of cpr = ceil(K / 32) chunks each (a region's last chunk
+// padded with centres that contribute exactly 0: pack_all.hip), chunk c belongs to region c / cpr.
+struct GramGamma {
+  const float* __restrict__ gamma;        // [B][R]
+  int R, cpr;
+};
+
+// ---- kernel ----------------------------------------------------------------------------------------------
+template <int DC, int BC, bool ROLL, bool GAMMA = false>
+__device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl, int mode, unsigned char* lds,
+                                          [[maybe_unused]] const GramGamma gm = GramGamma{nullptr, 1, 1}) {
+  static_assert(DC <= kGramDims, "eight coordinate slots");
+  const F16Args& a = ga.f;
+  constexpr int CBL = f16_chunk_bytes(DC);                   // K1h's chunk image (the VALU path reads its records)
+  constexpr int CB = kGramChunkBytes;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int S = a.S, QG = a.QG;
+  const int slice = wave / QG, qg = wave % QG;               // the QG waves of a slice are adjacent and share its ring
+  const int g = lane >> 4, n = lane & 15;
+  const long q0 = ((long)blockIdx.x * QG + qg) * 32;
+  const GramHdr* hp = ga.hdr;
+  long qrow[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    long q = q0 + t * 16 + n;
+    q = q < a.B ? q : a.B - 1;
+    qrow[t] = q < 0 ? 0 : q;
+  }
+  // ---- query-side operands: B[k = slot][column = query]
+  h4_t bhd[2];
+  h8_t btl[2][2];
+  const bool bad = gram_query_operands<DC>(a, hp, qrow, g, bhd, btl);
+  const bool wave_bad = __builtin_amdgcn_ballot_w64(bad) != 0ull;     // wave-uniform: the VALU distances for these 32 queries
+
+  const int c0 = (int)((long)a.nchunks * slice / S), c1 = (int)((long)a.nchunks * (slice + 1) / S);
+  const int na = c1 - c0;
+  int nsteps = 0;                                            // every wave of the block walks the longest slice (barriers)
+  for (int s2 = 0; s2 < S; ++s2) {
+    const int m = (int)((long)a.nchunks * (s2 + 1) / S) - (int)((long)a.nchunks * s2 / S);
+    nsteps = m > nsteps ? m : nsteps;
+  }
+  // Ring of kGramRing chunk images per slice: during step i the waves read the distance operands of chunk i + 1 and the W
+  // operands of chunk i while later chunks land (end_of_step below).
+  unsigned char* ring = lds + (size_t)slice * kGramRing * CB;
+  constexpr int NVI = CB / 1024;                             // 7 wave-instructions per chunk image
+  auto stage = [&](int k, int buf) {                         // chunk c0 + k of the slice -> ring slot buf; the QG waves share the copy
+    if (k >= na) return;
+    const unsigned char* gp = ga.gimg + (size_t)(c0 + k) * CB + lane * 16;
+    unsigned char* dst = ring + buf * CB;
+    for (int v = qg; v < NVI; v += QG)
+      __builtin_amdgcn_global_load_lds((gptr_t)(gp + v * 1024), (lptr_t)(dst + v * 1024), 16, 0, 0);
+  };
+  auto step_barrier = [&]() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+  auto next3 = [&](int b3) { return b3 == kGramRing - 1 ? 0 : b3 + 1; };
+  // A step touches chunks i (W) and i + 1 (distance operands).  One barrier per kGramPer = (kGramRing - 1) / 2 steps: behind it chunks
+  // i + 1 .. i + kGramPer + 1 are resident and the next kGramPer are requested into the slots of the chunks everybody has left
+  // (kGramRing = 3: a barrier per chunk; 5: one per two chunks).
+  constexpr int kGramPer = (kGramRing - 1) / 2;
+  static_assert(kGramRing == 2 * kGramPer + 1 && kGramPer >= 1, "ring = 2 x (steps per barrier) + 1");
+  // GAMMA: the lane's two region weights (one per query tile: the lane owns query n of both) are multiplied onto the 16 basis
+  // values of a step in front of the hi / lo split, so a chunk's contribution to both accumulators carries gamma of its region.
+  // |gamma| <= 1 keeps the products inside the f16 range of the split.  gamma rows lie R floats apart, so the weights travel as the
+  // chunk images do: behind each step barrier every wave requests, by one LDS-DMA dword per lane, the weights of its 32 queries
+  // for the kGramPer steps of the period after the next (lane = 32 x step-in-period + query) into its own double-buffered tile
+  // behind the rings; the vmcnt(0) of the following barrier, which the ring's copies need anyway, covers them, and a step reads its
+  // two values from LDS: no step waits for a load it has just issued, and no register is the target of a load in flight.
+  [[maybe_unused]] float* gtile = nullptr;                   // [2 periods][kGramPer <= 2 steps][32 queries] of this wave
+  [[maybe_unused]] const float* grow = nullptr;              // gamma row of the wave's first query (wave-uniform)
+  [[maybe_unused]] int glim = 0;                             // rows of the batch behind it, at most 31
+  if constexpr (GAMMA) {
+    static_assert(kGramPer <= 2, "a period's weights are one dword per lane");
+    gtile = reinterpret_cast<float*>(lds + (size_t)S * kGramRing * CB) + wave * 128;
+    const long qb = q0 < a.B ? q0 : a.B - 1;                 // the rows past the batch read the last row (as qrow)
+    grow = gm.gamma + qb * (long)gm.R;
+    glim = a.B - 1 - qb < 31 ? (int)(a.B - 1 - qb) : 31;
+  }
+  auto gamma_stage = [&](int period) {                       // the weights of steps period * kGramPer + (0, 1)
+    if constexpr (GAMMA) {
+      // no request past the block's last step: the epilogue reuses this LDS, and no barrier would wait for the copy
+      if (period * kGramPer >= nsteps) return;
+      // the lane's number from the execution mask, its row offset recomputed per request: nothing of this lives in a vector
+      // register across the steps (the kernel has none to spare)
+      int l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+      asm volatile("" : "+v"(l));
+      const int st = period * kGramPer + ((l >> 5) < kGramPer ? (l >> 5) : kGramPer - 1);
+      int reg = (c0 + st) / gm.cpr;                          // chunk c belongs to region c / cpr; past the slice: any valid region
+      reg = reg < gm.R ? reg : gm.R - 1;
+      const int ql = (l & 31) < glim ? (l & 31) : glim;
+      __builtin_amdgcn_global_load_lds((gptr_t)(grow + (unsigned)(ql * gm.R + reg)), (lptr_t)(gtile + (period & 1) * 64), 4, 0, 0);
+    }
+  };
+  [[maybe_unused]] float gcur[2] = {1.0f, 1.0f};
+  auto gamma_read = [&](int i) {                             // step i's two weights
+    if constexpr (GAMMA) {
+      const float* gp = gtile + ((i / kGramPer) & 1) * 64 + (i % kGramPer) * 32 + n;
+      gcur[0] = gp[0];
+      gcur[1] = gp[16];
+    }
+  };
+
+  auto end_of_step = [&](int i, int b0) {
+    if ((i % kGramPer) != kGramPer - 1) return;
+    step_barrier();
+#pragma unroll
+    for (int j = 0; j < kGramPer; ++j) {
+      int slot = b0 - (kGramPer - 1) + j;                    // slot of chunk i - (kGramPer - 1) + j
+      slot = slot < 0 ? slot + kGramRing : slot;
+      stage(i + kGramPer + 2 + j, slot);
+    }
+    gamma_stage(i / kGramPer + 2);                           // into the tile of the period that has just ended
+  };
+
+  f4_t acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};                // A1: ph * wh
+  f4_t acl[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};                // A2: pls * wh + ph * wls
+  auto distances = [&](const unsigned char* buf, f4_t (&u)[2][2]) { gram_distances(buf, lane, bhd, btl, u); };
+  // transcendental, hi / lo split and Phi x W of the 16 pairs in t16 with the W operands of chunk `buf`
+  auto products = [&](float (&t16)[16], const unsigned char* buf, auto pre) {
+    const h8_t bh = *reinterpret_cast<const h8_t*>(buf + kGramOpBytes + lane * 16);
+    const h8_t bl = *reinterpret_cast<const h8_t*>(buf + kGramOpBytes + kF16WBytes + lane * 16);
+    pre(t16);                                                // P = 2^kPhiExp * phi for the step's 16 pairs
+    if constexpr (GAMMA) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) t16[j] *= gcur[j >> 3];
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      unsigned wh[4], wl[4];
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) split_pair_mix(t16[t * 8 + 2 * jj], t16[t * 8 + 2 * jj + 1], wh[jj], wl[jj]);
+      const h8_t ah = __builtin_bit_cast(h8_t, u4_t{wh[0], wh[1], wh[2], wh[3]});
+      const h8_t al = __builtin_bit_cast(h8_t, u4_t{wl[0], wl[1], wl[2], wl[3]});
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[t], 0, 0, 0);
+      acl[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acl[t], 0, 0, 0);
+      acl[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acl[t], 0, 0, 0);
+    }
+  };
+
+#pragma unroll
+  for (int k = 0; k <= kGramPer; ++k) stage(k, k);
+  gamma_stage(0);
+  step_barrier();                                            // the first kGramPer + 1 chunks are there
+#pragma unroll
+  for (int k = kGramPer + 1; k < kGramRing; ++k) stage(k, k);
+  gamma_stage(1);
+  if (!wave_bad) {
+    // two steps per trip: the distances of chunk i + 1 are issued in front of the VALU work on chunk i
+    f4_t ua[2][2], ub[2][2];
+    if (na > 0) distances(ring, ua);
+    // trans16 is inline asm: the hazard recogniser does not see it read MFMA results.  In the loop the 12 distance MFMAs of the
+    // next chunk lie in front of it; a slice of ONE chunk reads them right away: explicit wait states, once
+    asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
+    int b0 = 0;                                              // ring slot of chunk i
+    [[maybe_unused]] unsigned long long tph[5] = {0, 0, 0, 0, 0};
+    auto one_step = [&](int i, f4_t (&ucur)[2][2], f4_t (&unxt)[2][2]) {
+      const int b1 = next3(b0);
+      [[maybe_unused]] const unsigned long long t0 = IRBFN_GRAM_T();
+      if (i + 1 < na) distances(ring + b1 * CB, unxt);       // issued in front of the VALU work on chunk i
+      if (i < na) {
+        gamma_read(i);
+        float t16[16];
+        products(t16, ring + b0 * CB, [&](float (&o)[16]) { trans16<BC>(ucur, o); });
+      }
+      [[maybe_unused]] const unsigned long long t2 = IRBFN_GRAM_T();
+      end_of_step(i, b0);
+      [[maybe_unused]] const unsigned long long t4 = IRBFN_GRAM_T();
+#ifdef IRBFN_GRAM_STAMPS
+      tph[1] += t2 - t0; tph[2] += t4 - t2; tph[4] += 1;
+#endif
+      b0 = b1;
+    };
+    for (int i = 0; i < nsteps; i += 2) {
+      one_step(i, ua, ub);
+      if (i + 1 < nsteps) one_step(i + 1, ub, ua);
+    }
+#ifdef IRBFN_GRAM_STAMPS
+    if (blockIdx.x < 2 && tid == 0)
+      for (int k = 0; k < 5; ++k) g_gram_stamps[blockIdx.x * 8 + k] = tph[k];
+#endif
+  } else {
+    // a query of this wave lies outside the representable box (or is not finite): K1h's distances for its 32 queries,
+    // same barriers and the same share of the copies
+    int b0 = 0;
+    for (int i = 0; i < nsteps; ++i) {
+      if (i < na) {
+        gamma_read(i);
+        float t16[16];
+        gram_valu_args<DC, BC, GAMMA>(a, qrow, g, reinterpret_cast<const float*>(a.img + (size_t)(c0 + i) * CBL), t16);
+        products(t16, ring + b0 * CB, [&](float (&o)[16]) { trans_block<BC, 16>(o); });
+      }
+      end_of_step(i, b0);
+      b0 = next3(b0);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[t][r] = __builtin_fmaf(acl[t][r], kLoScale, acc[t][r]);   // A1 + 2^-11 A2
+
+  // ---- smooth region gate of the single region (model.py:42-95), one value per query
+  const GateTables gt = a.gate;
+  float gam[2] = {0.0f, 0.0f};
+  if constexpr (GAMMA) {
+    gam[0] = gam[1] = 1.0f;                                  // the region weights are inside the sums
+  } else if (slice == 0) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      float gv = gt.n_ranges > 0 ? 1.0f : 0.0f;              // model.py:70
+#pragma unroll
+      for (int d = 0; d < DC; ++d)
+        if (d < gt.nsplit && gt.n_ranges > 0) {
+          const int e = d * gt.max_ranges + gt.dim_ranges[d];
+          gv *= gate_factor(a.x[qrow[t] * a.Dreal + d], gt.lo[e], gt.hi[e], gt.delta[d]);
+        }
+      gam[t] = gv;
+    }
+  }
+  narrow_epilogue<ROLL>(a, rl, mode, lds, acc, gam, S, slice, qg, q0, 1.0f / (gram_phi_scale<BC>() * kWScale));
+}
+
+}  // namespace irbfn

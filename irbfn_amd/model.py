@@ -290,6 +290,9 @@ class WCRBFNet:
         h = self._handle(torch)
         for k, v in opts.items():
             _lib.check(lib.irbfn_net_set_option(h, _lib.OPTIONS[k], int(v)), f"irbfn_net_set_option({k}={v})")
+            if k == "fwd_gamma_kernel":
+                # the option decides which images irbfn_net_set_params packs: the next bind packs again
+                self._bound_fp.pop(torch.cuda.current_device(), None)
         return self
 
     def __del__(self):
@@ -802,6 +805,12 @@ class ClusterWCRBFNet:
         self.stage = WCRBFNet(in_features=in_features, out_features=out_features, num_kernels=num_kernels,
                               basis_func=basis_func, num_regions=num_regions, lower_bounds=[], upper_bounds=[],
                               dimension_ranges=[], activation_idx=[], delta=[])
+
+    def set_options(self, **opts) -> "ClusterWCRBFNet":
+        """``WCRBFNet.set_options`` of the RBF stage, e.g. ``fwd_gamma_kernel=_lib.FWDG_K1G``: ``apply`` and the planning
+        tick on the matrix-core kernel ``rbf_fwd_f16gram_gamma`` / ``rbf_tick_f16gram_gamma``."""
+        self.stage.set_options(**opts)
+        return self
 
     def _bind_and_gate(self, params: dict, xd, torch, lib):
         """Binds the stage to the RBF leaves and runs the softmax gate (model.py:402-404) -> (logits, gamma), [B, R] each."""
