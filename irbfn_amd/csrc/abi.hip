@@ -71,6 +71,13 @@ int irbfn_net_create(irbfn_net** out_net, int D, int R, int K, int O, int basis,
   net->opt[IRBFN_OPT_FWD_F16_TERMS] = 3;
   net->opt[IRBFN_OPT_TICK_FUSED] = 1;
 
+  net->gate0.nsplit = nsplit; net->gate0.n_ranges = n_ranges;
+  if (nsplit > 0 && n_ranges > 0)
+    for (int d = 0; d < nsplit; ++d) {
+      const int e = d * net->max_ranges + dim_ranges_host[d];
+      net->gate0.lo[d] = lo_tab_host[e]; net->gate0.hi[d] = hi_tab_host[e]; net->gate0.delta[d] = delta_host[d];
+    }
+
   const size_t tab = (size_t)(nsplit > 0 ? nsplit : 1) * net->max_ranges;
   const size_t nr = (size_t)(n_ranges > 0 ? n_ranges : 1) * (nsplit > 0 ? nsplit : 1);
   hipError_t e = hipSuccess;

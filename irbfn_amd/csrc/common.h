@@ -56,6 +56,13 @@ struct GateTables {        // device pointers owned by the descriptor
   int nsplit, max_ranges, n_ranges;
 };
 
+// Region 0's row of the gate tables by value (host mirror in the descriptor, filled by irbfn_net_create): what the kernels
+// of one-region nets need of GateTables, without the pointer chase dim_ranges -> lo / hi.  lo[d] = lo_tab[d][dim_ranges[0][d]].
+struct GateRow {
+  float lo[kMaxSplit], hi[kMaxSplit], delta[kMaxSplit];
+  int nsplit, n_ranges;
+};
+
 __host__ __device__ constexpr int mfma_cw(int D) { return (D + 1 + 3) & ~3; }   // K1m record: c[D], scale, pad
 
 struct DynParams {         // dynamics.py:24-36
@@ -101,6 +108,7 @@ struct irbfn_net {
   float* gate_delta;
   int* gate_ranges;
   int nsplit, max_ranges, n_ranges;
+  irbfn::GateRow gate0;     // region 0's gate row (K1g passes it with the kernel arguments)
   // region-sparse path (rbf_sparse.hip): tables of the card, built by irbfn_net_create where the net is eligible
   float* sp_img;            // the net as the region-sparse kernels hold it in LDS (rbf_sparse.hip, sp_img_layout): centre
                             // table [n_ranges][RS], region index words, region masks, factor entries, Dense weight rows

@@ -314,6 +314,12 @@ static void gram_wide_geometry(const irbfn_net* net, int64_t B, int* SW_out, int
   *SW_out = SW; *QG_out = QG;
 }
 
+// The narrow K1g kernels cut the chunk range into slices in 32-bit arithmetic (gram_body: c0, c1), so nchunks x S must stay below
+// 2^31.  No net that exists gets there.  One-region kernels: irbfn_net_create accepts at most 2^30 centres, i.e. 2^25 chunks, and
+// gram_geometry at most S = 7 slices: nchunks x S < 2^28.  Padded regions (caller-provided weights): nchunks = R x cpr can
+// approach 2^30 at K = 1, but 2^31 / 7 chunk images of 7 KiB are 2 TB of device memory.
+static bool gram_slices_fit(int nchunks, int S) { return (long)nchunks * S < (1L << 31); }
+
 // K1g, narrow or wide: its image, the parameters inside the expansion's budget (checked by the caller), LDS
 static bool plan_gram(const irbfn_net* net, int64_t B, LaunchPlan* p) {
   if (!net->f16_img || !gram_eligible(net)) return false;
@@ -326,6 +332,7 @@ static bool plan_gram(const irbfn_net* net, int64_t B, LaunchPlan* p) {
     p->kind = LK_K1G_WIDE;
   } else {
     gram_geometry(net, B, (net->N + 31) / 32, &S, &QG);
+    if (!gram_slices_fit((net->N + 31) / 32, S)) return false;
     lds = gram_lds_bytes(S, QG, false);
     p->kind = LK_K1G;
   }
@@ -568,7 +575,7 @@ static LaunchPlan plan_gram_gamma(const irbfn_net* net, int64_t B, bool tick, in
     if (S * QG > 16) QG = 1;
   }
   p.lds = gram_lds_bytes(S, QG, tick, true);
-  if (p.lds > 160 * 1024) return p;
+  if (p.lds > 160 * 1024 || !gram_slices_fit(nchunks, S)) return p;
   p.kind = tick ? LK_TICK_K1G_GAMMA : LK_K1G_GAMMA; p.status = IRBFN_OK; p.mode = mode;
   p.S = S; p.QG = QG;
   p.grid = (int)(((B + 31) / 32 + QG - 1) / QG); p.block = S * QG * 64;

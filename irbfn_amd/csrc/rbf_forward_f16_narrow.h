@@ -20,6 +20,11 @@ __device__ __forceinline__ void narrow_epilogue(const F16Args& a, const F16Roll&
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4, n = lane & 15;
   // ---- sum the S centre slices in fixed order, scale, bias, store
+  float sc = 0.0f, bi = 0.0f;                                // loaded in front of the barriers: the waves wait there anyway
+  if (slice == 0 && n < a.O) {
+    sc = a.oscale[n] * inv_scale;                            // s_o * 2^-29 (K1h)
+    bi = a.bias[n];
+  }
   __syncthreads();                                           // every wave is done with its ring
   float* red = reinterpret_cast<float*>(lds);                // [QG][S][2][4][64]
   float* gl = red + (size_t)a.QG * S * 2 * 4 * 64;           // [QG][32]
@@ -31,8 +36,6 @@ __device__ __forceinline__ void narrow_epilogue(const F16Args& a, const F16Roll&
   if (slice == 0 && g == 0) { gl[qg * 32 + n] = gam[0]; gl[qg * 32 + 16 + n] = gam[1]; }
   __syncthreads();
   if (slice == 0 && n < a.O) {
-    const float sc = a.oscale[n] * inv_scale;                                   // s_o * 2^-29 (K1h)
-    const float bi = a.bias[n];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -75,7 +78,13 @@ __device__ __forceinline__ void narrow_epilogue(const F16Args& a, const F16Roll&
       auto ctl = [&](int i) {                                                                // u[i], i wave-uniform: static register index
         float v = u[0];
 #pragma unroll
-        for (int k = 1; k < 2 * kTickNarrowT; ++k) v = (i == k) ? u[k] : v;
+        for (int k = 1; k < 2 * kTickNarrowT; ++k) {
+          // through an opaque copy: a select between two loads of u[] otherwise becomes ONE load through a selected address,
+          // which keeps u[] in the private segment (scratch for every wave of the launch) instead of in registers
+          float uk = u[k];
+          asm("" : "+v"(uk));
+          v = (i == k) ? uk : v;
+        }
         return v;
       };
       if (mode == IRBFN_ROLLOUT_ST_SELECT || mode == IRBFN_ROLLOUT_ST_KS) {

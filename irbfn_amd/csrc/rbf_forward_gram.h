@@ -66,13 +66,26 @@ template <int BC>
 __host__ __device__ constexpr float gram_phi_scale() { return BC == BC_IMQ ? 128.0f : kPhiScale; }
 
 // Diagnosis build only (tools/build_variant.py ... -DIRBFN_GRAM_STAMPS): wave 0 of blocks 0 and 1 add up s_memtime per
-// phase of the step; no output depends on it and the regular build contains none of it.
+// phase of the step (words 0..4 of the block's 32) and stamp the phases of the launch (words 8 + k: s_memtime at kernel
+// entry, query operands ready, first barrier passed, loop start, loop end, gate done, last store; words 16 / 17:
+// s_memrealtime at entry and behind the last store); no output depends on it and the regular build contains none of it.
 #ifdef IRBFN_GRAM_STAMPS
-__device__ unsigned long long g_gram_stamps[32];
+__device__ unsigned long long g_gram_stamps[64];
 #define IRBFN_GRAM_T() __builtin_amdgcn_s_memtime()
+// every load and LDS access issued so far has returned when the stamp is taken
+#define IRBFN_GRAM_PHASE(k)                                                                            \
+  do {                                                                                                 \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                        \
+    if (blockIdx.x < 2 && threadIdx.x == 0) {                                                          \
+      g_gram_stamps[blockIdx.x * 32 + 8 + (k)] = __builtin_amdgcn_s_memtime();                         \
+      if ((k) == 0 || (k) == 6) g_gram_stamps[blockIdx.x * 32 + 16 + (k) / 6] = __builtin_amdgcn_s_memrealtime(); \
+    }                                                                                                  \
+  } while (0)
 #else
 #define IRBFN_GRAM_T() 0ull
+#define IRBFN_GRAM_PHASE(k) do { } while (0)
 #endif
+enum GramPhase : int { GP_ENTRY = 0, GP_OPERANDS, GP_BARRIER1, GP_LOOP0, GP_LOOP1, GP_GATE, GP_STORED };
 
 // ---- kernel ----------------------------------------------------------------------------------------------
 typedef float f2_t __attribute__((ext_vector_type(2)));
@@ -118,6 +131,8 @@ struct GramArgs {
   F16Args f;                              // x, img = K1h's image (records of the VALU path), oscale, bias, out, gate, B, ...
   const unsigned char* __restrict__ gimg; // [nchunks][kGramChunkBytes]
   const GramHdr* __restrict__ hdr;
+  GateRow g0;                             // the narrow kernels' gate: region 0's row by value, with the kernel arguments
+  int nsteps;                             // chunks of the longest of the S slices: the steps every wave of a block walks
 };
 
 // |v| < 2^E given as vh + vl -> normalised parts (float), as gram_parts_d
@@ -136,9 +151,29 @@ __device__ __forceinline__ void gram_parts_f(float vh, float vl, float inv, floa
 // over the four lanes that hold a query's coordinates (a commutative butterfly: the four lanes end with the same bits).  Returns
 // whether THIS lane's coordinates fall outside the representable box (|x'_i| >= 2^ex, Q >= 2^eq, NaN, Inf) or the header says the
 // net does not fit -- the callers take the ballot of the wave.
+// The lane's four coordinates xv[t][c] (query tile t, coordinate 2 g + c; 0 past the net's dimension) come from gram_query_loads:
+// one address per value, known at kernel entry, so the four loads -- and whatever else the caller loads between the two
+// calls -- are in flight together and the operands wait once.
 template <int DC>
-__device__ __forceinline__ bool gram_query_operands(const F16Args& a, const GramHdr* hp, const long (&qrow)[2], int g, h4_t (&bhd)[2],
-                                                    h8_t (&btl)[2][2]) {
+__device__ __forceinline__ void gram_query_loads(const F16Args& a, const GramHdr* hp, const long (&qrow)[2], int g, float (&xv)[2][2],
+                                                 float (&rv)[2]) {
+  // the origin's two coordinates of the lane go out with the x loads (r holds eight entries: no branch around the load)
+#pragma unroll
+  for (int c = 0; c < 2; ++c) rv[c] = hp->r[2 * g + c];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int i = 2 * g + c;
+      const bool in = i < DC && i < a.Dreal;
+      const float v = a.x[qrow[t] * a.Dreal + (in ? i : 0)];  // always inside the row: no branch around the load
+      xv[t][c] = in ? v : 0.0f;
+    }
+}
+
+template <int DC>
+__device__ __forceinline__ bool gram_query_operands(const F16Args& a, const GramHdr* hp, const float (&xin)[2][2], const float (&rin)[2],
+                                                    int g, h4_t (&bhd)[2], h8_t (&btl)[2][2]) {
   // The error-free sums below are written operation by operation: contracted into FMAs (hipcc's default, -ffp-contract=fast:
   // th = qh + sh * sh as one fma, tb = th - qh as fma(-sh', sh', th) when qh is itself a product) they lose the low word of Q --
   // 6e-8 of |x'|^2, which the cancellation against 2 c'x' and |c'|^2 turns into 4e-5 of the result for a query 28 widths from
@@ -154,15 +189,16 @@ __device__ __forceinline__ bool gram_query_operands(const F16Args& a, const Gram
   auto scale_of = [&](const GramSlot sl) -> float { return sl.kind == 0 ? 0.0f : __builtin_ldexpf(1.0f, gram_ax(gram_T(hx, sl))); };
   float rr[2];
 #pragma unroll
-  for (int c = 0; c < 2; ++c) rr[c] = (2 * g + c < DC) ? -hp->r[2 * g + c] : 0.0f;
+  for (int c = 0; c < 2; ++c) {
+    rr[c] = (2 * g + c < DC) ? -rin[c] : 0.0f;
+  }
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     float nx[2][3], nq[3];
     float qh = 0.0f, ql = 0.0f;
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      const int i = 2 * g + c;
-      const float xv = (i < DC && i < a.Dreal) ? a.x[qrow[t] * a.Dreal + i] : 0.0f;
+      const float xv = xin[t][c];
       const float sh = xv + rr[c];                           // TwoSum: x' = sh + sl exactly
       const float bb = sh - xv;
       const float sl = (xv - (sh - bb)) + (rr[c] - bb);
@@ -214,6 +250,13 @@ __device__ __forceinline__ bool gram_query_operands(const F16Args& a, const Gram
     }
   }
   return bad;
+}
+template <int DC>
+__device__ __forceinline__ bool gram_query_operands(const F16Args& a, const GramHdr* hp, const long (&qrow)[2], int g, h4_t (&bhd)[2],
+                                                    h8_t (&btl)[2][2]) {
+  float xv[2][2], rv[2];
+  gram_query_loads<DC>(a, hp, qrow, g, xv, rv);
+  return gram_query_operands<DC>(a, hp, xv, rv, g, bhd, btl);
 }
 // the tables say what the code above assumes
 static_assert(gram_head_slot(0).kind == 1 && gram_head_slot(4 * 3 + 1).dim == 7 && gram_head_slot(2).kind == 2 && gram_head_slot(6).kind == 3 &&
@@ -301,6 +344,7 @@ __device__ __forceinline__ void gram_valu_args(const F16Args& a, const long (&qr
 }
 
 // host side (rbf_forward_gram.hip, rbf_forward_gram_wide.hip, plan_tick_wide.hip)
+int gram_nsteps(int nchunks, int S);
 void gram_fill_args(const irbfn_net* net, const float* x, float* out, int64_t B, int S, int QG, GramArgs* a);
 int launch_forward_gram_wide(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s);
 

@@ -37,9 +37,13 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "rbf_forward_gram_body.h"
 
 namespace irbfn {
+
+constexpr int kMaxDevices = 64;     // devices the per-instance launch records cover (more: the attribute is set per launch)
 
 template <int DC, int BC>
 __global__ __launch_bounds__(1024, IRBFN_GRAM_WAVES) void rbf_fwd_f16gram(const GramArgs ga) {
@@ -69,21 +73,33 @@ size_t gram_image_bytes(const irbfn_net* net) {
 size_t gram_header_bytes() { return sizeof(GramHdr); }
 
 #ifdef IRBFN_GRAM_STAMPS
-extern "C" int irbfn_debug_gram_stamps(unsigned long long* out32) {
-  return (int)hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_gram_stamps), sizeof(unsigned long long) * 32);
+extern "C" int irbfn_debug_gram_stamps(unsigned long long* out64) {
+  return (int)hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_gram_stamps), sizeof(unsigned long long) * 64);
 }
 #endif
+
+// hipFuncAttributeMaxDynamicSharedMemorySize once per kernel instance and device, not per launch: `set` is the instance's own
+// record of the largest size it has asked for on each device.  Per device because the attribute is the device's (the multi-GPU
+// runs launch the same instance on every card), the size because one instance runs geometries of different LDS; a launch then
+// costs one hipGetDevice (a thread-local read) and one relaxed load.  The saving itself is host time only and is not measured.
+struct DynLdsSet { std::atomic<unsigned> bytes[kMaxDevices]; };
+static int ensure_dyn_lds(const void* kernel, size_t lds, DynLdsSet* set) {
+  if (lds <= 48 * 1024) return IRBFN_OK;
+  int dev = 0;
+  IRBFN_HIP_CHECK(hipGetDevice(&dev));
+  if (dev >= 0 && dev < kMaxDevices && set->bytes[dev].load(std::memory_order_relaxed) >= lds) return IRBFN_OK;
+  IRBFN_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (dev >= 0 && dev < kMaxDevices) set->bytes[dev].store((unsigned)lds, std::memory_order_relaxed);
+  return IRBFN_OK;
+}
 
 template <int DC>
 static int launch_gram_bc(const GramArgs& a, int bc, int grid, int block, size_t lds, hipStream_t s) {
 #define IRBFN_GCASE(BCV)                                                                                      \
   case BCV: {                                                                                                 \
     auto k = rbf_fwd_f16gram<DC, BCV>;                                                                        \
-    if (lds > 48 * 1024) {                                                                                    \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                    \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-      if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }                               \
-    }                                                                                                         \
+    static DynLdsSet set;                                                                                     \
+    if (const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k), lds, &set); rc != IRBFN_OK) return rc; \
     hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, s, a);                                                \
     break;                                                                                                    \
   }
@@ -102,6 +118,7 @@ static int launch_gram_bc(const GramArgs& a, int bc, int grid, int block, size_t
 size_t gram_lds_bytes(int S, int QG, bool tick, bool gamma) {
   size_t ring = (size_t)S * kGramRing * kGramChunkBytes;
   if (gamma) ring += (size_t)S * QG * 128 * sizeof(float);   // a double-buffered tile of region weights per wave
+  else ring += (size_t)QG * 32 * sizeof(float);              // the gate values of the block's queries, parked across the steps
   size_t red = (size_t)S * QG * 2 * 4 * 64 + (size_t)QG * 32;
   if (tick) red += (size_t)QG * 32 * (kTickNarrowCP + kTickNarrowSP);
   red *= sizeof(float);
@@ -126,11 +143,8 @@ static int launch_tick_gram_bc(const GramArgs& a, const F16Roll& rl, int mode, i
 #define IRBFN_GCASE(BCV)                                                                                      \
   case BCV: {                                                                                                 \
     auto k = rbf_tick_f16gram<DC, BCV>;                                                                       \
-    if (lds > 48 * 1024) {                                                                                    \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                    \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-      if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }                               \
-    }                                                                                                         \
+    static DynLdsSet set;                                                                                     \
+    if (const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k), lds, &set); rc != IRBFN_OK) return rc; \
     hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, s, a, rl, mode);                                      \
     break;                                                                                                    \
   }

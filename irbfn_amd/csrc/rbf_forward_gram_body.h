@@ -23,9 +23,15 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
   constexpr int CBL = f16_chunk_bytes(DC);                   // K1h's chunk image (the VALU path reads its records)
   constexpr int CB = kGramChunkBytes;
   const int tid = threadIdx.x, lane = tid & 63;
+  IRBFN_GRAM_PHASE(GP_ENTRY);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int S = a.S, QG = a.QG;
-  const int slice = wave / QG, qg = wave % QG;               // the QG waves of a slice are adjacent and share its ring
+  // slice = wave / QG, qg = wave % QG (the QG waves of a slice are adjacent and share its ring) without a division: S <= 7
+  // (gram_geometry), so seven scalar compares
+  int slice = 0;
+#pragma unroll
+  for (int s2 = 1; s2 < 8; ++s2) slice += wave >= s2 * QG ? 1 : 0;
+  const int qg = wave - slice * QG;
   const int g = lane >> 4, n = lane & 15;
   const long q0 = ((long)blockIdx.x * QG + qg) * 32;
   const GramHdr* hp = ga.hdr;
@@ -36,19 +42,48 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
     q = q < a.B ? q : a.B - 1;
     qrow[t] = q < 0 ? 0 : q;
   }
-  // ---- query-side operands: B[k = slot][column = query]
+  // ---- query-side operands: B[k = slot][column = query].  Every x load of the lane -- the operands' four and, in the slice-0
+  // waves, the gate's -- is issued before the first of them is waited for.
+  float xop[2][2], rop[2];
+  gram_query_loads<DC>(a, hp, qrow, g, xop, rop);
+  // ---- smooth region gate of the single region (model.py:42-95), one value per query: evaluated here by the slice-0 waves from
+  // region 0's row of the tables (GateRow, with the kernel arguments) and parked in an LDS tile of QG x 32 floats BEHIND the rings
+  // (the rings are overwritten during the steps, and the kernel has no vector register to spare across them); the tail reads
+  // the two values of a lane back.  A wave reads what its own lanes wrote: no barrier.
+  [[maybe_unused]] float* gpark = reinterpret_cast<float*>(lds + (size_t)S * kGramRing * CB) + qg * 32;
+  if constexpr (!GAMMA) {
+    if (slice == 0) {
+      const GateRow& gr = ga.g0;
+      float xg[2][DC];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int d = 0; d < DC; ++d) xg[t][d] = a.x[qrow[t] * a.Dreal + (d < gr.nsplit ? d : 0)];   // nsplit <= Dreal: inside the row
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        float gv = gr.n_ranges > 0 ? 1.0f : 0.0f;            // model.py:70
+#pragma unroll
+        for (int d = 0; d < DC; ++d)
+          if (d < gr.nsplit && gr.n_ranges > 0) gv *= gate_factor(xg[t][d], gr.lo[d], gr.hi[d], gr.delta[d]);
+        if (g == 0) gpark[t * 16 + n] = gv;
+      }
+    }
+  }
   h4_t bhd[2];
   h8_t btl[2][2];
-  const bool bad = gram_query_operands<DC>(a, hp, qrow, g, bhd, btl);
-  const bool wave_bad = __builtin_amdgcn_ballot_w64(bad) != 0ull;     // wave-uniform: the VALU distances for these 32 queries
+  const bool bad = gram_query_operands<DC>(a, hp, xop, rop, g, bhd, btl);
+  // wave-uniform: the VALU distances for these 32 queries (through readfirstlane, which tells the compiler so)
+  const bool wave_bad = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_ballot_w64(bad) != 0ull ? 1 : 0) != 0;
+#ifdef IRBFN_GRAM_STAMPS
+  asm volatile("" ::"s"((int)wave_bad), "v"(bhd[1]), "v"(btl[1][1]));
+#endif
+  IRBFN_GRAM_PHASE(GP_OPERANDS);
 
-  const int c0 = (int)((long)a.nchunks * slice / S), c1 = (int)((long)a.nchunks * (slice + 1) / S);
+  // chunks [c0, c1) of the slice in 32-bit arithmetic: nchunks * S < 2^31 (checked where the plan is made)
+  const unsigned nch = (unsigned)a.nchunks;
+  const int c0 = (int)(nch * (unsigned)slice / (unsigned)S), c1 = (int)(nch * (unsigned)(slice + 1) / (unsigned)S);
   const int na = c1 - c0;
-  int nsteps = 0;                                            // every wave of the block walks the longest slice (barriers)
-  for (int s2 = 0; s2 < S; ++s2) {
-    const int m = (int)((long)a.nchunks * (s2 + 1) / S) - (int)((long)a.nchunks * s2 / S);
-    nsteps = m > nsteps ? m : nsteps;
-  }
+  const int nsteps = ga.nsteps;                              // every wave of the block walks the longest slice (barriers): gram_fill_args
   // Ring of kGramRing chunk images per slice: during step i the waves read the distance operands of chunk i + 1 and the W
   // operands of chunk i while later chunks land (end_of_step below).
   unsigned char* ring = lds + (size_t)slice * kGramRing * CB;
@@ -149,9 +184,11 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
   for (int k = 0; k <= kGramPer; ++k) stage(k, k);
   gamma_stage(0);
   step_barrier();                                            // the first kGramPer + 1 chunks are there
+  IRBFN_GRAM_PHASE(GP_BARRIER1);
 #pragma unroll
   for (int k = kGramPer + 1; k < kGramRing; ++k) stage(k, k);
   gamma_stage(1);
+  IRBFN_GRAM_PHASE(GP_LOOP0);
   if (!wave_bad) {
     // two steps per trip: the distances of chunk i + 1 are issued in front of the VALU work on chunk i
     f4_t ua[2][2], ub[2][2];
@@ -184,7 +221,7 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
     }
 #ifdef IRBFN_GRAM_STAMPS
     if (blockIdx.x < 2 && tid == 0)
-      for (int k = 0; k < 5; ++k) g_gram_stamps[blockIdx.x * 8 + k] = tph[k];
+      for (int k = 0; k < 5; ++k) g_gram_stamps[blockIdx.x * 32 + k] = tph[k];
 #endif
   } else {
     // a query of this wave lies outside the representable box (or is not finite): K1h's distances for its 32 queries,
@@ -201,30 +238,26 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
       b0 = next3(b0);
     }
   }
+  IRBFN_GRAM_PHASE(GP_LOOP1);
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[t][r] = __builtin_fmaf(acl[t][r], kLoScale, acc[t][r]);   // A1 + 2^-11 A2
 
-  // ---- smooth region gate of the single region (model.py:42-95), one value per query
-  const GateTables gt = a.gate;
+  // ---- the gate values parked by the prologue
   float gam[2] = {0.0f, 0.0f};
   if constexpr (GAMMA) {
     gam[0] = gam[1] = 1.0f;                                  // the region weights are inside the sums
   } else if (slice == 0) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      float gv = gt.n_ranges > 0 ? 1.0f : 0.0f;              // model.py:70
-#pragma unroll
-      for (int d = 0; d < DC; ++d)
-        if (d < gt.nsplit && gt.n_ranges > 0) {
-          const int e = d * gt.max_ranges + gt.dim_ranges[d];
-          gv *= gate_factor(a.x[qrow[t] * a.Dreal + d], gt.lo[e], gt.hi[e], gt.delta[d]);
-        }
-      gam[t] = gv;
-    }
+    gam[0] = gpark[n];
+    gam[1] = gpark[16 + n];
   }
+#ifdef IRBFN_GRAM_STAMPS
+  asm volatile("" ::"v"(gam[0]), "v"(gam[1]));
+#endif
+  IRBFN_GRAM_PHASE(GP_GATE);
   narrow_epilogue<ROLL>(a, rl, mode, lds, acc, gam, S, slice, qg, q0, 1.0f / (gram_phi_scale<BC>() * kWScale));
+  IRBFN_GRAM_PHASE(GP_STORED);
 }
 
 }  // namespace irbfn

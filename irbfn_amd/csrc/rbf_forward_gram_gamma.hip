@@ -64,6 +64,7 @@ static void gamma_fill_args(const irbfn_net* net, const float* x, const float* g
   gram_fill_args(net, x, out, B, S, QG, a);
   gm->gamma = gamma; gm->R = net->R; gm->cpr = gram_gamma_cpr(net);
   a->f.nchunks = gm->R * gm->cpr;
+  a->nsteps = gram_nsteps(a->f.nchunks, S);
 }
 
 template <typename K, typename... Args>

@@ -44,12 +44,24 @@ size_t gram_wide_lds_bytes(const irbfn_net* net, int SW, int QG, size_t extra_re
   return ring > red ? ring : red;
 }
 
+// chunks of the longest of the S slices [nchunks s / S, nchunks (s + 1) / S): the steps every wave of a narrow block walks
+int gram_nsteps(int nchunks, int S) {
+  int nsteps = 0;
+  for (int s2 = 0; s2 < S; ++s2) {
+    const int m = (int)((long)nchunks * (s2 + 1) / S) - (int)((long)nchunks * s2 / S);
+    nsteps = m > nsteps ? m : nsteps;
+  }
+  return nsteps;
+}
+
 void gram_fill_args(const irbfn_net* net, const float* x, float* out, int64_t B, int S, int QG, GramArgs* a) {
   const int nchunks = (net->N + kF16Chunk - 1) / kF16Chunk;
   a->f.x = x; a->f.img = net->f16_img; a->f.oscale = net->f16_oscale; a->f.bias = net->bias; a->f.out = out; a->f.gate = net->gate();
   a->f.B = (long)B; a->f.Dreal = net->D; a->f.O = net->O; a->f.nchunks = nchunks; a->f.S = S; a->f.QG = QG;
   a->gimg = net->gram_img;
   a->hdr = reinterpret_cast<const GramHdr*>(net->gram_hdr);
+  a->g0 = net->gate0;
+  a->nsteps = gram_nsteps(nchunks, S);
 }
 
 int launch_forward_gram_wide(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s) {
