@@ -257,6 +257,7 @@ int irbfn_net_vjp_kernel_supported(irbfn_net* net, int kernel, int64_t B);
  * irbfn_train_seeds_fullint: loss_fn of train_step_fullint (scripts/train_nmpc.py:306-390):
  *   loss = mean|y_pred[:, [0,T]] - y[:, [0,T]]| + mean|final_pred - final_actual| (T-step inline bicycle), O = 2T.
  * partials_dev: scratch of irbfn_train_loss_partials() floats.
+ * B = 0 (every seed call): IRBFN_OK, *loss_dev = 0, gy_dev untouched; the row pointers may be NULL.
  * irbfn_adam_clip_step: optax.chain(clip_by_global_norm(max_grad_norm), adam(lr)) + apply_gradients
  *   (scripts/train_nmpc.py:231-233, :299) on flat float32 buffers of n elements; step_dev is the
  *   device-resident update count (incremented by the call).  max_grad_norm <= 0 disables clipping.
