@@ -327,7 +327,9 @@ int irbfn_lut_grid_lookup(const double* keys_dev, const int32_t* key_offsets_hos
                           int D, int OW, void* stream);
 /* Explicit-MPC table look-up, nearest-neighbour form (scipy KDTree.query at explicit_planner.py:383):
  * idx = argmin_n ||inputs[n] - x_b||_2 over inputs_dev [N,D] (float32; ties -> lowest n), dist_dev [B]
- * (optional), out_dev [B,OW] = table_dev[idx] (optional).  D in {3,4,7,8}. */
+ * (optional), out_dev [B,OW] = table_dev[idx] (optional).  D in {3,4,7,8}.  A query with no finite float32 distance to
+ * any row (a NaN or Inf component) gets idx = -1, dist = NaN and a NaN row of out_dev.  IRBFN_ERR_BAD_ARG, before the
+ * workspace is touched, when ceil(B / 8) exceeds the device's maxGridSize[1] (or B its maxGridSize[0]). */
 int64_t irbfn_lut_nearest_workspace_bytes(int64_t N, int64_t B);
 int irbfn_lut_nearest(const float* inputs_dev, const float* table_dev, const float* x_dev, int64_t* idx_dev,
                       float* dist_dev, float* out_dev, int64_t N, int64_t B, int D, int OW, void* ws_dev,
@@ -336,10 +338,12 @@ int irbfn_lut_nearest(const float* inputs_dev, const float* table_dev, const flo
 /* Way-point geometry of the planners' pure-pursuit front end, batched over B query points against ONE piecewise-linear
  * trajectory [N,2] (float64 device arrays as the NumPy callers hold them; one wave per point):
  * irbfn_nearest_point = nearest_point (src/irbfn_mpc/planner_utils.py:109-146): projection [B,2], distance, t in [0,1]
- *   and segment index of the closest point (first minimum, as np.argmin);
+ *   and segment index of the closest point (first minimum, as np.argmin; but a segment whose distance is NaN -- a repeated
+ *   or NaN way-point -- is skipped where np.argmin returns the first NaN; nothing left: (0, 0), inf, 0, segment 0);
  * irbfn_intersect_point = intersect_point (:149-233): first point one `radius` away along the trajectory from
- *   t_start (= i + t, may be NULL = 0), with wrap-around; found[b] = 0 where the reference returns (None, None, None)
- *   (then first_p / first_t are NaN); first_i may be -1 (the closing segment, :206). */
+ *   t_start (= i + t, may be NULL = 0; must not be NaN: the conversion to the start index is undefined), with
+ *   wrap-around; found[b] = 0 where the reference returns (None, None, None) (then first_p / first_t are NaN); first_i
+ *   may be -1 (the closing segment, :206). */
 int irbfn_nearest_point(const double* points_dev, const double* trajectory_dev, double* proj_dev, double* dist_dev,
                         double* t_dev, int32_t* seg_dev, int64_t B, int N, void* stream);
 int irbfn_intersect_point(const double* points_dev, const double* trajectory_dev, const double* t_start_dev, float radius,

@@ -16,7 +16,8 @@ namespace irbfn {
 // Python's float modulo: result has the sign of the divisor (b > 0 here)
 __device__ __forceinline__ double py_mod(double a, double b) {
   double r = fmod(a, b);
-  if (r != 0.0 && (r < 0.0) != (b < 0.0)) r += b;
+  if (r == 0.0) return copysign(0.0, b);          // fmod keeps the sign of a: -0.0 % pi is +0.0 in Python and NumPy
+  if ((r < 0.0) != (b < 0.0)) r += b;
   return r;
 }
 
@@ -25,6 +26,7 @@ __global__ __launch_bounds__(256) void plan_queries_cartesian_kernel(const doubl
                                                                      float* __restrict__ x_out,
                                                                      float* __restrict__ state0_out,
                                                                      int* __restrict__ mirror_out, long B) {
+#pragma clang fp contract(off)                   // NumPy rounds each product: a fused s*dx + c*dy flips the sign of an exact 0
   const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const double* p = pose + b * 7;                // [x, y, delta, v, theta, angv, beta]  (:240)
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(256) void lut_grid_lookup_kernel(const double* __re
   }
 }
 
-// ---- exact nearest neighbour: argmin_n ||inputs[n] - x_b||  (ties -> lowest n)
+// ---- exact nearest neighbour: argmin_n ||inputs[n] - x_b||  (ties -> lowest n; no finite distance -> idx -1, NaN)
 // One lane per table row, grid-stride; the QT queries of a tile are wave-uniform (scalar loads); per-block
 // (d2, n) minima go to a [B][nblocks] slab, a second kernel takes the fixed-order minimum: deterministic.
 template <int D, int QT>
@@ -202,12 +204,13 @@ __global__ __launch_bounds__(64) void lut_nearest_final_kernel(const float* __re
     const long oi = __shfl_xor(bi, off);
     if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
   }
+  const bool none = bi == 0x7fffffffffffffffL;   // no row compared below infinity (NaN / Inf query, or an overflowing d2)
   if (lane == 0) {
-    idx_out[b] = bi;
-    if (dist_out) dist_out[b] = sqrtf(bd);
+    idx_out[b] = none ? -1L : bi;
+    if (dist_out) dist_out[b] = none ? NAN : sqrtf(bd);
   }
-  if (out && table && bi != 0x7fffffffffffffffL)
-    for (int o = lane; o < OW; o += 64) out[b * OW + o] = table[bi * OW + o];
+  if (out && table)
+    for (int o = lane; o < OW; o += 64) out[b * OW + o] = none ? NAN : table[bi * OW + o];
 }
 
 template <int D>
@@ -225,7 +228,7 @@ using namespace irbfn;
 
 // ---- way-point geometry of the pure-pursuit front end (src/irbfn_mpc/planner_utils.py:109-240) -----------------
 // The reference runs nearest_point / intersect_point once per planner tick under numba; here they are batched over B
-// query points against ONE piecewise-linear trajectory (staged in LDS), one lane per point.  The arithmetic types
+// query points against ONE piecewise-linear trajectory, one wave per point.  The arithmetic types
 // follow the reference line by line: float32 segment vectors / squared lengths / dot products, float64 everything
 // else in nearest_point (:125-141); float32 trajectory, +1e-6f end points, float32 t in intersect_point (:160-170),
 // with the point kept in float64 as the callers pass it.  numba's typing of the mixed expressions cannot be
@@ -238,12 +241,15 @@ struct WayArgs {
 };
 
 // One WAVE per point: the lanes take the segments lane, lane + 64, ... and the wave picks the smallest distance (the
-// smallest segment index among equal distances: np.argmin's first minimum).  (One thread per point walking all N
+// smallest segment index among equal distances: np.argmin's first minimum).  A segment whose distance is NaN (a repeated
+// way-point: t = 0/0; a NaN way-point) is skipped, where np.argmin returns the first NaN: a deliberate departure, stated in the
+// oracle as nearest_point(skip_nan=True).  (One thread per point walking all N
 // segments with a float64 divide and square root each took 200 us at ANY batch size -- the planner calls this with one
 // point per tick.)
 __global__ __launch_bounds__(256) void nearest_point_kernel(const WayArgs a, double* __restrict__ proj,
                                                             double* __restrict__ dist, double* __restrict__ tt,
                                                             int* __restrict__ seg) {
+#pragma clang fp contract(off)                   // every product of the reference's lines is rounded before its sum
   const int lane = threadIdx.x & 63;
   const long b = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= a.B) return;                          // the whole wave
@@ -282,6 +288,7 @@ __global__ __launch_bounds__(256) void nearest_point_kernel(const WayArgs a, dou
 
 __device__ __forceinline__ bool circle_hit(const double* wp, int N, int i, double px, double py, float radius,
                                            bool first, float start_t, float& t_out, float& qx, float& qy) {
+#pragma clang fp contract(off)
   const int i0 = ((i % N) + N) % N, i1 = (((i + 1) % N) + N) % N;
   const float sx = (float)wp[2 * i0], sy = (float)wp[2 * i0 + 1];                         // trajectory.astype(float32) :160
   const float ex = (float)wp[2 * i1] + 1e-6f, ey = (float)wp[2 * i1 + 1] + 1e-6f;         // :163
@@ -315,6 +322,7 @@ __device__ __forceinline__ bool circle_hit(const double* wp, int N, int i, doubl
 __global__ __launch_bounds__(256) void intersect_point_kernel(const WayArgs a, const double* __restrict__ t0, float radius,
                                                               int wrap, float* __restrict__ first_p, int* __restrict__ first_i,
                                                               float* __restrict__ first_t, int* __restrict__ found) {
+#pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
   const long b = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= a.B) return;                          // the whole wave
@@ -414,6 +422,12 @@ int irbfn_lut_nearest(const float* inputs_dev, const float* table_dev, const flo
   if (N < 1 || B < 0 || OW < 0) return IRBFN_ERR_BAD_ARG;
   if (B == 0) return IRBFN_OK;
   if (!inputs_dev || !x_dev || !idx_dev || !ws_dev || (out_dev && !table_dev)) return IRBFN_ERR_BAD_ARG;
+  // the scan puts ceil(B / 8) query tiles on gridDim.y and the final kernel B blocks on gridDim.x: the device's limits
+  int dev = 0, max_y = 0, max_x = 0;
+  IRBFN_HIP_CHECK(hipGetDevice(&dev));
+  IRBFN_HIP_CHECK(hipDeviceGetAttribute(&max_y, hipDeviceAttributeMaxGridDimY, dev));   // hipDeviceProp_t::maxGridSize[1]
+  IRBFN_HIP_CHECK(hipDeviceGetAttribute(&max_x, hipDeviceAttributeMaxGridDimX, dev));
+  if ((B + 7) / 8 > (int64_t)max_y || B > (int64_t)max_x) return IRBFN_ERR_BAD_ARG;
   if (ws_bytes < irbfn_lut_nearest_workspace_bytes(N, B)) return IRBFN_ERR_BAD_ARG;
   const int cap = 2048;
   long want = (N + 255) / 256;

@@ -61,7 +61,9 @@ class ExplicitTable:
         return idx, out
 
     def nearest(self, lookup):
-        """-> (row index [B] int64, distance [B], outputs [B, OW])."""
+        """-> (row index [B] int64, distance [B], outputs [B, OW]); ties go to the lowest row index.  A query with no
+        finite distance to any row (a NaN or Inf component; scipy's KDTree.query raises ValueError there) gets index -1,
+        distance NaN and a NaN output row.  Raises ValueError when B is too large for one launch on this device."""
         torch, lib = self._torch, _lib.load()
         x = self._x(lookup, torch.float32)
         B = x.shape[0]

@@ -4,7 +4,7 @@
 launch (the predicted controls stay in LDS between the network and the roll-out), plus the batched
 query construction / mirror trick around it (irbfn_planner.py:181-208, :456-492).  The
 way-point search of the reference planner (numba ``nearest_point`` / ``intersect_point``,
-planner_utils.py:109-240: sequential, mixed float32/float64) stays host-side and out of scope."""
+planner_utils.py:109-240) is batched in ``irbfn_amd.planner_utils``."""
 from __future__ import annotations
 
 import ctypes as C

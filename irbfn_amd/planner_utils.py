@@ -28,7 +28,9 @@ def _f64(a, torch):
 
 def nearest_point(points, trajectory):
     """Batched ``nearest_point`` (planner_utils.py:109-146).  points [B,2] (or [2]), trajectory [N,2] ->
-    (projections [B,2], dists [B], t [B], segment index [B]) as device tensors (float64 / int32)."""
+    (projections [B,2], dists [B], t [B], segment index [B]) as device tensors (float64 / int32).  A segment whose
+    distance is NaN (a repeated or NaN way-point) is skipped, where the reference's np.argmin returns the first NaN; if
+    every distance is NaN the result is ((0, 0), inf, 0, 0)."""
     torch = _lib.require_gpu()
     lib = _lib.load()
     pd, td = _f64(points, torch).reshape(-1, 2), _f64(trajectory, torch)
@@ -45,7 +47,8 @@ def nearest_point(points, trajectory):
 def intersect_point(points, radius, trajectory, t=None, wrap=False):
     """Batched ``intersect_point`` (planner_utils.py:149-233).  points [B,2], trajectory [N,2], t [B] = i + t of
     the search start (None = 0) -> (first_p [B,2] float32, first_i [B] int32, first_t [B] float32, found [B] int32);
-    rows with found == 0 are the reference's ``(None, None, None)`` (NaN / undefined index)."""
+    rows with found == 0 are the reference's ``(None, None, None)`` (NaN / undefined index).  ``t`` must not hold NaN:
+    its conversion to the start index is undefined."""
     torch = _lib.require_gpu()
     lib = _lib.load()
     pd, td = _f64(points, torch).reshape(-1, 2), _f64(trajectory, torch)

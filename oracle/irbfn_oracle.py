@@ -731,13 +731,20 @@ DYN_PARAMS_KAT1 = [1.0, 1.0489, 0.04712, 0.15875, 0.17145, 5.0, 5.0, 0.074, 0.1,
 # ---------------------------------------------------------------------------------------------------
 # planner front end: literal per-row restatements
 # ---------------------------------------------------------------------------------------------------
-def plan_query_cartesian(pose, goal):
+def plan_query_cartesian(pose, goal, unfused=False):
     """One (pose, goal) pair -> (rbf_in [7] float32, mirror, states [7] float32).
     src/irbfn_mpc/irbfn_planner.py:160-166 (pose), :181-201 (query), :240 (states)."""
     x, y, delta, v, theta, angv, beta = [float(t) for t in pose]
     ref_point = np.asarray(goal, np.float64)
     rot = np.array([[np.cos(-theta), -np.sin(-theta)], [np.sin(-theta), np.cos(-theta)]])     # :181-183
-    goal_local = np.dot(rot, (ref_point[:2] - np.array([x, y])))                               # :184
+    d = ref_point[:2] - np.array([x, y])
+    if unfused:
+        # what irbfn_plan_queries_cartesian pins: two rounded products and one sum.  np.dot leaves that to its BLAS, which may
+        # fuse the second product into the sum; a goal straight ahead then gives +-1e-16 instead of exactly 0 and the mirror
+        # flag depends on the library.
+        goal_local = np.array([rot[0, 0] * d[0] + rot[0, 1] * d[1], rot[1, 0] * d[0] + rot[1, 1] * d[1]])
+    else:
+        goal_local = np.dot(rot, d)                                                            # :184
     goal_theta = ref_point[2] - theta                                                          # :185
     goal_needs_mirror = goal_local[1] < 0                                                      # :188
     rbf_in = np.array([v, goal_local[0],
@@ -786,7 +793,11 @@ def lut_nearest(inputs, lookup):
 # f-4 way-point geometry -- src/irbfn_mpc/planner_utils.py:109-233 (numba in the reference: the same lines without
 # the decorator; numba's typing of the mixed float32 / float64 expressions cannot be checked here: parity unpinned)
 # --------------------------------------------------------------------------
-def nearest_point(point, trajectory):
+def nearest_point(point, trajectory, skip_nan=False):
+    """skip_nan=False is the literal line :141: np.argmin returns the FIRST NaN distance (a repeated way-point gives
+    t = 0/0), so one degenerate segment hides every other.  skip_nan=True states what irbfn_nearest_point does instead:
+    the first minimum among the distances that are not NaN; none left -> the scalar loop's defaults
+    ((0, 0), inf, 0.0, 0)."""
     diffs = (trajectory[1:, :] - trajectory[:-1, :]).astype(np.float32)           # :125
     l2s = diffs[:, 0] ** 2 + diffs[:, 1] ** 2                                     # :126
     dots = np.empty((trajectory.shape[0] - 1,))
@@ -801,7 +812,12 @@ def nearest_point(point, trajectory):
     for i in range(dists.shape[0]):
         temp = point - projections[i]
         dists[i] = np.sqrt(np.sum(temp * temp))
-    k = int(np.argmin(dists))
+    if skip_nan:
+        if np.isnan(dists).all():
+            return np.zeros(2), np.inf, 0.0, 0
+        k = int(np.nanargmin(dists))
+    else:
+        k = int(np.argmin(dists))                                                 # :141
     return projections[k], dists[k], t[k], k
 
 
