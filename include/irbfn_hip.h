@@ -300,6 +300,39 @@ int irbfn_adam_clip_step_f64(double* params_dev, const double* grads_dev, double
                              int* step_dev, double lr, double beta1, double beta2, double eps, double max_grad_norm,
                              double* partials_dev, void* stream);
 
+/* ---- Evaluating a net on a table: roll-out error statistics on device ---------------------------------------
+ * What scripts/eval_irbfn_dnmpc.py:92-167 does on the host (roll the label controls and the predicted controls out side by side,
+ * :95-159, and report position / heading / velocity errors, :162-167; deprecated/evaluate.py:265-283 likewise for trajectory end
+ * points).  The METRIC DEFINITIONS below are this project's own: those lines of the reference are not in the snapshot this
+ * library was written from, so parity with its numbers is unpinned.
+ * Per row b < B both control sets y_dev[b], y_pred_dev[b] ([a_0..a_{T-1}, sv_0..sv_{T-1}]) are rolled out for T steps from
+ * state0_dev[b] (the row layout of irbfn_plan_tick: [B,7] single-track, [B,1] = v0 inline bicycle, [B,8] Frenet) to the final
+ * states a (label) and p (prediction); the row's M = S + 2 float32 metrics are
+ *   m < S : |p_m - a_m|                    (plain difference, no angle wrapping, as the training losses take it)
+ *   S     : hypotf(p_0 - a_0, p_1 - a_1)   position error (Cartesian x, y; Frenet: s, e_y)
+ *   S + 1 : mean_j |y_pred[b,j] - y[b,j]|  over the 2T controls.
+ * Modes ST_SELECT, ST_KS, FULLINT, FRENET_LS (S = 7, 7, 5, 8), any 1 <= T <= 64; SPIRAL has no controls.
+ * Statistics per metric, merged across calls (accumulate != 0 adds this call's rows to what the buffers hold; 0 resets first):
+ *   stats_dev  [M][4] double : n (rows whose value is finite), sum, sum_sq, max; a value that is not finite enters none of
+ *                              them and no bin (the caller gets their number as rows - n); max is -inf while n = 0
+ *   argmax_dev [M] int64     : row0 + b of the LOWEST row that attains max; -1 while n = 0
+ *   hist_dev   [M][512] int64: bin = clamp((float_bits(e) >> 20) - 696, 0, 511): exponent and three mantissa bits, eight bins per
+ *                              octave.  edge(k) = 2^(-40 + k / 8) * (1 + (k mod 8) / 8) (integer k / 8); bin 0 = [0, edge(1)), bin k =
+ *                              [edge(k), edge(k + 1)), bin 511 = everything finite from edge(511) up.  Consecutive edges differ by a
+ *                              factor <= 9/8: a quantile read off the histogram is bracketed by its bin's edges.
+ *                              1.0 -> 320, 1.125 -> 321, <= 2^-40 -> 0, >= 2^24 -> 511.
+ * err_dev [B][M] (optional, NULL skips the stores): the per-row metrics.  Deterministic, bit-identical across repeats.
+ * workspace_dev: irbfn_eval_workspace_bytes(mode) bytes, 8-byte aligned.  dyn_params_host: NULL for FULLINT.
+ * B = 0: IRBFN_OK; reset outputs under accumulate = 0, untouched outputs otherwise.  IRBFN_ERR_BAD_ARG: unknown mode, B < 0,
+ * T < 1, a NULL stats / argmax / hist / workspace, a NULL row pointer with B > 0, missing dynamics parameters, a workspace too
+ * small.  IRBFN_ERR_UNSUPPORTED: T > 64, a mode without controls. */
+int irbfn_eval_num_metrics(int mode);            /* S + 2; < 0 for a mode without controls or an unknown one */
+int64_t irbfn_eval_workspace_bytes(int mode);    /* < 0 where irbfn_eval_num_metrics is */
+int irbfn_eval_rollout_errors(int mode, const float* state0_dev, const float* y_pred_dev, const float* y_dev,
+                              const float* dyn_params_host, int64_t B, int T, int64_t row0, int accumulate,
+                              float* err_dev /* or NULL */, double* stats_dev, int64_t* argmax_dev, int64_t* hist_dev,
+                              void* workspace_dev, int64_t workspace_bytes, void* stream);
+
 /* ---- Batched planner front / back end ------------------------------------------------------
  * Query construction + mirror trick of IRBFNPlanner.plan (src/irbfn_mpc/irbfn_planner.py:181-201):
  * pose [B,7] = [x, y, delta, v, theta, angv, beta] (:240), goal [B,4] = ref_point [x, y, theta, v] (:170-171),

@@ -7,6 +7,7 @@ Host side is Python (like the reference) over a C-ABI shared library of hand-wri
 * ``irbfn_amd.model``         ``WCRBFNet(**model_card).apply(params, x)``
 * ``irbfn_amd.dynamics``      ``integrate_st_mult``, ``dynamic_st_onestep_aux``, ``integrate_frenet_mult``
 * ``irbfn_amd.planner_utils`` ``integrate_path_mult``
+* ``irbfn_amd.evaluate``      ``evaluate_table`` / ``rollout_errors``: roll-out error statistics of a net on a whole table
 * ``irbfn_amd.autograd``      ``torch.autograd`` wrappers (the ``jax.grad`` surface)
 * ``irbfn_amd.distributed``   one-process-per-GPU sharding, RCCL broadcast of the parameters
 

@@ -55,6 +55,9 @@ SIGNATURES = {
     "irbfn_train_seeds_fullint_f64": (_i, [_fp, _fp, _fp, _d, _fp, _fp, _fp, _i64, _i, _i, _vp]),
     "irbfn_train_seeds_frenet_fullint_f64": (_i, [_fp, _fp, _fp, _fp, _d, _fp, _fp, _fp, _i64, _i, _i, _vp]),
     "irbfn_adam_clip_step_f64": (_i, [_fp, _fp, _fp, _fp, _i64, _vp, _d, _d, _d, _d, _d, _fp, _vp]),
+    "irbfn_eval_num_metrics": (_i, [_i]),
+    "irbfn_eval_workspace_bytes": (_i64, [_i]),
+    "irbfn_eval_rollout_errors": (_i, [_i, _fp, _fp, _fp, _fp, _i64, _i, _i64, _i, _fp, _fp, _ip, _ip, _vp, _i64, _vp]),
     "irbfn_plan_queries_cartesian": (_i, [_fp, _fp, _fp, _fp, _ip, _i64, _vp]),
     "irbfn_plan_queries_frenet": (_i, [_fp, _fp, _fp, _fp, _ip, _i64, _vp]),
     "irbfn_plan_tick": (_i, [_vp, _i, _fp, _ip, _fp, _fp, _fp, _fp, _i64, _i, _vp]),

@@ -59,6 +59,7 @@ UNITS = [
     ("plan_tick_wide.hip", "plan_tick_wide.o", ["-mllvm", "-pragma-unroll-threshold=100000", "-fno-slp-vectorize"]),
     ("rollout_vjp.hip", "rollout_vjp.o", ["-mllvm", "-pragma-unroll-threshold=100000", "-fno-slp-vectorize"]),
     ("train_step.hip", "train_step.o", []),
+    ("eval_errors.hip", "eval_errors.o", []),          # K6: roll-out error statistics of a table (rolled step loop)
     ("mlp_head.hip", "mlp_head.o", []),
     ("planner_front.hip", "planner_front.o", []),
 ]

@@ -432,6 +432,26 @@ int irbfn_plan_tick_gamma(irbfn_net* net, int mode, const float* x_dev, const fl
                                       as_stream(stream));
 }
 
+int irbfn_eval_num_metrics(int mode) { return eval_num_metrics(mode); }
+
+int64_t irbfn_eval_workspace_bytes(int mode) { return eval_workspace_bytes(mode); }
+
+int irbfn_eval_rollout_errors(int mode, const float* state0_dev, const float* y_pred_dev, const float* y_dev,
+                              const float* dyn_params_host, int64_t B, int T, int64_t row0, int accumulate, float* err_dev,
+                              double* stats_dev, int64_t* argmax_dev, int64_t* hist_dev, void* workspace_dev,
+                              int64_t workspace_bytes, void* stream) {
+  if (rollout_state_dim(mode) < 0 || B < 0 || T < 1) return IRBFN_ERR_BAD_ARG;
+  if (!stats_dev || !argmax_dev || !hist_dev || !workspace_dev) return IRBFN_ERR_BAD_ARG;
+  if (B > 0 && (!state0_dev || !y_pred_dev || !y_dev)) return IRBFN_ERR_BAD_ARG;
+  DynParams dp;
+  int rc = load_dyn(mode, dyn_params_host, &dp);
+  if (rc != IRBFN_OK) return rc;
+  if (eval_num_metrics(mode) < 0 || T > 64) return IRBFN_ERR_UNSUPPORTED;
+  if (workspace_bytes < eval_workspace_bytes(mode)) return IRBFN_ERR_BAD_ARG;
+  return launch_eval_errors(mode, state0_dev, y_pred_dev, y_dev, dp, B, T, row0, accumulate, err_dev, stats_dev, argmax_dev,
+                            hist_dev, workspace_dev, as_stream(stream));
+}
+
 int irbfn_net_last_launch(const irbfn_net* net, char* name_buf, int name_len, int* grid, int* block) {
   if (!net) return IRBFN_ERR_BAD_ARG;
   if (name_buf && name_len > 0) {

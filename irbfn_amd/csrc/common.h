@@ -260,6 +260,12 @@ int launch_rollout_forward_split(int mode, const float* state0, const float* con
                                  float* states, int64_t B, int T, hipStream_t s);
 int launch_rollout_vjp(int mode, const float* x0u, const DynParams& dp, const float* gstates,
                        float* g_x0u, int64_t B, int T, float clip_tie, hipStream_t s);
+// roll-out error statistics of a table (eval_errors.hip): M = S + 2 metrics per row, < 0 for a mode without controls
+int eval_num_metrics(int mode);
+int64_t eval_workspace_bytes(int mode);
+int launch_eval_errors(int mode, const float* state0, const float* y_pred, const float* y, const DynParams& dp, int64_t B, int T,
+                       int64_t row0, int accumulate, float* err, double* stats, int64_t* argmax, int64_t* hist, void* ws,
+                       hipStream_t s);
 int launch_unmirror(float* controls, const int* mirror, int64_t B, int O, int sv0, hipStream_t s);
 // the head kernels read h1 rows with 16-byte vector loads: the three head entry points refuse any other h1_dev
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
