@@ -501,6 +501,34 @@ int irbfn_f64_vjp_x(const irbfn_f64_card* card, const double* centers_dev, const
                     const double* kernel_dev, const double* x_dev, const double* gout_dev, double* gx_dev, int64_t B,
                     void* workspace_dev, int64_t workspace_bytes, void* stream);
 
+/* k-means on a table: one Lloyd iteration per call (kmeans.hip).  The reference derives the centres of its fixed-centre nets
+ * ("constraint clustering -> centre files") and the cluster labels of train_step_fullint_withcluster in notebooks that are
+ * not in its snapshot: parity with its clustering is unpinned; the arithmetic below is pinned against a float64 statement.
+ *   d2[n,k]  = the float32 chain d2 = fmaf(t, t, d2), t = x[n,d] - c[k,d], d = 0 .. D-1, from 0 (no Gram expansion);
+ *   label[n] = argmin_k d2[n,k], ties to the lowest k; labels_dev [N] is read (for `moved`) and then overwritten: fill it with
+ *              -1 before the first iteration.  d2_dev [N] (optional) = d2[n, label[n]].
+ *   A row with a non-finite component, or whose float32 d2 to every centre is not finite, gets label -1 and d2 = NaN and
+ *   enters no sum, no count and no statistic (the rule of irbfn_lut_nearest).  A centre with a non-finite component is never
+ *   chosen.
+ *   new_centers_dev [K,D] (optional; NULL = assign only) = the float32 mean of the rows labelled k: the sums are exact 64-bit
+ *   integers on a per-column fixed-point grid of 2^-S max|x[:,d]| with S = 62 - bits(N), so the mean is within
+ *   (2^-24 + 2^-S) max_n |x[n,d]| of the real one, in any order.  A cluster with no row keeps its old centre bit for bit and
+ *   counts[k] = 0.  counts_dev [K] (optional) is exact.  new_centers_dev must not alias centers_dev.
+ *   stats_dev [4] (float64): the number of finite rows; the inertia = sum of d2[n, label[n]] over them; moved = the number of
+ *   them whose label differs from the value labels_dev held on entry; max_k ||new_k - old_k||^2 taken in float64 from the
+ *   float32 centres (0 when new_centers_dev is NULL).
+ *   Every output is bit-identical across repeats.
+ * Supported: 1 <= D <= 16 (as irbfn_cluster_gate), 1 <= K <= 65536, any N >= 0 (grid-stride; no grid-limit refusal); outside it
+ * IRBFN_ERR_UNSUPPORTED.  K < 1, D < 1, N < 0, a NULL x / centers / labels / stats with N > 0, or a workspace that is NULL,
+ * not 8-byte aligned or smaller than irbfn_kmeans_workspace_bytes(N, K, D): IRBFN_ERR_BAD_ARG.  All of these are decided
+ * before any HIP call.  N = 0: IRBFN_OK, no launch, the outputs untouched.  irbfn_kmeans_workspace_bytes returns the same
+ * negative codes for sizes it refuses. */
+int64_t irbfn_kmeans_workspace_bytes(int64_t N, int K, int D);
+int irbfn_kmeans_step(const float* x_dev /*[N,D]*/, const float* centers_dev /*[K,D]*/, int32_t* labels_dev /*[N] in/out*/,
+                      float* d2_dev /*[N] or NULL*/, float* new_centers_dev /*[K,D] or NULL = assign only*/,
+                      int64_t* counts_dev /*[K] or NULL*/, double* stats_dev /*[4]*/, int64_t N, int K, int D,
+                      void* workspace_dev, int64_t workspace_bytes, void* stream);
+
 /* Diagnostics */
 int irbfn_abi_version(void);
 int irbfn_device_count(void);

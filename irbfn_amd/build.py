@@ -60,6 +60,7 @@ UNITS = [
     ("rollout_vjp.hip", "rollout_vjp.o", ["-mllvm", "-pragma-unroll-threshold=100000", "-fno-slp-vectorize"]),
     ("train_step.hip", "train_step.o", []),
     ("eval_errors.hip", "eval_errors.o", []),          # K6: roll-out error statistics of a table (rolled step loop)
+    ("kmeans.hip", "kmeans.o", []),                    # K7: one Lloyd iteration of k-means on a table
     ("mlp_head.hip", "mlp_head.o", []),
     ("planner_front.hip", "planner_front.o", []),
 ]

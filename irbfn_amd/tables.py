@@ -118,9 +118,13 @@ class DeviceTable:
     (train_nmpc.py:456-467 does both on the host).  288 GB of HBM holds any table the reference names
     (the largest, 8x19x19x64x8x6x12 rows x 17 floats, is 7 GB)."""
 
-    def __init__(self, flat_inputs, flat_outputs, device=None, seed: int = 0, dtype=np.float32):
+    def __init__(self, flat_inputs, flat_outputs, device=None, seed: int = 0, dtype=np.float32, labels=None,
+                 num_classes: Optional[int] = None):
         """dtype: of the resident rows (NumPy or torch dtype); float64 for the float64 training state of a
-        ``use_float64`` net, whose steps would otherwise cast every batch."""
+        ``use_float64`` net, whose steps would otherwise cast every batch.
+        labels: the cluster label of every row (``kmeans.fit(...).labels``; array or tensor [N], -1 = none), kept as an
+        int32 column on the device; ``epoch`` then yields the one-hot ``cluster_ids`` of
+        ``train_step_fullint_withcluster`` as a third entry.  num_classes: their width R (required with labels)."""
         from . import _lib
         torch = _lib.require_gpu()
         dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -129,6 +133,16 @@ class DeviceTable:
         self.y = torch.as_tensor(np.ascontiguousarray(flat_outputs, dtype=npd)).to(dev)
         if self.x.shape[0] != self.y.shape[0]:
             raise ValueError("inputs and outputs differ in row count")
+        self.labels, self.num_classes = None, None
+        if labels is not None:
+            if num_classes is None or int(num_classes) < 1:
+                raise ValueError("labels need num_classes >= 1")
+            lab = labels.detach() if isinstance(labels, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(labels))
+            if lab.dim() != 1 or lab.shape[0] != self.x.shape[0] or lab.dtype.is_floating_point:
+                raise ValueError("labels must be one integer per table row")
+            self.labels, self.num_classes = lab.to(dev, torch.int32).contiguous(), int(num_classes)
+            if bool(((self.labels < -1) | (self.labels >= self.num_classes)).any()):
+                raise ValueError(f"labels must lie in [-1, {self.num_classes})")
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(int(seed))
         self._torch = torch
@@ -139,9 +153,16 @@ class DeviceTable:
     def epoch(self, batch_size: int):
         """Yields (batch_x, batch_y) for ``len // batch_size`` full batches of a fresh permutation (the
         remainder is dropped, train_nmpc.py:459-464).  The permutation stream is torch's, not
-        jax.random's: batch COMPOSITION is not comparable with the reference, only its distribution."""
+        jax.random's: batch COMPOSITION is not comparable with the reference, only its distribution.
+        A labelled table yields (batch_x, batch_y, ids): ids [B, num_classes] float32 one-hot, a zero row for label -1."""
         torch = self._torch
         n = (len(self) // batch_size) * batch_size
         perm = torch.randperm(len(self), device=self.x.device, generator=self.gen)[:n].view(-1, batch_size)
         for rows in perm:
-            yield self.x.index_select(0, rows), self.y.index_select(0, rows)
+            if self.labels is None:
+                yield self.x.index_select(0, rows), self.y.index_select(0, rows)
+            else:
+                lab = self.labels.index_select(0, rows).to(torch.int64)
+                ids = torch.zeros((batch_size, self.num_classes + 1), dtype=torch.float32, device=self.x.device)
+                ids.scatter_(1, lab.remainder(self.num_classes + 1).unsqueeze(1), 1.0)      # -1 -> the spare last column
+                yield self.x.index_select(0, rows), self.y.index_select(0, rows), ids[:, :self.num_classes].contiguous()

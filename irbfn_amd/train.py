@@ -289,11 +289,22 @@ def train_step_fullint_withcluster(state: ClusterTrainState, x, y, cluster_ids, 
 def train_epoch(state: TrainState, table, batch_size: int, only_onestep: bool = False, dyn_params=None):
     """scripts/train_nmpc.py:455-486: one pass over a ``tables.DeviceTable``.  Returns (state, losses [steps]
     on the device) -- the reference fetches every batch loss to the host (``jax.device_get``, :477-481);
-    here nothing synchronises until the caller reads ``losses``."""
+    here nothing synchronises until the caller reads ``losses``.
+    A ``ClusterTrainState`` takes a labelled table (``DeviceTable(labels=, num_classes=)``) and ``dyn_params`` and runs
+    ``train_step_fullint_withcluster`` (scripts/train_nmpc_frenet.py:424-453) on every batch."""
     torch = _lib.require_gpu()
     losses = []
-    for bx, by in table.epoch(batch_size):
-        if only_onestep:
+    cluster = isinstance(state, ClusterTrainState)
+    if cluster:
+        if getattr(table, "labels", None) is None:
+            raise ValueError("train_epoch with a ClusterTrainState needs a labelled table: DeviceTable(labels=, num_classes=)")
+        if dyn_params is None:
+            raise ValueError("train_epoch with a ClusterTrainState needs dyn_params")
+    for batch in table.epoch(batch_size):
+        bx, by = batch[0], batch[1]
+        if cluster:
+            state, loss = train_step_fullint_withcluster(state, bx, by, batch[2], dyn_params)
+        elif only_onestep:
             state, loss = train_step_oneint(state, bx, by, dyn_params)
         else:
             state, loss = train_step_fullint(state, bx, by)
