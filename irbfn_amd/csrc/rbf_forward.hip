@@ -285,13 +285,23 @@ static bool gram_wide_preferred(const irbfn_net* net, int64_t B) {
 // second, thin round of blocks costs a wave's whole latency-bound pass over its slice; blocks of FOUR waves with all the centres
 // (S = 1, QG = 4: four resident per CU, 4096 groups at once) spread the same work over the chip in one round
 // (profiles/r03_gram_geometry_sweep.txt: N = 1000, B = 80000: 40.7 vs 47.4 us; N = 2048: 67 vs 73; N = 4096: 121 vs 122).
+// S = 2 with more than 1024 groups would put two blocks of eight waves on a CU; ONE block of sixteen (S = 2, QG = 8) keeps the CU's
+// sixteen waves and streams each chunk image into LDS once instead of twice: half the LDS-DMA requests per wave, whose issue is the
+// largest cost of a step that is not arithmetic (profiles/k1g_setup_and_refills.txt: config 2 83.4 -> 81.4 us).  QG does not enter
+// the order of any sum.  gram_default_qg is the one statement of the rule (plan_gram_gamma's forced S takes it too).
+static int gram_default_qg(int S, long groups) {
+  if (S == 1 && groups > 2048 && groups <= 3072) return 4;
+  if (S == 2 && groups > 1024) return 8;
+  return 8 / S > 0 ? 8 / S : 1;
+}
+
 static void gram_geometry(const irbfn_net* net, int64_t B, int nchunks, int* S_out, int* QG_out) {
   const long groups = (B + 31) / 32;
   int S = groups <= 512 ? 4 : (groups <= 2048 ? 2 : 1);
   while (S > 1 && nchunks / (2 * S) < 4) S /= 2;            // at least 8 chunks per wave
   S = opt_or(net, IRBFN_OPT_FWD_F16_S, S);
   if (S > 7 || S > nchunks) S = 1;
-  int QG = opt_or(net, IRBFN_OPT_FWD_F16_QG, (S == 1 && groups > 2048 && groups <= 3072) ? 4 : 8 / S);
+  int QG = opt_or(net, IRBFN_OPT_FWD_F16_QG, gram_default_qg(S, groups));
   if (S * QG > 16) QG = 1;
   *S_out = S; *QG_out = QG;
 }
@@ -430,6 +440,8 @@ static LaunchPlan plan_tick(const irbfn_net* net, int mode, int64_t B, int T, bo
   if (gram_tick && net->opt[IRBFN_OPT_TICK_FUSED] != 0 && tick_narrow_compiled(net, mode, T)) {
     geometry(LK_TICK_K1G, fp.S, fp.QG);
     t.lds = gram_lds_bytes(fp.S, fp.QG, true);
+    // S = 2, QG = 8 (gram_default_qg) is the largest tick: 117 KB.  A tick tile that grew past 160 KB would send the batches above 1024
+    // groups to the K1h tick below without a word; tests/test_gpu_gram_setup.py asserts by name that they run rbf_tick_f16gram.
     if (t.lds <= 160 * 1024) return t;
   }
   if (tick_narrow_k1h(net, fp, mode, T, &t.lds)) {
@@ -571,7 +583,7 @@ static LaunchPlan plan_gram_gamma(const irbfn_net* net, int64_t B, bool tick, in
   const int fs = net->opt[IRBFN_OPT_FWD_F16_S];
   if (fs > 0 && fs <= 7 && S != fs) {
     S = fs;
-    QG = opt_or(net, IRBFN_OPT_FWD_F16_QG, 8 / S > 0 ? 8 / S : 1);
+    QG = opt_or(net, IRBFN_OPT_FWD_F16_QG, gram_default_qg(S, (B + 31) / 32));
     if (S * QG > 16) QG = 1;
   }
   p.lds = gram_lds_bytes(S, QG, tick, true);

@@ -143,9 +143,15 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
     }
   };
 
+#ifdef IRBFN_GRAM_STAMPS
+  unsigned long long t_refill = 0;                           // s_memtime behind the step barrier, 0 in a step without one
+#endif
   auto end_of_step = [&](int i, int b0) {
     if ((i % kGramPer) != kGramPer - 1) return;
     step_barrier();
+#ifdef IRBFN_GRAM_STAMPS
+    t_refill = IRBFN_GRAM_T();
+#endif
 #pragma unroll
     for (int j = 0; j < kGramPer; ++j) {
       int slot = b0 - (kGramPer - 1) + j;                    // slot of chunk i - (kGramPer - 1) + j
@@ -208,10 +214,15 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
         products(t16, ring + b0 * CB, [&](float (&o)[16]) { trans16<BC>(ucur, o); });
       }
       [[maybe_unused]] const unsigned long long t2 = IRBFN_GRAM_T();
+#ifdef IRBFN_GRAM_STAMPS
+      t_refill = 0;
+#endif
       end_of_step(i, b0);
       [[maybe_unused]] const unsigned long long t4 = IRBFN_GRAM_T();
 #ifdef IRBFN_GRAM_STAMPS
-      tph[1] += t2 - t0; tph[2] += t4 - t2; tph[4] += 1;
+      // the refill requests behind the barrier (address arithmetic and one LDS-DMA issue per piece) are stamped on their own
+      const unsigned long long t3 = t_refill != 0 ? t_refill : t4;
+      tph[1] += t2 - t0; tph[2] += t3 - t2; tph[3] += t4 - t3; tph[4] += 1;
 #endif
       b0 = b1;
     };
