@@ -101,7 +101,7 @@ struct irbfn_net {
   int* vjp_flags;           // K2g: ring of 64 hand-over words (rbf_vjp.hip); zero at creation, never reset
   int vjp_gen;              // K2g: generation number of the last VJP call
   float* small_part;            // K1s workspace part[NB][B][OP] (small-batch latency kernel)
-  unsigned int* small_ticket;   // K1s arrival counters [64], zero between launches
+  unsigned int* small_ticket;   // K1s arrival counters [8192], zero between launches
   // raw parameter pointers are NOT kept: set_params copies what it needs
   float* gate_lo;
   float* gate_hi;

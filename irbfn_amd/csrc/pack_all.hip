@@ -70,12 +70,15 @@ __device__ __forceinline__ void records_body(const PackArgs& a, int vb) {
 }
 
 // recm[n] = { c[0..D), scale at [D], zeros to CW, W[k][0..OW) zero padded }; centres n >= N (padding to the MFMA chunk): zeros
+// but for the scale, which is that of sigma = 1 -- a scale of 0 makes r2 * scale NaN for a query with an infinite coordinate, and
+// NaN x (weight 0) is NaN in every output of that query; with a scale that is not 0 phi is 0 there, as for the real centres
 __device__ __forceinline__ void mfma_records_body(const PackArgs& a, int vb) {
   const int n = vb * kPackBlock + threadIdx.x;
   if (n >= a.Npad) return;
   float* r = a.recm + (size_t)n * (a.CW + a.OW);
   if (n >= a.N) {
     for (int j = 0; j < a.CW + a.OW; ++j) r[j] = 0.0f;
+    r[a.D] = a.bclass == BC_GAUSS ? -1.0f : 1.0f;
     return;
   }
   const int k = n % a.K;

@@ -190,7 +190,12 @@ static bool plan_mfma(const irbfn_net* net, int64_t B, LaunchPlan* p) {
   nw = pow2_floor(nw);
   const int chunks = net->Npad / 16;
   while (nw > 1 && chunks / nw < 2) nw /= 2;
-  const size_t lds = mfma_lds_bytes(net, QJ, nw);
+  // the reduction tile [nw][16 QJ][16 NT + 1] grows with nw (NT = 7, 8 at nw = 16: 231 / 264 KB): fewer waves, as plan_qlane does
+  size_t lds = mfma_lds_bytes(net, QJ, nw);
+  while (lds > 160 * 1024 && nw > 1) {
+    nw /= 2;
+    lds = mfma_lds_bytes(net, QJ, nw);
+  }
   if (lds > 160 * 1024) return false;
   const int NT = (net->O + 15) / 16;
   if (NT == 5 || NT == 6) return false;          // compiled for NT = 1..4, 7, 8

@@ -10,7 +10,7 @@
 // operands are float4 loads.  The result leaves the lane D[row = centre 4 g + r][col = query qs], r = 0..3: one query column and
 // four centre rows, so the lane's pair work (distance with the differences kept, one block of four transcendentals, D FMAs of
 // s (x - c)) and its D running sums belong to ONE query, and the final reduction is over the four lane groups and the NW waves,
-// in a fixed order.  The records are K1m's image (recm: centre, scale, padded weight row; centres past N are zero records and
+// in a fixed order.  The records are K1m's image (recm: centre, scale, padded weight row; centres past N have zero weight rows and
 // contribute exactly 0); a wave reads its 16-centre chunks straight from L2 -- 16 B of weights per MFMA, the four centres of a
 // lane group as 16-lane broadcasts -- there is no LDS ring.
 //
