@@ -153,10 +153,16 @@ typedef enum irbfn_fwd_gamma_kernel {
 typedef enum irbfn_vjp_kernel { IRBFN_VJP_AUTO = 0, IRBFN_VJP_K2 = 1, IRBFN_VJP_K2H = 2, IRBFN_VJP_K2R = 3, IRBFN_VJP_K2G = 4,
                                 IRBFN_VJP_K2M = 5 } irbfn_vjp_kernel;
 /* K2: all-float32 VALU; K2H: hbar and dW on the f16 matrix cores; K2R: region-sparse pair lists; K2G: the squared distances (K1g's
- * expansion) and the centre gradients on the matrix cores as well -- automatic from 16384 queries where K1g's expansion fits;
+ * expansion) and the centre gradients on the matrix cores as well -- automatic in front of K2H from 8192 queries and 2.5e7
+ * (query, centre) pairs where K1g's expansion fits;
  * K2M: hbar and dW on the f32 matrix cores (full f32 operands), one region, gaussian / inverse quadratic / inverse multiquadric,
  * padded d in {3, 4, 7, 8}, 16 < O <= 128 -- forced only, IRBFN_VJP_AUTO never selects it.
- * A forced kernel that cannot take the net answers IRBFN_ERR_UNSUPPORTED at the call that would launch it. */
+ * IRBFN_VJP_K2H is a preference: on a net K2H cannot take (several regions, O > 16, a d-dependent basis), below 2048 queries and
+ * with caller-provided region weights the call runs K2 with status IRBFN_OK.  IRBFN_VJP_K2G, IRBFN_VJP_K2R and IRBFN_VJP_K2M are
+ * forces: where the kernel cannot take the net or the batch, the call that would launch it answers IRBFN_ERR_UNSUPPORTED and
+ * irbfn_net_vjp_kernel_supported answers 0.  (Every option but IRBFN_VJP_K2 and IRBFN_VJP_K2M reaches K2H first, so
+ * IRBFN_VJP_K2R refuses only where K2H does not take the call; irbfn_net_vjp_gamma does not look at IRBFN_VJP_K2R.)
+ * The workspace size does not depend on the option. */
 typedef enum irbfn_vjpx_kernel { IRBFN_VJPX_AUTO = 0, IRBFN_VJPX_K5 = 1, IRBFN_VJPX_K5M = 2 } irbfn_vjpx_kernel;
 /* Kernels of irbfn_net_vjp_x.  K5 (rbf_vjpx_qlane): all-float32 VALU, every net the forward's K1 takes.  K5M (rbf_vjpx_mfma):
  * hbar = gout W^T on the f32 matrix cores (full f32 operands); one region, gaussian family / inverse quadratic / inverse

@@ -213,41 +213,39 @@ int64_t irbfn_net_vjp_workspace_bytes(const irbfn_net* net, int64_t B) {
   return vjp_workspace_bytes(net, B);
 }
 
+// the arguments the three parameter-VJP entries share: BAD_ARG before NO_PARAMS before the workspace size, computed once
+static int vjp_args_status(const irbfn_net* net, bool pointers_ok, int64_t B, const void* ws, int64_t ws_bytes) {
+  if (!net || B < 0 || !pointers_ok) return IRBFN_ERR_BAD_ARG;
+  if (!net->has_params) return IRBFN_ERR_NO_PARAMS;
+  const int64_t need = vjp_workspace_bytes(net, B);
+  return ws_bytes < need || (!ws && need > 0) ? IRBFN_ERR_BAD_ARG : IRBFN_OK;
+}
+
 int irbfn_net_vjp(irbfn_net* net, const float* x_dev, const float* gout_dev, float* g_centers_dev,
                   float* g_log_sigs_dev, float* g_kernel_dev, float* g_bias_dev, int64_t B,
                   void* workspace_dev, int64_t workspace_bytes, void* stream) {
-  if (!net || B < 0 || !g_centers_dev || !g_log_sigs_dev || !g_kernel_dev || !g_bias_dev)
-    return IRBFN_ERR_BAD_ARG;
-  if (B > 0 && (!x_dev || !gout_dev)) return IRBFN_ERR_BAD_ARG;
-  if (!net->has_params) return IRBFN_ERR_NO_PARAMS;
-  if (workspace_bytes < vjp_workspace_bytes(net, B) || (!workspace_dev && vjp_workspace_bytes(net, B) > 0))
-    return IRBFN_ERR_BAD_ARG;
-  return launch_vjp(net, x_dev, gout_dev, g_centers_dev, g_log_sigs_dev, g_kernel_dev, g_bias_dev, B,
-                    workspace_dev, workspace_bytes, as_stream(stream));
+  const bool ok = g_centers_dev && g_log_sigs_dev && g_kernel_dev && g_bias_dev && (B <= 0 || (x_dev && gout_dev));
+  if (const int rc = vjp_args_status(net, ok, B, workspace_dev, workspace_bytes); rc != IRBFN_OK) return rc;
+  return launch_vjp(net, x_dev, gout_dev, g_centers_dev, g_log_sigs_dev, g_kernel_dev, g_bias_dev, B, workspace_dev,
+                    as_stream(stream), nullptr, false);
 }
 
 int irbfn_net_vjp_frozen(irbfn_net* net, const float* x_dev, const float* gout_dev, float* g_centers_dev,
                          float* g_log_sigs_dev, float* g_kernel_dev, float* g_bias_dev, int64_t B,
                          void* workspace_dev, int64_t workspace_bytes, void* stream) {
-  if (!net || B < 0 || !g_kernel_dev || !g_bias_dev) return IRBFN_ERR_BAD_ARG;
-  if (B > 0 && (!x_dev || !gout_dev)) return IRBFN_ERR_BAD_ARG;
-  if (!net->has_params) return IRBFN_ERR_NO_PARAMS;
-  if (workspace_bytes < vjp_workspace_bytes(net, B) || (!workspace_dev && vjp_workspace_bytes(net, B) > 0))
-    return IRBFN_ERR_BAD_ARG;
-  return launch_vjp_frozen(net, x_dev, gout_dev, g_centers_dev, g_log_sigs_dev, g_kernel_dev, g_bias_dev, B, workspace_dev,
-                           workspace_bytes, as_stream(stream));
+  const bool ok = g_kernel_dev && g_bias_dev && (B <= 0 || (x_dev && gout_dev));
+  if (const int rc = vjp_args_status(net, ok, B, workspace_dev, workspace_bytes); rc != IRBFN_OK) return rc;
+  return launch_vjp(net, x_dev, gout_dev, g_centers_dev, g_log_sigs_dev, g_kernel_dev, g_bias_dev, B, workspace_dev,
+                    as_stream(stream), nullptr, true);
 }
 
 int irbfn_net_vjp_gamma(irbfn_net* net, const float* x_dev, const float* gamma_dev, const float* gout_dev,
                         float* g_centers_dev, float* g_log_sigs_dev, float* g_kernel_dev, float* g_bias_dev, float* dgamma_dev,
                         int64_t B, void* workspace_dev, int64_t workspace_bytes, void* stream) {
-  if (!net || B < 0 || !g_centers_dev || !g_log_sigs_dev || !g_kernel_dev || !g_bias_dev) return IRBFN_ERR_BAD_ARG;
-  if (B > 0 && (!x_dev || !gout_dev || !gamma_dev)) return IRBFN_ERR_BAD_ARG;
-  if (!net->has_params) return IRBFN_ERR_NO_PARAMS;
-  if (workspace_bytes < vjp_workspace_bytes(net, B) || (!workspace_dev && vjp_workspace_bytes(net, B) > 0))
-    return IRBFN_ERR_BAD_ARG;
+  const bool ok = g_centers_dev && g_log_sigs_dev && g_kernel_dev && g_bias_dev && (B <= 0 || (x_dev && gout_dev && gamma_dev));
+  if (const int rc = vjp_args_status(net, ok, B, workspace_dev, workspace_bytes); rc != IRBFN_OK) return rc;
   int rc = launch_vjp(net, x_dev, gout_dev, g_centers_dev, g_log_sigs_dev, g_kernel_dev, g_bias_dev, B, workspace_dev,
-                      workspace_bytes, as_stream(stream), B > 0 ? gamma_dev : nullptr);
+                      as_stream(stream), B > 0 ? gamma_dev : nullptr, false);
   if (rc == IRBFN_OK && dgamma_dev) rc = launch_dgamma(net, x_dev, gout_dev, dgamma_dev, B, as_stream(stream));
   return rc;
 }

@@ -125,8 +125,8 @@ struct irbfn_net {
 };
 
 namespace irbfn {
-// The kernel a forward or planning tick runs and its launch geometry, decided in one place (plan_forward / plan_tick,
-// rbf_forward.hip); the launchers take the plan as it is.  record_launch writes irbfn_net_last_launch's name from it.
+// The kernel a forward, planning tick or parameter VJP runs and its launch geometry, decided in one place (plan_forward /
+// plan_tick, rbf_forward.hip; plan_vjp, rbf_vjp.hip); the launchers take the plan as it is.  record_launch writes irbfn_net_last_launch's name from it.
 enum LaunchKind : int {
   LK_NONE = 0,       // nothing runs: `status` says why
   LK_K1S,            // rbf_fwd_clane: small batches
@@ -141,11 +141,13 @@ enum LaunchKind : int {
   LK_TICK_K1H,       // rbf_tick_f16mfma
   LK_TICK_K1G_WIDE,  // rbf_tick_f16gram_wide
   LK_TICK_K1H_WIDE,  // rbf_tick_f16mfma_wide
-  LK_K2G,            // rbf_vjp_f16gram (the VJP plan, rbf_vjp.hip, launches it; named here with the others)
+  LK_K2G,            // rbf_vjp_f16gram, K2h behind it (plan_vjp, rbf_vjp.hip, chooses the VJP's kind; `mode`: the live leaves)
   LK_K2,             // rbf_vjp_kernel (`gated`: region weights per lane)
   LK_K2M,            // rbf_vjp_mfma (rbf_vjp_mfma.hip; Q: padded width OW, nw: centre tiles per wave, S: query slabs)
   LK_K1G_GAMMA,      // rbf_fwd_f16gram_gamma (caller-provided region weights)
-  LK_TICK_K1G_GAMMA  // rbf_tick_f16gram_gamma
+  LK_TICK_K1G_GAMMA, // rbf_tick_f16gram_gamma
+  LK_K2H,            // rbf_vjp_f16mfma and
+  LK_K2R             // rbf_vjp_sparse: record_launch gives neither a name, the previous launch's stands
 };
 
 struct F16Geom {           // K1h's block geometry where the dispatch reached K1h (forced AUTO / K1H, its image, B >= 65)
@@ -228,12 +230,10 @@ void small_geometry(const irbfn_net* net, int64_t B, LaunchPlan* p);
 int launch_forward_small(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s);
 int launch_gate(irbfn_net* net, const float* x, float* gamma, int64_t B, hipStream_t s);
 int64_t vjp_workspace_bytes(const irbfn_net* net, int64_t B);
-int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs,
-               float* g_kernel, float* g_bias, int64_t B, void* ws, int64_t ws_bytes, hipStream_t s,
-               const float* gamma_ext = nullptr);
-// irbfn_net_vjp_frozen: a null g_centers / g_log_sigs is a frozen leaf, neither computed (where K2g takes the net) nor written
-int launch_vjp_frozen(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs, float* g_kernel,
-                      float* g_bias, int64_t B, void* ws, int64_t ws_bytes, hipStream_t s);
+// the parameter VJP.  gamma_ext: caller-provided region weights (irbfn_net_vjp_gamma), else null.  frozen: irbfn_net_vjp_frozen -- a null
+// g_centers / g_log_sigs is a frozen leaf, neither computed (where K2g takes the net) nor written
+int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs, float* g_kernel,
+               float* g_bias, int64_t B, void* ws, hipStream_t s, const float* gamma_ext, bool frozen);
 // K2m (rbf_vjp_mfma.hip): one region, fast basis, padded d in {3, 4, 7, 8}, 16 < O <= 128
 bool vjpm_eligible(const irbfn_net* net);
 size_t vjpm_qrec_bytes(const irbfn_net* net, int64_t B);

@@ -417,41 +417,28 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-struct VjpPlan {
-  int groups, QSB, per_wave, Npad, V, bias_blocks;
+struct VjpLayout {
+  int groups, Npad, V, QS, bias_blocks;
   long rows_per_block;
+  int QSB;         // dense slabs [QSB][V][Npad] allocated at off_part: K2 runs with all of them, K2h / K2g / K2m with at most as many
+  int SL;          // K2r: slices per region = its own slabs [SL][V][Npad] at off_sp_part (0 where K2r cannot take the net)
   size_t off_gamma, off_part, off_bias, off_qrec, off_qblk, off_misc, total;
-  int QS;
-  bool use_h;      // K2h (matrix-core VJP) instead of K2
-  bool use_g;      // K2g (u and the centre gradients on the matrix cores too) in front of K2h
-  bool use_sp;     // K2r (region-sparse VJP, rbf_sparse.hip) instead of K2
-  bool use_m;      // K2m (hbar and dW on the f32 matrix cores, rbf_vjp_mfma.hip): forced only, never automatic
-  int SL;          // K2r: slices per region (<= QSB slabs are allocated)
-  size_t off_sp, off_sp_part;   // K2r: pair lists, slabs
-  size_t off_qm;                // K2m: its query records
-  int status;      // IRBFN_OK, or why nothing runs (a forced kernel that cannot take the net, LDS)
+  size_t off_sp, off_sp_part, off_qm;   // K2r: pair lists, slabs; K2m: its query records
 };
 
-// The VJP's kernel, its slab count and its workspace layout.  The layout depends on the net and B alone
-// (irbfn_net_vjp_workspace_bytes); gamma_ext: caller-provided region weights (ClusterWCRBFNet).
-// vg_mode: K2g's live-leaf mode (irbfn_net_vjp_frozen; 0 = all leaves): its waves per SIMD set the resident block count
-static VjpPlan make_plan(const irbfn_net* net, int64_t B, const float* gamma_ext = nullptr, int vg_mode = 0) {
-  VjpPlan p;
+// The VJP's workspace (irbfn_net_vjp_workspace_bytes): every kernel the net is eligible for has its part, whichever runs, so the
+// layout reads the net and B > 0 alone -- no option, no region weights, no leaf mode.
+static VjpLayout vjp_layout(const irbfn_net* net, int64_t B) {
+  VjpLayout p;
   p.groups = (net->N + kWave - 1) / kWave;
   p.Npad = p.groups * kWave;
   p.V = net->DC + 1 + net->OP;
   long qsb = (8192 + (long)p.groups * 4 - 1) / ((long)p.groups * 4);
   long max_qsb = (B + 4 * 64 - 1) / (4 * 64);       // >= 64 queries per wave
-  if (max_qsb < 1) max_qsb = 1;
   if (qsb > max_qsb) qsb = max_qsb;
-  if (qsb < 1) qsb = 1;
   if (qsb > 4096) qsb = 4096;
   p.QSB = (int)qsb;
-  const long slices = qsb * 4;
-  p.per_wave = (int)((B + slices - 1) / slices);
-  if (p.per_wave < 1) p.per_wave = 1;
   p.bias_blocks = (int)(B < 256 * 64 ? (B + 63) / 64 : 256);
-  if (p.bias_blocks < 1) p.bias_blocks = 1;
   p.rows_per_block = (B + p.bias_blocks - 1) / p.bias_blocks;
   auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   size_t off = 0;
@@ -460,76 +447,102 @@ static VjpPlan make_plan(const irbfn_net* net, int64_t B, const float* gamma_ext
   p.off_bias = off;  off += al((size_t)p.bias_blocks * net->O * sizeof(float));
   p.QS = (net->DC + 1 + net->OP + 3) & ~3;
   p.off_qrec = off;  off += al((size_t)B * p.QS * sizeof(float));
-  // K2h: packed 32-query blocks + (absmax, scales); IRBFN_OPT_VJP_KERNEL = IRBFN_VJP_K2 / IRBFN_VJP_K2H forces one
-  const int vk = net->opt[IRBFN_OPT_VJP_KERNEL];
-  p.use_h = vjph_eligible(net) && vk != IRBFN_VJP_K2 && B >= 2048;
+  // K2h / K2g: packed 32-query blocks + (absmax, scales)
   const size_t blkb = vjph_block_bytes(net) > vjpg_block_bytes() ? vjph_block_bytes(net) : vjpg_block_bytes();
   p.off_qblk = off;  off += al(vjph_eligible(net) ? (size_t)((B + 31) / 32) * blkb : 0);
-  // K2g in front of K2h from 8192 queries and 2.5e7 (query, centre) pairs (tools/sweep_vjp_batch.py: 4096 centres: K2g 57.6 vs K2h 64.3 us at
-  // B = 12288, a tie at 8192; 1000 centres: 50.1 vs 52.1 at 24576, 46.3 vs 45.0 at 16384)
-  p.use_g = p.use_h && vjpg_eligible(net) && (vk == IRBFN_VJP_K2G || (vk == IRBFN_VJP_AUTO && B >= 8192 && (long long)B * net->N >= 25000000LL));
   p.off_misc = off;  off += al((size_t)(p.bias_blocks + 8) * sizeof(float));
-  // K2r: several regions with a sparse gate (automatic where the forward takes K1r; IRBFN_VJP_K2R forces it where eligible)
-  p.use_sp = sparse_vjp_eligible(net) && (vk == IRBFN_VJP_K2R || (vk == IRBFN_VJP_AUTO && sparse_preferred(net, B)));
   p.SL = 0;
-  p.off_sp = off;
-  p.off_sp_part = off;
+  p.off_sp = p.off_sp_part = off;
   if (sparse_vjp_eligible(net)) {
     off += al(sparse_vjp_workspace_bytes(net, B));
     p.SL = sparse_vjp_slices(net, B);
-    p.off_sp_part = off;                          // K2r's own slabs [SL][V][Npad]
+    p.off_sp_part = off;
     off += al((size_t)p.SL * p.V * p.Npad * sizeof(float));
-  }
-  if (p.use_g) {
-    // K2g: a block = 4 waves = 128 centres; slices so that the launch is ONE resident round (3 or 4 waves per SIMD: 768 / 1024 blocks), at
-    // least 8 query blocks each (profiles/r03_vjp_qsb_sweep.txt: config 3 198 -> 195 us, the reference's 1000-centre net at
-    // B = 80000 107 -> 101 us against 1024 blocks)
-    const long nqb = (B + 31) / 32;
-    const long gb = ((net->N + 31) / 32 + 3) / 4;
-    // rbf_vjp_gram.hip: 4 waves per SIMD where hbar is one MFMA (O <= 10), else 3 (the frozen-leaf modes: more, vjpg_waves)
-    const long resident = vg_mode == 0 ? (net->O <= 10 ? 1024 : 768) : 256L * vjpg_waves(vg_mode, net->O);
-    long q2 = (resident + gb - 1) / gb;
-    if (q2 > 64) q2 = 64;                                  // small nets: the slab reduce grows with the slices (N = 1000, B = 80000: 64 slices 84 us, 96: 91)
-    if (q2 * 8 > nqb) q2 = (nqb + 7) / 8;
-    if (q2 < 1) q2 = 1;
-    if (q2 < p.QSB) p.QSB = (int)q2;          // never more slabs than were allocated above
-  } else if (p.use_h) {
-    // fewer, longer query slices than K2 (3 waves per SIMD resident): halves the slab traffic of the reduce kernel
-    const long gh = (net->N + 31) / 32;                    // blocks of 4 waves x 2 tiles of 16 centres
-    long q2 = (6144 + gh * 4 - 1) / (gh * 4);
-    const long nqb = (B + 31) / 32;
-    if (q2 * 4 > nqb) q2 = (nqb + 3) / 4;
-    if (q2 < 1) q2 = 1;
-    if (q2 < p.QSB) p.QSB = (int)q2;          // never more slabs than were allocated above
   }
   p.off_qm = off;
   if (vjpm_eligible(net)) off += al(vjpm_qrec_bytes(net, B));
   p.total = off;
-  // the kernel
-  p.status = IRBFN_OK;
-  p.use_m = false;
-  if (vk == IRBFN_VJP_K2M) {                    // IRBFN_VJP_AUTO never takes K2m: every net keeps the kernel (and the bits) it had
-    p.use_h = p.use_g = p.use_sp = false;
-    p.use_m = vjpm_eligible(net) && gamma_ext == nullptr;
-    if (!p.use_m) p.status = IRBFN_ERR_UNSUPPORTED;
-    else p.QSB = vjpm_slices(net, B, p.QSB);    // never more slabs than were allocated above
+  return p;
+}
+
+// LDS of the gate tables that K2's query packing (vjp_pack_queries_kernel) stages
+static size_t gate_tables_lds(const irbfn_net* net) {
+  return ((size_t)net->nsplit * net->max_ranges * kWave + (size_t)net->n_ranges * net->nsplit) * sizeof(float);
+}
+
+// K2g's query slices.  A block = 4 waves = 128 centres; slices so that the launch is ONE resident round (3 or 4 waves per SIMD: 768 /
+// 1024 blocks), at least 8 query blocks each (profiles/r03_vjp_qsb_sweep.txt: config 3 198 -> 195 us, the reference's 1000-centre
+// net at B = 80000 107 -> 101 us against 1024 blocks)
+static long vjpg_slices(const irbfn_net* net, int64_t B, int vg_mode, long blocks) {
+  // rbf_vjp_gram.hip: 4 waves per SIMD where hbar is one MFMA (O <= 10), else 3 (the frozen-leaf modes: more, vjpg_waves)
+  const long resident = vg_mode == 0 ? (net->O <= 10 ? 1024 : 768) : 256L * vjpg_waves(vg_mode, net->O);
+  const long nqb = (B + 31) / 32;
+  long q = (resident + blocks - 1) / blocks;
+  if (q > 64) q = 64;                                  // small nets: the slab reduce grows with the slices (N = 1000, B = 80000: 64 slices 84 us, 96: 91)
+  if (q * 8 > nqb) q = (nqb + 7) / 8;
+  return q < 1 ? 1 : q;
+}
+
+// K2h's: fewer, longer query slices than K2 (3 waves per SIMD resident), which halves the slab traffic of the reduce kernel
+static long vjph_slices(int64_t B, long blocks) {
+  const long nqb = (B + 31) / 32;
+  long q = (6144 + blocks * 4 - 1) / (blocks * 4);
+  if (q * 4 > nqb) q = (nqb + 3) / 4;
+  return q < 1 ? 1 : q;
+}
+
+// The VJP's kernel for B > 0 queries, decided here and nowhere else; written as plan_forward (rbf_forward.hip) is: the forced-only
+// kernel first, then the automatic order, which the other options cut short.  `forced`: IRBFN_OPT_VJP_KERNEL, or the kernel
+// irbfn_net_vjp_kernel_supported asks about.  gamma_ext: caller-provided region weights (irbfn_net_vjp_gamma); only the gated K2
+// takes them.  vg_mode: the live leaves of an irbfn_net_vjp_frozen call (0: all), which K2g alone looks at.
+// Returns kind + status (a plan without a kernel says IRBFN_ERR_UNSUPPORTED), p.S = the slabs the kernel runs with -- at most the
+// layout's -- and what record_launch names (K2h and K2r have no name: the previous one stands).
+static LaunchPlan plan_vjp(const irbfn_net* net, int64_t B, int forced, bool gamma_ext, int vg_mode, const VjpLayout& L) {
+  LaunchPlan p;
+  p.block = 256;
+  auto take = [&](int kind, long slabs, long groups) {
+    p.kind = kind; p.status = IRBFN_OK;
+    p.S = (int)(slabs < L.QSB ? slabs : L.QSB);       // never more slabs than the layout allocated
+    p.grid = (int)(groups * p.S);
+  };
+  // K2m: forced only -- IRBFN_VJP_AUTO never takes it, so every net keeps the kernel (and the bits) it had
+  if (forced == IRBFN_VJP_K2M) {
+    if (!vjpm_eligible(net) || gamma_ext) return p;
+    take(LK_K2M, vjpm_slices(net, B, L.QSB), vjpm_groups(net));
+    vjpm_names(net, &p.Q, &p.nw);
     return p;
   }
-  if (gamma_ext) p.use_h = false;                // the gated K2 (with the slab count chosen above)
-  if (vk == IRBFN_VJP_K2G && !(p.use_h && p.use_g)) p.status = IRBFN_ERR_UNSUPPORTED;   // a forced kernel that cannot take the net
-  if (p.use_h && vjph_lds_bytes(net) > 64 * 1024) p.status = IRBFN_ERR_UNSUPPORTED;
-  if (p.use_h) return p;
-  if (gamma_ext) {
-    p.use_sp = false;
-  } else if (p.use_sp && !sparse_vjp_lds_fits(net)) {
-    p.use_sp = false;                            // K2r's pair tables do not fit: K2, unless K2r was forced
-    if (vk == IRBFN_VJP_K2R) p.status = IRBFN_ERR_UNSUPPORTED;
-  } else if (!p.use_sp && vk == IRBFN_VJP_K2R) {
-    p.status = IRBFN_ERR_UNSUPPORTED;            // a forced kernel that cannot take the net
+  // K2h: every option but K2 reaches it, IRBFN_VJP_K2R included -- so IRBFN_VJP_K2H is a preference (below 2048 queries, or on a
+  // net K2h cannot take, the call goes on to K2), and a forced K2r refuses only where K2h does not take the call
+  if (vjph_eligible(net) && forced != IRBFN_VJP_K2 && B >= 2048 && !gamma_ext) {
+    // K2g in front of K2h from 8192 queries and 2.5e7 (query, centre) pairs (tools/sweep_vjp_batch.py: 4096 centres: K2g 57.6 vs
+    // K2h 64.3 us at B = 12288, a tie at 8192; 1000 centres: 50.1 vs 52.1 at 24576, 46.3 vs 45.0 at 16384)
+    const bool gram = vjpg_eligible(net) &&
+                      (forced == IRBFN_VJP_K2G || (forced == IRBFN_VJP_AUTO && B >= 8192 && (long long)B * net->N >= 25000000LL));
+    if (forced == IRBFN_VJP_K2G && !gram) return p;
+    if (vjph_lds_bytes(net) > 64 * 1024) return p;
+    const long gh = (net->N + 31) / 32, gb = (gh + 3) / 4;      // K2h: blocks of 4 waves x 2 tiles of 16 centres; K2g: 128 centres
+    if (gram) take(LK_K2G, vjpg_slices(net, B, vg_mode, gb), gb);
+    else take(LK_K2H, vjph_slices(B, gh), gh);
+    p.mode = vg_mode;
+    return p;
   }
-  if (p.use_sp) return p;
-  const size_t glds = ((size_t)net->nsplit * net->max_ranges * kWave + (size_t)net->gate().n_ranges * net->nsplit) * sizeof(float);
-  if (glds > 64 * 1024) p.status = IRBFN_ERR_UNSUPPORTED;     // K2's query packing: the gate tables
+  if (forced == IRBFN_VJP_K2G) return p;
+  // K2r: several regions with a sparse gate (automatic where the forward takes K1r).  Where its pair tables do not fit, K2 runs
+  // instead, unless K2r was forced.  With caller-provided region weights the option is not looked at.
+  if (!gamma_ext) {
+    const bool sparse = sparse_vjp_eligible(net) && (forced == IRBFN_VJP_K2R || (forced == IRBFN_VJP_AUTO && sparse_preferred(net, B)));
+    if (sparse && sparse_vjp_lds_fits(net)) {
+      p.kind = LK_K2R; p.status = IRBFN_OK; p.S = L.SL;
+      return p;
+    }
+    if (forced == IRBFN_VJP_K2R) return p;
+  }
+  // K2: every net; gated where the region weights differ between the lanes of a wave
+  p.lds = gate_tables_lds(net);
+  if (p.lds > 64 * 1024) return p;
+  take(LK_K2, L.QSB, L.groups);
+  p.gated = net->R > 1 || gamma_ext;
   return p;
 }
 
@@ -779,15 +792,11 @@ int launch_softmax_xent(const float* logits, const float* labels, float* glogits
 }
 
 int vjp_kernel_supported(const irbfn_net* net, int kernel, int64_t B) {
-  irbfn_net probe = *net;                        // the plan reads the option from the descriptor: ask a copy
-  probe.opt[IRBFN_OPT_VJP_KERNEL] = kernel;
-  return make_plan(&probe, B > 0 ? B : 1).status == IRBFN_OK ? 1 : 0;
+  if (B < 1) B = 1;
+  return plan_vjp(net, B, kernel, false, 0, vjp_layout(net, B)).status == IRBFN_OK ? 1 : 0;
 }
 
-int64_t vjp_workspace_bytes(const irbfn_net* net, int64_t B) {
-  if (B <= 0) return 0;
-  return (int64_t)make_plan(net, B).total;
-}
+int64_t vjp_workspace_bytes(const irbfn_net* net, int64_t B) { return B <= 0 ? 0 : (int64_t)vjp_layout(net, B).total; }
 
 template <int D, int OP>
 static int launch_vjp_bc(const VjpArgs& a, int bc, bool gated, dim3 grid, hipStream_t s) {
@@ -829,138 +838,130 @@ static int launch_vjp_d(const VjpArgs& a, int OP, int bc, bool gated, dim3 grid,
   }
 }
 
-// frozen: irbfn_net_vjp_frozen -- a null g_centers / g_log_sigs is neither written nor, where K2g takes the net, computed
-static int vjp_impl(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs,
-                    float* g_kernel, float* g_bias, int64_t B, void* ws, hipStream_t s, const float* gamma_ext, bool frozen) {
-  const long n_c = (long)net->N * net->D, n_l = net->N, n_k = (long)net->K * net->O;
+// One parameter-VJP call as its launch sequences see it
+struct VjpCall {
+  irbfn_net* net;
+  const float *x, *gout, *gamma_ext;
+  float *g_centers, *g_log_sigs, *g_kernel, *g_bias;   // a null g_centers / g_log_sigs: a frozen leaf (irbfn_net_vjp_frozen)
+  int64_t B;
+  char* ws;
+  hipStream_t s;
+  int red_mode;                                  // launch_vjp_reduce: -1 the all-live kernel, 0 the live-leaf kernel of every frozen call
+  template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }
+};
+
+// the bias column sums per block; bmax: the block maxima of |g| as well (K2h / K2g pack g to f16 with them)
+static int bias_partials(const VjpCall& c, const VjpLayout& L, float* bmax) {
+  hipLaunchKernelGGL(colsum_partial_kernel, dim3(L.bias_blocks), dim3(256), 256 * sizeof(float), c.s, c.gout, c.at<float>(L.off_bias),
+                     (long)c.B, c.net->O, L.rows_per_block, bmax);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
+
+static int slab_reduce(const VjpCall& c, const VjpLayout& L, float* slabs, int slices, int mode, const int* flag = nullptr, int gen = 0) {
+  return launch_vjp_reduce(c.net, slabs, c.g_centers, c.g_log_sigs, c.g_kernel, slices, L.V, L.Npad, c.s, c.at<float>(L.off_bias), c.g_bias,
+                           L.bias_blocks, mode, flag, gen);
+}
+
+// the tail of K2m, K2r and K2: the bias column sums (no block maxima: nobody packs g to f16 there), then the slab reduce
+static int bias_and_reduce(const VjpCall& c, const VjpLayout& L, float* slabs, int slices) {
+  const int rc = bias_partials(c, L, nullptr);
+  return rc != IRBFN_OK ? rc : slab_reduce(c, L, slabs, slices, c.red_mode);
+}
+
+// K2h, or K2g with K2h behind it
+static int launch_vjp_k2h(const VjpCall& c, const VjpLayout& L, const LaunchPlan& p) {
+  irbfn_net* net = c.net;
+  float* part = c.at<float>(L.off_part);
+  unsigned char* qblk = c.at<unsigned char>(L.off_qblk);
+  float* bmax = c.at<float>(L.off_misc);         // [bias_blocks] max |g| per block
+  float* scales = bmax + L.bias_blocks;          // [2]
+  int rc = bias_partials(c, L, bmax);
+  if (rc != IRBFN_OK) return rc;
+  const bool gram = p.kind == LK_K2G, live = gram && p.mode != 0;      // live: slabs of the live rows only (they fit in the full-row slabs)
+  const int* run_if = nullptr;
+  int run_gen = 0;
+  if (gram) {
+    // K2g first; a query outside its representable box raises the flag, K2g returns at once and K2h -- launched behind it
+    // with the complementary test -- does the work
+    // The flag is a generation number in a small ring of net-owned words (zero at creation): call `gen` stores gen into word
+    // gen % 64 when it has such a query, nobody resets anything -- a memset per call was a launch of its own.
+    if (++net->vjp_gen <= 0) net->vjp_gen = 1;
+    run_gen = net->vjp_gen;
+    int* flag = net->vjp_flags + (run_gen & 63);
+    record_launch(net, p);
+    rc = live ? launch_vjp_gram_live(net, p.mode, c.x, c.gout, c.B, qblk, bmax, L.bias_blocks, scales, flag, run_gen, part, p.S, L.Npad, c.s)
+              : launch_vjp_gram(net, c.x, c.gout, c.B, qblk, bmax, L.bias_blocks, scales, flag, run_gen, part, p.S, L.Npad, c.s);
+    if (rc != IRBFN_OK) return rc;
+    run_if = flag;
+  }
+  rc = launch_vjp_f16(net, c.x, c.gout, c.B, qblk, bmax, L.bias_blocks, scales, part, p.S, L.Npad, c.s, run_if, run_gen);
+  if (rc != IRBFN_OK) return rc;
+  // live: which of K2g and K2h wrote the slabs is known on the device only: the flag
+  return live ? slab_reduce(c, L, part, p.S, p.mode, run_if, run_gen) : slab_reduce(c, L, part, p.S, c.red_mode);
+}
+
+static int launch_vjp_k2m(const VjpCall& c, const VjpLayout& L, const LaunchPlan& p) {
+  float* part = c.at<float>(L.off_part);
+  record_launch(c.net, p);
+  const int rc = launch_vjp_mfma(c.net, c.x, c.gout, c.B, c.at<float>(L.off_qm), part, p.S, L.Npad, c.s);
+  return rc != IRBFN_OK ? rc : bias_and_reduce(c, L, part, p.S);
+}
+
+// K2r: pair lists per region -> one wave per (region, slice) -> the same fixed-order slab reduce; no query packing
+static int launch_vjp_k2r(const VjpCall& c, const VjpLayout& L, const LaunchPlan& p) {
+  float* part = c.at<float>(L.off_sp_part);
+  const int rc = launch_vjp_sparse(c.net, c.x, c.gout, c.B, c.ws + L.off_sp, part, p.S, L.Npad, c.s);
+  return rc != IRBFN_OK ? rc : bias_and_reduce(c, L, part, p.S);
+}
+
+static int launch_vjp_k2(const VjpCall& c, const VjpLayout& L, const LaunchPlan& p) {
+  irbfn_net* net = c.net;
+  float *qrec = c.at<float>(L.off_qrec), *gamma = c.at<float>(L.off_gamma), *part = c.at<float>(L.off_part);
+  hipLaunchKernelGGL(vjp_pack_queries_kernel, dim3((unsigned)((c.B + kWave - 1) / kWave)), dim3(256), p.lds, c.s, c.x, c.gout, qrec, gamma,
+                     net->gate(), (long)c.B, net->D, net->DC, net->O, net->OP, L.QS, net->R);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  VjpArgs a;
+  a.qrec = qrec; a.gamma = c.gamma_ext ? c.gamma_ext : gamma; a.rec = net->rec; a.sig2 = net->sig2; a.part = part;
+  a.B = (long)c.B; a.Dreal = net->D; a.O = net->O; a.N = net->N; a.K = net->K; a.R = net->R; a.S = net->S;
+  a.basis = net->basis; a.Npad = L.Npad; a.gscale = gauss_scale(net->basis);
+  a.per_wave = (int)((c.B + p.S * 4L - 1) / (p.S * 4L));      // four waves per slab, each its share of the queries
+  const dim3 grid(L.groups, p.S);
+  record_launch(net, p);
+  int rc;
+  switch (net->DC) {
+    case 3: rc = launch_vjp_d<3>(a, net->OP, net->bclass, p.gated, grid, c.s); break;
+    case 4: rc = launch_vjp_d<4>(a, net->OP, net->bclass, p.gated, grid, c.s); break;
+    case 7: rc = launch_vjp_d<7>(a, net->OP, net->bclass, p.gated, grid, c.s); break;
+    case 8: rc = launch_vjp_d<8>(a, net->OP, net->bclass, p.gated, grid, c.s); break;
+    default: rc = IRBFN_ERR_UNSUPPORTED;
+  }
+  return rc != IRBFN_OK ? rc : bias_and_reduce(c, L, part, p.S);
+}
+
+int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs, float* g_kernel,
+               float* g_bias, int64_t B, void* ws, hipStream_t s, const float* gamma_ext, bool frozen) {
   if (B == 0) {
-    if (g_centers) IRBFN_HIP_CHECK(hipMemsetAsync(g_centers, 0, n_c * sizeof(float), s));
-    if (g_log_sigs) IRBFN_HIP_CHECK(hipMemsetAsync(g_log_sigs, 0, n_l * sizeof(float), s));
-    IRBFN_HIP_CHECK(hipMemsetAsync(g_kernel, 0, n_k * sizeof(float), s));
+    if (g_centers) IRBFN_HIP_CHECK(hipMemsetAsync(g_centers, 0, (size_t)net->N * net->D * sizeof(float), s));
+    if (g_log_sigs) IRBFN_HIP_CHECK(hipMemsetAsync(g_log_sigs, 0, (size_t)net->N * sizeof(float), s));
+    IRBFN_HIP_CHECK(hipMemsetAsync(g_kernel, 0, (size_t)net->K * net->O * sizeof(float), s));
     IRBFN_HIP_CHECK(hipMemsetAsync(g_bias, 0, (size_t)net->O * sizeof(float), s));
     return IRBFN_OK;
   }
   // K2g's mode: the centres frozen -> NO_CENTRES, the widths too -> LINEAR; live centres with frozen widths take the full
   // computation (no upstream layer class freezes the widths alone)
-  const int vg_mode = g_centers ? 0 : (g_log_sigs ? 1 : 2);
-  const int red_mode = frozen ? 0 : -1;          // reduce: the live-leaf kernel for every frozen call
-  const VjpPlan p = make_plan(net, B, gamma_ext, frozen ? vg_mode : 0);
-  if (p.status != IRBFN_OK) return p.status;
-  char* base = static_cast<char*>(ws);
-  float* gamma = reinterpret_cast<float*>(base + p.off_gamma);
-  float* part = reinterpret_cast<float*>(base + p.off_part);
-  float* bpart = reinterpret_cast<float*>(base + p.off_bias);
-  // the tail of K2m, K2r and K2: the bias column sums (no block maxima: nobody packs g to f16 there), then the slab reduce
-  auto bias_and_reduce = [&](float* slabs, int slices) -> int {
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(p.bias_blocks), dim3(256), 256 * sizeof(float), s, gout, bpart,
-                       (long)B, net->O, p.rows_per_block, (float*)nullptr);
-    IRBFN_HIP_CHECK(hipGetLastError());
-    return launch_vjp_reduce(net, slabs, g_centers, g_log_sigs, g_kernel, slices, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, red_mode);
-  };
-  if (p.use_h) {
-    float* bmax = reinterpret_cast<float*>(base + p.off_misc);           // [bias_blocks] max |g| per block
-    float* scales = bmax + p.bias_blocks;                                // [2]
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(p.bias_blocks), dim3(256), 256 * sizeof(float), s, gout, bpart,
-                       (long)B, net->O, p.rows_per_block, bmax);
-    IRBFN_HIP_CHECK(hipGetLastError());
-    int rch;
-    const int* run_if = nullptr;
-    int run_gen = 0;
-    if (p.use_g) {
-      // K2g first; a query outside its representable box raises the flag, K2g returns at once and K2h -- launched behind it
-      // with the complementary test -- does the work
-      // The flag is a generation number in a small ring of net-owned words (zero at creation): call `gen` stores gen into word
-      // gen % 64 when it has such a query, nobody resets anything -- a memset per call was a launch of its own.
-      if (++net->vjp_gen <= 0) net->vjp_gen = 1;
-      run_gen = net->vjp_gen;
-      int* flag = net->vjp_flags + (run_gen & 63);
-      LaunchPlan k;
-      k.kind = LK_K2G; k.S = p.QSB;
-      k.grid = (int)((((net->N + 31) / 32 + 3) / 4) * p.QSB); k.block = 256;
-      if (frozen && vg_mode != 0) k.mode = vg_mode;
-      record_launch(net, k);
-      if (frozen && vg_mode != 0) {
-        // slabs of the live rows only (they fit in the full-row slabs of the plan)
-        rch = launch_vjp_gram_live(net, vg_mode, x, gout, B, reinterpret_cast<unsigned char*>(base + p.off_qblk), bmax, p.bias_blocks,
-                                   scales, flag, run_gen, part, p.QSB, p.Npad, s);
-      } else {
-        rch = launch_vjp_gram(net, x, gout, B, reinterpret_cast<unsigned char*>(base + p.off_qblk), bmax, p.bias_blocks, scales, flag,
-                              run_gen, part, p.QSB, p.Npad, s);
-      }
-      if (rch != IRBFN_OK) return rch;
-      run_if = flag;
-    }
-    rch = launch_vjp_f16(net, x, gout, B, reinterpret_cast<unsigned char*>(base + p.off_qblk), bmax, p.bias_blocks,
-                         scales, part, p.QSB, p.Npad, s, run_if, run_gen);
-    if (rch != IRBFN_OK) return rch;
-    if (p.use_g && frozen && vg_mode != 0)       // which of K2g and K2h wrote the slabs is known on the device only: the flag
-      return launch_vjp_reduce(net, part, g_centers, g_log_sigs, g_kernel, p.QSB, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, vg_mode,
-                               run_if, run_gen);
-    return launch_vjp_reduce(net, part, g_centers, g_log_sigs, g_kernel, p.QSB, p.V, p.Npad, s, bpart, g_bias, p.bias_blocks, red_mode);
+  const int vg_mode = !frozen || g_centers ? 0 : (g_log_sigs ? 1 : 2);
+  const VjpLayout L = vjp_layout(net, B);
+  const LaunchPlan p = plan_vjp(net, B, net->opt[IRBFN_OPT_VJP_KERNEL], gamma_ext != nullptr, vg_mode, L);
+  const VjpCall c = {net, x, gout, gamma_ext, g_centers, g_log_sigs, g_kernel, g_bias, B, static_cast<char*>(ws), s, frozen ? 0 : -1};
+  switch (p.kind) {
+    case LK_K2G:
+    case LK_K2H: return launch_vjp_k2h(c, L, p);
+    case LK_K2M: return launch_vjp_k2m(c, L, p);
+    case LK_K2R: return launch_vjp_k2r(c, L, p);
+    case LK_K2: return launch_vjp_k2(c, L, p);
+    default: return p.status;
   }
-
-  if (p.use_m) {
-    LaunchPlan k;
-    k.kind = LK_K2M; k.S = p.QSB;
-    vjpm_names(net, &k.Q, &k.nw);
-    k.grid = vjpm_groups(net) * p.QSB; k.block = 256;
-    record_launch(net, k);
-    const int rcm = launch_vjp_mfma(net, x, gout, B, reinterpret_cast<float*>(base + p.off_qm), part, p.QSB, p.Npad, s);
-    if (rcm != IRBFN_OK) return rcm;
-    return bias_and_reduce(part, p.QSB);
-  }
-
-  if (p.use_sp) {
-    // K2r: pair lists per region -> one wave per (region, slice) -> the same fixed-order slab reduce; no query packing
-    float* sp_part = reinterpret_cast<float*>(base + p.off_sp_part);
-    const int rcs = launch_vjp_sparse(net, x, gout, B, base + p.off_sp, sp_part, p.SL, p.Npad, s);
-    if (rcs != IRBFN_OK) return rcs;
-    return bias_and_reduce(sp_part, p.SL);
-  }
-  float* qrec = reinterpret_cast<float*>(base + p.off_qrec);
-  {
-    const size_t glds = ((size_t)net->nsplit * net->max_ranges * kWave + (size_t)net->gate().n_ranges * net->nsplit) * sizeof(float);
-    hipLaunchKernelGGL(vjp_pack_queries_kernel, dim3((unsigned)((B + kWave - 1) / kWave)), dim3(256), glds, s, x, gout,
-                       qrec, gamma, net->gate(), (long)B, net->D, net->DC, net->O, net->OP, p.QS, net->R);
-    IRBFN_HIP_CHECK(hipGetLastError());
-  }
-  int rc = IRBFN_OK;
-
-  VjpArgs a;
-  a.qrec = qrec; a.gamma = gamma_ext ? gamma_ext : gamma; a.rec = net->rec; a.sig2 = net->sig2; a.part = part;
-  a.B = (long)B; a.Dreal = net->D; a.O = net->O; a.N = net->N; a.K = net->K; a.R = net->R; a.S = net->S;
-  a.basis = net->basis; a.Npad = p.Npad; a.per_wave = p.per_wave; a.gscale = gauss_scale(net->basis);
-  const dim3 grid(p.groups, p.QSB);
-  const bool gated = net->R > 1 || gamma_ext != nullptr;
-  {
-    LaunchPlan k;
-    k.kind = LK_K2; k.gated = gated;
-    k.grid = (int)(grid.x * grid.y); k.block = 256;
-    record_launch(net, k);
-  }
-  switch (net->DC) {
-    case 3: rc = launch_vjp_d<3>(a, net->OP, net->bclass, gated, grid, s); break;
-    case 4: rc = launch_vjp_d<4>(a, net->OP, net->bclass, gated, grid, s); break;
-    case 7: rc = launch_vjp_d<7>(a, net->OP, net->bclass, gated, grid, s); break;
-    case 8: rc = launch_vjp_d<8>(a, net->OP, net->bclass, gated, grid, s); break;
-    default: rc = IRBFN_ERR_UNSUPPORTED;
-  }
-  if (rc != IRBFN_OK) return rc;
-
-  return bias_and_reduce(part, p.QSB);
-}
-
-int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs,
-               float* g_kernel, float* g_bias, int64_t B, void* ws, int64_t ws_bytes, hipStream_t s,
-               const float* gamma_ext) {
-  (void)ws_bytes;
-  return vjp_impl(net, x, gout, g_centers, g_log_sigs, g_kernel, g_bias, B, ws, s, gamma_ext, false);
-}
-
-int launch_vjp_frozen(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs, float* g_kernel,
-                      float* g_bias, int64_t B, void* ws, int64_t ws_bytes, hipStream_t s) {
-  (void)ws_bytes;
-  return vjp_impl(net, x, gout, g_centers, g_log_sigs, g_kernel, g_bias, B, ws, s, nullptr, true);
 }
 
 }  // namespace irbfn
