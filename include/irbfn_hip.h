@@ -151,7 +151,7 @@ typedef enum irbfn_fwd_gamma_kernel {
                           call for a net outside these shapes or parameters outside K1g's expansion; nothing else is launched in its place */
 } irbfn_fwd_gamma_kernel;
 typedef enum irbfn_vjp_kernel { IRBFN_VJP_AUTO = 0, IRBFN_VJP_K2 = 1, IRBFN_VJP_K2H = 2, IRBFN_VJP_K2R = 3, IRBFN_VJP_K2G = 4,
-                                IRBFN_VJP_K2M = 5 } irbfn_vjp_kernel;
+                                IRBFN_VJP_K2M = 5, IRBFN_VJP_K2G_GAMMA = 6 } irbfn_vjp_kernel;
 /* K2: all-float32 VALU; K2H: hbar and dW on the f16 matrix cores; K2R: region-sparse pair lists; K2G: the squared distances (K1g's
  * expansion) and the centre gradients on the matrix cores as well -- automatic in front of K2H from 8192 queries and 2.5e7
  * (query, centre) pairs where K1g's expansion fits;
@@ -162,7 +162,15 @@ typedef enum irbfn_vjp_kernel { IRBFN_VJP_AUTO = 0, IRBFN_VJP_K2 = 1, IRBFN_VJP_
  * forces: where the kernel cannot take the net or the batch, the call that would launch it answers IRBFN_ERR_UNSUPPORTED and
  * irbfn_net_vjp_kernel_supported answers 0.  (Every option but IRBFN_VJP_K2 and IRBFN_VJP_K2M reaches K2H first, so
  * IRBFN_VJP_K2R refuses only where K2H does not take the call; irbfn_net_vjp_gamma does not look at IRBFN_VJP_K2R.)
- * The workspace size does not depend on the option. */
+ * K2G_GAMMA (rbf_vjp_f16gram_gamma): K2G's loop for irbfn_net_vjp_gamma -- over the R regions of the net, each padded to whole chunks
+ * of 32 centres (the images of IRBFN_FWDG_K1G), gamma[b][region] multiplied onto the basis values per pair; slabs in the padded order,
+ * fixed-order reduce, no atomics.  A force, and only irbfn_net_vjp_gamma takes it: irbfn_net_vjp and irbfn_net_vjp_frozen answer
+ * IRBFN_ERR_UNSUPPORTED under it; irbfn_net_vjp_kernel_supported, which speaks of irbfn_net_vjp, does not know the value (< 0).  Gaussian family / inverse quadratic / inverse multiquadric,
+ * padded d in {3, 4, 7, 8}, O <= 16, any R, K, B >= 1, every finite gamma with |gamma| <= 1; a net outside these shapes or parameters
+ * outside K1g's expansion: IRBFN_ERR_UNSUPPORTED, nothing is launched in its place.  A call with a query outside K1g's box is done by
+ * the gated K2 behind it and returns K2's bits.  d gamma comes from the float32 kernel of every other path.  Selecting it allocates
+ * the images on a net of several regions; the next irbfn_net_set_params fills them (until then: IRBFN_ERR_NO_PARAMS).
+ * The workspace size does not depend on the option (it grows for a net that holds the padded images). */
 typedef enum irbfn_vjpx_kernel { IRBFN_VJPX_AUTO = 0, IRBFN_VJPX_K5 = 1, IRBFN_VJPX_K5M = 2 } irbfn_vjpx_kernel;
 /* Kernels of irbfn_net_vjp_x.  K5 (rbf_vjpx_qlane): all-float32 VALU, every net the forward's K1 takes.  K5M (rbf_vjpx_mfma):
  * hbar = gout W^T on the f32 matrix cores (full f32 operands); one region, gaussian family / inverse quadratic / inverse

@@ -23,7 +23,7 @@ OPTIONS = {"fwd_kernel": 0, "fwd_f16_terms": 2, "fwd_f16_s": 7, "fwd_f16_qg": 8,
            "vjpx_kernel": 16, "fwd_gamma_kernel": 17}
 FWD_AUTO, FWD_K1, FWD_K1M, FWD_K1H, FWD_K1R, FWD_K1G = 0, 1, 2, 3, 4, 5
 FWDG_AUTO, FWDG_K1, FWDG_K1G = 0, 1, 2          # irbfn_fwd_gamma_kernel (OPTIONS["fwd_gamma_kernel"])
-VJP_AUTO, VJP_K2, VJP_K2H, VJP_K2R, VJP_K2G, VJP_K2M = 0, 1, 2, 3, 4, 5
+VJP_AUTO, VJP_K2, VJP_K2H, VJP_K2R, VJP_K2G, VJP_K2M, VJP_K2G_GAMMA = 0, 1, 2, 3, 4, 5, 6
 VJPX_AUTO, VJPX_K5, VJPX_K5M = 0, 1, 2
 
 # every symbol include/irbfn_hip.h declares: (name, restype, argtypes)

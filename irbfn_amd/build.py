@@ -44,7 +44,7 @@ UNITS = [
     ("rbf_forward_gram_gamma.hip", "rbf_forward_gram_gamma.o", []),    # K1g over padded regions, caller-provided region weights
     ("rbf_vjp.hip", "rbf_vjp.o", [] + _SLP),
     ("rbf_vjp_f16.hip", "rbf_vjp_f16.o", ["-fno-slp-vectorize"]),
-    ("rbf_vjp_gram.hip", "rbf_vjp_gram.o", ["-fno-slp-vectorize"]),
+    ("rbf_vjp_gram.hip", "rbf_vjp_gram.o", ["-fno-slp-vectorize"]),   # K2g, and the same loop over padded regions with caller-provided region weights
     ("rbf_vjp_mfma.hip", "rbf_vjp_mfma.o", []),        # K2m: hbar and dW on the f32 matrix cores   # VGPR operands: plain FMAs (2.4 cyc) beat packed (4.7) + pairing moves
     # x-VJP: plan + launchers, K5 per compiled D (as K1), K5m
     ("rbf_vjpx.hip", "rbf_vjpx.o", []),

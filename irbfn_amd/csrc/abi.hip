@@ -170,7 +170,11 @@ int irbfn_net_set_option(irbfn_net* net, int option, int value) {
   if (!net || !option_known(option) || value < 0) return IRBFN_ERR_BAD_ARG;
   switch (option) {
     case IRBFN_OPT_FWD_KERNEL: if (value > IRBFN_FWD_K1G) return IRBFN_ERR_BAD_ARG; break;
-    case IRBFN_OPT_VJP_KERNEL: if (value > IRBFN_VJP_K2M) return IRBFN_ERR_BAD_ARG; break;
+    case IRBFN_OPT_VJP_KERNEL:
+      if (value > IRBFN_VJP_K2G_GAMMA) return IRBFN_ERR_BAD_ARG;
+      if (value == IRBFN_VJP_K2G_GAMMA)
+        if (const int rc = gram_gamma_select(net); rc != IRBFN_OK) return rc;
+      break;
     case IRBFN_OPT_VJPX_KERNEL: if (value > IRBFN_VJPX_K5M) return IRBFN_ERR_BAD_ARG; break;
     case IRBFN_OPT_FWD_F16_TERMS: if (value != 1 && value != 2 && value != 3) return IRBFN_ERR_BAD_ARG; break;
     case IRBFN_OPT_FWD_F16_S:
@@ -346,6 +350,7 @@ int irbfn_net_forward_rollout(irbfn_net* net, int mode, const float* x_dev, cons
 }
 
 int irbfn_net_vjp_kernel_supported(irbfn_net* net, int kernel, int64_t B) {
+  // the kernels of irbfn_net_vjp: IRBFN_VJP_K2G_GAMMA, which only irbfn_net_vjp_gamma takes, is no argument of this question
   if (!net || kernel < IRBFN_VJP_AUTO || kernel > IRBFN_VJP_K2M || B < 0) return IRBFN_ERR_BAD_ARG;
   return vjp_kernel_supported(net, kernel, B);
 }

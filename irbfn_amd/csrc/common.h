@@ -146,6 +146,7 @@ enum LaunchKind : int {
   LK_K2M,            // rbf_vjp_mfma (rbf_vjp_mfma.hip; Q: padded width OW, nw: centre tiles per wave, S: query slabs)
   LK_K1G_GAMMA,      // rbf_fwd_f16gram_gamma (caller-provided region weights)
   LK_TICK_K1G_GAMMA, // rbf_tick_f16gram_gamma
+  LK_K2G_GAMMA,      // rbf_vjp_f16gram_gamma, the gated K2 behind it (irbfn_net_vjp_gamma under IRBFN_VJP_K2G_GAMMA; S: query slabs)
   LK_K2H,            // rbf_vjp_f16mfma and
   LK_K2R             // rbf_vjp_sparse: record_launch gives neither a name, the previous launch's stands
 };
@@ -207,6 +208,7 @@ int launch_forward_gram(irbfn_net* net, const LaunchPlan& p, const float* x, flo
 int gram_gamma_cpr(const irbfn_net* net);
 bool gram_gamma_eligible(const irbfn_net* net);
 int gram_gamma_select(irbfn_net* net);
+bool gram_gamma_wanted(const irbfn_net* net);   // an option of the net selects a kernel that reads the padded images
 int launch_forward_gram_gamma(irbfn_net* net, const LaunchPlan& p, const float* x, const float* gamma, float* out, int64_t B,
                               hipStream_t s);
 int launch_tick_gram_gamma(irbfn_net* net, const LaunchPlan& p, const float* x, const float* gamma, const int* mirror,

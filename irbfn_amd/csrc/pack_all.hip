@@ -424,10 +424,10 @@ int launch_pack_all(irbfn_net* net, const float* centers, const float* log_sigs,
   PackArgs a{};
   a.centers = centers; a.log_sigs = log_sigs; a.kernel = kernel; a.bias = bias;
   a.rec = net->rec; a.bias_out = net->bias; a.sig2 = net->sig2; a.recm = net->recm; a.oscale = net->f16_oscale;
-  // A net of several regions has the images only once it selected K1g for its region-weighted forward (gram_gamma_select),
-  // in the padded chunk order; while the option is off they are not packed (and say so)
+  // A net of several regions has the images only once it selected K1g for its region-weighted forward or K2g for its
+  // region-weighted VJP (gram_gamma_select), in the padded chunk order; while both options are off they are not packed (and say so)
   const bool gam = net->R > 1 && net->f16_img != nullptr;
-  const bool gam_on = gam && net->opt[IRBFN_OPT_FWD_GAMMA_KERNEL] == IRBFN_FWDG_K1G;
+  const bool gam_on = gam && gram_gamma_wanted(net);
   unsigned char* const f16_img = (gam && !gam_on) ? nullptr : net->f16_img;
   unsigned char* const gram_img = (gam && !gam_on) ? nullptr : net->gram_img;
   if (gam) net->gamma_packed = gam_on ? 1 : 0;

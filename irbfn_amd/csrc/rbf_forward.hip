@@ -508,6 +508,7 @@ void record_launch(irbfn_net* net, const LaunchPlan& p) {
     case LK_K2G:                 // mode: K2g's live leaves (irbfn_net_vjp_frozen) -- 1 no centres, 2 the Dense leaves only
       snprintf(n, len, "rbf_vjp_f16gram%s<D=%d,BC=%d,QSB=%d>", p.mode == 1 ? "/no_centres" : (p.mode == 2 ? "/linear" : ""), D, BC, p.S);
       break;
+    case LK_K2G_GAMMA: snprintf(n, len, "rbf_vjp_f16gram_gamma<D=%d,BC=%d,QSB=%d>", D, BC, p.S); break;
     case LK_K2: snprintf(n, len, "rbf_vjp_kernel<D=%d,OP=%d,BC=%d,GATED=%d>", D, net->OP, BC, (int)p.gated); break;
     case LK_K2M: snprintf(n, len, "rbf_vjp_mfma<D=%d,OW=%d,BC=%d,CT=%d,QSB=%d>", D, p.Q, BC, p.nw, p.S); break;
     default: return;

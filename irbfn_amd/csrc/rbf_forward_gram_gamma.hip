@@ -34,10 +34,27 @@ bool gram_gamma_eligible(const irbfn_net* net) {
   return net->bclass != BC_GENERIC && net->O <= 16 && (net->DC == 3 || net->DC == 4 || net->DC == 7 || net->DC == 8);
 }
 
+bool gram_gamma_wanted(const irbfn_net* net) {
+  return net->opt[IRBFN_OPT_FWD_GAMMA_KERNEL] == IRBFN_FWDG_K1G || net->opt[IRBFN_OPT_VJP_KERNEL] == IRBFN_VJP_K2G_GAMMA;
+}
+
 // A net of one region has K1g's images already, and its chunk order is the padded one.  A net of several regions gets them
-// here, when it selects the kernel; the next irbfn_net_set_params fills them.
+// here, when it selects the kernel (this forward, or rbf_vjp_f16gram_gamma, which also takes K2g's ring of hand-over words); the
+// next irbfn_net_set_params fills them.
 int gram_gamma_select(irbfn_net* net) {
-  if (!gram_gamma_eligible(net) || net->R == 1 || net->gram_img) return IRBFN_OK;       // not eligible: refused at the call
+  if (!gram_gamma_eligible(net) || net->R == 1) return IRBFN_OK;                        // not eligible: refused at the call
+  if (!net->vjp_flags) {
+    void* f = nullptr;
+    hipError_t e = hipMalloc(&f, 64 * sizeof(int));
+    if (e == hipSuccess) e = hipMemset(f, 0, 64 * sizeof(int));
+    if (e != hipSuccess) {
+      g_last_hip_error = (int)e;
+      if (f) (void)hipFree(f);
+      return IRBFN_ERR_HIP;
+    }
+    net->vjp_flags = static_cast<int*>(f);
+  }
+  if (net->gram_img) return IRBFN_OK;
   const size_t nchunks = (size_t)net->R * gram_gamma_cpr(net);
   void* bufs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   const size_t bytes[5] = {nchunks * f16_chunk_bytes(net->DC, 1), 128 * sizeof(float), nchunks * kGramChunkBytes, sizeof(GramHdr),

@@ -32,6 +32,8 @@ struct VjpArgs {
   long B;
   int Dreal, O, N, K, R, S, basis, Npad, per_wave;
   float gscale;
+  const int* __restrict__ flag;     // GATED behind rbf_vjp_f16gram_gamma: run only if *flag == gen (null: always)
+  int gen;
 };
 
 // d phi / d(d2) from phi and d2.  The fast classes need phi only; the generic class covers the bases that depend on
@@ -128,6 +130,8 @@ __global__ __launch_bounds__(256) void rbf_vjp_kernel(const VjpArgs a) {
   extern __shared__ float lds[];
   constexpr int V = D + 1 + OP;
   constexpr int LP = kWave + 1;
+  if constexpr (GATED)
+    if (a.flag != nullptr && *a.flag != a.gen) return;       // the matrix-core kernel in front of this launch did the work
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -334,6 +338,69 @@ __global__ __launch_bounds__(256) void vjp_reduce_live_kernel(float* __restrict_
   else part[(size_t)v * Npad + n] = s;                      // slab 0 (R > 1: full slab rows, kb = DC + 1)
 }
 
+// The slab reduce behind rbf_vjp_f16gram_gamma.  Which kernel wrote slabs is known on the device only: the matrix-core kernel its
+// own [QSG][V][NpadG] in the padded chunk order (centre k of region r in column 32 cpr r + k; padding columns are never read), or,
+// where the flag holds `gen`, the gated K2 behind it K2's [QSB][V][Npad].  The sums run in the order of vjp_reduce_kernel, so a
+// handed-over call returns the bits of a forced K2 call.
+struct VjpGammaSlabs {
+  float *gpart, *kpart;
+  int QSG, QSB, NpadG, Npad, cpr;
+  const int* flag;
+  int gen;
+};
+__global__ __launch_bounds__(256) void vjp_reduce_gamma_kernel(const VjpGammaSlabs sl, float* __restrict__ g_centers,
+                                                               float* __restrict__ g_log_sigs, float* __restrict__ g_kernel, int V,
+                                                               int N, int K, int R, int D, int DC, int O,
+                                                               const float* __restrict__ bpart, float* __restrict__ g_bias, int bias_blocks) {
+  __shared__ float sm[4][kWave];
+  const int l = threadIdx.x & (kWave - 1), sg = threadIdx.x >> 6;
+  if (blockIdx.y == (unsigned)V) {
+    const int o = blockIdx.x, t = threadIdx.x;
+    if (o >= O || bpart == nullptr) return;
+    float* sb = &sm[0][0];
+    float sacc = 0.0f;
+    for (int b = t; b < bias_blocks; b += 256) sacc += bpart[(size_t)b * O + o];
+    sb[t] = sacc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {             // fixed tree -> deterministic
+      if (t < w) sb[t] += sb[t + w];
+      __syncthreads();
+    }
+    if (t == 0) g_bias[o] = sb[0];
+    return;
+  }
+  const int v = blockIdx.y, n = blockIdx.x * kWave + l;
+  if ((v >= D && v < DC) || v > DC + O) return;            // padded coordinate / output slots (whole block)
+  const bool k2 = *sl.flag == sl.gen;
+  float* part = k2 ? sl.kpart : sl.gpart;
+  const int QS = k2 ? sl.QSB : sl.QSG, Np = k2 ? sl.Npad : sl.NpadG;
+  const int col = k2 ? n : (n / K) * sl.cpr * 32 + n % K;
+  float s = 0.0f;
+  if (n < N)
+    for (int q = sg; q < QS; q += 4) s += part[((size_t)q * V + v) * Np + col];
+  sm[sg][l] = s;
+  __syncthreads();
+  if (sg != 0 || n >= N) return;
+  s = (sm[0][l] + sm[1][l]) + (sm[2][l] + sm[3][l]);
+  if (v < D) g_centers[(size_t)n * D + v] = s;
+  else if (v == DC) g_log_sigs[n] = s;
+  else if (R == 1) g_kernel[(size_t)n * O + (v - DC - 1)] = s;
+  else part[(size_t)v * Np + col] = s;                      // slab 0
+}
+
+__global__ __launch_bounds__(64) void vjp_reduce_regions_gamma_kernel(const VjpGammaSlabs sl, float* __restrict__ g_kernel, int K, int R,
+                                                                      int DC, int O) {
+  const int k = blockIdx.x, o = blockIdx.y, lane = threadIdx.x;
+  const bool k2 = *sl.flag == sl.gen;
+  const float* part = k2 ? sl.kpart : sl.gpart;
+  const int Np = k2 ? sl.Npad : sl.NpadG, rs = k2 ? K : sl.cpr * 32;
+  float s = 0.0f;
+  for (int r = lane; r < R; r += kWave) s += part[(size_t)(DC + 1 + o) * Np + (size_t)r * rs + k];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);      // fixed tree: deterministic
+  if (lane == 0) g_kernel[(size_t)k * O + o] = s;
+}
+
 // vg_mode: -1 the all-live path (vjp_reduce_kernel); else vjp_reduce_live_kernel with the slabs' layout (K2g's VgMode; 0 = the
 // full rows of every other kernel) -- and, behind a frozen-leaf K2g, the hand-over flag that says K2h wrote full rows instead
 int launch_vjp_reduce(const irbfn_net* net, float* part, float* g_centers, float* g_log_sigs, float* g_kernel, int QSB, int V,
@@ -424,6 +491,10 @@ struct VjpLayout {
   int SL;          // K2r: slices per region = its own slabs [SL][V][Npad] at off_sp_part (0 where K2r cannot take the net)
   size_t off_gamma, off_part, off_bias, off_qrec, off_qblk, off_misc, total;
   size_t off_sp, off_sp_part, off_qm;   // K2r: pair lists, slabs; K2m: its query records
+  // rbf_vjp_f16gram_gamma (a net that holds the padded images): slabs [QSG][V][NpadG] in the padded chunk order at off_gpart (one
+  // region: the padded order is the plain one and the slabs are K2's), the region weights as tiles [nqb][R][32] at off_gtile
+  int QSG, NpadG;
+  size_t off_gtile, off_gpart;
 };
 
 // The VJP's workspace (irbfn_net_vjp_workspace_bytes): every kernel the net is eligible for has its part, whichever runs, so the
@@ -449,7 +520,8 @@ static VjpLayout vjp_layout(const irbfn_net* net, int64_t B) {
   p.off_qrec = off;  off += al((size_t)B * p.QS * sizeof(float));
   // K2h / K2g: packed 32-query blocks + (absmax, scales)
   const size_t blkb = vjph_block_bytes(net) > vjpg_block_bytes() ? vjph_block_bytes(net) : vjpg_block_bytes();
-  p.off_qblk = off;  off += al(vjph_eligible(net) ? (size_t)((B + 31) / 32) * blkb : 0);
+  const bool gam = vjpgg_eligible(net) && net->gram_img != nullptr;
+  p.off_qblk = off;  off += al(vjph_eligible(net) ? (size_t)((B + 31) / 32) * blkb : (gam ? (size_t)((B + 31) / 32) * vjpg_block_bytes() : 0));
   p.off_misc = off;  off += al((size_t)(p.bias_blocks + 8) * sizeof(float));
   p.SL = 0;
   p.off_sp = p.off_sp_part = off;
@@ -461,6 +533,24 @@ static VjpLayout vjp_layout(const irbfn_net* net, int64_t B) {
   }
   p.off_qm = off;
   if (vjpm_eligible(net)) off += al(vjpm_qrec_bytes(net, B));
+  p.QSG = 0; p.NpadG = 0;
+  p.off_gtile = p.off_gpart = off;
+  if (gam) {
+    const long nqb = (B + 31) / 32, nch = (long)net->R * gram_gamma_cpr(net), gb = (nch + 3) / 4;
+    long q = (256L * vjpgg_waves() + gb - 1) / gb;           // one resident round, at least 8 query blocks a slice: as vjpg_slices
+    if (q > 64) q = 64;
+    if (q * 8 > nqb) q = (nqb + 7) / 8;
+    q = q < 1 ? 1 : q;
+    off += al((size_t)nqb * net->R * 32 * sizeof(float));
+    if (net->R == 1) {
+      p.QSG = (int)(q < p.QSB ? q : p.QSB); p.NpadG = p.Npad;
+      p.off_gpart = p.off_part;
+    } else {
+      p.QSG = (int)q; p.NpadG = (int)(nch * 32);
+      p.off_gpart = off;
+      off += al((size_t)p.QSG * p.V * p.NpadG * sizeof(float));
+    }
+  }
   p.total = off;
   return p;
 }
@@ -510,6 +600,17 @@ static LaunchPlan plan_vjp(const irbfn_net* net, int64_t B, int forced, bool gam
     if (!vjpm_eligible(net) || gamma_ext) return p;
     take(LK_K2M, vjpm_slices(net, B, L.QSB), vjpm_groups(net));
     vjpm_names(net, &p.Q, &p.nw);
+    return p;
+  }
+  // rbf_vjp_f16gram_gamma: forced only, irbfn_net_vjp_gamma only; any B.  The gated K2 stands behind it for a call with a query
+  // outside K1g's box, so what K2 needs must hold as well.  NO_PARAMS: the images were allocated after the last irbfn_net_set_params
+  if (forced == IRBFN_VJP_K2G_GAMMA) {
+    if (!gamma_ext || !vjpgg_eligible(net) || L.QSG < 1 || net->vjp_flags == nullptr) return p;
+    if (!(net->gram_img && net->f16_img && (net->R == 1 || net->gamma_packed))) { p.status = IRBFN_ERR_NO_PARAMS; return p; }
+    if (!net->gram_ok || gate_tables_lds(net) > 64 * 1024) return p;
+    p.kind = LK_K2G_GAMMA; p.status = IRBFN_OK;
+    p.S = L.QSG;
+    p.grid = (int)(((long)net->R * gram_gamma_cpr(net) + 3) / 4 * p.S);
     return p;
   }
   // K2h: every option but K2 reaches it, IRBFN_VJP_K2R included -- so IRBFN_VJP_K2H is a preference (below 2048 queries, or on a
@@ -915,28 +1016,67 @@ static int launch_vjp_k2r(const VjpCall& c, const VjpLayout& L, const LaunchPlan
   return rc != IRBFN_OK ? rc : bias_and_reduce(c, L, part, p.S);
 }
 
-static int launch_vjp_k2(const VjpCall& c, const VjpLayout& L, const LaunchPlan& p) {
+// K2's query packing and main kernel.  run_if: behind rbf_vjp_f16gram_gamma (caller-provided region weights, so the packing writes
+// none of its own) the main kernel runs only where the word holds run_gen
+static int launch_vjp_k2_main(const VjpCall& c, const VjpLayout& L, const LaunchPlan& p, const int* run_if = nullptr, int run_gen = 0) {
   irbfn_net* net = c.net;
   float *qrec = c.at<float>(L.off_qrec), *gamma = c.at<float>(L.off_gamma), *part = c.at<float>(L.off_part);
   hipLaunchKernelGGL(vjp_pack_queries_kernel, dim3((unsigned)((c.B + kWave - 1) / kWave)), dim3(256), p.lds, c.s, c.x, c.gout, qrec, gamma,
-                     net->gate(), (long)c.B, net->D, net->DC, net->O, net->OP, L.QS, net->R);
+                     net->gate(), (long)c.B, net->D, net->DC, net->O, net->OP, L.QS, run_if ? 1 : net->R);
   IRBFN_HIP_CHECK(hipGetLastError());
   VjpArgs a;
+  a.flag = run_if; a.gen = run_gen;
   a.qrec = qrec; a.gamma = c.gamma_ext ? c.gamma_ext : gamma; a.rec = net->rec; a.sig2 = net->sig2; a.part = part;
   a.B = (long)c.B; a.Dreal = net->D; a.O = net->O; a.N = net->N; a.K = net->K; a.R = net->R; a.S = net->S;
   a.basis = net->basis; a.Npad = L.Npad; a.gscale = gauss_scale(net->basis);
   a.per_wave = (int)((c.B + p.S * 4L - 1) / (p.S * 4L));      // four waves per slab, each its share of the queries
   const dim3 grid(L.groups, p.S);
-  record_launch(net, p);
-  int rc;
+  if (!run_if) record_launch(net, p);
   switch (net->DC) {
-    case 3: rc = launch_vjp_d<3>(a, net->OP, net->bclass, p.gated, grid, c.s); break;
-    case 4: rc = launch_vjp_d<4>(a, net->OP, net->bclass, p.gated, grid, c.s); break;
-    case 7: rc = launch_vjp_d<7>(a, net->OP, net->bclass, p.gated, grid, c.s); break;
-    case 8: rc = launch_vjp_d<8>(a, net->OP, net->bclass, p.gated, grid, c.s); break;
-    default: rc = IRBFN_ERR_UNSUPPORTED;
+    case 3: return launch_vjp_d<3>(a, net->OP, net->bclass, p.gated, grid, c.s);
+    case 4: return launch_vjp_d<4>(a, net->OP, net->bclass, p.gated, grid, c.s);
+    case 7: return launch_vjp_d<7>(a, net->OP, net->bclass, p.gated, grid, c.s);
+    case 8: return launch_vjp_d<8>(a, net->OP, net->bclass, p.gated, grid, c.s);
+    default: return IRBFN_ERR_UNSUPPORTED;
   }
-  return rc != IRBFN_OK ? rc : bias_and_reduce(c, L, part, p.S);
+}
+
+static int launch_vjp_k2(const VjpCall& c, const VjpLayout& L, const LaunchPlan& p) {
+  const int rc = launch_vjp_k2_main(c, L, p);
+  return rc != IRBFN_OK ? rc : bias_and_reduce(c, L, c.at<float>(L.off_part), p.S);
+}
+
+// rbf_vjp_f16gram_gamma, the gated K2 behind it: a query outside K1g's box raises this call's flag (as for K2g, launch_vjp_k2h), the
+// matrix-core kernel returns at once and K2 -- launched behind it with the complementary test -- does the work
+static int launch_vjp_k2g_gamma(const VjpCall& c, const VjpLayout& L, const LaunchPlan& p) {
+  irbfn_net* net = c.net;
+  const LaunchPlan pk = plan_vjp(net, c.B, IRBFN_VJP_K2, true, 0, L);
+  if (pk.kind != LK_K2) return pk.status;
+  float* bmax = c.at<float>(L.off_misc);         // [bias_blocks] max |g| per block
+  float* scales = bmax + L.bias_blocks;          // [2]
+  int rc = bias_partials(c, L, bmax);
+  if (rc != IRBFN_OK) return rc;
+  if (++net->vjp_gen <= 0) net->vjp_gen = 1;
+  const int gen = net->vjp_gen;
+  int* flag = net->vjp_flags + (gen & 63);
+  record_launch(net, p);
+  rc = launch_vjp_gram_gamma(net, c.x, c.gamma_ext, c.gout, c.B, c.at<unsigned char>(L.off_qblk), c.at<float>(L.off_gtile), bmax,
+                             L.bias_blocks, scales, flag, gen, c.at<float>(L.off_gpart), p.S, L.NpadG, c.s);
+  if (rc != IRBFN_OK) return rc;
+  rc = launch_vjp_k2_main(c, L, pk, flag, gen);
+  if (rc != IRBFN_OK) return rc;
+  const VjpGammaSlabs sl = {c.at<float>(L.off_gpart), c.at<float>(L.off_part), p.S, pk.S, L.NpadG, L.Npad, gram_gamma_cpr(net), flag, gen};
+  unsigned gx = (unsigned)((net->N + kWave - 1) / kWave);
+  if (gx < (unsigned)net->O) gx = (unsigned)net->O;
+  hipLaunchKernelGGL(vjp_reduce_gamma_kernel, dim3(gx, L.V + 1), dim3(256), 0, c.s, sl, c.g_centers, c.g_log_sigs, c.g_kernel, L.V, net->N,
+                     net->K, net->R, net->D, net->DC, net->O, c.at<float>(L.off_bias), c.g_bias, L.bias_blocks);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  if (net->R > 1) {
+    hipLaunchKernelGGL(vjp_reduce_regions_gamma_kernel, dim3(net->K, net->O), dim3(kWave), 0, c.s, sl, c.g_kernel, net->K, net->R, net->DC,
+                       net->O);
+    IRBFN_HIP_CHECK(hipGetLastError());
+  }
+  return IRBFN_OK;
 }
 
 int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs, float* g_kernel,
@@ -960,6 +1100,7 @@ int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_cente
     case LK_K2M: return launch_vjp_k2m(c, L, p);
     case LK_K2R: return launch_vjp_k2r(c, L, p);
     case LK_K2: return launch_vjp_k2(c, L, p);
+    case LK_K2G_GAMMA: return launch_vjp_k2g_gamma(c, L, p);
     default: return p.status;
   }
 }

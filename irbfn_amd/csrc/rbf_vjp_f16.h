@@ -32,5 +32,12 @@ int vjpg_waves(int mode, int O);                  // waves per SIMD of a mode's 
 int vjpg_slab_rows(int mode, int DC, int OP);     // slab rows of a mode: [d centers] [d log_sigs] d kernel
 int launch_vjp_gram_live(irbfn_net* net, int mode, const float* x, const float* gout, int64_t B, unsigned char* qblk, const float* bmax,
                          int nbmax, float* scales, int* flag, int gen, float* part, int QSB, int Npad, hipStream_t s);
+// rbf_vjp_f16gram_gamma (rbf_vjp_gram.hip): K2g over the R regions padded to whole chunks, caller-provided region weights gamma[B][R];
+// slabs in the padded chunk order (Npad >= 32 R cpr), gtile: workspace of 32 R floats per 32-query block
+bool vjpgg_eligible(const irbfn_net* net);        // the net's shape; the images and the pack's verdict are the planner's
+int vjpgg_waves();
+int launch_vjp_gram_gamma(irbfn_net* net, const float* x, const float* gamma, const float* gout, int64_t B, unsigned char* qblk,
+                          float* gtile, const float* bmax, int nbmax, float* scales, int* flag, int gen, float* part, int QSB, int Npad,
+                          hipStream_t s);
 
 }  // namespace irbfn

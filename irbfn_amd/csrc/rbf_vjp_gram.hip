@@ -20,6 +20,9 @@
 //
 // A query outside K1g's representable box (rbf_forward_gram.h) cannot be expanded: the pre-pass raises a flag, this kernel
 // returns at once and K2h -- launched behind it with the complementary test -- does the work.
+//
+// rbf_vjp_f16gram_gamma is the same loop for a net evaluated with caller-provided region weights gamma[B][R] (irbfn_net_vjp_gamma,
+// IRBFN_VJP_K2G_GAMMA): the chunks of R regions padded to whole chunks, gamma multiplied onto P per pair, the gated K2 behind it.
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -39,8 +42,14 @@ constexpr int kVgOC = 10;                                // up to this many outp
 // matrix cores honour: a (hi, lo) pair then keeps 2^-36 ABSOLUTE against operands of size 2^-2, beyond float32.  The gaussian
 // (ET = 33) needs no multiplication of hbar at all any more, the other bases one by 2^-(ET - 33).
 // (The gaussian's basis value is taken as phi itself here -- see kVgShift in the kernel -- so its factor is 2^-19: 2^-9 and 2^-10.)
-__host__ __device__ constexpr int vg_exp_a(int bc) { return bc == BC_GAUSS ? 9 : 16; }
-__host__ __device__ constexpr int vg_exp_b(int bc) { return bc == BC_GAUSS ? 10 : 17; }
+// rbf_vjp_f16gram_gamma multiplies the region weight onto P in front of the ungained (hi, lo) split of the dW operand, which is good
+// to 2^-25 ABSOLUTE below 2^-4: with gamma ~ 1 / R that is every term of a net of 500 regions (dW then misses float32 by two orders
+// of magnitude).  So its weights arrive as gamma 2^G with P gamma 2^G <= 2^14, the size split_pair_plain is made for: G = 14 -
+// log2(PS).  tts takes 2^-G back through hbar -- the gaussian's operand scales become the other bases' (2^-16, 2^-17: ET = 33, as
+// when its P was 2^14 phi), the inverse multiquadric's 2^-7 joins the factor it multiplies hbar with anyway -- dW through its scale.
+__host__ __device__ constexpr int vg_gamma_gain(int bc) { return bc == BC_GAUSS ? 14 : (bc == BC_IQ ? 0 : 7); }
+__host__ __device__ constexpr int vg_exp_a(int bc, bool gamma = false) { return bc == BC_GAUSS && !gamma ? 9 : 16; }
+__host__ __device__ constexpr int vg_exp_b(int bc, bool gamma = false) { return bc == BC_GAUSS && !gamma ? 10 : 17; }
 constexpr float kVgCrossA = 1.0f / 32.0f, kVgCrossB = 1.0f / 64.0f;      // kVgCrossA * kVgCrossB = kLoScale (2^-11)
 static_assert(kVgCrossA * kVgCrossB == kLoScale, "cross terms of the (hi, lo) scheme");
 
@@ -75,7 +84,8 @@ __global__ __launch_bounds__(192) void vjp_pack_blocks_gram_kernel(const float* 
                                                                   const float* __restrict__ bmax, int nbmax,
                                                                   const float* __restrict__ oscale, const GramHdr* __restrict__ hdr,
                                                                   unsigned char* __restrict__ qblk, float* __restrict__ scales,
-                                                                  int* __restrict__ flag, int gen, GateTables gt, long B, int D, int O, int expA) {
+                                                                  int* __restrict__ flag, int gen, GateTables gt, long B, int D, int O, int expA,
+                                                                  int unit_gate) {
   const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
   const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long q0 = (long)blockIdx.x * 32;
@@ -123,8 +133,8 @@ __global__ __launch_bounds__(192) void vjp_pack_blocks_gram_kernel(const float* 
   float gm = 0.0f;
   if (lane < 32 && q0 + lane < B) {
     const long q = q0 + lane;
-    gm = gt.n_ranges > 0 ? 1.0f : 0.0f;
-    for (int d = 0; d < gt.nsplit && gt.n_ranges > 0; ++d) {
+    gm = (gt.n_ranges > 0 || unit_gate) ? 1.0f : 0.0f;       // unit_gate: the region weights join in the main kernel's loop
+    for (int d = 0; d < gt.nsplit && gt.n_ranges > 0 && !unit_gate; ++d) {
       const int e = d * gt.max_ranges + gt.dim_ranges[d];
       gm *= gate_factor(x[q * D + d], gt.lo[e], gt.hi[e], gt.delta[d]);
     }
@@ -243,6 +253,11 @@ struct VjpGArgs {
   int O, OP, N, S, Npad, bpb, cstride, nchunks;
   float gscale;
 };
+// rbf_vjp_f16gram_gamma on top: the region weights as tiles [query block][region][32]; chunk c = region c / cpr, K real centres each
+struct VjpGGamma {
+  const float* __restrict__ gtile;
+  int R, K, cpr;
+};
 
 #ifndef IRBFN_K2G_WAVES
 #define IRBFN_K2G_WAVES 3       // waves per SIMD the register allocation must allow where hbar takes two MFMAs (O > 10): 138 VGPRs
@@ -263,6 +278,9 @@ struct VjpGArgs {
 #ifndef IRBFN_K2G_WAVES_LIN
 #define IRBFN_K2G_WAVES_LIN 6
 #endif
+#ifndef IRBFN_K2G_WAVES_GAMMA
+#define IRBFN_K2G_WAVES_GAMMA 3  // rbf_vjp_f16gram_gamma: the region weights of two query blocks (16 VGPRs) on top of K2g's
+#endif
 __host__ __device__ constexpr int vg_waves(int mode, bool oc) {
   return mode == VG_ALL ? (oc ? IRBFN_K2G_WAVES_OC : IRBFN_K2G_WAVES)
                         : (mode == VG_NO_CENTRES ? (oc ? IRBFN_K2G_WAVES_NC_OC : IRBFN_K2G_WAVES_NC) : IRBFN_K2G_WAVES_LIN);
@@ -270,8 +288,10 @@ __host__ __device__ constexpr int vg_waves(int mode, bool oc) {
 // OC: O <= kVgOC -- hbar's three products (hi x hi, lo x hi, hi x lo over <= 10 outputs: 30 of 32 slots) in ONE 16x16x32 MFMA; the
 // cross terms' B operands carry the 2^-11 of the (hi, lo) scheme, so nothing is left to combine on the VALU (28 instead of 32
 // MFMAs and 16 VALU instructions fewer per 32 x 32 pairs)
-template <int DC, int BC, bool OC, int MODE>
-__global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const VjpGArgs a) {
+// GAMMA (rbf_vjp_f16gram_gamma): the chunks are those of R regions padded to cpr whole chunks each (pack_all.hip); a wave's chunk
+// lies in ONE region, whose weight gamma[q, region] is multiplied onto P per pair -- in front of the dW split and, through P, into tts
+template <int DC, int BC, bool OC, int MODE, bool GAMMA>
+__device__ __forceinline__ void vg_body(const VjpGArgs& a, const VjpGGamma& gm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr int SLOT = vg_slot_bytes(MODE);                  // one ring slot: the pieces of a block image this mode reads
   constexpr bool kHbar = MODE != VG_LINEAR;                  // hbar, tt and d log_sigs
@@ -286,6 +306,9 @@ __global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const
   const int chunk = bx * 4 + wave;                   // this wave's 32 centres
   const bool active = chunk < a.nchunks;
   const int cb = chunk * 32;
+  // GAMMA: the region of this wave's chunk and the chunk's first centre within it; centre (ct, n) is real below K
+  const int reg = GAMMA ? (active ? chunk : 0) / gm.cpr : 0;
+  const int kr0 = GAMMA ? ((active ? chunk : 0) - reg * gm.cpr) * 32 : 0;
   const float sg = a.scales[0], sh = a.scales[1];
   // Gaussian: the head sum starts from -14 (gram_heads2c), so u = alpha d^2 itself and the transcendental returns phi (PS = 1):
   // no subtraction per pair for d log_sigs.  phi <= 1 as an ungained (hi, lo) pair is good to 2^-25 absolute -- of a gradient's
@@ -294,9 +317,11 @@ __global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const
   constexpr float PS = kVgShift ? 1.0f : gram_phi_scale<BC>();                 // the basis value arrives as P = PS phi
   // tt_true = tts * KT:  tts = hb * P^p * 2^-ET (|tts| < 2^15), hb = gamma hbar 2^30 / s_h, dphi/dd2 = const * phi^p
   constexpr int ET = BC == BC_GAUSS ? 19 : (BC == BC_IQ ? 47 : 40);       // 34 + p log2(PS) - 15
-  constexpr int kVgExpA = vg_exp_a(BC), kVgExpB = vg_exp_b(BC);
-  const float cE = __builtin_ldexpf(1.0f, -(ET - kVgExpA - kVgExpB));      // what the operand scales leave of 2^-ET (gaussian: 1)
-  static_assert(ET >= kVgExpA + kVgExpB, "operand scales");
+  constexpr int kVgExpA = vg_exp_a(BC, GAMMA), kVgExpB = vg_exp_b(BC, GAMMA);
+  constexpr int EH = ET + (GAMMA ? vg_gamma_gain(BC) : 0);                 // GAMMA: hbar takes back the gain of the region weights
+  static_assert(!GAMMA || PS * (1 << vg_gamma_gain(BC)) == 16384.0f, "P gamma 2^G <= 2^14");
+  const float cE = __builtin_ldexpf(1.0f, -(EH - kVgExpA - kVgExpB));      // what the operand scales leave of 2^-EH (gaussian: 1)
+  static_assert(EH >= kVgExpA + kVgExpB, "operand scales");
   const float KT = sh * (1.0f / (kWScale * kWScale)) * __builtin_ldexpf(1.0f, ET) *
                    (BC == BC_GAUSS ? -a.gscale / PS : (BC == BC_IQ ? -1.0f / (PS * PS) : -0.5f / (PS * PS * PS)));
 
@@ -316,12 +341,18 @@ __global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const
       cbt[ct][1] = *reinterpret_cast<const h8_t*>(ci + kGramHeadBytes + (ct * 2 + 1) * 1024 + lane * 16);
       int cid = cb + ct * 16 + n;
       cid = cid < a.N ? cid : a.N - 1;
+      bool real = true;                                      // GAMMA: a padding centre has no Dense row: hbar = 0, so tt = 0
+      if constexpr (GAMMA) {
+        const int kr = kr0 + ct * 16 + n;
+        real = kr < gm.K;
+        cid = reg * gm.K + (real ? kr : gm.K - 1);
+      }
       const float* rp = a.rec + (size_t)cid * a.S;
       if constexpr (!kHbar) continue;                      // LINEAR: no hbar operands
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int o = 4 * g + j;
-        const float w = o < a.O ? rp[DC + 1 + o] / a.oscale[o] * sclB : 0.0f;
+        const float w = (o < a.O && real) ? rp[DC + 1 + o] / a.oscale[o] * sclB : 0.0f;
         _Float16 h, l;
         split_static_f16(w, h, l);
         wth[ct][j] = h;
@@ -330,7 +361,7 @@ __global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const
       for (int j = 0; j < 8; ++j) {
         const int k = 8 * g + j;
         const int o = OC ? (k < 30 ? k % 10 : 16) : 8 * (g & 1) + j;
-        const float w = o < a.O ? rp[DC + 1 + o] / a.oscale[o] * sclB : 0.0f;
+        const float w = (o < a.O && real) ? rp[DC + 1 + o] / a.oscale[o] * sclB : 0.0f;
         _Float16 h, l;
         split_static_f16(w, h, l);
         if (OC) wt2[ct][j] = k < 10 ? h : (_Float16)((float)(k < 20 ? h : l) * kVgCrossB);   // exact (power of two) down to the subnormals
@@ -359,9 +390,24 @@ __global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const
   stage(1, 1);
   step_barrier();
   stage(2, 2);
+  // GAMMA: the weights of the lane's 8 queries 16 (j >> 2) + 4 g + (j & 3) of its wave's region, two 16-byte loads a block ahead
+  // (the step barrier's vmcnt(0) covers them)
+  f4_t gmn[2] = {f4_t{0, 0, 0, 0}, f4_t{0, 0, 0, 0}};
+  auto gamma_load = [&](int k) {
+    if (k >= nb || !active) return;
+    const float* gp = gm.gtile + ((size_t)(qb0 + k) * gm.R + reg) * 32 + 4 * g;
+    gmn[0] = *reinterpret_cast<const f4_t*>(gp);
+    gmn[1] = *reinterpret_cast<const f4_t*>(gp + 16);
+  };
+  if constexpr (GAMMA) gamma_load(0);
   int b0 = 0;
   for (int i = 0; i < nb; ++i) {
     const unsigned char* cur = lds + b0 * SLOT;
+    f4_t gmc[2];
+    if constexpr (GAMMA) {
+      gmc[0] = gmn[0]; gmc[1] = gmn[1];
+      gamma_load(i + 1);
+    }
     if (active) {
       float hq[2][8], tq[2][8];                              // P and tts of the lane's 8 queries x 2 centre tiles
 #pragma unroll
@@ -394,7 +440,7 @@ __global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const
 #pragma unroll
           for (int r = 0; r < 4 && kHbar; ++r) {
             if (!OC) hb[ct][r] = __builtin_fmaf(hl[r], kLoScale, hb[ct][r]);
-            if (ET > kVgExpA + kVgExpB) hb[ct][r] *= cE;
+            if (EH > kVgExpA + kVgExpB) hb[ct][r] *= cE;
           }
         }
         float t8[8];
@@ -403,14 +449,15 @@ __global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float P = t8[ct * 4 + r];
+            float P = t8[ct * 4 + r];
+            if constexpr (GAMMA) P *= gmc[s][r];               // query 16 s + 4 g + r
             if constexpr (!kHbar) {
               hq[ct][4 * s + r] = P;
               continue;
             }
             float pw = P;
-            if constexpr (BC == BC_IQ) pw = P * P;
-            if constexpr (BC == BC_IMQ) pw = P * P * P;
+            if constexpr (BC == BC_IQ) pw = P * t8[ct * 4 + r];       // GAMMA: one factor carries the region weight
+            if constexpr (BC == BC_IMQ) pw = P * t8[ct * 4 + r] * t8[ct * 4 + r];
             const float tts = hb[ct][r] * pw;
             // alpha d2 (gaussian: u - 14) resp. d2 / sigma^2 (others: 2^14 u - 1) per pair; the centre's own factor at the end.
             // (sum tts u - 14 sum tts with the sum from the dC product's column of ones saves this instruction and costs a factor
@@ -466,8 +513,13 @@ __global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const
   constexpr int LSR = vg_ls_row(MODE, DC), KB = vg_kernel_row(MODE, DC);
   const int V = KB + a.OP;
   float* dst = a.part + (size_t)by * V * a.Npad;
-  const float wscale = sg * (1.0f / (PS * kWScale));         // s_g / (scale of the basis values x 2^15)
+  const float wscale = sg * (1.0f / (PS * kWScale)) * (GAMMA ? __builtin_ldexpf(1.0f, -vg_gamma_gain(BC)) : 1.0f);   // s_g / (scale of the basis values x 2^15)
   const float xs = __builtin_ldexpf(1.0f, a.hdr->ex - kWExp);   // x' operand: x' 2^-ex 2^15
+  // the centre behind slab column cb + local: its index in the net, -1 for padding (GAMMA: the slabs keep the padded order)
+  auto real_of = [&](int local) {
+    if constexpr (GAMMA) return kr0 + local < gm.K ? reg * gm.K + kr0 + local : -1;
+    else return cb + local < a.N ? cb + local : -1;
+  };
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct) {
     // d log_sigs: the 4 lane groups hold different queries of centre n
@@ -476,15 +528,19 @@ __global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const
     v += __shfl_xor(v, 32);
     const int cid = cb + ct * 16 + n;
     if (kHbar && g == 0 && cid < a.Npad) {
-      const int cc = cid < a.N ? cid : a.N - 1;
+      int cc = cid < a.N ? cid : a.N - 1;
+      bool real = cid < a.N;
+      if constexpr (GAMMA) { const int rc = real_of(ct * 16 + n); real = rc >= 0; cc = real ? rc : 0; }
       const float scr = a.rec[(size_t)cc * a.S + DC];        // gaussian: alpha = -a log2(e) / sigma^2; others: 1 / sigma^2
-      dst[(size_t)LSR * a.Npad + cid] = cid < a.N ? -2.0f * a.sig2[cc] * KT * v / scr : 0.0f;
+      dst[(size_t)LSR * a.Npad + cid] = real ? -2.0f * a.sig2[cc] * KT * v / scr : 0.0f;
     }
     // d kernel: D rows = outputs 4 g + r, column = centre n
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int o = 4 * g + r;
-      if (o < a.OP && cid < a.Npad) dst[(size_t)(KB + o) * a.Npad + cid] = __builtin_fmaf(dWl[ct][r], kLoScale, dW[ct][r]) * wscale;
+      float dw = __builtin_fmaf(dWl[ct][r], kLoScale, dW[ct][r]) * wscale;
+      if constexpr (GAMMA) dw = real_of(ct * 16 + n) >= 0 ? dw : 0.0f;      // a padding centre's column of basis values is not a gradient
+      if (o < a.OP && cid < a.Npad) dst[(size_t)(KB + o) * a.Npad + cid] = dw;
     }
     // d centers: D rows = centres 4 g + r, column n = coordinate (n < DC) / the sum of tt (n = 8)
 #pragma unroll
@@ -494,14 +550,28 @@ __global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const
       const int c2 = cb + ct * 16 + 4 * g + r;
       if (n < DC && c2 < a.Npad) {
         float out = 0.0f;
-        if (c2 < a.N) {
-          const float cp = n < kGramDims ? a.rec[(size_t)c2 * a.S + n] - a.hdr->r[n] : 0.0f;
-          out = -2.0f * a.sig2[c2] * KT * (dv * xs - cp * st);
+        int rc = c2;
+        bool real = c2 < a.N;
+        if constexpr (GAMMA) { rc = real_of(ct * 16 + 4 * g + r); real = rc >= 0; }
+        if (real) {
+          const float cp = n < kGramDims ? a.rec[(size_t)rc * a.S + n] - a.hdr->r[n] : 0.0f;
+          out = -2.0f * a.sig2[rc] * KT * (dv * xs - cp * st);
         }
         dst[(size_t)n * a.Npad + c2] = out;
       }
     }
   }
+}
+
+template <int DC, int BC, bool OC, int MODE>
+__global__ __launch_bounds__(256, vg_waves(MODE, OC)) void rbf_vjp_f16gram(const VjpGArgs a) {
+  vg_body<DC, BC, OC, MODE, false>(a, VjpGGamma{});
+}
+
+// K2g over the padded regions of a net evaluated with caller-provided region weights (irbfn_net_vjp_gamma, IRBFN_VJP_K2G_GAMMA)
+template <int DC, int BC, bool OC>
+__global__ __launch_bounds__(256, IRBFN_K2G_WAVES_GAMMA) void rbf_vjp_f16gram_gamma(const VjpGArgs a, const VjpGGamma gm) {
+  vg_body<DC, BC, OC, VG_ALL, true>(a, gm);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------
@@ -537,16 +607,36 @@ static int launch_vjpg_live_dc(const VjpGArgs& a, int bc, dim3 grid, hipStream_t
   return IRBFN_OK;
 }
 
+template <int DC>
+static int launch_vjpg_gamma_dc(const VjpGArgs& a, const VjpGGamma& gm, int bc, dim3 grid, hipStream_t s) {
+  const size_t lds = (size_t)3 * vg_slot_bytes(VG_ALL);
+#define IRBFN_VG_GAMMA(BCV)                                                                                                     \
+  case BCV:                                                                                                                    \
+    if (a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram_gamma<DC, BCV, true>), grid, dim3(256), lds, s, a, gm);            \
+    else hipLaunchKernelGGL((rbf_vjp_f16gram_gamma<DC, BCV, false>), grid, dim3(256), lds, s, a, gm);                        \
+    break;
+  switch (bc) {
+    IRBFN_VG_GAMMA(BC_GAUSS)
+    IRBFN_VG_GAMMA(BC_IQ)
+    IRBFN_VG_GAMMA(BC_IMQ)
+    default: return IRBFN_ERR_UNSUPPORTED;
+  }
+#undef IRBFN_VG_GAMMA
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
+
 template <int MODE>
 static int launch_vjp_gram_mode(irbfn_net* net, const float* x, const float* gout, int64_t B, unsigned char* qblk, const float* bmax,
-                                int nbmax, float* scales, int* flag, int gen, float* part, int QSB, int Npad, hipStream_t s) {
+                                int nbmax, float* scales, int* flag, int gen, float* part, int QSB, int Npad, hipStream_t s,
+                                const float* gtile = nullptr) {
   const long nqb = (B + 31) / 32;
   const GramHdr* hdr = reinterpret_cast<const GramHdr*>(net->gram_hdr);
   const dim3 pg((unsigned)nqb), pb(192);
 #define IRBFN_VG_PRE(DCV)                                                                                                        \
   case DCV:                                                                                                                     \
     hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<DCV, MODE>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, \
-                       scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass));                            \
+                       scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass, gtile != nullptr), gtile != nullptr ? 1 : 0);  \
     break;
   switch (net->DC) {
     IRBFN_VG_PRE(3) IRBFN_VG_PRE(4) IRBFN_VG_PRE(7) IRBFN_VG_PRE(8)
@@ -562,6 +652,21 @@ static int launch_vjp_gram_mode(irbfn_net* net, const float* x, const float* gou
   a.cstride = gram_chunk_bytes((net->O + 15) / 16);
   a.nchunks = (net->N + 31) / 32;
   a.gscale = gauss_scale(net->basis);
+  if (gtile != nullptr) {
+    if constexpr (MODE == VG_ALL) {
+      const VjpGGamma gm = {gtile, net->R, net->K, gram_gamma_cpr(net)};
+      a.nchunks = gm.R * gm.cpr;                             // the padded chunk order of the images
+      const dim3 gg((a.nchunks + 3) / 4, QSB);
+      switch (net->DC) {
+        case 3: return launch_vjpg_gamma_dc<3>(a, gm, net->bclass, gg, s);
+        case 4: return launch_vjpg_gamma_dc<4>(a, gm, net->bclass, gg, s);
+        case 7: return launch_vjpg_gamma_dc<7>(a, gm, net->bclass, gg, s);
+        case 8: return launch_vjpg_gamma_dc<8>(a, gm, net->bclass, gg, s);
+        default: return IRBFN_ERR_UNSUPPORTED;
+      }
+    }
+    return IRBFN_ERR_BAD_ARG;
+  }
   const dim3 grid((a.nchunks + 3) / 4, QSB);
   switch (net->DC) {
     case 3: return launch_vjpg_live_dc<3, MODE>(a, net->bclass, grid, s);
@@ -587,6 +692,41 @@ int launch_vjp_gram_live(irbfn_net* net, int mode, const float* x, const float* 
     case VG_LINEAR: return launch_vjp_gram_mode<VG_LINEAR>(net, x, gout, B, qblk, bmax, nbmax, scales, flag, gen, part, QSB, Npad, s);
     default: return IRBFN_ERR_BAD_ARG;
   }
+}
+
+// ---- rbf_vjp_f16gram_gamma: caller-provided region weights (irbfn_net_vjp_gamma under IRBFN_VJP_K2G_GAMMA) ------------------
+bool vjpgg_eligible(const irbfn_net* net) { return gram_gamma_eligible(net) && net->DC <= kGramDims; }
+int vjpgg_waves() { return IRBFN_K2G_WAVES_GAMMA; }
+
+// gamma[B][R] -> tiles [query block][region][32] of gamma 2^G (vg_gamma_gain): a block takes 32 queries x 64 regions through LDS,
+// so that the rows are read and the tiles written over consecutive addresses; queries past B hold 0
+__global__ __launch_bounds__(256) void vjp_pack_gamma_tiles_kernel(const float* __restrict__ gamma, float* __restrict__ gtile, long B,
+                                                                   int R, float gain) {
+  __shared__ float t[32][65];
+  const int tid = threadIdx.x;
+  const long q0 = (long)blockIdx.x * 32;
+  const int r0 = blockIdx.y * 64;
+  for (int idx = tid; idx < 32 * 64; idx += 256) {
+    const int q = idx >> 6, r = idx & 63;
+    t[q][r] = (q0 + q < B && r0 + r < R) ? gamma[(q0 + q) * R + r0 + r] * gain : 0.0f;
+  }
+  __syncthreads();
+  float* dst = gtile + ((size_t)blockIdx.x * R + r0) * 32;
+  for (int idx = tid; idx < 32 * 64; idx += 256) {
+    const int r = idx >> 5, q = idx & 31;
+    if (r0 + r < R) dst[(size_t)r * 32 + q] = t[q][r];
+  }
+}
+
+// x, gamma, gout -> slabs part[QSB][V][Npad] in the padded chunk order (Npad >= 32 R cpr); gtile: workspace [nqb][R][32]
+int launch_vjp_gram_gamma(irbfn_net* net, const float* x, const float* gamma, const float* gout, int64_t B, unsigned char* qblk,
+                          float* gtile, const float* bmax, int nbmax, float* scales, int* flag, int gen, float* part, int QSB, int Npad,
+                          hipStream_t s) {
+  const long nqb = (B + 31) / 32;
+  hipLaunchKernelGGL(vjp_pack_gamma_tiles_kernel, dim3((unsigned)nqb, (unsigned)((net->R + 63) / 64)), dim3(256), 0, s, gamma, gtile,
+                     (long)B, net->R, ldexpf(1.0f, vg_gamma_gain(net->bclass)));
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return launch_vjp_gram_mode<VG_ALL>(net, x, gout, B, qblk, bmax, nbmax, scales, flag, gen, part, QSB, Npad, s, gtile);
 }
 
 }  // namespace irbfn

@@ -290,8 +290,8 @@ class WCRBFNet:
         h = self._handle(torch)
         for k, v in opts.items():
             _lib.check(lib.irbfn_net_set_option(h, _lib.OPTIONS[k], int(v)), f"irbfn_net_set_option({k}={v})")
-            if k == "fwd_gamma_kernel":
-                # the option decides which images irbfn_net_set_params packs: the next bind packs again
+            if k == "fwd_gamma_kernel" or (k == "vjp_kernel" and self.num_regions > 1):
+                # the option decides which images irbfn_net_set_params packs (FWDG_K1G, VJP_K2G_GAMMA): the next bind packs again
                 self._bound_fp.pop(torch.cuda.current_device(), None)
         return self
 
