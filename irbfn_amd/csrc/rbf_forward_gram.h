@@ -294,15 +294,16 @@ __device__ __forceinline__ void gram_heads2c(const h4_t& a, const h4_t (&b)[2], 
 
 // the argument of the transcendental for the 2 x 2 tiles (query tile t, centre tile ct) of the chunk image at `buf`: head sum
 // (exact), then the tails
-__device__ __forceinline__ void gram_distances(const unsigned char* buf, int lane, const h4_t (&bhd)[2], const h8_t (&btl)[2][2],
-                                               f4_t (&u)[2][2]) {
+// (`l8`, `l16`: the lane's 8 and 16 bytes at the start of the image, buf + lane * 8 and buf + lane * 16)
+__device__ __forceinline__ void gram_distances_at(const unsigned char* l8, const unsigned char* l16, const h4_t (&bhd)[2],
+                                                  const h8_t (&btl)[2][2], f4_t (&u)[2][2]) {
   h4_t ahd[2];
   h8_t atl[2][2];
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct) {
-    ahd[ct] = *reinterpret_cast<const h4_t*>(buf + ct * 512 + lane * 8);
-    atl[ct][0] = *reinterpret_cast<const h8_t*>(buf + kGramHeadBytes + (ct * 2 + 0) * 1024 + lane * 16);
-    atl[ct][1] = *reinterpret_cast<const h8_t*>(buf + kGramHeadBytes + (ct * 2 + 1) * 1024 + lane * 16);
+    ahd[ct] = *reinterpret_cast<const h4_t*>(l8 + ct * 512);
+    atl[ct][0] = *reinterpret_cast<const h8_t*>(l16 + kGramHeadBytes + (ct * 2 + 0) * 1024);
+    atl[ct][1] = *reinterpret_cast<const h8_t*>(l16 + kGramHeadBytes + (ct * 2 + 1) * 1024);
   }
   gram_heads(ahd, bhd, u);                                     // exact head sums
 #pragma unroll
@@ -312,6 +313,10 @@ __device__ __forceinline__ void gram_distances(const unsigned char* buf, int lan
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct)
         u[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(atl[ct][hf], btl[t][hf], u[t][ct], 0, 0, 0);
+}
+__device__ __forceinline__ void gram_distances(const unsigned char* buf, int lane, const h4_t (&bhd)[2], const h8_t (&btl)[2][2],
+                                               f4_t (&u)[2][2]) {
+  gram_distances_at(buf + lane * 8, buf + lane * 16, bhd, btl, u);
 }
 
 // The same arguments on the VALU from K1h's centre records `recs` of the chunk (a wave with a query outside the box): t16[t * 8 + j] for

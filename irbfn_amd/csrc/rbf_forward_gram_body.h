@@ -88,12 +88,37 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
   // operands of chunk i while later chunks land (end_of_step below).
   unsigned char* ring = lds + (size_t)slice * kGramRing * CB;
   constexpr int NVI = CB / 1024;                             // 7 wave-instructions per chunk image
-  auto stage = [&](int k, int buf) {                         // chunk c0 + k of the slice -> ring slot buf; the QG waves share the copy
+  // The one-region instances carry the address of their refills: a wave requests pieces qg, qg + QG, ... of every chunk image of
+  // its slice, and the chunks are staged in order (k = 0, 1, 2, ... from the prologue on), so gnext is the lane's 16 bytes of piece
+  // qg of the NEXT chunk to stage, advanced by one image per staged chunk: one 64-bit add per chunk where the address built from k
+  // costs a 64-bit multiply-add per chunk and an add per piece.  Past the slice (k >= na) nothing is staged, and nothing after it
+  // either: the pointer stays.  The GAMMA instances, which have no register to spare (they spill already), build it from k.
+  [[maybe_unused]] int npc = 0;                              // pieces of a chunk image this wave requests
+#pragma unroll
+  for (int p = 0; p < NVI; ++p) npc += qg + p * QG < NVI ? 1 : 0;
+  [[maybe_unused]] const unsigned char* gnext = ga.gimg + (size_t)c0 * CB + qg * 1024 + lane * 16;
+  auto stage = [&](int k, int buf) __attribute__((always_inline)) {   // chunk c0 + k of the slice -> ring slot buf; the QG waves share the copy
     if (k >= na) return;
-    const unsigned char* gp = ga.gimg + (size_t)(c0 + k) * CB + lane * 16;
     unsigned char* dst = ring + buf * CB;
-    for (int v = qg; v < NVI; v += QG)
-      __builtin_amdgcn_global_load_lds((gptr_t)(gp + v * 1024), (lptr_t)(dst + v * 1024), 16, 0, 0);
+    if constexpr (GAMMA) {
+      const unsigned char* gp = ga.gimg + (size_t)(c0 + k) * CB + lane * 16;
+      for (int v = qg; v < NVI; v += QG)
+        __builtin_amdgcn_global_load_lds((gptr_t)(gp + v * 1024), (lptr_t)(dst + v * 1024), 16, 0, 0);
+    } else {
+      // piece qg from the pointer itself; QG < 7: the further pieces in a rolled loop, one add each as before (unrolled to
+      // seven pieces with their LDS addresses as constants the ten-step trip wants 70 scalar registers and spills them)
+      if (npc > 0) {
+        const unsigned char* gp = gnext;
+        unsigned char* lp = dst + qg * 1024;
+        __builtin_amdgcn_global_load_lds((gptr_t)gp, (lptr_t)lp, 16, 0, 0);
+        for (int p = 1; p < npc; ++p) {
+          gp += QG * 1024;
+          lp += QG * 1024;
+          __builtin_amdgcn_global_load_lds((gptr_t)gp, (lptr_t)lp, 16, 0, 0);
+        }
+      }
+      gnext += CB;
+    }
   };
   auto step_barrier = [&]() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   auto next3 = [&](int b3) { return b3 == kGramRing - 1 ? 0 : b3 + 1; };
@@ -146,8 +171,9 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
 #ifdef IRBFN_GRAM_STAMPS
   unsigned long long t_refill = 0;                           // s_memtime behind the step barrier, 0 in a step without one
 #endif
-  auto end_of_step = [&](int i, int b0) {
-    if ((i % kGramPer) != kGramPer - 1) return;
+  // par = i % kGramPer, which the caller knows without a division
+  auto end_of_step = [&](int i, int b0, int par) __attribute__((always_inline)) {
+    if (par != kGramPer - 1) return;
     step_barrier();
 #ifdef IRBFN_GRAM_STAMPS
     t_refill = IRBFN_GRAM_T();
@@ -163,11 +189,11 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
 
   f4_t acc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};                // A1: ph * wh
   f4_t acl[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};                // A2: pls * wh + ph * wls
-  auto distances = [&](const unsigned char* buf, f4_t (&u)[2][2]) { gram_distances(buf, lane, bhd, btl, u); };
   // transcendental, hi / lo split and Phi x W of the 16 pairs in t16 with the W operands of chunk `buf`
-  auto products = [&](float (&t16)[16], const unsigned char* buf, auto pre) {
-    const h8_t bh = *reinterpret_cast<const h8_t*>(buf + kGramOpBytes + lane * 16);
-    const h8_t bl = *reinterpret_cast<const h8_t*>(buf + kGramOpBytes + kF16WBytes + lane * 16);
+  // (`l16`: the lane's 16 bytes at the start of the image, buf + lane * 16)
+  auto products = [&](float (&t16)[16], const unsigned char* l16, auto pre) __attribute__((always_inline)) {
+    const h8_t bh = *reinterpret_cast<const h8_t*>(l16 + kGramOpBytes);
+    const h8_t bl = *reinterpret_cast<const h8_t*>(l16 + kGramOpBytes + kF16WBytes);
     pre(t16);                                                // P = 2^kPhiExp * phi for the step's 16 pairs
     if constexpr (GAMMA) {
 #pragma unroll
@@ -196,39 +222,71 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
   gamma_stage(1);
   IRBFN_GRAM_PHASE(GP_LOOP0);
   if (!wave_bad) {
-    // two steps per trip: the distances of chunk i + 1 are issued in front of the VALU work on chunk i
+    // the distances of chunk i + 1 are issued in front of the VALU work on chunk i: ua / ub hold them in turn
     f4_t ua[2][2], ub[2][2];
-    if (na > 0) distances(ring, ua);
+    if (na > 0) gram_distances(ring, lane, bhd, btl, ua);
     // trans16 is inline asm: the hazard recogniser does not see it read MFMA results.  In the loop the 12 distance MFMAs of the
     // next chunk lie in front of it; a slice of ONE chunk reads them right away: explicit wait states, once
     asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-    int b0 = 0;                                              // ring slot of chunk i
     [[maybe_unused]] unsigned long long tph[5] = {0, 0, 0, 0, 0};
-    auto one_step = [&](int i, f4_t (&ucur)[2][2], f4_t (&unxt)[2][2]) {
+    // The lane's two bases into the slice's ring (8-byte head records; 16-byte tail and W records).  The one-region instances
+    // hold them as registers the compiler takes as given: with the slot a constant (below) every LDS read of a step is one of the
+    // two plus an immediate, at most (kGramRing - 1) x 7168 + 6144 -- no vector add per read group.
+    unsigned o8 = (unsigned)(slice * kGramRing * CB) + lane * 8, o16 = (unsigned)(slice * kGramRing * CB) + lane * 16;
+    if constexpr (!GAMMA) asm volatile("" : "+v"(o8), "+v"(o16));
+    const unsigned char* const r8 = lds + o8;
+    const unsigned char* const r16 = lds + o16;
+    static_assert((kGramRing - 1) * CB + kGramOpBytes + kF16WBytes + 16 <= 65536, "the offset field of ds_read has 16 bits");
+    // step i: chunk i in ring slot b0, chunk i + 1 in the next slot; par = i % kGramPer; all: the caller knows i + 1 < na
+    auto one_step = [&](int i, int b0, int par, f4_t (&ucur)[2][2], f4_t (&unxt)[2][2], bool all = false) __attribute__((always_inline)) {
       const int b1 = next3(b0);
       [[maybe_unused]] const unsigned long long t0 = IRBFN_GRAM_T();
-      if (i + 1 < na) distances(ring + b1 * CB, unxt);       // issued in front of the VALU work on chunk i
-      if (i < na) {
+      if (all || i + 1 < na) gram_distances_at(r8 + b1 * CB, r16 + b1 * CB, bhd, btl, unxt);   // issued in front of the VALU work on chunk i
+      if (all || i < na) {
         gamma_read(i);
         float t16[16];
-        products(t16, ring + b0 * CB, [&](float (&o)[16]) { trans16<BC>(ucur, o); });
+        products(t16, r16 + b0 * CB, [&](float (&o)[16]) { trans16<BC>(ucur, o); });
       }
       [[maybe_unused]] const unsigned long long t2 = IRBFN_GRAM_T();
 #ifdef IRBFN_GRAM_STAMPS
       t_refill = 0;
 #endif
-      end_of_step(i, b0);
+      end_of_step(i, b0, par);
       [[maybe_unused]] const unsigned long long t4 = IRBFN_GRAM_T();
 #ifdef IRBFN_GRAM_STAMPS
       // the refill requests behind the barrier (address arithmetic and one LDS-DMA issue per piece) are stamped on their own
       const unsigned long long t3 = t_refill != 0 ? t_refill : t4;
       tph[1] += t2 - t0; tph[2] += t3 - t2; tph[3] += t4 - t3; tph[4] += 1;
 #endif
-      b0 = b1;
     };
-    for (int i = 0; i < nsteps; i += 2) {
-      one_step(i, ua, ub);
-      if (i + 1 < nsteps) one_step(i + 1, ub, ua);
+    static_assert(2 % kGramPer == 0, "a pair of steps is a whole number of barrier periods");
+    int i = 0;
+    // One-region instances: trips of kGramTrip = 2 x kGramRing steps.  After that many the ring slot is 0 again, ua / ub have the
+    // roles of the first step and a barrier period has just ended, so the slot, the roles and the place in the period of each
+    // step of a trip are constants.  A wave takes a trip only while its OWN slice reaches past it (i + kGramTrip < na), so the
+    // steps of a trip ask for no chunk that is not there and carry no branch around their halves: two steps between barriers are
+    // one block of straight code.  Which loop runs a step does not matter to the block: every wave passes the barrier of every
+    // odd step either way.  (The GAMMA instances keep the rolled loop below for all their steps: the long trip costs them
+    // spills.)
+    if constexpr (!GAMMA) {
+      constexpr int kGramTrip = 2 * kGramRing;
+      for (; i + kGramTrip <= nsteps && i + kGramTrip < na; i += kGramTrip) {
+#pragma unroll
+        for (int j = 0; j < kGramTrip; j += 2) {
+          one_step(i + j, j % kGramRing, j % kGramPer, ua, ub, true);
+          one_step(i + j + 1, (j + 1) % kGramRing, (j + 1) % kGramPer, ub, ua, true);
+        }
+      }
+    }
+    // the steps that are left (the end of the slice, a short slice, the steps past a shorter slice), two per trip, from slot 0 on
+    int b0 = 0;                                              // ring slot of chunk i
+    for (; i < nsteps; i += 2) {
+      one_step(i, b0, 0, ua, ub);
+      b0 = next3(b0);
+      if (i + 1 < nsteps) {
+        one_step(i + 1, b0, 1 % kGramPer, ub, ua);
+        b0 = next3(b0);
+      }
     }
 #ifdef IRBFN_GRAM_STAMPS
     if (blockIdx.x < 2 && tid == 0)
@@ -243,9 +301,9 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
         gamma_read(i);
         float t16[16];
         gram_valu_args<DC, BC, GAMMA>(a, qrow, g, reinterpret_cast<const float*>(a.img + (size_t)(c0 + i) * CBL), t16);
-        products(t16, ring + b0 * CB, [&](float (&o)[16]) { trans_block<BC, 16>(o); });
+        products(t16, ring + b0 * CB + lane * 16, [&](float (&o)[16]) { trans_block<BC, 16>(o); });
       }
-      end_of_step(i, b0);
+      end_of_step(i, b0, i % kGramPer);
       b0 = next3(b0);
     }
   }
