@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
+#include "dispatch.h"
 #include "irbfn_hip.h"
 
 namespace irbfn {
@@ -47,6 +50,33 @@ extern thread_local int g_last_hip_error;
       return IRBFN_ERR_HIP;                           \
     }                                                 \
   } while (0)
+
+constexpr int kMaxDevices = 64;     // devices the per-instance launch records cover (more: the attribute is set per launch)
+
+// hipFuncAttributeMaxDynamicSharedMemorySize once per kernel instance and device, not per launch: `set` is the instance's own
+// record of the largest size it has asked for on each device.  Per device because the attribute is the device's (the multi-GPU
+// runs launch the same instance on every card), the size because one instance runs geometries of different LDS; a launch then
+// costs one hipGetDevice (a thread-local read) and one relaxed load.  The saving itself is host time only and is not measured.
+struct DynLdsSet { std::atomic<unsigned> bytes[kMaxDevices]; };
+inline int ensure_dyn_lds(const void* kernel, size_t lds, DynLdsSet* set) {
+  if (lds <= 48 * 1024) return IRBFN_OK;
+  int dev = 0;
+  IRBFN_HIP_CHECK(hipGetDevice(&dev));
+  if (dev >= 0 && dev < kMaxDevices && set->bytes[dev].load(std::memory_order_relaxed) >= lds) return IRBFN_OK;
+  IRBFN_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (dev >= 0 && dev < kMaxDevices) set->bytes[dev].store((unsigned)lds, std::memory_order_relaxed);
+  return IRBFN_OK;
+}
+
+// The one launch of every kernel instance K: raise K's dynamic-LDS cap where this size needs it, launch, check.
+template <auto K, class... Args>
+int launch_kernel(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
+  static DynLdsSet set;
+  if (const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(K), lds, &set); rc != IRBFN_OK) return rc;
+  hipLaunchKernelGGL(K, grid, block, lds, s, args...);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  return IRBFN_OK;
+}
 
 struct GateTables {        // device pointers owned by the descriptor
   const float* lo;         // [nsplit][max_ranges]

@@ -342,19 +342,14 @@ static int launch_kmeans_step(const float* x, const float* c, int32_t* labels, f
   const int64_t wantc = (N + 255) / 256;
   const int nbc = !a.sums ? 0 : (wantc > kKmColBlocks ? kKmColBlocks : (int)wantc);
   a.ncol = nbc;
-  switch (D) {
-#define IRBFN_KM_CASE(d)                                                                                       \
-    case d:                                                                                                    \
-      if (nbc > 0) hipLaunchKernelGGL(kmeans_colmax_kernel<d>, dim3(nbc), dim3(256), 0, s, x, (long)N, a.vec, km_colpart(ws, K, d)); \
-      hipLaunchKernelGGL(kmeans_assign_kernel<d>, dim3(nb), dim3(256), 0, s, a);                               \
-      break;
-    IRBFN_KM_CASE(1) IRBFN_KM_CASE(2) IRBFN_KM_CASE(3) IRBFN_KM_CASE(4) IRBFN_KM_CASE(5) IRBFN_KM_CASE(6) IRBFN_KM_CASE(7)
-    IRBFN_KM_CASE(8) IRBFN_KM_CASE(9) IRBFN_KM_CASE(10) IRBFN_KM_CASE(11) IRBFN_KM_CASE(12) IRBFN_KM_CASE(13)
-    IRBFN_KM_CASE(14) IRBFN_KM_CASE(15) IRBFN_KM_CASE(16)
-#undef IRBFN_KM_CASE
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
+  const int rc = dispatch<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(D, [&](auto d) {
+    if (nbc > 0) {
+      const int rcc = launch_kernel<kmeans_colmax_kernel<d()>>(dim3(nbc), dim3(256), 0, s, x, (long)N, a.vec, km_colpart(ws, K, d()));
+      if (rcc != IRBFN_OK) return rcc;
+    }
+    return launch_kernel<kmeans_assign_kernel<d()>>(dim3(nb), dim3(256), 0, s, a);
+  });
+  if (rc != IRBFN_OK) return rc;
   hipLaunchKernelGGL(kmeans_update_kernel, dim3((K + 255) / 256), dim3(256), 0, s, c, newc, reinterpret_cast<long*>(counts), stats,
                      ws, K, D, a.S, nb);
   IRBFN_HIP_CHECK(hipGetLastError());

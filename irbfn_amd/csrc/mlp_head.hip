@@ -735,16 +735,6 @@ __global__ __launch_bounds__(256) void mlp_head_bwd_reduce_kernel(const float* _
 
 using namespace irbfn;
 
-// Launch a 256-thread head kernel with `lds` bytes of dynamic LDS (more than the default limit: raise the kernel's own first).
-template <typename K, typename... A>
-static int launch_head(K k, unsigned blocks, size_t lds, hipStream_t s, A... args) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }
-  hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, s, args...);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
 // blocks of the two forward kernels: four 32-row tiles (one per wave) at a time, at most 512 blocks
 static unsigned head_tile_blocks(int64_t B) {
   const long tiles = (B + kHeadTR - 1) / kHeadTR;
@@ -762,8 +752,8 @@ extern "C" int irbfn_mlp_head_forward(const float* h1_dev, const float* w2_dev, 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (O <= 16) {                                               // matrix-core head (every model card of the reference: O = 2 or 10)
     const size_t lds = ((size_t)64 * kHeadP + 64 * kHeadGP + 4 * (size_t)kHeadTR * kHeadP) * sizeof(float);
-    return launch_head(mlp_head_fwd_mfma_kernel<64, 64>, head_tile_blocks(B), lds, s, h1_dev, w2_dev, b2_dev, w3_dev, b3_dev, out_dev,
-                       (long)B, O);
+    return launch_kernel<mlp_head_fwd_mfma_kernel<64, 64>>(dim3(head_tile_blocks(B)), dim3(256), lds, s, h1_dev, w2_dev, b2_dev, w3_dev,
+                                                           b3_dev, out_dev, (long)B, O);
   }
   const size_t lds = (size_t)kWave * (64 + 1) * sizeof(float);
   hipLaunchKernelGGL((mlp_head_kernel<64, 64>), dim3((unsigned)((B + kWave - 1) / kWave)), dim3(kWave), lds, s, h1_dev,
@@ -787,8 +777,8 @@ int irbfn::launch_mlp_head_tick(const float* h1, const float* w2, const float* b
   }
   if (states && T * rollout_state_dim(mode) > kHeadP - 1) return IRBFN_ERR_UNSUPPORTED;   // the staging tile: 64 floats per row
   const size_t lds = ((size_t)64 * kHeadP + 64 * kHeadGP + 4 * (size_t)kHeadTickWave) * sizeof(float);
-  return launch_head(mlp_head_tick_kernel<64, 64>, head_tile_blocks(B), lds, s, h1, w2, b2, w3, b3, mirror, state0, dp, controls,
-                     states, (long)B, O, T, mode);
+  return launch_kernel<mlp_head_tick_kernel<64, 64>>(dim3(head_tile_blocks(B)), dim3(256), lds, s, h1, w2, b2, w3, b3, mirror, state0, dp,
+                                                     controls, states, (long)B, O, T, mode);
 }
 
 int irbfn::mlp_head_tick_needs_controls(int O) { return O > 2 * kHeadTickT ? 1 : 0; }
@@ -813,8 +803,8 @@ extern "C" int irbfn_mlp_head_vjp(const float* h1_dev, const float* w2_dev, cons
   size_t lf = 64 * kHeadP + 64 * kHeadGP + 4 * (size_t)(2 * kHeadTR * kHeadP + kHeadTR * kHeadGP);
   const size_t cf = 4 * (size_t)(64 * 64 + 64 + 64 * 16 + 16);
   lf = lf > cf ? lf : cf;
-  const int rc = launch_head(mlp_head_bwd_mfma_kernel<64, 64>, kHeadBwdBlocks, lf * sizeof(float), s, h1_dev, w2_dev, b2_dev, w3_dev,
-                             gout_dev, gh1_dev, static_cast<float*>(ws_dev), (long)B, O);
+  const int rc = launch_kernel<mlp_head_bwd_mfma_kernel<64, 64>>(dim3(kHeadBwdBlocks), dim3(256), lf * sizeof(float), s, h1_dev, w2_dev,
+                                                                 b2_dev, w3_dev, gout_dev, gh1_dev, static_cast<float*>(ws_dev), (long)B, O);
   if (rc != IRBFN_OK) return rc;
   hipLaunchKernelGGL(mlp_head_bwd_reduce_kernel, dim3((n + 63) / 64), dim3(256), 0, s, static_cast<const float*>(ws_dev),
                      kHeadBwdBlocks, n, gw2_dev, gb2_dev, gw3_dev, gb3_dev, H1 * H2, H2, H2 * O);

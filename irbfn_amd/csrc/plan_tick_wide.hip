@@ -22,50 +22,6 @@ __global__ __launch_bounds__(512) void rbf_tick_f16gram_wide(const GramArgs a, c
   wide_gram_body<DC, BC, NT, MODE>(a, r, lds);
 }
 
-template <int BC, int MODE>
-static int launch_gtick_inst(const GramArgs& a, const F16Roll& r, int grid, int block, size_t lds, hipStream_t s) {
-  auto k = rbf_tick_f16gram_wide<7, BC, 7, MODE>;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, s, a, r);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-template <int MODE>
-static int launch_gtick_bc(int bc, const GramArgs& a, const F16Roll& r, int grid, int block, size_t lds, hipStream_t s) {
-  switch (bc) {
-    case BC_GAUSS: return launch_gtick_inst<BC_GAUSS, MODE>(a, r, grid, block, lds, s);
-    case BC_IQ: return launch_gtick_inst<BC_IQ, MODE>(a, r, grid, block, lds, s);
-    case BC_IMQ: return launch_gtick_inst<BC_IMQ, MODE>(a, r, grid, block, lds, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
-template <int BC, int MODE>
-static int launch_tick_inst(const F16Args& a, const F16Roll& r, int grid, int block, size_t lds, hipStream_t s) {
-  auto k = rbf_tick_f16mfma_wide<7, BC, 7, MODE>;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, s, a, r);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-template <int MODE>
-static int launch_tick_bc(int bc, const F16Args& a, const F16Roll& r, int grid, int block, size_t lds, hipStream_t s) {
-  switch (bc) {
-    case BC_GAUSS: return launch_tick_inst<BC_GAUSS, MODE>(a, r, grid, block, lds, s);
-    case BC_IQ: return launch_tick_inst<BC_IQ, MODE>(a, r, grid, block, lds, s);
-    case BC_IMQ: return launch_tick_inst<BC_IMQ, MODE>(a, r, grid, block, lds, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
 // is the one-launch tick compiled for this net / horizon / mode?
 bool tick_wide_compiled(const irbfn_net* net, int mode, int T) {
   if (mode != IRBFN_ROLLOUT_ST_SELECT && mode != IRBFN_ROLLOUT_ST_KS) return false;
@@ -98,17 +54,22 @@ int launch_tick_wide(irbfn_net* net, const LaunchPlan& p, const float* x, const 
   r.state0 = state0; r.states = states; r.mirror = mirror; r.T = T; r.dp = dp;
   r.wlds = (int)tick_out_floats();
   const bool ks = p.mode == IRBFN_ROLLOUT_ST_KS;
+  const dim3 grid(p.grid), block(p.block);
   if (p.kind == LK_TICK_K1G_WIDE) {                // K1g's wide body: the distances on the matrix cores as well
     GramArgs a;
     gram_fill_args(net, x, controls, B, p.S, p.QG, &a);
-    return ks ? launch_gtick_bc<IRBFN_ROLLOUT_ST_KS>(net->bclass, a, r, p.grid, p.block, p.lds, s)
-              : launch_gtick_bc<IRBFN_ROLLOUT_ST_SELECT>(net->bclass, a, r, p.grid, p.block, p.lds, s);
+    return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+      return ks ? launch_kernel<rbf_tick_f16gram_wide<7, bc(), 7, IRBFN_ROLLOUT_ST_KS>>(grid, block, p.lds, s, a, r)
+                : launch_kernel<rbf_tick_f16gram_wide<7, bc(), 7, IRBFN_ROLLOUT_ST_SELECT>>(grid, block, p.lds, s, a, r);
+    });
   }
   F16Args a;
   a.x = x; a.img = net->f16_img; a.oscale = net->f16_oscale; a.bias = net->bias; a.out = controls; a.gate = net->gate();
   a.B = (long)B; a.Dreal = net->D; a.O = net->O; a.nchunks = (net->N + kF16Chunk - 1) / kF16Chunk; a.S = p.S; a.QG = p.QG;
-  return ks ? launch_tick_bc<IRBFN_ROLLOUT_ST_KS>(net->bclass, a, r, p.grid, p.block, p.lds, s)
-            : launch_tick_bc<IRBFN_ROLLOUT_ST_SELECT>(net->bclass, a, r, p.grid, p.block, p.lds, s);
+  return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+    return ks ? launch_kernel<rbf_tick_f16mfma_wide<7, bc(), 7, IRBFN_ROLLOUT_ST_KS>>(grid, block, p.lds, s, a, r)
+              : launch_kernel<rbf_tick_f16mfma_wide<7, bc(), 7, IRBFN_ROLLOUT_ST_SELECT>>(grid, block, p.lds, s, a, r);
+  });
 }
 
 }  // namespace irbfn

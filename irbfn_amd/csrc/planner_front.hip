@@ -213,15 +213,6 @@ __global__ __launch_bounds__(64) void lut_nearest_final_kernel(const float* __re
     for (int o = lane; o < OW; o += 64) out[b * OW + o] = none ? NAN : table[bi * OW + o];
 }
 
-template <int D>
-static int nearest_launch(const float* inputs, const float* x, float* pd, long* pi, long N, long B, int nblocks,
-                          hipStream_t s) {
-  constexpr int QT = 8;
-  hipLaunchKernelGGL((lut_nearest_kernel<D, QT>), dim3((unsigned)nblocks, (unsigned)((B + QT - 1) / QT)), dim3(256), 0, s,
-                     inputs, x, pd, pi, N, B, nblocks);
-  return IRBFN_OK;
-}
-
 }  // namespace irbfn
 
 using namespace irbfn;
@@ -436,14 +427,12 @@ int irbfn_lut_nearest(const float* inputs_dev, const float* table_dev, const flo
   long* pi = reinterpret_cast<long*>(reinterpret_cast<char*>(ws_dev) + (size_t)B * cap * sizeof(float));
   // 8-byte alignment of the index slab: B * cap * 4 is a multiple of 8 because cap is even
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (D) {
-    case 3: nearest_launch<3>(inputs_dev, x_dev, pd, pi, N, B, nblocks, s); break;
-    case 4: nearest_launch<4>(inputs_dev, x_dev, pd, pi, N, B, nblocks, s); break;
-    case 7: nearest_launch<7>(inputs_dev, x_dev, pd, pi, N, B, nblocks, s); break;
-    case 8: nearest_launch<8>(inputs_dev, x_dev, pd, pi, N, B, nblocks, s); break;
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
+  constexpr int QT = 8;
+  const int rc = dispatch<3, 4, 7, 8>(D, [&](auto d) {
+    return launch_kernel<lut_nearest_kernel<d(), QT>>(dim3((unsigned)nblocks, (unsigned)((B + QT - 1) / QT)), dim3(256), 0, s, inputs_dev,
+                                                     x_dev, pd, pi, (long)N, (long)B, nblocks);
+  });
+  if (rc != IRBFN_OK) return rc;
   hipLaunchKernelGGL(lut_nearest_final_kernel, dim3((unsigned)B), dim3(64), 0, s, pd, pi, nblocks, table_dev,
                      reinterpret_cast<long*>(idx_dev), dist_dev, out_dev, OW);
   IRBFN_HIP_CHECK(hipGetLastError());

@@ -10,10 +10,10 @@
 
 namespace irbfn {
 
-int launch_forward_d3(const FwdArgs&, int, int, int, bool, bool, int, size_t, hipStream_t, int*);
-int launch_forward_d4(const FwdArgs&, int, int, int, bool, bool, int, size_t, hipStream_t, int*);
-int launch_forward_d7(const FwdArgs&, int, int, int, bool, bool, int, size_t, hipStream_t, int*);
-int launch_forward_d8(const FwdArgs&, int, int, int, bool, bool, int, size_t, hipStream_t, int*);
+int launch_forward_d3(const FwdArgs&, int, int, int, bool, bool, int, size_t, hipStream_t);
+int launch_forward_d4(const FwdArgs&, int, int, int, bool, bool, int, size_t, hipStream_t);
+int launch_forward_d7(const FwdArgs&, int, int, int, bool, bool, int, size_t, hipStream_t);
+int launch_forward_d8(const FwdArgs&, int, int, int, bool, bool, int, size_t, hipStream_t);
 
 static const int kCompiledOP[] = {2, 4, 5, 8, 10, 16, 32, 64, 100, 128};
 
@@ -132,7 +132,7 @@ static LaunchPlan plan_qlane(const irbfn_net* net, int64_t B, bool gated, bool r
   // --- Q: two queries per lane halve the scalar-stream traffic per pair, but the kernel is VALU-issue
   // bound and more resident waves hide the scalar-load latency better (measured: Q=1,NW=16 152 us vs
   // Q=2,NW=16 175 us at cfg-2), so Q = 2 only once Q = 1 alone over-subscribes the chip.  The Q = 2 instances exist for
-  // the fast bases only (launch_bc, rbf_forward_kernels.hip): generic bases stay at Q = 1 at every B.
+  // the fast bases only (launch_forward_d<D>, rbf_forward_kernels.hip): generic bases stay at Q = 1 at every B.
   int Q = 1;
   const bool q2_compiled = (OP == 2 || OP == 5 || OP == 10) && net->bclass != BC_GENERIC;
   if (q2_compiled && B >= (int64_t)kWave * 32768) Q = 2;
@@ -535,12 +535,11 @@ static void fill_args(irbfn_net* net, FwdArgs& a, const float* x, float* out, in
 }
 
 static int launch_qlane(irbfn_net* net, const LaunchPlan& p, const FwdArgs& a, hipStream_t s) {
-  int grid = 0;
   switch (net->DC) {
-    case 3: return launch_forward_d3(a, net->OP, p.Q, net->bclass, p.gated, p.roll, p.nw, p.lds, s, &grid);
-    case 4: return launch_forward_d4(a, net->OP, p.Q, net->bclass, p.gated, p.roll, p.nw, p.lds, s, &grid);
-    case 7: return launch_forward_d7(a, net->OP, p.Q, net->bclass, p.gated, p.roll, p.nw, p.lds, s, &grid);
-    case 8: return launch_forward_d8(a, net->OP, p.Q, net->bclass, p.gated, p.roll, p.nw, p.lds, s, &grid);
+    case 3: return launch_forward_d3(a, net->OP, p.Q, net->bclass, p.gated, p.roll, p.nw, p.lds, s);
+    case 4: return launch_forward_d4(a, net->OP, p.Q, net->bclass, p.gated, p.roll, p.nw, p.lds, s);
+    case 7: return launch_forward_d7(a, net->OP, p.Q, net->bclass, p.gated, p.roll, p.nw, p.lds, s);
+    case 8: return launch_forward_d8(a, net->OP, p.Q, net->bclass, p.gated, p.roll, p.nw, p.lds, s);
     default: return IRBFN_ERR_UNSUPPORTED;
   }
 }

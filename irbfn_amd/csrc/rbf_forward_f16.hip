@@ -389,44 +389,6 @@ size_t f16_image_bytes(const irbfn_net* net) {
   return (size_t)nchunks * f16_chunk_bytes(net->DC, f16_nt(net));
 }
 
-template <int DC, int NT>
-static int launch_f16w_bc(const F16Args& a, int bc, int grid, int block, size_t lds, bool pipe, hipStream_t s) {
-#define IRBFN_WCASE(BCV)                                                                                      \
-  case BCV: {                                                                                                 \
-    auto k = pipe ? rbf_fwd_f16mfma_wide_pipe<DC, BCV, NT> : rbf_fwd_f16mfma_wide<DC, BCV, NT>;               \
-    if (lds > 48 * 1024) {                                                                                    \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                    \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-      if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }                               \
-    }                                                                                                         \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, s, a);                                                \
-    break;                                                                                                    \
-  }
-  switch (bc) {
-    IRBFN_WCASE(BC_GAUSS)
-    IRBFN_WCASE(BC_IQ)
-    IRBFN_WCASE(BC_IMQ)
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-#undef IRBFN_WCASE
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-template <int DC>
-static int launch_f16w_dc(const F16Args& a, int NT, int bc, int grid, int block, size_t lds, bool pipe, hipStream_t s) {
-  switch (NT) {
-    case 2: return launch_f16w_bc<DC, 2>(a, bc, grid, block, lds, pipe, s);
-    case 3: return launch_f16w_bc<DC, 3>(a, bc, grid, block, lds, pipe, s);
-    case 4: return launch_f16w_bc<DC, 4>(a, bc, grid, block, lds, pipe, s);
-    case 5: return launch_f16w_bc<DC, 5>(a, bc, grid, block, lds, pipe, s);
-    case 6: return launch_f16w_bc<DC, 6>(a, bc, grid, block, lds, pipe, s);
-    case 7: return launch_f16w_bc<DC, 7>(a, bc, grid, block, lds, pipe, s);
-    case 8: return launch_f16w_bc<DC, 8>(a, bc, grid, block, lds, pipe, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
 // final block geometry of the wide kernels and the choice between them: the pipelined kernel (kWideRing chunk buffers
 // per slice) wherever its ring fits the 160 KB of LDS
 void f16_wide_normalize(const irbfn_net* net, int* SW, int* QG, bool* pipe) {
@@ -452,43 +414,15 @@ static int launch_forward_f16_wide(irbfn_net* net, const LaunchPlan& p, const fl
   const int NT = f16_nt(net);
   F16Args a;
   f16_fill_args(net, p, x, out, B, &a);
-  switch (net->DC) {
-    case 3: return launch_f16w_dc<3>(a, NT, net->bclass, p.grid, p.block, p.lds, p.pipe, s);
-    case 4: return launch_f16w_dc<4>(a, NT, net->bclass, p.grid, p.block, p.lds, p.pipe, s);
-    case 7: return launch_f16w_dc<7>(a, NT, net->bclass, p.grid, p.block, p.lds, p.pipe, s);
-    case 8: return launch_f16w_dc<8>(a, NT, net->bclass, p.grid, p.block, p.lds, p.pipe, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
-template <int DC, int TERMS, bool BF = false>
-static int launch_f16_bc(const F16Args& a, int bc, int grid, int block, size_t lds, hipStream_t s) {
-  switch (bc) {
-    case BC_GAUSS: hipLaunchKernelGGL((rbf_fwd_f16mfma<DC, BC_GAUSS, TERMS, BF>), dim3(grid), dim3(block), lds, s, a); break;
-    case BC_IQ: hipLaunchKernelGGL((rbf_fwd_f16mfma<DC, BC_IQ, TERMS, BF>), dim3(grid), dim3(block), lds, s, a); break;
-    case BC_IMQ: hipLaunchKernelGGL((rbf_fwd_f16mfma<DC, BC_IMQ, TERMS, BF>), dim3(grid), dim3(block), lds, s, a); break;
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-template <int DC>
-static int launch_f16_dc(const F16Args& a, int terms, int bc, int grid, int block, size_t lds, hipStream_t s) {
-  if (terms == 2) return launch_f16_bc<DC, 1, true>(a, bc, grid, block, lds, s);       // plain bf16 operands
-  return terms == 1 ? launch_f16_bc<DC, 1>(a, bc, grid, block, lds, s) : launch_f16_bc<DC, 3>(a, bc, grid, block, lds, s);
-}
-
-template <int DC>
-static int launch_tick_narrow_bc(const F16Args& a, const F16Roll& rl, int mode, int bc, int grid, int block, size_t lds, hipStream_t s) {
-  switch (bc) {
-    case BC_GAUSS: hipLaunchKernelGGL((rbf_tick_f16mfma<DC, BC_GAUSS>), dim3(grid), dim3(block), lds, s, a, rl, mode); break;
-    case BC_IQ: hipLaunchKernelGGL((rbf_tick_f16mfma<DC, BC_IQ>), dim3(grid), dim3(block), lds, s, a, rl, mode); break;
-    case BC_IMQ: hipLaunchKernelGGL((rbf_tick_f16mfma<DC, BC_IMQ>), dim3(grid), dim3(block), lds, s, a, rl, mode); break;
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
+  const dim3 grid(p.grid), block(p.block);
+  return dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    return dispatch<2, 3, 4, 5, 6, 7, 8>(NT, [&](auto nt) {
+      return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+        return p.pipe ? launch_kernel<rbf_fwd_f16mfma_wide_pipe<dc(), bc(), nt()>>(grid, block, p.lds, s, a)
+                      : launch_kernel<rbf_fwd_f16mfma_wide<dc(), bc(), nt()>>(grid, block, p.lds, s, a);
+      });
+    });
+  });
 }
 
 // is the one-launch tick of a narrow net compiled for this net / mode / horizon?
@@ -514,21 +448,25 @@ int launch_tick_f16_narrow(irbfn_net* net, const LaunchPlan& p, const float* x, 
   f16_fill_args(net, p, x, controls, B, &a);
   F16Roll rl;
   rl.state0 = state0; rl.states = states; rl.mirror = mirror; rl.T = T; rl.wlds = 0; rl.dp = dp;
-  return net->DC == 7 ? launch_tick_narrow_bc<7>(a, rl, p.mode, net->bclass, p.grid, p.block, p.lds, s)
-                      : launch_tick_narrow_bc<8>(a, rl, p.mode, net->bclass, p.grid, p.block, p.lds, s);
+  return dispatch<7, 8>(net->DC, [&](auto dc) {
+    return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+      return launch_kernel<rbf_tick_f16mfma<dc(), bc()>>(dim3(p.grid), dim3(p.block), p.lds, s, a, rl, p.mode);
+    });
+  });
 }
 
 int launch_forward_f16(irbfn_net* net, const LaunchPlan& p, const float* x, float* out, int64_t B, hipStream_t s) {
   if (p.kind == LK_K1H_WIDE) return launch_forward_f16_wide(net, p, x, out, B, s);
   F16Args a;
   f16_fill_args(net, p, x, out, B, &a);
-  switch (net->DC) {
-    case 3: return launch_f16_dc<3>(a, p.terms, net->bclass, p.grid, p.block, p.lds, s);
-    case 4: return launch_f16_dc<4>(a, p.terms, net->bclass, p.grid, p.block, p.lds, s);
-    case 7: return launch_f16_dc<7>(a, p.terms, net->bclass, p.grid, p.block, p.lds, s);
-    case 8: return launch_f16_dc<8>(a, p.terms, net->bclass, p.grid, p.block, p.lds, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
+  const dim3 grid(p.grid), block(p.block);
+  return dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+      if (p.terms == 2) return launch_kernel<rbf_fwd_f16mfma<dc(), bc(), 1, true>>(grid, block, p.lds, s, a);   // plain bf16 operands
+      return p.terms == 1 ? launch_kernel<rbf_fwd_f16mfma<dc(), bc(), 1>>(grid, block, p.lds, s, a)
+                          : launch_kernel<rbf_fwd_f16mfma<dc(), bc(), 3>>(grid, block, p.lds, s, a);
+    });
+  });
 }
 
 }  // namespace irbfn

@@ -37,13 +37,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include <atomic>
-
 #include "rbf_forward_gram_body.h"
 
 namespace irbfn {
-
-constexpr int kMaxDevices = 64;     // devices the per-instance launch records cover (more: the attribute is set per launch)
 
 template <int DC, int BC>
 __global__ __launch_bounds__(1024, IRBFN_GRAM_WAVES) void rbf_fwd_f16gram(const GramArgs ga) {
@@ -78,42 +74,6 @@ extern "C" int irbfn_debug_gram_stamps(unsigned long long* out64) {
 }
 #endif
 
-// hipFuncAttributeMaxDynamicSharedMemorySize once per kernel instance and device, not per launch: `set` is the instance's own
-// record of the largest size it has asked for on each device.  Per device because the attribute is the device's (the multi-GPU
-// runs launch the same instance on every card), the size because one instance runs geometries of different LDS; a launch then
-// costs one hipGetDevice (a thread-local read) and one relaxed load.  The saving itself is host time only and is not measured.
-struct DynLdsSet { std::atomic<unsigned> bytes[kMaxDevices]; };
-static int ensure_dyn_lds(const void* kernel, size_t lds, DynLdsSet* set) {
-  if (lds <= 48 * 1024) return IRBFN_OK;
-  int dev = 0;
-  IRBFN_HIP_CHECK(hipGetDevice(&dev));
-  if (dev >= 0 && dev < kMaxDevices && set->bytes[dev].load(std::memory_order_relaxed) >= lds) return IRBFN_OK;
-  IRBFN_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if (dev >= 0 && dev < kMaxDevices) set->bytes[dev].store((unsigned)lds, std::memory_order_relaxed);
-  return IRBFN_OK;
-}
-
-template <int DC>
-static int launch_gram_bc(const GramArgs& a, int bc, int grid, int block, size_t lds, hipStream_t s) {
-#define IRBFN_GCASE(BCV)                                                                                      \
-  case BCV: {                                                                                                 \
-    auto k = rbf_fwd_f16gram<DC, BCV>;                                                                        \
-    static DynLdsSet set;                                                                                     \
-    if (const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k), lds, &set); rc != IRBFN_OK) return rc; \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, s, a);                                                \
-    break;                                                                                                    \
-  }
-  switch (bc) {
-    IRBFN_GCASE(BC_GAUSS)
-    IRBFN_GCASE(BC_IQ)
-    IRBFN_GCASE(BC_IMQ)
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-#undef IRBFN_GCASE
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
 // S centre slices x QG query groups of 32 per block (tick: the one-launch tick's control and state tiles on top)
 size_t gram_lds_bytes(int S, int QG, bool tick, bool gamma) {
   size_t ring = (size_t)S * kGramRing * kGramChunkBytes;
@@ -129,34 +89,11 @@ int launch_forward_gram(irbfn_net* net, const LaunchPlan& p, const float* x, flo
   if (p.kind == LK_K1G_WIDE) return launch_forward_gram_wide(net, p, x, out, B, s);
   GramArgs a;
   gram_fill_args(net, x, out, B, p.S, p.QG, &a);
-  switch (net->DC) {
-    case 3: return launch_gram_bc<3>(a, net->bclass, p.grid, p.block, p.lds, s);
-    case 4: return launch_gram_bc<4>(a, net->bclass, p.grid, p.block, p.lds, s);
-    case 7: return launch_gram_bc<7>(a, net->bclass, p.grid, p.block, p.lds, s);
-    case 8: return launch_gram_bc<8>(a, net->bclass, p.grid, p.block, p.lds, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
-template <int DC>
-static int launch_tick_gram_bc(const GramArgs& a, const F16Roll& rl, int mode, int bc, int grid, int block, size_t lds, hipStream_t s) {
-#define IRBFN_GCASE(BCV)                                                                                      \
-  case BCV: {                                                                                                 \
-    auto k = rbf_tick_f16gram<DC, BCV>;                                                                       \
-    static DynLdsSet set;                                                                                     \
-    if (const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k), lds, &set); rc != IRBFN_OK) return rc; \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, s, a, rl, mode);                                      \
-    break;                                                                                                    \
-  }
-  switch (bc) {
-    IRBFN_GCASE(BC_GAUSS)
-    IRBFN_GCASE(BC_IQ)
-    IRBFN_GCASE(BC_IMQ)
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-#undef IRBFN_GCASE
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
+  return dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+      return launch_kernel<rbf_fwd_f16gram<dc(), bc()>>(dim3(p.grid), dim3(p.block), p.lds, s, a);
+    });
+  });
 }
 
 // The one-launch planning tick of a narrow net on K1g (rbf_tick_f16gram)
@@ -166,8 +103,11 @@ int launch_tick_gram_narrow(irbfn_net* net, const LaunchPlan& p, const float* x,
   gram_fill_args(net, x, controls, B, p.S, p.QG, &a);
   F16Roll rl;
   rl.state0 = state0; rl.states = states; rl.mirror = mirror; rl.T = T; rl.wlds = 0; rl.dp = dp;
-  return net->DC == 7 ? launch_tick_gram_bc<7>(a, rl, p.mode, net->bclass, p.grid, p.block, p.lds, s)
-                      : launch_tick_gram_bc<8>(a, rl, p.mode, net->bclass, p.grid, p.block, p.lds, s);
+  return dispatch<7, 8>(net->DC, [&](auto dc) {
+    return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+      return launch_kernel<rbf_tick_f16gram<dc(), bc()>>(dim3(p.grid), dim3(p.block), p.lds, s, a, rl, p.mode);
+    });
+  });
 }
 
 }  // namespace irbfn

@@ -84,49 +84,16 @@ static void gamma_fill_args(const irbfn_net* net, const float* x, const float* g
   a->nsteps = gram_nsteps(a->f.nchunks, S);
 }
 
-template <typename K, typename... Args>
-static int launch_gg(K k, int grid, int block, size_t lds, hipStream_t s, Args... args) {
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, s, args...);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-template <int DC>
-static int launch_gg_fwd(const GramArgs& a, const GramGamma& gm, int bc, const LaunchPlan& p, hipStream_t s) {
-  switch (bc) {
-    case BC_GAUSS: return launch_gg(rbf_fwd_f16gram_gamma<DC, BC_GAUSS>, p.grid, p.block, p.lds, s, a, gm);
-    case BC_IQ: return launch_gg(rbf_fwd_f16gram_gamma<DC, BC_IQ>, p.grid, p.block, p.lds, s, a, gm);
-    case BC_IMQ: return launch_gg(rbf_fwd_f16gram_gamma<DC, BC_IMQ>, p.grid, p.block, p.lds, s, a, gm);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
-template <int DC>
-static int launch_gg_tick(const GramArgs& a, const GramGamma& gm, const F16Roll& rl, int bc, const LaunchPlan& p, hipStream_t s) {
-  switch (bc) {
-    case BC_GAUSS: return launch_gg(rbf_tick_f16gram_gamma<DC, BC_GAUSS>, p.grid, p.block, p.lds, s, a, gm, rl, p.mode);
-    case BC_IQ: return launch_gg(rbf_tick_f16gram_gamma<DC, BC_IQ>, p.grid, p.block, p.lds, s, a, gm, rl, p.mode);
-    case BC_IMQ: return launch_gg(rbf_tick_f16gram_gamma<DC, BC_IMQ>, p.grid, p.block, p.lds, s, a, gm, rl, p.mode);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
 int launch_forward_gram_gamma(irbfn_net* net, const LaunchPlan& p, const float* x, const float* gamma, float* out, int64_t B,
                               hipStream_t s) {
   GramArgs a;
   GramGamma gm;
   gamma_fill_args(net, x, gamma, out, B, p.S, p.QG, &a, &gm);
-  switch (net->DC) {
-    case 3: return launch_gg_fwd<3>(a, gm, net->bclass, p, s);
-    case 4: return launch_gg_fwd<4>(a, gm, net->bclass, p, s);
-    case 7: return launch_gg_fwd<7>(a, gm, net->bclass, p, s);
-    case 8: return launch_gg_fwd<8>(a, gm, net->bclass, p, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
+  return dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+      return launch_kernel<rbf_fwd_f16gram_gamma<dc(), bc()>>(dim3(p.grid), dim3(p.block), p.lds, s, a, gm);
+    });
+  });
 }
 
 // The one-launch planning tick (rbf_tick_f16gram_gamma): d = 7 or 8, as tick_narrow_compiled says
@@ -137,7 +104,11 @@ int launch_tick_gram_gamma(irbfn_net* net, const LaunchPlan& p, const float* x, 
   gamma_fill_args(net, x, gamma, controls, B, p.S, p.QG, &a, &gm);
   F16Roll rl;
   rl.state0 = state0; rl.states = states; rl.mirror = mirror; rl.T = T; rl.wlds = 0; rl.dp = dp;
-  return net->DC == 7 ? launch_gg_tick<7>(a, gm, rl, net->bclass, p, s) : launch_gg_tick<8>(a, gm, rl, net->bclass, p, s);
+  return dispatch<7, 8>(net->DC, [&](auto dc) {
+    return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+      return launch_kernel<rbf_tick_f16gram_gamma<dc(), bc()>>(dim3(p.grid), dim3(p.block), p.lds, s, a, gm, rl, p.mode);
+    });
+  });
 }
 
 }  // namespace irbfn

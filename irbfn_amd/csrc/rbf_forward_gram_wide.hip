@@ -11,30 +11,6 @@ __global__ __launch_bounds__(512) void rbf_fwd_f16gram_wide(const GramArgs ga) {
   wide_gram_body<DC, BC, NT, -1>(ga, F16Roll{}, lds);
 }
 
-template <int DC, int NT>
-static int launch_gw_bc(const GramArgs& a, int bc, int grid, int block, size_t lds, hipStream_t s) {
-#define IRBFN_GWCASE(BCV)                                                                                     \
-  case BCV: {                                                                                                 \
-    auto k = rbf_fwd_f16gram_wide<DC, BCV, NT>;                                                                \
-    if (lds > 48 * 1024) {                                                                                    \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                    \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-      if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }                               \
-    }                                                                                                         \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, s, a);                                                \
-    break;                                                                                                    \
-  }
-  switch (bc) {
-    IRBFN_GWCASE(BC_GAUSS)
-    IRBFN_GWCASE(BC_IQ)
-    IRBFN_GWCASE(BC_IMQ)
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-#undef IRBFN_GWCASE
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
 // the rings of SW slices, three chunk images each
 size_t gram_wide_ring_bytes(const irbfn_net* net, int SW) { return (size_t)SW * 3 * gram_chunk_bytes((net->O + 15) / 16); }
 
@@ -68,21 +44,13 @@ int launch_forward_gram_wide(irbfn_net* net, const LaunchPlan& p, const float* x
   const int NT = (net->O + 15) / 16;
   GramArgs a;
   gram_fill_args(net, x, out, B, p.S, p.QG, &a);
-  int rc;
-#define IRBFN_GW_NT(DCV)                                                                      \
-  switch (NT) {                                                                               \
-    case 2: rc = launch_gw_bc<DCV, 2>(a, net->bclass, p.grid, p.block, p.lds, s); break;      \
-    case 3: rc = launch_gw_bc<DCV, 3>(a, net->bclass, p.grid, p.block, p.lds, s); break;      \
-    case 4: rc = launch_gw_bc<DCV, 4>(a, net->bclass, p.grid, p.block, p.lds, s); break;      \
-    case 5: rc = launch_gw_bc<DCV, 5>(a, net->bclass, p.grid, p.block, p.lds, s); break;      \
-    case 6: rc = launch_gw_bc<DCV, 6>(a, net->bclass, p.grid, p.block, p.lds, s); break;      \
-    case 7: rc = launch_gw_bc<DCV, 7>(a, net->bclass, p.grid, p.block, p.lds, s); break;      \
-    case 8: rc = launch_gw_bc<DCV, 8>(a, net->bclass, p.grid, p.block, p.lds, s); break;      \
-    default: rc = IRBFN_ERR_UNSUPPORTED;                                                      \
-  }
-  if (net->DC == 7) { IRBFN_GW_NT(7) } else { IRBFN_GW_NT(8) }
-#undef IRBFN_GW_NT
-  return rc;
+  return dispatch<7, 8>(net->DC, [&](auto dc) {
+    return dispatch<2, 3, 4, 5, 6, 7, 8>(NT, [&](auto nt) {
+      return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+        return launch_kernel<rbf_fwd_f16gram_wide<dc(), bc(), nt()>>(dim3(p.grid), dim3(p.block), p.lds, s, a);
+      });
+    });
+  });
 }
 
 }  // namespace irbfn

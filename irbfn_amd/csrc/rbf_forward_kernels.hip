@@ -309,70 +309,31 @@ __global__ __launch_bounds__((OP * Q > 48) ? 512 : 1024) void rbf_fwd_qlane(cons
 // ------------------------------------------------------------------------------------------------
 // host-side dispatch for this D
 // ------------------------------------------------------------------------------------------------
-template <int D, int OP, int Q, int BC, bool GATED, bool ROLL>
-static int launch_one(const FwdArgs& a, int nw, size_t lds_bytes, hipStream_t s, int* grid_out) {
-  constexpr int ROWS = kWave * Q;
-  const long tiles = (a.B + ROWS - 1) / ROWS;
-  auto kern = rbf_fwd_qlane<D, OP, Q, BC, GATED, ROLL>;
-  if (lds_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(nw * kWave), lds_bytes, s, a);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  *grid_out = (int)tiles;
-  return IRBFN_OK;
-}
-
-template <int D, int OP, int Q, bool ROLL>
-static int launch_bc(const FwdArgs& a, int bc, bool gated, int nw, size_t lds, hipStream_t s, int* g) {
-#define IRBFN_CASE(BCV)                                                                   \
-  case BCV:                                                                               \
-    return gated ? launch_one<D, OP, Q, BCV, true, ROLL>(a, nw, lds, s, g)                \
-                 : launch_one<D, OP, Q, BCV, false, ROLL>(a, nw, lds, s, g);
-  switch (bc) {
-    IRBFN_CASE(BC_GAUSS)
-    IRBFN_CASE(BC_IQ)
-    IRBFN_CASE(BC_IMQ)
-    case BC_GENERIC:
-      if constexpr (ROLL) return IRBFN_ERR_UNSUPPORTED;   // fused roll-out: fast bases only
-      else if (Q != 1) return IRBFN_ERR_UNSUPPORTED;
-      else
-        return gated ? launch_one<D, OP, 1, BC_GENERIC, true, false>(a, nw, lds, s, g)
-                     : launch_one<D, OP, 1, BC_GENERIC, false, false>(a, nw, lds, s, g);
-  }
-#undef IRBFN_CASE
-  return IRBFN_ERR_UNSUPPORTED;
-}
-
 #define IRBFN_CAT2(a, b) a##b
 #define IRBFN_CAT(a, b) IRBFN_CAT2(a, b)
 
-// int launch_forward_d<D>(args, OP, Q, bclass, gated, roll, nw, lds_bytes, stream, &grid)
+// int launch_forward_d<D>(args, OP, Q, bclass, gated, roll, nw, lds_bytes, stream)
 int IRBFN_CAT(launch_forward_d, IRBFN_INST_D)(const FwdArgs& a, int OP, int Q, int bc, bool gated, bool roll,
-                                             int nw, size_t lds, hipStream_t s, int* grid_out) {
+                                             int nw, size_t lds, hipStream_t s) {
   constexpr int D = IRBFN_INST_D;
-#define IRBFN_OPQ(OPV, QV)                                                      \
-  if (OP == OPV && Q == QV) {                                                   \
-    return roll ? launch_bc<D, OPV, QV, true>(a, bc, gated, nw, lds, s, grid_out) \
-                : launch_bc<D, OPV, QV, false>(a, bc, gated, nw, lds, s, grid_out); \
-  }
-  IRBFN_OPQ(2, 1)
-  IRBFN_OPQ(2, 2)
-  IRBFN_OPQ(4, 1)
-  IRBFN_OPQ(5, 1)
-  IRBFN_OPQ(5, 2)
-  IRBFN_OPQ(8, 1)
-  IRBFN_OPQ(10, 1)
-  IRBFN_OPQ(10, 2)
-  IRBFN_OPQ(16, 1)
-  IRBFN_OPQ(32, 1)
-  IRBFN_OPQ(64, 1)
-  IRBFN_OPQ(100, 1)
-  IRBFN_OPQ(128, 1)
-#undef IRBFN_OPQ
-  return IRBFN_ERR_UNSUPPORTED;
+  return dispatch<2, 4, 5, 8, 10, 16, 32, 64, 100, 128>(OP, [&](auto op) {
+    auto with_q = [&](auto q) {
+      const dim3 grid((unsigned)((a.B + kWave * q() - 1) / (kWave * q()))), block(nw * kWave);
+      return dispatch<BC_GAUSS, BC_IQ, BC_IMQ, BC_GENERIC>(bc, [&](auto bcv) {
+        auto run = [&](auto rl) {                  // rl: the fused roll-out, as a std::bool_constant
+          return gated ? launch_kernel<rbf_fwd_qlane<D, op(), q(), bcv(), true, rl()>>(grid, block, lds, s, a)
+                       : launch_kernel<rbf_fwd_qlane<D, op(), q(), bcv(), false, rl()>>(grid, block, lds, s, a);
+        };
+        // BC_GENERIC is compiled with one query per lane only and without the fused roll-out (fast bases only)
+        if constexpr (bcv() != BC_GENERIC) return roll ? run(std::true_type{}) : run(std::false_type{});
+        else if constexpr (q() == 1) return roll ? (int)IRBFN_ERR_UNSUPPORTED : run(std::false_type{});
+        else return (int)IRBFN_ERR_UNSUPPORTED;
+      });
+    };
+    // the (OP, Q) pairs are a list, not a product: two queries per lane only at OP 2, 5 and 10
+    if constexpr (op() == 2 || op() == 5 || op() == 10) return dispatch<1, 2>(Q, with_q);
+    else return dispatch<1>(Q, with_q);
+  });
 }
 
 }  // namespace irbfn

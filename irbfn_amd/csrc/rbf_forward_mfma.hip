@@ -186,62 +186,6 @@ bool mfma_eligible(const irbfn_net* net) {
   return net->R == 1 && net->bclass != BC_GENERIC && net->D >= 2 && net->D <= 8 && net->O <= 128;
 }
 
-
-template <int D, int NT, int QJ>
-static int launch_mfma_bc(const MfmaArgs& a, int bc, int nw, size_t lds, long tiles, hipStream_t s) {
-#define IRBFN_MCASE(BCV)                                                                             \
-  case BCV: {                                                                                        \
-    auto k = rbf_fwd_mfma<D, NT, QJ, BCV>;                                                           \
-    if (lds > 48 * 1024) {                                                                           \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                           \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
-      if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }                      \
-    }                                                                                                \
-    hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(nw * kWave), lds, s, a);                       \
-    break;                                                                                           \
-  }
-  switch (bc) {
-    IRBFN_MCASE(BC_GAUSS)
-    IRBFN_MCASE(BC_IQ)
-    IRBFN_MCASE(BC_IMQ)
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-#undef IRBFN_MCASE
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-template <int D>
-static int launch_mfma_d(const MfmaArgs& a, int NT, int QJ, int bc, int nw, size_t lds, long tiles, hipStream_t s) {
-  if (QJ == 4) {
-    switch (NT) {
-      case 1: return launch_mfma_bc<D, 1, 4>(a, bc, nw, lds, tiles, s);
-      case 2: return launch_mfma_bc<D, 2, 4>(a, bc, nw, lds, tiles, s);
-      case 3: return launch_mfma_bc<D, 3, 4>(a, bc, nw, lds, tiles, s);
-      case 4: return launch_mfma_bc<D, 4, 4>(a, bc, nw, lds, tiles, s);
-    }
-  } else if (QJ == 2) {
-    switch (NT) {
-      case 1: return launch_mfma_bc<D, 1, 2>(a, bc, nw, lds, tiles, s);
-      case 2: return launch_mfma_bc<D, 2, 2>(a, bc, nw, lds, tiles, s);
-      case 3: return launch_mfma_bc<D, 3, 2>(a, bc, nw, lds, tiles, s);
-      case 4: return launch_mfma_bc<D, 4, 2>(a, bc, nw, lds, tiles, s);
-      case 7: return launch_mfma_bc<D, 7, 2>(a, bc, nw, lds, tiles, s);
-      case 8: return launch_mfma_bc<D, 8, 2>(a, bc, nw, lds, tiles, s);
-    }
-  } else if (QJ == 1) {
-    switch (NT) {
-      case 1: return launch_mfma_bc<D, 1, 1>(a, bc, nw, lds, tiles, s);
-      case 2: return launch_mfma_bc<D, 2, 1>(a, bc, nw, lds, tiles, s);
-      case 3: return launch_mfma_bc<D, 3, 1>(a, bc, nw, lds, tiles, s);
-      case 4: return launch_mfma_bc<D, 4, 1>(a, bc, nw, lds, tiles, s);
-      case 7: return launch_mfma_bc<D, 7, 1>(a, bc, nw, lds, tiles, s);
-      case 8: return launch_mfma_bc<D, 8, 1>(a, bc, nw, lds, tiles, s);
-    }
-  }
-  return IRBFN_ERR_UNSUPPORTED;
-}
-
 size_t mfma_lds_bytes(const irbfn_net* net, int QJ, int nw) {
   const int D = net->D, OW = 16 * ((net->O + 15) / 16);
   const int RS = mfma_cw(D) + OW;
@@ -259,16 +203,19 @@ int launch_forward_mfma(irbfn_net* net, const LaunchPlan& p, const float* x, flo
   MfmaArgs a;
   a.x = x; a.recm = net->recm; a.bias = net->bias; a.out = out; a.gate = net->gate(); a.B = (long)B;
   a.O = net->O; a.Npad = net->Npad; a.basis = net->basis;
-  switch (D) {
-    case 2: return launch_mfma_d<2>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
-    case 3: return launch_mfma_d<3>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
-    case 4: return launch_mfma_d<4>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
-    case 5: return launch_mfma_d<5>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
-    case 6: return launch_mfma_d<6>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
-    case 7: return launch_mfma_d<7>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
-    case 8: return launch_mfma_d<8>(a, NT, p.QJ, net->bclass, p.nw, p.lds, p.grid, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
+  const dim3 grid((unsigned)p.grid), block(p.nw * kWave);
+  return dispatch<2, 3, 4, 5, 6, 7, 8>(D, [&](auto d) {
+    return dispatch<4, 2, 1>(p.QJ, [&](auto qj) {
+      auto with_nt = [&](auto nt) {
+        return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+          return launch_kernel<rbf_fwd_mfma<d(), nt(), qj(), bc()>>(grid, block, p.lds, s, a);
+        });
+      };
+      // the output tiles compiled depend on QJ: four query tiles per wave exist up to NT = 4 only
+      if constexpr (qj() == 4) return dispatch<1, 2, 3, 4>(NT, with_nt);
+      else return dispatch<1, 2, 3, 4, 7, 8>(NT, with_nt);
+    });
+  });
 }
 
 }  // namespace irbfn

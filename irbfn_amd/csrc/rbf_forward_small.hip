@@ -176,40 +176,6 @@ bool small_eligible(const irbfn_net* net, int64_t B) {
   return B <= kTiledMaxB && net->OP <= 16;
 }
 
-template <int D, int OP, int QT>
-static int launch_small_bc(const SmallArgs& a, int bc, dim3 grid, hipStream_t s) {
-  switch (bc) {
-    case BC_GAUSS: hipLaunchKernelGGL((rbf_fwd_clane<D, OP, BC_GAUSS, QT>), grid, dim3(256), 0, s, a); break;
-    case BC_IQ: hipLaunchKernelGGL((rbf_fwd_clane<D, OP, BC_IQ, QT>), grid, dim3(256), 0, s, a); break;
-    case BC_IMQ: hipLaunchKernelGGL((rbf_fwd_clane<D, OP, BC_IMQ, QT>), grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((rbf_fwd_clane<D, OP, BC_GENERIC, QT>), grid, dim3(256), 0, s, a); break;
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-template <int D>
-static int launch_small_d(const SmallArgs& a, int OP, int QT, int bc, dim3 grid, hipStream_t s) {
-#define IRBFN_SCASE(OPV)                                                     \
-  case OPV:                                                                  \
-    if (QT == 1) return launch_small_bc<D, OPV, 1>(a, bc, grid, s);          \
-    return IRBFN_ERR_UNSUPPORTED;
-  switch (OP) {
-    IRBFN_SCASE(2)
-    IRBFN_SCASE(4)
-    IRBFN_SCASE(5)
-    IRBFN_SCASE(8)
-    IRBFN_SCASE(10)
-    IRBFN_SCASE(16)
-    IRBFN_SCASE(32)
-    IRBFN_SCASE(64)
-    IRBFN_SCASE(100)
-    IRBFN_SCASE(128)
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-#undef IRBFN_SCASE
-}
-
 void small_geometry(const irbfn_net* net, int64_t B, LaunchPlan* p) {
   const int QT = B <= kSmallMaxB ? 1 : 8;
   const long qtiles = (B + QT - 1) / QT;
@@ -234,13 +200,15 @@ int launch_forward_small(irbfn_net* net, const LaunchPlan& p, const float* x, fl
   a.B = (int)B; a.Dreal = net->D; a.O = net->O; a.N = net->N; a.K = net->K; a.S = net->S; a.basis = net->basis;
   a.cpl = p.cpl;
   const dim3 grid((unsigned)p.nb, (unsigned)((B + p.QT - 1) / p.QT));
-  switch (net->DC) {
-    case 3: return launch_small_d<3>(a, net->OP, p.QT, net->bclass, grid, s);
-    case 4: return launch_small_d<4>(a, net->OP, p.QT, net->bclass, grid, s);
-    case 7: return launch_small_d<7>(a, net->OP, p.QT, net->bclass, grid, s);
-    case 8: return launch_small_d<8>(a, net->OP, p.QT, net->bclass, grid, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
+  return dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    return dispatch<2, 4, 5, 8, 10, 16, 32, 64, 100, 128>(net->OP, [&](auto op) {
+      return dispatch<1>(p.QT, [&](auto qt) {       // the query-tiled form (QT = 8) is not compiled
+        return dispatch<BC_GAUSS, BC_IQ, BC_IMQ, BC_GENERIC>(net->bclass, [&](auto bc) {
+          return launch_kernel<rbf_fwd_clane<dc(), op(), bc(), qt()>>(grid, dim3(256), 0, s, a);
+        });
+      });
+    });
+  });
 }
 
 }  // namespace irbfn

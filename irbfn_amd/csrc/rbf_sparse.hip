@@ -614,54 +614,6 @@ __global__ __launch_bounds__(kSpNT) void rbf_fwd_sparse(const SpArgs a) {
 // ---------------------------------------------------------------------------------------------------------------
 // host dispatch
 // ---------------------------------------------------------------------------------------------------------------
-template <int D, int OP, int BC, bool ROLL, bool GC>
-static int sp_launch_gc(const SpArgs& a, size_t lds, hipStream_t s, int* grid_out) {
-  auto k = rbf_fwd_sparse<D, OP, BC, ROLL, GC>;
-  // the attribute call is a slow host call (it made back-to-back launches host-bound at ~30 us each): once per
-  // instance and device is enough -- the largest size any card may ask for
-  static thread_local int attr_dev = -1;
-  int dev = 0;
-  IRBFN_HIP_CHECK(hipGetDevice(&dev));
-  if (attr_dev != dev) {
-    IRBFN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)kSpMaxLds));
-    attr_dev = dev;
-  }
-  const long grid = (a.B + kSpNT - 1) / kSpNT;
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kSpNT), lds, s, a);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  *grid_out = (int)grid;
-  return IRBFN_OK;
-}
-
-template <int D, int OP, int BC, bool ROLL>
-static int sp_launch_one(const SpArgs& a, size_t lds, hipStream_t s, int* grid_out) {
-  return a.gc ? sp_launch_gc<D, OP, BC, ROLL, true>(a, lds, s, grid_out) : sp_launch_gc<D, OP, BC, ROLL, false>(a, lds, s, grid_out);
-}
-
-template <int D, int OP, bool ROLL>
-static int sp_launch_bc(const SpArgs& a, int bc, size_t lds, hipStream_t s, int* g) {
-  switch (bc) {
-    case BC_GAUSS: return sp_launch_one<D, OP, BC_GAUSS, ROLL>(a, lds, s, g);
-    case BC_IQ: return sp_launch_one<D, OP, BC_IQ, ROLL>(a, lds, s, g);
-    case BC_IMQ: return sp_launch_one<D, OP, BC_IMQ, ROLL>(a, lds, s, g);
-    default:
-      if constexpr (ROLL) return IRBFN_ERR_UNSUPPORTED;
-      else return sp_launch_one<D, OP, BC_GENERIC, false>(a, lds, s, g);
-  }
-}
-
-template <int D, bool ROLL>
-static int sp_launch_d(const SpArgs& a, int OPS, int bc, size_t lds, hipStream_t s, int* g) {
-  switch (OPS) {
-    case 2: return sp_launch_bc<D, 2, ROLL>(a, bc, lds, s, g);
-    case 5: if constexpr (ROLL) return IRBFN_ERR_UNSUPPORTED; else return sp_launch_bc<D, 5, false>(a, bc, lds, s, g);
-    case 10: return sp_launch_bc<D, 10, ROLL>(a, bc, lds, s, g);
-    case 16: return sp_launch_bc<D, 16, ROLL>(a, bc, lds, s, g);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
 #ifdef IRBFN_SP_STAMPS
 extern "C" int irbfn_debug_sparse_stamps(unsigned long long* out32) {
   return (int)hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_sp_stamps), sizeof(unsigned long long) * 32);
@@ -709,16 +661,24 @@ int launch_forward_sparse(irbfn_net* net, const LaunchPlan& p, const float* x, f
   a.mirror = mirror; a.sv0 = sv0;
   if (p.roll) { a.state0 = state0; a.states = states; a.T = T; a.mode = mode; a.dp = *dp; }
   a.gc = p.gc;
-  int grid = 0;
-  switch (net->DC) {
-    case 3: return sp_launch_d<3, false>(a, net->sp_OPS, net->bclass, p.lds, s, &grid);
-    case 4: return sp_launch_d<4, false>(a, net->sp_OPS, net->bclass, p.lds, s, &grid);
-    case 7: return p.roll ? sp_launch_d<7, true>(a, net->sp_OPS, net->bclass, p.lds, s, &grid)
-                          : sp_launch_d<7, false>(a, net->sp_OPS, net->bclass, p.lds, s, &grid);
-    case 8: return p.roll ? sp_launch_d<8, true>(a, net->sp_OPS, net->bclass, p.lds, s, &grid)
-                          : sp_launch_d<8, false>(a, net->sp_OPS, net->bclass, p.lds, s, &grid);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
+  const dim3 grid((unsigned)((a.B + kSpNT - 1) / kSpNT)), block(kSpNT);
+  // the tick (roll) is compiled for d = 7 and 8, the fast bases and OPS 2, 10 and 16 (sparse_geometry)
+  auto launch = [&](auto dc, auto roll) {
+    return dispatch<2, 5, 10, 16>(net->sp_OPS, [&](auto op) {
+      return dispatch<BC_GAUSS, BC_IQ, BC_IMQ, BC_GENERIC>(net->bclass, [&](auto bc) {
+        if constexpr (roll() && (op() == 5 || bc() == BC_GENERIC)) return (int)IRBFN_ERR_UNSUPPORTED;
+        else
+          return a.gc ? launch_kernel<rbf_fwd_sparse<dc(), op(), bc(), roll(), true>>(grid, block, p.lds, s, a)
+                      : launch_kernel<rbf_fwd_sparse<dc(), op(), bc(), roll(), false>>(grid, block, p.lds, s, a);
+      });
+    });
+  };
+  return dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    if constexpr (dc() >= 7) {
+      if (p.roll) return launch(dc, std::true_type{});
+    }
+    return launch(dc, std::false_type{});
+  });
 }
 
 
@@ -1133,31 +1093,6 @@ __global__ __launch_bounds__(kWave) void rbf_vjp_sparse(const SpVjpArgs a) {
   }
 }
 
-template <int D, int OP>
-static int spv_launch_bc(const SpVjpArgs& a, int bc, dim3 grid, size_t lds, hipStream_t s) {
-  switch (bc) {
-    case BC_GAUSS: hipLaunchKernelGGL((rbf_vjp_sparse<D, OP, BC_GAUSS>), grid, dim3(kWave), lds, s, a); break;
-    case BC_IQ: hipLaunchKernelGGL((rbf_vjp_sparse<D, OP, BC_IQ>), grid, dim3(kWave), lds, s, a); break;
-    case BC_IMQ: hipLaunchKernelGGL((rbf_vjp_sparse<D, OP, BC_IMQ>), grid, dim3(kWave), lds, s, a); break;
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-template <int D>
-static int spv_launch_d(const SpVjpArgs& a, int OP, int bc, dim3 grid, size_t lds, hipStream_t s) {
-  switch (OP) {
-    case 2: return spv_launch_bc<D, 2>(a, bc, grid, lds, s);
-    case 4: return spv_launch_bc<D, 4>(a, bc, grid, lds, s);
-    case 5: return spv_launch_bc<D, 5>(a, bc, grid, lds, s);
-    case 8: return spv_launch_bc<D, 8>(a, bc, grid, lds, s);
-    case 10: return spv_launch_bc<D, 10>(a, bc, grid, lds, s);
-    case 16: return spv_launch_bc<D, 16>(a, bc, grid, lds, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
 bool sparse_vjp_eligible(const irbfn_net* net) {
   return net->sp_ok && net->bclass != BC_GENERIC && net->OP <= 16 && (size_t)net->K * (net->DC + 1 + net->OP) * 4 <= 60 * 1024;
 }
@@ -1221,28 +1156,10 @@ int launch_vjp_sparse(irbfn_net* net, const float* x, const float* gout, int64_t
   pa.RS = net->sp_RS; pa.K = net->K; pa.cap = net->sp_cap; pa.nblk = w.nblk; pa.cnt = cnt; pa.loff = loff; pa.pairs = pairs;
   const size_t lds = sparse_pairs_lds(net);
   const dim3 gridp((unsigned)w.nblk);
-#define IRBFN_SPP(DV)                                                                                                \
-  do {                                                                                                               \
-    auto k = sparse_pairs_kernel<DV>;                                                                                \
-    static thread_local int attr_dev = -1;                                                                           \
-    int dev = 0;                                                                                                     \
-    IRBFN_HIP_CHECK(hipGetDevice(&dev));                                                                             \
-    if (attr_dev != dev) {                                                                                           \
-      IRBFN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                          (int)kSpMaxLds));                                                          \
-      attr_dev = dev;                                                                                                \
-    }                                                                                                                \
-    hipLaunchKernelGGL(k, gridp, dim3(kSpNT), lds, s, pa);                                                           \
-    IRBFN_HIP_CHECK(hipGetLastError());                                                                              \
-  } while (0)
-  switch (net->DC) {
-    case 3: IRBFN_SPP(3); break;
-    case 4: IRBFN_SPP(4); break;
-    case 7: IRBFN_SPP(7); break;
-    case 8: IRBFN_SPP(8); break;
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-#undef IRBFN_SPP
+  int rc = dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    return launch_kernel<sparse_pairs_kernel<dc()>>(gridp, dim3(kSpNT), lds, s, pa);
+  });
+  if (rc != IRBFN_OK) return rc;
   hipLaunchKernelGGL(sparse_scan_kernel, dim3(nr), dim3(256), 0, s, cnt, pre, tot, w.nblk, nr);
   IRBFN_HIP_CHECK(hipGetLastError());
   SpVjpArgs va;
@@ -1256,15 +1173,13 @@ int launch_vjp_sparse(irbfn_net* net, const float* x, const float* gout, int64_t
   va.gscale = gauss_scale(net->basis);
   const dim3 gridv(net->R, SL);                  // every region gets its slab rows (zeros where no query is live)
   const size_t ldsv = (size_t)net->K * (net->DC + 1 + net->OP) * 4;
-  int rc;
-  switch (net->DC) {
-    case 3: rc = spv_launch_d<3>(va, net->OP, net->bclass, gridv, ldsv, s); break;
-    case 4: rc = spv_launch_d<4>(va, net->OP, net->bclass, gridv, ldsv, s); break;
-    case 7: rc = spv_launch_d<7>(va, net->OP, net->bclass, gridv, ldsv, s); break;
-    case 8: rc = spv_launch_d<8>(va, net->OP, net->bclass, gridv, ldsv, s); break;
-    default: rc = IRBFN_ERR_UNSUPPORTED;
-  }
-  return rc;
+  return dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    return dispatch<2, 4, 5, 8, 10, 16>(net->OP, [&](auto op) {
+      return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+        return launch_kernel<rbf_vjp_sparse<dc(), op(), bc()>>(gridv, dim3(kWave), ldsv, s, va);
+      });
+    });
+  });
 }
 
 }  // namespace irbfn

@@ -687,32 +687,15 @@ __global__ __launch_bounds__(64) void dgamma_kernel(const float* __restrict__ x,
   if (b < B) dgamma[b * R + r] = acc;
 }
 
-template <int D>
-static int launch_dgamma_d(const irbfn_net* net, const float* x, const float* g, float* dgamma, int64_t B, hipStream_t s) {
-  const dim3 grid((unsigned)((B + kWave - 1) / kWave), net->R), block(kWave);
-#define IRBFN_DG(OPV)                                                                                                \
-  case OPV:                                                                                                          \
-    hipLaunchKernelGGL((dgamma_kernel<D, OPV>), grid, block, 0, s, x, g, net->rec, dgamma, (long)B, net->D, net->O,  \
-                       net->K, net->R, net->S, net->bclass, net->basis);                                             \
-    break;
-  switch (net->OP) {
-    IRBFN_DG(2) IRBFN_DG(4) IRBFN_DG(5) IRBFN_DG(8) IRBFN_DG(10) IRBFN_DG(16)
-    default: return IRBFN_ERR_UNSUPPORTED;       // O <= 16
-  }
-#undef IRBFN_DG
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
 int launch_dgamma(irbfn_net* net, const float* x, const float* gout, float* dgamma, int64_t B, hipStream_t s) {
   if (B == 0) return IRBFN_OK;
-  switch (net->DC) {
-    case 3: return launch_dgamma_d<3>(net, x, gout, dgamma, B, s);
-    case 4: return launch_dgamma_d<4>(net, x, gout, dgamma, B, s);
-    case 7: return launch_dgamma_d<7>(net, x, gout, dgamma, B, s);
-    case 8: return launch_dgamma_d<8>(net, x, gout, dgamma, B, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
+  const dim3 grid((unsigned)((B + kWave - 1) / kWave), net->R), block(kWave);
+  return dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    return dispatch<2, 4, 5, 8, 10, 16>(net->OP, [&](auto op) {       // O <= 16
+      return launch_kernel<dgamma_kernel<dc(), op()>>(grid, block, 0, s, x, gout, net->rec, dgamma, (long)B, net->D, net->O, net->K,
+                                                      net->R, net->S, net->bclass, net->basis);
+    });
+  });
 }
 
 // softmax backward of the cluster gate (model.py:402-404): d logits = gamma * (d gamma - sum_s gamma_s d gamma_s)
@@ -899,46 +882,6 @@ int vjp_kernel_supported(const irbfn_net* net, int kernel, int64_t B) {
 
 int64_t vjp_workspace_bytes(const irbfn_net* net, int64_t B) { return B <= 0 ? 0 : (int64_t)vjp_layout(net, B).total; }
 
-template <int D, int OP>
-static int launch_vjp_bc(const VjpArgs& a, int bc, bool gated, dim3 grid, hipStream_t s) {
-  constexpr int V = D + 1 + OP;
-  const size_t lds = (size_t)4 * V * (kWave + 1) * sizeof(float);
-  auto launch = [&](auto k) -> int {
-    if (lds > 48 * 1024)
-      IRBFN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a);
-    IRBFN_HIP_CHECK(hipGetLastError());
-    return IRBFN_OK;
-  };
-#define IRBFN_VCASE(BCV) \
-  case BCV: return gated ? launch(rbf_vjp_kernel<D, OP, BCV, true>) : launch(rbf_vjp_kernel<D, OP, BCV, false>);
-  switch (bc) {
-    IRBFN_VCASE(BC_GAUSS)
-    IRBFN_VCASE(BC_IQ)
-    IRBFN_VCASE(BC_IMQ)
-    IRBFN_VCASE(BC_GENERIC)
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-#undef IRBFN_VCASE
-}
-
-template <int D>
-static int launch_vjp_d(const VjpArgs& a, int OP, int bc, bool gated, dim3 grid, hipStream_t s) {
-  switch (OP) {
-    case 2: return launch_vjp_bc<D, 2>(a, bc, gated, grid, s);
-    case 4: return launch_vjp_bc<D, 4>(a, bc, gated, grid, s);
-    case 5: return launch_vjp_bc<D, 5>(a, bc, gated, grid, s);
-    case 8: return launch_vjp_bc<D, 8>(a, bc, gated, grid, s);
-    case 10: return launch_vjp_bc<D, 10>(a, bc, gated, grid, s);
-    case 16: return launch_vjp_bc<D, 16>(a, bc, gated, grid, s);
-    case 32: return launch_vjp_bc<D, 32>(a, bc, gated, grid, s);
-    case 64: return launch_vjp_bc<D, 64>(a, bc, gated, grid, s);
-    case 100: return launch_vjp_bc<D, 100>(a, bc, gated, grid, s);
-    case 128: return launch_vjp_bc<D, 128>(a, bc, gated, grid, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
 // One parameter-VJP call as its launch sequences see it
 struct VjpCall {
   irbfn_net* net;
@@ -1032,13 +975,16 @@ static int launch_vjp_k2_main(const VjpCall& c, const VjpLayout& L, const Launch
   a.per_wave = (int)((c.B + p.S * 4L - 1) / (p.S * 4L));      // four waves per slab, each its share of the queries
   const dim3 grid(L.groups, p.S);
   if (!run_if) record_launch(net, p);
-  switch (net->DC) {
-    case 3: return launch_vjp_d<3>(a, net->OP, net->bclass, p.gated, grid, c.s);
-    case 4: return launch_vjp_d<4>(a, net->OP, net->bclass, p.gated, grid, c.s);
-    case 7: return launch_vjp_d<7>(a, net->OP, net->bclass, p.gated, grid, c.s);
-    case 8: return launch_vjp_d<8>(a, net->OP, net->bclass, p.gated, grid, c.s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
+  return dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    return dispatch<2, 4, 5, 8, 10, 16, 32, 64, 100, 128>(net->OP, [&](auto op) {
+      constexpr int V = dc() + 1 + op();
+      const size_t lds = (size_t)4 * V * (kWave + 1) * sizeof(float);
+      return dispatch<BC_GAUSS, BC_IQ, BC_IMQ, BC_GENERIC>(net->bclass, [&](auto bc) {
+        return p.gated ? launch_kernel<rbf_vjp_kernel<dc(), op(), bc(), true>>(grid, dim3(256), lds, c.s, a)
+                       : launch_kernel<rbf_vjp_kernel<dc(), op(), bc(), false>>(grid, dim3(256), lds, c.s, a);
+      });
+    });
+  });
 }
 
 static int launch_vjp_k2(const VjpCall& c, const VjpLayout& L, const LaunchPlan& p) {

@@ -363,19 +363,6 @@ bool vjph_eligible(const irbfn_net* net) {
 
 size_t vjph_block_bytes(const irbfn_net* net) { return (size_t)32 * vjph_rfq(net->DC) * 4 + 4096; }
 
-// the launched instance: CT = 2 tiles of 16 centres per wave
-template <int DC>
-static int launch_vjph_bc(const VjpHArgs& a, int bc, dim3 grid, size_t lds, hipStream_t s) {
-  switch (bc) {
-    case BC_GAUSS: hipLaunchKernelGGL((rbf_vjp_f16mfma<DC, BC_GAUSS, 2>), grid, dim3(256), lds, s, a); break;
-    case BC_IQ: hipLaunchKernelGGL((rbf_vjp_f16mfma<DC, BC_IQ, 2>), grid, dim3(256), lds, s, a); break;
-    case BC_IMQ: hipLaunchKernelGGL((rbf_vjp_f16mfma<DC, BC_IMQ, 2>), grid, dim3(256), lds, s, a); break;
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
 size_t vjph_lds_bytes(const irbfn_net* net) {
   const int V = net->DC + 1 + net->OP;
   const size_t ring = (size_t)4 * 2 * vjph_block_bytes(net);
@@ -400,13 +387,12 @@ int launch_vjp_f16(irbfn_net* net, const float* x, const float* gout, int64_t B,
   a.run_if = run_if; a.run_gen = run_gen;
   const dim3 grid((net->N + 31) / 32, QSB);
   const size_t lds = vjph_lds_bytes(net);
-  switch (net->DC) {
-    case 3: return launch_vjph_bc<3>(a, net->bclass, grid, lds, s);
-    case 4: return launch_vjph_bc<4>(a, net->bclass, grid, lds, s);
-    case 7: return launch_vjph_bc<7>(a, net->bclass, grid, lds, s);
-    case 8: return launch_vjph_bc<8>(a, net->bclass, grid, lds, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
+  return dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+      // the launched instance: CT = 2 tiles of 16 centres per wave
+      return launch_kernel<rbf_vjp_f16mfma<dc(), bc(), 2>>(grid, dim3(256), lds, s, a);
+    });
+  });
 }
 
 }  // namespace irbfn

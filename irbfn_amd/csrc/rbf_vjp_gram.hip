@@ -587,45 +587,6 @@ int vjpg_slab_rows(int mode, int DC, int OP) { return vg_kernel_row(mode, DC) + 
 
 static_assert(vg_slot_bytes(VG_ALL) == kVgBlock, "the all-live ring slot is the whole block image");
 
-template <int DC, int MODE>
-static int launch_vjpg_live_dc(const VjpGArgs& a, int bc, dim3 grid, hipStream_t s) {
-  const size_t lds = (size_t)3 * vg_slot_bytes(MODE);
-  constexpr bool kOC = MODE == VG_LINEAR;                    // LINEAR has no hbar: one instance serves every O
-#define IRBFN_VG_LIVE(BCV)                                                                                                      \
-  case BCV:                                                                                                                    \
-    if (kOC || a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BCV, true, MODE>), grid, dim3(256), lds, s, a);      \
-    else hipLaunchKernelGGL((rbf_vjp_f16gram<DC, BCV, kOC, MODE>), grid, dim3(256), lds, s, a);                          \
-    break;
-  switch (bc) {
-    IRBFN_VG_LIVE(BC_GAUSS)
-    IRBFN_VG_LIVE(BC_IQ)
-    IRBFN_VG_LIVE(BC_IMQ)
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-#undef IRBFN_VG_LIVE
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-template <int DC>
-static int launch_vjpg_gamma_dc(const VjpGArgs& a, const VjpGGamma& gm, int bc, dim3 grid, hipStream_t s) {
-  const size_t lds = (size_t)3 * vg_slot_bytes(VG_ALL);
-#define IRBFN_VG_GAMMA(BCV)                                                                                                     \
-  case BCV:                                                                                                                    \
-    if (a.O <= kVgOC) hipLaunchKernelGGL((rbf_vjp_f16gram_gamma<DC, BCV, true>), grid, dim3(256), lds, s, a, gm);            \
-    else hipLaunchKernelGGL((rbf_vjp_f16gram_gamma<DC, BCV, false>), grid, dim3(256), lds, s, a, gm);                        \
-    break;
-  switch (bc) {
-    IRBFN_VG_GAMMA(BC_GAUSS)
-    IRBFN_VG_GAMMA(BC_IQ)
-    IRBFN_VG_GAMMA(BC_IMQ)
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-#undef IRBFN_VG_GAMMA
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
 template <int MODE>
 static int launch_vjp_gram_mode(irbfn_net* net, const float* x, const float* gout, int64_t B, unsigned char* qblk, const float* bmax,
                                 int nbmax, float* scales, int* flag, int gen, float* part, int QSB, int Npad, hipStream_t s,
@@ -633,17 +594,12 @@ static int launch_vjp_gram_mode(irbfn_net* net, const float* x, const float* gou
   const long nqb = (B + 31) / 32;
   const GramHdr* hdr = reinterpret_cast<const GramHdr*>(net->gram_hdr);
   const dim3 pg((unsigned)nqb), pb(192);
-#define IRBFN_VG_PRE(DCV)                                                                                                        \
-  case DCV:                                                                                                                     \
-    hipLaunchKernelGGL((vjp_pack_blocks_gram_kernel<DCV, MODE>), pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, \
-                       scales, flag, gen, net->gate(), (long)B, net->D, net->O, vg_exp_a(net->bclass, gtile != nullptr), gtile != nullptr ? 1 : 0);  \
-    break;
-  switch (net->DC) {
-    IRBFN_VG_PRE(3) IRBFN_VG_PRE(4) IRBFN_VG_PRE(7) IRBFN_VG_PRE(8)
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-#undef IRBFN_VG_PRE
-  IRBFN_HIP_CHECK(hipGetLastError());
+  const int rc = dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    return launch_kernel<vjp_pack_blocks_gram_kernel<dc(), MODE>>(pg, pb, 0, s, x, gout, bmax, nbmax, net->f16_oscale, hdr, qblk, scales, flag,
+                                                                 gen, net->gate(), (long)B, net->D, net->O,
+                                                                 vg_exp_a(net->bclass, gtile != nullptr), gtile != nullptr ? 1 : 0);
+  });
+  if (rc != IRBFN_OK) return rc;
   VjpGArgs a;
   a.qblk = qblk; a.scales = scales; a.gimg = net->gram_img; a.hdr = hdr; a.flag = flag; a.gen = gen; a.rec = net->rec; a.sig2 = net->sig2;
   a.oscale = net->f16_oscale; a.part = part;
@@ -657,24 +613,25 @@ static int launch_vjp_gram_mode(irbfn_net* net, const float* x, const float* gou
       const VjpGGamma gm = {gtile, net->R, net->K, gram_gamma_cpr(net)};
       a.nchunks = gm.R * gm.cpr;                             // the padded chunk order of the images
       const dim3 gg((a.nchunks + 3) / 4, QSB);
-      switch (net->DC) {
-        case 3: return launch_vjpg_gamma_dc<3>(a, gm, net->bclass, gg, s);
-        case 4: return launch_vjpg_gamma_dc<4>(a, gm, net->bclass, gg, s);
-        case 7: return launch_vjpg_gamma_dc<7>(a, gm, net->bclass, gg, s);
-        case 8: return launch_vjpg_gamma_dc<8>(a, gm, net->bclass, gg, s);
-        default: return IRBFN_ERR_UNSUPPORTED;
-      }
+      const size_t lds = (size_t)3 * vg_slot_bytes(VG_ALL);
+      return dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+        return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+          return a.O <= kVgOC ? launch_kernel<rbf_vjp_f16gram_gamma<dc(), bc(), true>>(gg, dim3(256), lds, s, a, gm)
+                              : launch_kernel<rbf_vjp_f16gram_gamma<dc(), bc(), false>>(gg, dim3(256), lds, s, a, gm);
+        });
+      });
     }
     return IRBFN_ERR_BAD_ARG;
   }
   const dim3 grid((a.nchunks + 3) / 4, QSB);
-  switch (net->DC) {
-    case 3: return launch_vjpg_live_dc<3, MODE>(a, net->bclass, grid, s);
-    case 4: return launch_vjpg_live_dc<4, MODE>(a, net->bclass, grid, s);
-    case 7: return launch_vjpg_live_dc<7, MODE>(a, net->bclass, grid, s);
-    case 8: return launch_vjpg_live_dc<8, MODE>(a, net->bclass, grid, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
+  const size_t lds = (size_t)3 * vg_slot_bytes(MODE);
+  constexpr bool kOC = MODE == VG_LINEAR;                    // LINEAR has no hbar: one instance serves every O
+  return dispatch<3, 4, 7, 8>(net->DC, [&](auto dc) {
+    return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+      return kOC || a.O <= kVgOC ? launch_kernel<rbf_vjp_f16gram<dc(), bc(), true, MODE>>(grid, dim3(256), lds, s, a)
+                                 : launch_kernel<rbf_vjp_f16gram<dc(), bc(), kOC, MODE>>(grid, dim3(256), lds, s, a);
+    });
+  });
 }
 
 // x, gout -> slabs part[QSB][V][Npad].  qblk / scales / flag: workspace; bmax: per-block max |g| written by colsum_partial_kernel

@@ -36,7 +36,7 @@ __device__ __forceinline__ float dphi_dd2_fast(float phi, float gscale) {     //
 __host__ __device__ constexpr int vjpm_xw(int DC) { return (DC + 1 + 3) & ~3; }   // x[DC], gamma, padding
 
 static int vjpm_ow(int O) { return O <= 32 ? 32 : (O <= 64 ? 64 : 128); }
-static int vjpm_ct(int OW) { return OW <= 64 ? 2 : 1; }          // centre tiles per wave: the W and dW registers bound it
+static constexpr int vjpm_ct(int OW) { return OW <= 64 ? 2 : 1; }          // centre tiles per wave: the W and dW registers bound it
 
 bool vjpm_eligible(const irbfn_net* net) {
   const bool d_ok = net->DC == 3 || net->DC == 4 || net->DC == 7 || net->DC == 8;
@@ -266,28 +266,6 @@ __global__ __launch_bounds__(256) void rbf_vjp_mfma(const VjpmArgs a) {
   }
 }
 
-template <int D, int OW, int CT>
-static int launch_vjpm_bc(const VjpmArgs& a, int bc, dim3 grid, size_t lds, hipStream_t s) {
-  switch (bc) {
-    case BC_GAUSS: hipLaunchKernelGGL((rbf_vjp_mfma<D, OW, BC_GAUSS, CT>), grid, dim3(256), lds, s, a); break;
-    case BC_IQ: hipLaunchKernelGGL((rbf_vjp_mfma<D, OW, BC_IQ, CT>), grid, dim3(256), lds, s, a); break;
-    case BC_IMQ: hipLaunchKernelGGL((rbf_vjp_mfma<D, OW, BC_IMQ, CT>), grid, dim3(256), lds, s, a); break;
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-template <int D>
-static int launch_vjpm_d(const VjpmArgs& a, int OW, int bc, dim3 grid, size_t lds, hipStream_t s) {
-  switch (OW) {
-    case 32: return launch_vjpm_bc<D, 32, 2>(a, bc, grid, lds, s);
-    case 64: return launch_vjpm_bc<D, 64, 2>(a, bc, grid, lds, s);
-    case 128: return launch_vjpm_bc<D, 128, 1>(a, bc, grid, lds, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
 // qm: vjpm_qrec_bytes(net, B) of workspace; part: QSB slabs of V = DC + 1 + OP rows x Npad centres
 int launch_vjp_mfma(irbfn_net* net, const float* x, const float* gout, int64_t B, float* qm, float* part, int QSB, int Npad,
                     hipStream_t s) {
@@ -306,13 +284,13 @@ int launch_vjp_mfma(irbfn_net* net, const float* x, const float* gout, int64_t B
   a.gscale = gauss_scale(net->basis);
   const dim3 grid((unsigned)vjpm_groups(net), (unsigned)QSB);
   const size_t lds = (size_t)4 * a.V * (16 * CT + 1) * sizeof(float);     // <= 38.5 KB
-  switch (DC) {
-    case 3: return launch_vjpm_d<3>(a, OW, net->bclass, grid, lds, s);
-    case 4: return launch_vjpm_d<4>(a, OW, net->bclass, grid, lds, s);
-    case 7: return launch_vjpm_d<7>(a, OW, net->bclass, grid, lds, s);
-    case 8: return launch_vjpm_d<8>(a, OW, net->bclass, grid, lds, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
+  return dispatch<3, 4, 7, 8>(DC, [&](auto dc) {
+    return dispatch<32, 64, 128>(OW, [&](auto ow) {
+      return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+        return launch_kernel<rbf_vjp_mfma<dc(), ow(), bc(), vjpm_ct(ow())>>(grid, dim3(256), lds, s, a);
+      });
+    });
+  });
 }
 
 }  // namespace irbfn

@@ -200,48 +200,18 @@ __global__ __launch_bounds__((OP > 48) ? 512 : 1024) void rbf_vjpx_qlane(const V
   }
 }
 
-template <int D, int OP, int BC>
-static int launch_one(const VjpxArgs& a, int nw, size_t lds_bytes, hipStream_t s) {
-  auto kern = rbf_vjpx_qlane<D, OP, BC>;
-  if (lds_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { g_last_hip_error = (int)e; return IRBFN_ERR_HIP; }
-  }
-  const long tiles = (a.B + kWave - 1) / kWave;
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(nw * kWave), lds_bytes, s, a);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-template <int D, int OP>
-static int launch_bc(const VjpxArgs& a, int bc, int nw, size_t lds, hipStream_t s) {
-  switch (bc) {
-    case BC_GAUSS: return launch_one<D, OP, BC_GAUSS>(a, nw, lds, s);
-    case BC_IQ: return launch_one<D, OP, BC_IQ>(a, nw, lds, s);
-    case BC_IMQ: return launch_one<D, OP, BC_IMQ>(a, nw, lds, s);
-    case BC_GENERIC: return launch_one<D, OP, BC_GENERIC>(a, nw, lds, s);
-  }
-  return IRBFN_ERR_UNSUPPORTED;
-}
-
 #define IRBFN_CAT2(a, b) a##b
 #define IRBFN_CAT(a, b) IRBFN_CAT2(a, b)
 
 int IRBFN_CAT(launch_vjpx_d, IRBFN_INST_D)(const VjpxArgs& a, int OP, int bc, int nw, size_t lds, hipStream_t s) {
   constexpr int D = IRBFN_INST_D;
-  switch (OP) {                                  // the forward's compiled widths (padded_O)
-    case 2: return launch_bc<D, 2>(a, bc, nw, lds, s);
-    case 4: return launch_bc<D, 4>(a, bc, nw, lds, s);
-    case 5: return launch_bc<D, 5>(a, bc, nw, lds, s);
-    case 8: return launch_bc<D, 8>(a, bc, nw, lds, s);
-    case 10: return launch_bc<D, 10>(a, bc, nw, lds, s);
-    case 16: return launch_bc<D, 16>(a, bc, nw, lds, s);
-    case 32: return launch_bc<D, 32>(a, bc, nw, lds, s);
-    case 64: return launch_bc<D, 64>(a, bc, nw, lds, s);
-    case 100: return launch_bc<D, 100>(a, bc, nw, lds, s);
-    case 128: return launch_bc<D, 128>(a, bc, nw, lds, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
+  const long tiles = (a.B + kWave - 1) / kWave;
+  // the forward's compiled widths (padded_O)
+  return dispatch<2, 4, 5, 8, 10, 16, 32, 64, 100, 128>(OP, [&](auto op) {
+    return dispatch<BC_GAUSS, BC_IQ, BC_IMQ, BC_GENERIC>(bc, [&](auto bcv) {
+      return launch_kernel<rbf_vjpx_qlane<D, op(), bcv()>>(dim3((unsigned)tiles), dim3(nw * kWave), lds, s, a);
+    });
+  });
 }
 
 }  // namespace irbfn

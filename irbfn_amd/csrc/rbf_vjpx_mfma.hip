@@ -194,50 +194,20 @@ VjpxPlan plan_vjpx_mfma(const irbfn_net* net, int64_t B) {
   return p;
 }
 
-template <int D, int NT>
-static int launch_bc(const VjpxMfmaArgs& a, int bc, const VjpxPlan& p, hipStream_t s) {
-  const dim3 grid((unsigned)p.grid), block(p.block);
-  switch (bc) {
-    case BC_GAUSS: hipLaunchKernelGGL((rbf_vjpx_mfma<D, NT, BC_GAUSS>), grid, block, p.lds, s, a); break;
-    case BC_IQ: hipLaunchKernelGGL((rbf_vjpx_mfma<D, NT, BC_IQ>), grid, block, p.lds, s, a); break;
-    case BC_IMQ: hipLaunchKernelGGL((rbf_vjpx_mfma<D, NT, BC_IMQ>), grid, block, p.lds, s, a); break;
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
-}
-
-template <int D>
-static int launch_d(const VjpxMfmaArgs& a, int NT, int bc, const VjpxPlan& p, hipStream_t s) {
-  switch (NT) {
-    case 1: return launch_bc<D, 1>(a, bc, p, s);
-    case 2: return launch_bc<D, 2>(a, bc, p, s);
-    case 3: return launch_bc<D, 3>(a, bc, p, s);
-    case 4: return launch_bc<D, 4>(a, bc, p, s);
-    case 5: return launch_bc<D, 5>(a, bc, p, s);
-    case 6: return launch_bc<D, 6>(a, bc, p, s);
-    case 7: return launch_bc<D, 7>(a, bc, p, s);
-    case 8: return launch_bc<D, 8>(a, bc, p, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
-}
-
 int launch_vjpx_mfma(irbfn_net* net, const VjpxPlan& p, const float* x, const float* gout, float* gx, int64_t B, hipStream_t s) {
   VjpxMfmaArgs a;
   memset(&a, 0, sizeof(a));
   a.x = x; a.g = gout; a.recm = net->recm; a.gx = gx; a.gate = net->gate(); a.B = (long)B;
   a.O = net->O; a.Npad = net->Npad;
   const int NT = (net->O + 15) / 16;
-  switch (net->D) {
-    case 2: return launch_d<2>(a, NT, net->bclass, p, s);
-    case 3: return launch_d<3>(a, NT, net->bclass, p, s);
-    case 4: return launch_d<4>(a, NT, net->bclass, p, s);
-    case 5: return launch_d<5>(a, NT, net->bclass, p, s);
-    case 6: return launch_d<6>(a, NT, net->bclass, p, s);
-    case 7: return launch_d<7>(a, NT, net->bclass, p, s);
-    case 8: return launch_d<8>(a, NT, net->bclass, p, s);
-    default: return IRBFN_ERR_UNSUPPORTED;
-  }
+  const dim3 grid((unsigned)p.grid), block(p.block);
+  return dispatch<2, 3, 4, 5, 6, 7, 8>(net->D, [&](auto d) {
+    return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(NT, [&](auto nt) {
+      return dispatch<BC_GAUSS, BC_IQ, BC_IMQ>(net->bclass, [&](auto bc) {
+        return launch_kernel<rbf_vjpx_mfma<d(), nt(), bc()>>(grid, block, p.lds, s, a);
+      });
+    });
+  });
 }
 
 }  // namespace irbfn

@@ -471,12 +471,7 @@ template <int MODE>
 static int launch_vjp_park(const RollVjpArgs& a, hipStream_t s) {
   const size_t lds = (size_t)a.T * ModeTraits<MODE>::NP * kWave * sizeof(float);
   if (lds > 150 * 1024) return IRBFN_ERR_UNSUPPORTED;
-  auto kern = rollout_vjp_park_kernel<MODE>;
-  if (lds > 48 * 1024)
-    IRBFN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)((a.B + kWave - 1) / kWave)), dim3(kWave), lds, s, a);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  return IRBFN_OK;
+  return launch_kernel<rollout_vjp_park_kernel<MODE>>(dim3((unsigned)((a.B + kWave - 1) / kWave)), dim3(kWave), lds, s, a);
 }
 
 // K4 up to T = 50, the park kernel beyond
