@@ -28,7 +28,8 @@
 // the order of the float32 sum (K1 splits the centres over waves).
 //
 // The list capacity is a HARD bound computed on the host from the card (max number of simultaneously non-zero
-// ranges per dimension, intervals widened by 1e-4), nets whose bound or tables do not fit are served by the dense K1.
+// ranges per dimension, intervals widened by 1e-4, their product times the largest number of rows of dimension_ranges that
+// name one combination of ranges), nets whose bound or tables do not fit are served by the dense K1.
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -141,6 +142,22 @@ int sparse_setup(irbfn_net* net, const float* lo, const float* hi, const float* 
     mean *= (U > L) ? std::max(1.0, covered / (U - L)) : (double)used.size();
   }
   if (E > kSpMaxE) return IRBFN_OK;
+  // cap and mean count COMBINATIONS of ranges so far; rows of dimension_ranges that name the same combination are live together
+  // (each is a region of its own): the bound times the largest number of rows that share one combination, the expectation times
+  // the rows per distinct combination.  A card with distinct rows: factors 1 and 1.0, nothing changes.
+  {
+    std::vector<std::vector<int>> combos(nr);
+    for (int r = 0; r < nr; ++r) combos[r].assign(dr + (size_t)r * ns, dr + (size_t)(r + 1) * ns);
+    std::sort(combos.begin(), combos.end());
+    int distinct = 0, most = 0, run = 0;
+    for (int r = 0; r < nr; ++r) {
+      run = (r > 0 && combos[r] == combos[r - 1]) ? run + 1 : 1;
+      if (run == 1) ++distinct;
+      most = std::max(most, run);
+    }
+    cap *= most;
+    mean *= (double)nr / distinct;
+  }
   cap = std::min(cap, (double)nr);
   mean = std::min(mean, (double)nr);
   if (cap > kSpMaxCap) return IRBFN_OK;
