@@ -91,20 +91,52 @@ enum GramPhase : int { GP_ENTRY = 0, GP_OPERANDS, GP_BARRIER1, GP_LOOP0, GP_LOOP
 typedef float f2_t __attribute__((ext_vector_type(2)));
 typedef unsigned u2_t __attribute__((ext_vector_type(2)));
 
-// The (hi, lo) pair of f16_split.h in three instructions per value instead of four: hi = the packed round-toward-zero
-// conversion itself (the leading 11 bits of P wherever P is a normal f16 number), lo = 2^11 (P - hi) as one v_fma_mix_f32
-// that reads hi as the f16 number it is: fma(hi, -2^11, 2^11 P) is exact (every term a multiple of the last bit of P).
+// The (hi, lo) pair of f16_split.h in five instructions per value pair instead of eight: hi = the packed round-toward-zero
+// conversion itself (the leading 11 bits of P wherever P is a normal f16 number), lo = 2^11 (P - hi) with the residual from one
+// v_fma_mix_f32 per value that reads hi as the f16 number it is (exact: every term a multiple of the last bit of P).
 // (v_pk_add_f32 / v_pk_mul_f32 for the subtraction and the gain: measured slower -- packed f32 VALU costs more than the two
 // plain instructions it replaces, MI355X_MICROARCH.md constants table.  v_fma_mixlo_f16 + v_fma_mixhi_f16 writing the two halves of
 // the lo pair directly -- 2 instructions instead of 3 -- measured 5 % SLOWER at config 2: 92.1 vs 87.4 us, profiles/r03_gram_experiments.txt.)
+//
+// The 2^11 gain of a value PAIR is one instruction: the residuals d = P - hi come out of the two v_fma_mix_f32 unscaled
+// (fma(hi, -1, P): exact, the low bits of P) into an aligned register pair, and one v_lshl_add_u64 adds 11 to both exponent
+// fields (bits(2048 d) = bits(d) + (11 << 23) for a normal d of either sign with room in the exponent; |d| < 2^4 here, so
+// neither dword carries: the low one not into the high one).  Five instructions per pair instead of six (beside MFMAs the add
+// costs 4.4 cycles per pair and SIMD, the two multiplies 8.4: tools/ubench.hip split, profiles/k1g_split_gain.txt; the inline
+// constant of the mixes costs what their SGPR operand did).  The pair is bit-identical to the form with the two multiplies (ADD64 = false: q = 2048 P, then
+// fma(hi, -2048, q)) for every P the kernels produce (tests/test_split_gain_cpu.py sweeps it):
+//   - d == 0 (P has no bits below hi's last; P = +-0, where fma(-0, -1, -0) = +0 as fma(-0, -2048, -0) did): the add makes
+//     2^-116 of +0, which the round-toward-zero conversion turns into the +0 the other form has;
+//   - P subnormal or below 2^-103, where d is a subnormal float and the add does not scale it: both forms give a value
+//     below 2^-115 with the sign of P, and the conversion its signed zero.
+//   (Adding the gain to P in front of the mixes -- in place, P being dead behind the hi conversion -- costs the same five
+//   instructions but turns P = -0, which the region-weighted instances produce (an underflowed basis value times a negative
+//   weight), into -2^-116 and its lo into -0 where the multiplies give +0.)
+// P infinite does not arise (the arguments of the reciprocal bases are >= 1, the exponential's are <= 14), and a NaN -- a
+// NaN query, which takes the VALU distances -- stays a NaN in hi and so in its row's output, whatever the add makes of lo.
+#ifndef IRBFN_SPLIT_ADD64
+#define IRBFN_SPLIT_ADD64 1     // 0: the gain as two v_mul_f32 (A/B builds: tools/build_variant.py ... -DIRBFN_SPLIT_ADD64=0)
+#endif
+constexpr unsigned long long kLoGainBits2 = 0x0580000005800000ull;      // 11 << 23 in both dwords
+template <bool ADD64 = (IRBFN_SPLIT_ADD64 != 0)>
 __device__ __forceinline__ void split_pair_mix(float p0, float p1, unsigned& hi, unsigned& lo) {
   hi = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(p0, p1));
-  const float q0 = p0 * kLoGain, q1 = p1 * kLoGain;
-  const float ng = -kLoGain;
-  float d0, d1;
-  asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d0) : "v"(hi), "s"(ng), "v"(q0));
-  asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d1) : "v"(hi), "s"(ng), "v"(q1));
-  lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(d0, d1));
+  if constexpr (ADD64) {
+    float d0, d1;
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d0) : "v"(hi), "v"(p0));
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d1) : "v"(hi), "v"(p1));
+    f2_t d = {d0, d1};
+    // plain C++ (u64 + constant) may lower to v_add_co + v_addc_co: the instruction is named
+    asm("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(d) : "s"(kLoGainBits2));
+    lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(d[0], d[1]));
+  } else {
+    const float q0 = p0 * kLoGain, q1 = p1 * kLoGain;
+    const float ng = -kLoGain;
+    float d0, d1;
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d0) : "v"(hi), "s"(ng), "v"(q0));
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d1) : "v"(hi), "s"(ng), "v"(q1));
+    lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(d0, d1));
+  }
 }
 
 // the step's 16 transcendentals back to back (rbf_forward.h, trans_block), from the MFMA result registers into fresh ones
