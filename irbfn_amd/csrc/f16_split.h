@@ -55,4 +55,16 @@ __device__ __forceinline__ void split_static_f16(float v, _Float16& hi, _Float16
   lo = (_Float16)((w - (float)hi) * kLoGain);    // residual exact in f32, |.| <= 2^14
 }
 
+// A cotangent over the batch scale, pack time.  The scale is the power of two above the largest FINITE |g| of the batch
+// (colsum_partial_kernel), so v is |v| <= 1, NaN or +-Inf.  NaN splits into (NaN, NaN) by itself.  +-Inf as (Inf, Inf - Inf)
+// would be a NaN too; it becomes (+-65504, +-Inf) instead: A1 stays finite and A2 = als * bh + ah * bls is the infinity with
+// the sign of v * bh, which is the product's (bh carries the sign of b; bls, of either sign, meets the finite ah only).
+__device__ __forceinline__ void split_cotangent_f16(float v, _Float16& hi, _Float16& lo) {
+  split_static_f16(v, hi, lo);
+  if (__builtin_isinf(v)) {
+    hi = (_Float16)__builtin_copysignf(65504.0f, v);
+    lo = (_Float16)v;
+  }
+}
+
 }  // namespace irbfn

@@ -431,7 +431,8 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
                                                               float* __restrict__ bmax) {
   extern __shared__ float sm[];                // [256]
   __shared__ float smax[256];
-  float mx = 0.0f;                             // max |g| of this block's rows (K2h operand scale), NaN wins
+  float mx = 0.0f;                             // max FINITE |g| of this block's rows: the K2h / K2g operand scale (a NaN or Inf
+                                               // reaches the f16 operands as such whatever the scale; split_cotangent_f16)
   const long r0 = (long)blockIdx.x * rows_per_block;
   long r1 = r0 + rows_per_block;
   r1 = r1 < B ? r1 : B;
@@ -448,7 +449,7 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
         const float v = base[i];
         s += v;
         const float av = fabsf(v);
-        mx = (av > mx || av != av) ? av : mx;
+        mx = (av > mx && av <= 3.402823466e38f) ? av : mx;
       }
     sm[t] = t < stride ? s : 0.0f;
     __syncthreads();
@@ -464,7 +465,7 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
         const float v = base[rr * O + o];
         s += v;
         const float av = fabsf(v);
-        mx = (av > mx || av != av) ? av : mx;
+        mx = (av > mx && av <= 3.402823466e38f) ? av : mx;
       }
       part[(size_t)blockIdx.x * O + o] = s;
     }
@@ -475,7 +476,7 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
     for (int w = 128; w > 0; w >>= 1) {
       if (threadIdx.x < w) {
         const float o2 = smax[threadIdx.x + w], m2 = smax[threadIdx.x];
-        smax[threadIdx.x] = (o2 > m2 || o2 != o2) ? o2 : m2;
+        smax[threadIdx.x] = o2 > m2 ? o2 : m2;
       }
       __syncthreads();
     }

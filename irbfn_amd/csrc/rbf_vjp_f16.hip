@@ -34,7 +34,7 @@ typedef unsigned u2v __attribute__((ext_vector_type(2)));
 
 // ---- pre-pass ----------------------------------------------------------------------------------------------
 __device__ __forceinline__ float pow2_ceil_scale(float mx) {
-  if (!(mx > 0.0f) || !(mx < 3.0e38f)) return 1.0f;          // zero / Inf / NaN: unscaled
+  if (!(mx > 0.0f) || !(mx < 3.0e38f)) return 1.0f;          // no finite non-zero element (or one above 3e38): unscaled
   int e;
   (void)frexpf(mx, &e);
   return ldexpf(1.0f, e);
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(64) void vjp_pack_blocks_kernel(const float* __rest
       float v = 0.0f;
       if (q < B && o < O) v = gout[q * O + o] * (oscale[o] / sh);
       _Float16 h, l;
-      split_static_f16(v, h, l);
+      split_cotangent_f16(v, h, l);
       hi[j] = h;
       lo[j] = l;
     }
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(64) void vjp_pack_blocks_kernel(const float* __rest
       float v = 0.0f;
       if (q < B && n < O) v = gq * gout[q * O + n] / sg;
       _Float16 h, l;
-      split_static_f16(v, h, l);
+      split_cotangent_f16(v, h, l);
       hi[j] = h;
       lo[j] = l;
     }

@@ -54,7 +54,7 @@ constexpr float kVgCrossA = 1.0f / 32.0f, kVgCrossB = 1.0f / 64.0f;      // kVgC
 static_assert(kVgCrossA * kVgCrossB == kLoScale, "cross terms of the (hi, lo) scheme");
 
 __device__ __forceinline__ float vg_pow2_ceil_scale(float mx) {
-  if (!(mx > 0.0f) || !(mx < 3.0e38f)) return 1.0f;          // zero / Inf / NaN: unscaled
+  if (!(mx > 0.0f) || !(mx < 3.0e38f)) return 1.0f;          // no finite non-zero element (or one above 3e38): unscaled
   int e;
   (void)frexpf(mx, &e);
   return ldexpf(1.0f, e);
@@ -190,6 +190,7 @@ __global__ __launch_bounds__(192) void vjp_pack_blocks_gram_kernel(const float* 
   const float xinv = __builtin_ldexpf(1.0f, -hdr->ex);
   const float rn = n < D && n < kGramDims ? hdr->r[n] : 0.0f;
   h8_t th, tl, xh, xl;
+  bool nonfinite = false;                      // a NaN or Inf cotangent: the operand pairs below cannot carry it through the sums
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int ql = 16 * (j >> 2) + 4 * g + (j & 3);
@@ -197,6 +198,7 @@ __global__ __launch_bounds__(192) void vjp_pack_blocks_gram_kernel(const float* 
     const float gq = __shfl(gm, ql);
     float v = 0.0f, xv = 0.0f;
     if (q < B && n < O) v = gq * gout[q * O + n] / sg;
+    nonfinite |= q < B && n < O && !(__builtin_fabsf(gout[q * O + n]) <= 3.402823466e38f);
     if (MODE == VG_ALL && q < B) xv = n < D ? (x[q * D + n] - rn) * xinv : (n == kGramDims ? 1.0f : 0.0f);
     _Float16 h, l;
     split_static_f16(v, h, l);
@@ -204,6 +206,9 @@ __global__ __launch_bounds__(192) void vjp_pack_blocks_gram_kernel(const float* 
     split_static_f16(xv, h, l);
     xh[j] = h; xl[j] = l;
   }
+  // ... so the call is handed over as for a query outside the box: K2h (split_cotangent_f16), or the gated K2, does the work.
+  // This role reads every element of g in every mode.
+  if (__builtin_amdgcn_ballot_w64(nonfinite) != 0ull && lane == 0) atomicExch(flag, gen);
   gT[lane] = th; gT[64 + lane] = tl;
   if constexpr (MODE == VG_ALL) { xB[lane] = xh; xB[64 + lane] = xl; }      // x' only where the centres are live
 }

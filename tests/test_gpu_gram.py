@@ -491,6 +491,40 @@ def test_vjp_gram_hands_over_when_a_query_leaves_the_box(gpu):
         assert np.abs(a[grp][name].cpu().numpy() - gr).max() <= 2e-5 * (np.abs(gr).max() + 1e-30), (grp, name)
 
 
+@pytest.mark.parametrize("poison", ["nan_g", "inf_g"])
+def test_vjp_gram_non_finite_cotangent(gpu, poison):
+    """One NaN or +Inf cotangent element in a batch whose every column holds a finite |g| >= 2 (the poisoned batches of
+    tests/test_gpu_k2h.py): the batch scale comes from the finite elements, the pre-pass hands the call over to K2h, and the
+    non-finite gradient elements are the float64 restatement's -- no other column of d kernel, no finite element out of bounds."""
+    import torch
+    import _k2_util as k2
+    cfg, P, x, g = _vjp_case("imq_d3", np.random.default_rng(11))
+    g = g.copy()
+    if poison == "nan_g":
+        g[17, 1] = np.nan
+    else:
+        g[40, 2] = np.inf
+    if not (np.abs(np.nan_to_num(g, nan=0.0, posinf=0.0)).max(axis=0) >= 2).all():
+        pytest.fail("test inputs, not the code under test: a cotangent column without an element of |g| >= 2")
+    net = WCRBFNet.from_config(cfg)
+    xt, gt = torch.from_numpy(x).cuda(), torch.from_numpy(g).cuda()
+    net.set_options(vjp_kernel=_lib.VJP_K2G)
+    a = net.vjp(P, xt, gt)["params"]
+    assert net.last_launch()["kernel"].startswith("rbf_vjp_f16gram<"), net.last_launch()
+    net.set_options(vjp_kernel=_lib.VJP_K2)
+    b = net.vjp(P, xt, gt)["params"]
+    net.set_options(vjp_kernel=_lib.VJP_AUTO)
+    ref = k2.vjp_reference(cfg["basis_func"], P, x, g, k2.tanh_gate(cfg, x))
+    for (grp, name), leaf in zip(LEAVES, k2.LEAVES):
+        ga, gb, gr = a[grp][name].cpu().numpy(), b[grp][name].cpu().numpy(), ref[leaf][0]
+        assert k2.same_nonfinite(ga, gr), (poison, name, int(np.isnan(ga).sum()), int(np.isinf(ga).sum()), int(np.isnan(gr).sum()), int(np.isinf(gr).sum()))
+        fin = np.isfinite(gr)
+        if fin.any():
+            scale = np.abs(gr[fin]).max() + 1e-30
+            ea, eb = np.abs(ga[fin] - gr[fin]).max() / scale, np.abs(gb[fin] - gr[fin]).max() / scale
+            assert ea <= max(2e-5, 2.0 * eb), (poison, name, ea, eb)
+
+
 def test_vjp_gram_is_refused_where_the_expansion_is(gpu):
     import torch
     cfg, P, x, *_ = load_ckpt_fixture("dnmpc_128regions")

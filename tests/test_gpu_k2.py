@@ -16,63 +16,23 @@ import numpy as np
 import pytest
 
 import _k2_util as k2
+import _vjp_guard_util as guarded
+from _vjp_guard_util import make_net
 from irbfn_amd import _lib
-from irbfn_amd.model import ClusterWCRBFNet, WCRBFNet
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
 BY_TAG = {s["tag"]: s for s in k2.TABLE}
-
-
-def make_net(case):
-    if case.cluster:
-        return ClusterWCRBFNet(in_features=case.D, out_features=case.O, num_kernels=case.K, basis_func=case.basis, num_regions=case.R)
-    return WCRBFNet.from_config(case.cfg)
-
-
-def vjp_guarded(torch, net, case, x=None, g=None, option=_lib.VJP_K2):
-    """One VJP into views of a flat NaN buffer -> ({leaf: float32 array}, what the launch reports, the buffer's bits)."""
-    R, K, D, O = case.R, case.K, case.D, case.O
-    shapes = {"centers": (R, K, D), "log_sigs": (R, K), "kernel": (K, O), "bias": (O,)}
-    if case.cluster:
-        shapes.update(ckernel=(D, R), cbias=(R,))
-    total = GUARD + sum(int(np.prod(s)) + GUARD for s in shapes.values())
-    buf = torch.full((total,), float("nan"), dtype=torch.float32, device="cuda")
-    views, spans, off = {}, {}, GUARD
-    for n, s in shapes.items():
-        size = int(np.prod(s))
-        views[n], spans[n] = buf[off:off + size].view(s), (off, off + size)
-        off += size + GUARD
-    out = {"params": {"rbf_list": {"centers": views["centers"], "log_sigs": views["log_sigs"]},
-                      "linear": {"kernel": views["kernel"], "bias": views["bias"]}}}
-    if case.cluster:
-        out["params"]["cluster"] = {"kernel": views["ckernel"], "bias": views["cbias"]}
-    xd = torch.from_numpy(case.x if x is None else x).cuda()
-    gd = torch.from_numpy(case.g if g is None else g).cuda()
-    net.set_options(vjp_kernel=option)
-    try:
-        net.vjp(case.params, xd, gd, out=out)
-    finally:
-        net.set_options(vjp_kernel=_lib.VJP_AUTO)
-    torch.cuda.synchronize()
-    launch = getattr(net, "stage", net).last_launch()
-    host = buf.cpu().numpy()
-    guard = np.ones(total, bool)
-    for a, b in spans.values():
-        guard[a:b] = False
-    assert np.isnan(host[guard]).all(), f"{case.tag}: {launch['kernel']} wrote outside its leaves"
-    return {n: host[a:b].reshape(shapes[n]) for n, (a, b) in spans.items()}, launch, host.view(np.uint32)
 
 
 def run_twice(torch, net, case, x=None, g=None, option=_lib.VJP_K2, B=None):
     """Two runs, bit-identical; the launch is the one the restated rules give."""
     plan = case.plan() if B is None else k2.k2_plan(case.N, B, case.D, case.O, case.basis, case.gated)
-    got, launch, bits = vjp_guarded(torch, net, case, x, g, option)
-    assert launch["kernel"] == plan["name"] and launch["grid"] == plan["grid"] and launch["block"] == 256, (case.tag, launch, plan)
-    _, launch2, bits2 = vjp_guarded(torch, net, case, x, g, option)
-    assert launch2 == launch and np.array_equal(bits, bits2), f"{case.tag}: two runs differ in some bit"
-    return got, bits
+
+    def expect(launch):
+        assert launch["kernel"] == plan["name"] and launch["grid"] == plan["grid"] and launch["block"] == 256, (case.tag, launch, plan)
+
+    return guarded.run_twice(torch, net, case, expect, x, g, option)
 
 
 def check(case, got):
