@@ -25,7 +25,7 @@ namespace irbfn {
 constexpr int kPackBlock = 256;
 constexpr int kStatsCentres = 1024;                          // centres per S block
 constexpr int kStatsVals = 18;                               // [0, 8) max_i, [8, 16) -min_i, 16 max |alpha|, 17 not finite
-constexpr int kGramLdsMax = gram_chunk_bytes(8);             // O <= 128
+constexpr int kGramLdsMax = gram_chunk_stride(8);             // O <= 128
 
 struct PackArgs {
   const float* __restrict__ centers;
@@ -314,8 +314,10 @@ __device__ inline void gram_parts_c2(double v, int E, double (&n)[4]) {
   n[3] = (double)(_Float16)(float)r3;
 }
 
-// One block per chunk; sixteen work items per centre-in-chunk: item `part` fills head slot `part` and the tail slots 4 part .. 4 part + 3
-// (rbf_forward_gram.h: the slot tables say which product sits where) and the W values of output `part` of every column tile.
+// One block per chunk; sixteen work items per centre-in-chunk: item `part` fills the folded slots 4 part .. 4 part + 3 (of the 64:
+// operand part / 8, k = 4 (part & 7) + i) of the forward kernels' operands, head slot `part` and the tail slots 4 part .. 4 part + 3
+// of K2g's unfolded records behind the image (rbf_forward_gram.h: the slot tables say which product sits where) and the W values
+// of output `part` of every column tile.
 __device__ __forceinline__ void gram_image_body(const PackArgs& a, int c, unsigned char* simg, GramHdr& hs, float* tot) {
   const int tid = threadIdx.x;
   if (tid < kStatsVals) {
@@ -331,7 +333,8 @@ __device__ __forceinline__ void gram_image_body(const PackArgs& a, int c, unsign
   __syncthreads();
   const GramHdr h = hs;
   const int NT = a.NT, D = a.D;
-  const int CB = gram_chunk_bytes(NT);
+  const int CB = gram_chunk_stride(NT);                      // operands, W tiles, K2g's records
+  unsigned char* const pv = simg + gram_chunk_bytes(NT);      // K2g's records
   unsigned char* p = simg;
   for (int it = tid; it < kF16Chunk * 16; it += kPackBlock) {
     const int part = it >> 5, kk = it & 31;                  // a wave = two parts x 32 centres: (nearly) one path per wave
@@ -339,12 +342,16 @@ __device__ __forceinline__ void gram_image_body(const PackArgs& a, int c, unsign
     const int n = reg * a.KR + kr;
     const bool real = kr < a.KR;
     const int ct = kk >> 4, row = kk & 15;                   // centre tile, A-operand row
-    _Float16* head = reinterpret_cast<_Float16*>(p + ct * 512);                // lane (g, row): k = 4 g + j
+    _Float16* head = reinterpret_cast<_Float16*>(pv + ct * 512);                // lane (g, row): k = 4 g + j
     auto put_head = [&](int s, double v, int T) { head[((s >> 2) * 16 + row) * 4 + (s & 3)] = (_Float16)(float)(v * gram_pow2(T - gram_ax(T))); };
     auto put_tail = [&](int s, double v, int T) {
       const int half = s >> 5, g = (s >> 3) & 3, j = s & 7;
-      _Float16* tail = reinterpret_cast<_Float16*>(p + kGramHeadBytes + (ct * 2 + half) * 1024);
+      _Float16* tail = reinterpret_cast<_Float16*>(pv + kGramHeadBytes + (ct * 2 + half) * 1024);
       tail[(g * 16 + row) * 8 + j] = (_Float16)(float)(v * gram_pow2(T - gram_ax(T)));
+    };
+    auto put_fold = [&](int o, int k, double v, int T) {        // lane (g, row) of [ct][operand]: k = 8 g + j
+      _Float16* op = reinterpret_cast<_Float16*>(p + (ct * 2 + o) * 1024);
+      op[((k >> 3) * 16 + row) * 8 + (k & 7)] = (_Float16)(float)(v * gram_pow2(T - gram_ax(T)));
     };
     double alpha = 0.0, beta = 0.0;
     if (h.ok) {
@@ -381,6 +388,11 @@ __device__ __forceinline__ void gram_image_body(const PackArgs& a, int c, unsign
     for (int i = 0; i < 4; ++i) {
       const GramSlot sl = gram_tail_slot(4 * part + i);
       put_tail(4 * part + i, centre_value(sl), gram_T(h, sl));
+    }
+    for (int i = 0; i < 4; ++i) {
+      const int o = part >> 3, k = 4 * (part & 7) + i;
+      const GramSlot sl = gram_fold_slot(o, k);
+      put_fold(o, k, centre_value(sl), gram_T(h, sl));
     }
     // W rows in the k order of the Phi x W product: centre 16 ct + 4 g + r <-> k = 8 g + 4 ct + r
     const int g = row >> 2, j = ct * 4 + (row & 3);

@@ -9,11 +9,15 @@ namespace irbfn {
 
 typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
 
+constexpr int kGramOpBytes = 2 * 2 * 64 * 16;                    // [ct][operand][lane] 8 halfs: 4 KiB of distance operands per chunk
+constexpr int gram_chunk_bytes(int NT = 1) { return kGramOpBytes + NT * 2 * kF16WBytes; }   // + W hi, W lo per column tile
+constexpr int kGramChunkBytes = gram_chunk_bytes(1);                              // 6 KiB (narrow nets): what a ring slot holds
+// K2g (rbf_vjp_gram.hip) keeps the unfolded form -- a 16x16x16 MFMA of the heads, two 16x16x32 of the tails -- and reads its
+// centre-side records behind each chunk image: the forward kernels never copy them
 constexpr int kGramHeadBytes = 2 * 64 * 8;                       // [ct][lane] 4 halfs
 constexpr int kGramTailBytes = 2 * 2 * 64 * 16;                  // [ct][half][lane] 8 halfs
-constexpr int kGramOpBytes = kGramHeadBytes + kGramTailBytes;                     // 5 KiB of distance operands per chunk
-constexpr int gram_chunk_bytes(int NT = 1) { return kGramOpBytes + NT * 2 * kF16WBytes; }   // + W hi, W lo per column tile
-constexpr int kGramChunkBytes = gram_chunk_bytes(1);                              // 7 KiB (narrow nets)
+constexpr int kGramVjpBytes = kGramHeadBytes + kGramTailBytes;   // 5 KiB
+constexpr int gram_chunk_stride(int NT = 1) { return gram_chunk_bytes(NT) + kGramVjpBytes; }   // chunk image to chunk image in memory
 constexpr int kGramDims = 8;                                    // coordinates the slot tables hold (d <= 8: the Frenet nets have 8)
 #ifndef IRBFN_GRAM_RING
 #define IRBFN_GRAM_RING 5       // chunk images per centre slice in the LDS ring of the narrow kernel: 3 (a barrier per chunk) or 5 (one per two)
@@ -31,7 +35,8 @@ struct GramHdr {
 };
 
 // ---- the slot tables: which product sits in which k-slot ---------------------------------------------------------
-// A lane of an operand holds the slots of ONE lane group g = lane >> 4: head slots 4 g + j (j < 4), tail slots 32 hf + 8 g + j (j < 8).
+// The forward kernels: two k = 32 operands per 16 x 16 tile (gram_fold_slot below).  K2g: the unfolded tables, which follow.
+// A lane of an unfolded operand holds the slots of ONE lane group g = lane >> 4: head slots 4 g + j (j < 4), tail slots 32 hf + 8 g + j (j < 8).
 // The products of coordinate i live with group i / 2 -- its head in head slot 4 (i / 2) + (i & 1), its five tail combinations in tail
 // slots 32 (i & 1) + 8 (i / 2) + m -- so a lane of the query side splits just ITS two coordinates (gram_query_operands); the
 // Q x alpha and 1 x c2 products fill free slots of the groups 0..2.  (Until round 3's last version the slots ran coordinate by
@@ -53,6 +58,65 @@ __host__ __device__ constexpr GramSlot gram_tail_slot(int s) {
                          : (g == 1 && hf == 0 && j == 5 ? GramSlot{3, 0, 3, 0} : GramSlot{0, 0, 0, 0}));
 }
 static_assert(kGramDims == 8, "four lane groups x two coordinates");
+
+// The folded tables of the forward kernels: slot k of operand o (two v_mfma_f32_16x16x32_f16 per tile, the first with C = 0).
+// A lane of group g holds k = 8 g + j (j < 8) of BOTH operands.
+//   operand 0, k 0..15 (groups 0, 1): the eleven HEADS and nothing else.  The MFMA sums the eight products of a lane group
+//     aligned to the group's largest and accumulates the groups in ascending k: two groups of fixed-point heads on one grid
+//     inside the 2^24-unit budget are summed and accumulated exactly, and the tails behind them (groups 2, 3, then operand 1)
+//     meet the CANCELLED head sum, as they did behind the 16x16x16 MFMA (tools/probe_mfma_accum.hip fold,
+//     profiles/k1g_fold_heads.txt: a million tiles bit-identical to the unfolded form).
+//   operand 0, k 16..31 and operand 1: the 47 tails.
+// Group g splits coordinates 2 g and 2 g + 1 (gram_query_operands_fold).  Groups 0 / 1 keep their own two heads and take
+// those of groups 2 / 3 (coordinates 4, 5 / 6, 7); their ten tails overflow their eight slots of operand 1 by the (1, 1)
+// combinations, which groups 2 / 3 take in return: ONE exchange across lane ^ 32 per query tile.  Q is known to every lane (the
+// butterfly), so Q x alpha and the c2 parts sit wherever a slot is free.
+__host__ __device__ constexpr GramSlot gram_fold_slot(int o, int k) {
+  const int g = k >> 3, j = k & 7;
+  if (o == 0 && g < 2)
+    return j < 2 ? GramSlot{1, 2 * g + j, 0, 0}
+                 : (j < 4 ? GramSlot{1, 4 + 2 * g + (j - 2), 0, 0}
+                          : (g == 0 ? (j == 4 ? GramSlot{2, 0, 0, 0} : GramSlot{0, 0, 0, 0})
+                                    : (j == 4 ? GramSlot{3, 0, 0, 0} : (j == 5 ? GramSlot{3, 0, 1, 0} : GramSlot{0, 0, 0, 0}))));
+  if (o == 0)                                                // groups 2, 3: coordinate 2 g, the (1, 1) tails of 2 (g - 2) and 2 (g - 2) + 1
+    return j < 5 ? GramSlot{1, 2 * g, gram_comb_p(j), gram_comb_q(j)}
+                 : (j < 7 ? GramSlot{1, 2 * (g - 2) + (j - 5), 1, 1} : (g == 2 ? GramSlot{3, 0, 3, 0} : GramSlot{0, 0, 0, 0}));
+  if (g < 2) return GramSlot{1, 2 * g + (j >> 2), gram_comb_p(j & 3), gram_comb_q(j & 3)};      // four tails of each of its two
+  if (j < 5) return GramSlot{1, 2 * g + 1, gram_comb_p(j), gram_comb_q(j)};
+  const int m = (g - 2) * 3 + (j - 5);                       // Q x alpha combinations 0..4, then the third c2 part
+  return m < 5 ? GramSlot{2, 0, gram_comb_p(m), gram_comb_q(m)} : GramSlot{3, 0, 2, 0};
+}
+// every product of the expansion exactly once, heads (p = q = 0; c2: p < 2) in k < 16 of operand 0 and nowhere else
+__host__ __device__ constexpr bool gram_slot_is_head(const GramSlot sl) { return sl.kind == 3 ? sl.p < 2 : (sl.kind != 0 && sl.p + sl.q == 0); }
+__host__ __device__ constexpr int gram_fold_count(int kind, int dim, int p, int q) {
+  int c = 0;
+  for (int o = 0; o < 2; ++o)
+    for (int k = 0; k < 32; ++k) {
+      const GramSlot sl = gram_fold_slot(o, k);
+      c += (sl.kind == kind && sl.dim == dim && sl.p == p && sl.q == q) ? 1 : 0;
+    }
+  return c;
+}
+__host__ __device__ constexpr bool gram_fold_tables_ok() {
+  int used = 0;
+  for (int o = 0; o < 2; ++o)
+    for (int k = 0; k < 32; ++k) {
+      const GramSlot sl = gram_fold_slot(o, k);
+      used += sl.kind != 0 ? 1 : 0;
+      if (sl.kind != 0 && gram_slot_is_head(sl) != (o == 0 && k < 16)) return false;       // no head at k >= 16, no tail below
+    }
+  if (used != 8 * 6 + 6 + 4) return false;                   // nothing twice, given that everything below is there once
+  for (int p = 0; p < 3; ++p)
+    for (int q = 0; p + q < 3; ++q) {
+      for (int d = 0; d < kGramDims; ++d)
+        if (gram_fold_count(1, d, p, q) != 1) return false;
+      if (gram_fold_count(2, 0, p, q) != 1) return false;
+    }
+  for (int p = 0; p < 4; ++p)
+    if (gram_fold_count(3, 0, p, 0) != 1) return false;
+  return true;
+}
+static_assert(gram_fold_tables_ok(), "folded slot tables");
 // power-of-two weight of a slot's product and its split between the two operands (both kept near 2^(T/2))
 __host__ __device__ inline int gram_T(const GramHdr& h, const GramSlot sl) {
   return sl.kind == 1 ? h.ex + h.ec - 11 * (sl.p + sl.q) : (sl.kind == 2 ? h.eq + h.ea - 11 * (sl.p + sl.q) : h.e2 - 11 * sl.p);
@@ -161,7 +225,7 @@ __device__ __forceinline__ void trans16(const f4_t (&u)[2][2], float (&o)[16]) {
 
 struct GramArgs {
   F16Args f;                              // x, img = K1h's image (records of the VALU path), oscale, bias, out, gate, B, ...
-  const unsigned char* __restrict__ gimg; // [nchunks][kGramChunkBytes]
+  const unsigned char* __restrict__ gimg; // [nchunks][gram_chunk_stride]: a chunk's image, then K2g's records
   const GramHdr* __restrict__ hdr;
   GateRow g0;                             // the narrow kernels' gate: region 0's row by value, with the kernel arguments
   int nsteps;                             // chunks of the longest of the S slices: the steps every wave of a block walks
@@ -178,8 +242,10 @@ __device__ __forceinline__ void gram_parts_f(float vh, float vl, float inv, floa
 }
 
 // Query-side operands of the expansion for the wave's two query tiles (rows qrow[t] of x): B[k = slot][column = query (lane & 15)],
-// slots 4 g + j of the head MFMA, 32 hf + 8 g + j of the tail MFMAs (g = lane >> 4).  A lane splits the two coordinates 2 g and
-// 2 g + 1 of its queries (the slot tables above put exactly their products into its slots); Q = |x'|^2 is summed in double-float
+// a lane holding the slots of its group g = lane >> 4 (forward: 8 g + j of both operands, gram_query_operands_fold; K2g: 4 g + j
+// of the head MFMA, 32 hf + 8 g + j of the tail MFMAs, gram_query_operands).  A lane splits the two coordinates 2 g and
+// 2 g + 1 of its queries (gram_query_parts; the slot tables above put their products into its slots, but for the one exchange of
+// the folded form); Q = |x'|^2 is summed in double-float
 // over the four lanes that hold a query's coordinates (a commutative butterfly: the four lanes end with the same bits).  Returns
 // whether THIS lane's coordinates fall outside the representable box (|x'_i| >= 2^ex, Q >= 2^eq, NaN, Inf) or the header says the
 // net does not fit -- the callers take the ballot of the wave.
@@ -203,22 +269,20 @@ __device__ __forceinline__ void gram_query_loads(const F16Args& a, const GramHdr
     }
 }
 
+// the normalised parts of the lane's two coordinates (nx[t][c][part]) and of Q (nq[t][part]) for the two query tiles
 template <int DC>
-__device__ __forceinline__ bool gram_query_operands(const F16Args& a, const GramHdr* hp, const float (&xin)[2][2], const float (&rin)[2],
-                                                    int g, h4_t (&bhd)[2], h8_t (&btl)[2][2]) {
+__device__ __forceinline__ bool gram_query_parts(const GramHdr* hp, const float (&xin)[2][2], const float (&rin)[2], int g,
+                                                 float (&nx)[2][2][3], float (&nq)[2][3]) {
   // The error-free sums below are written operation by operation: contracted into FMAs (hipcc's default, -ffp-contract=fast:
   // th = qh + sh * sh as one fma, tb = th - qh as fma(-sh', sh', th) when qh is itself a product) they lose the low word of Q --
   // 6e-8 of |x'|^2, which the cancellation against 2 c'x' and |c'|^2 turns into 4e-5 of the result for a query 28 widths from
   // the origin of the expansion (tests/test_gpu_gram.py::test_gram_ill_conditioned_columns[outlier_far_centre])
 #pragma clang fp contract(off)
   static_assert(DC <= kGramDims, "eight coordinate slots");
-  const int ex = hp->ex, ec = hp->ec, eq = hp->eq, ea = hp->ea, e2 = hp->e2;
-  GramHdr hx;                                                // exponents only (gram_T)
-  hx.ex = ex; hx.ec = ec; hx.eq = eq; hx.ea = ea; hx.e2 = e2;
+  const int ex = hp->ex, eq = hp->eq;
   bool bad = hp->ok == 0;
   const float xinv = __builtin_ldexpf(1.0f, -ex), qinv = __builtin_ldexpf(1.0f, -eq);
   const float xlim = __builtin_ldexpf(1.0f, ex) * 0.999f, qlim = __builtin_ldexpf(1.0f, eq) * 0.999f;
-  auto scale_of = [&](const GramSlot sl) -> float { return sl.kind == 0 ? 0.0f : __builtin_ldexpf(1.0f, gram_ax(gram_T(hx, sl))); };
   float rr[2];
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
@@ -226,7 +290,6 @@ __device__ __forceinline__ bool gram_query_operands(const F16Args& a, const Gram
   }
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    float nx[2][3], nq[3];
     float qh = 0.0f, ql = 0.0f;
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -235,7 +298,7 @@ __device__ __forceinline__ bool gram_query_operands(const F16Args& a, const Gram
       const float bb = sh - xv;
       const float sl = (xv - (sh - bb)) + (rr[c] - bb);
       bad = bad || !(__builtin_fabsf(sh) < xlim);            // NaN / Inf / outside the box
-      gram_parts_f(sh, sl, xinv, nx[c]);
+      gram_parts_f(sh, sl, xinv, nx[t][c]);
       const float ph = sh * sh;                              // Q += x'^2 in double-float
       const float pl = __builtin_fmaf(sh, sh, -ph) + 2.0f * sh * sl;
       const float th = qh + ph;
@@ -252,7 +315,24 @@ __device__ __forceinline__ bool gram_query_operands(const F16Args& a, const Gram
       qh = th;
     }
     bad = bad || !(qh < qlim);
-    gram_parts_f(qh, ql, qinv, nq);
+    gram_parts_f(qh, ql, qinv, nq[t]);
+  }
+  return bad;
+}
+
+// K2g's operands (the unfolded tables): B[k = slot][column = query], slots 4 g + j of the head MFMA, 32 hf + 8 g + j of the tail MFMAs
+template <int DC>
+__device__ __forceinline__ bool gram_query_operands(const F16Args& a, const GramHdr* hp, const float (&xin)[2][2], const float (&rin)[2],
+                                                    int g, h4_t (&bhd)[2], h8_t (&btl)[2][2]) {
+  GramHdr hx;                                                // exponents only (gram_T)
+  hx.ex = hp->ex; hx.ec = hp->ec; hx.eq = hp->eq; hx.ea = hp->ea; hx.e2 = hp->e2;
+  auto scale_of = [&](const GramSlot sl) -> float { return sl.kind == 0 ? 0.0f : __builtin_ldexpf(1.0f, gram_ax(gram_T(hx, sl))); };
+  float nxa[2][2][3], nqa[2][3];
+  const bool bad = gram_query_parts<DC>(hp, xin, rin, g, nxa, nqa);
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const float (&nx)[2][3] = nxa[t];
+    const float (&nq)[3] = nqa[t];
     // head slots 4 g + j: the two coordinates' heads, then (group 0) Q x alpha, (groups 1, 2) the two c2 heads
     {
       const float sc = scale_of(gram_head_slot(0));          // kind 1, p = q = 0: the same weight in every group
@@ -283,12 +363,63 @@ __device__ __forceinline__ bool gram_query_operands(const F16Args& a, const Gram
   }
   return bad;
 }
+
+// The forward kernels' operands (gram_fold_slot): bq[t][o][j] = slot 8 g + j of operand o for query tile t.  A lane converts the
+// parts of its own two coordinates; what its slots hold of another group's comes as one dword per tile from lane ^ 32:
+// groups 2 / 3 send their two heads, groups 0 / 1 their two (1, 1) tails.
+template <int DC>
+__device__ __forceinline__ bool gram_query_operands_fold(const F16Args& a, const GramHdr* hp, const float (&xin)[2][2],
+                                                         const float (&rin)[2], int g, h8_t (&bq)[2][2]) {
+  typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+  GramHdr hx;                                                // exponents only (gram_T)
+  hx.ex = hp->ex; hx.ec = hp->ec; hx.eq = hp->eq; hx.ea = hp->ea; hx.e2 = hp->e2;
+  auto scale_of = [&](const GramSlot sl) -> float { return sl.kind == 0 ? 0.0f : __builtin_ldexpf(1.0f, gram_ax(gram_T(hx, sl))); };
+  float nxa[2][2][3], nqa[2][3];
+  const bool bad = gram_query_parts<DC>(hp, xin, rin, g, nxa, nqa);
+  const bool lower = g < 2;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const float (&nx)[2][3] = nxa[t];
+    const float (&nq)[3] = nqa[t];
+    const float sc0 = scale_of(GramSlot{1, 0, 0, 0}), sc11 = scale_of(GramSlot{1, 0, 1, 1});
+    const h2_t mine = lower ? h2_t{(_Float16)(nx[0][1] * sc11), (_Float16)(nx[1][1] * sc11)}
+                            : h2_t{(_Float16)(nx[0][0] * sc0), (_Float16)(nx[1][0] * sc0)};
+    const h2_t theirs = __builtin_bit_cast(h2_t, __shfl_xor(__builtin_bit_cast(int, mine), 32));
+    // the value of a slot as group gg has it, from this lane's parts (the select below keeps the lane's own group's)
+    auto value = [&](const GramSlot sl, int gg) -> float {
+      if (sl.kind == 0) return 0.0f;
+      if (sl.kind == 2) return nq[sl.p] * scale_of(sl);
+      if (sl.kind == 3) return scale_of(sl);
+      return nx[sl.dim & 1][sl.p] * scale_of(sl);            // an own coordinate: dim = 2 gg or 2 gg + 1
+    };
+#pragma unroll
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        _Float16 v[4];
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+          const GramSlot sl = gram_fold_slot(o, 8 * gg + j);
+          const bool foreign = sl.kind == 1 && (sl.dim >> 1) != gg;       // arrives from lane ^ 32, in the order it was packed
+          v[gg] = foreign ? theirs[sl.dim & 1] : (_Float16)value(sl, gg);
+        }
+        bq[t][o][j] = g == 0 ? v[0] : (g == 1 ? v[1] : (g == 2 ? v[2] : v[3]));
+      }
+  }
+  return bad;
+}
 template <int DC>
 __device__ __forceinline__ bool gram_query_operands(const F16Args& a, const GramHdr* hp, const long (&qrow)[2], int g, h4_t (&bhd)[2],
                                                     h8_t (&btl)[2][2]) {
   float xv[2][2], rv[2];
   gram_query_loads<DC>(a, hp, qrow, g, xv, rv);
   return gram_query_operands<DC>(a, hp, xv, rv, g, bhd, btl);
+}
+template <int DC>
+__device__ __forceinline__ bool gram_query_operands_fold(const F16Args& a, const GramHdr* hp, const long (&qrow)[2], int g, h8_t (&bq)[2][2]) {
+  float xv[2][2], rv[2];
+  gram_query_loads<DC>(a, hp, qrow, g, xv, rv);
+  return gram_query_operands_fold<DC>(a, hp, xv, rv, g, bq);
 }
 // the tables say what the code above assumes
 static_assert(gram_head_slot(0).kind == 1 && gram_head_slot(4 * 3 + 1).dim == 7 && gram_head_slot(2).kind == 2 && gram_head_slot(6).kind == 3 &&
@@ -297,19 +428,12 @@ static_assert(gram_tail_slot(32 + 8 * 2 + 4).kind == 1 && gram_tail_slot(32 + 8 
               gram_tail_slot(32 + 6).kind == 2 && gram_tail_slot(32 + 7).kind == 3 && gram_tail_slot(32 + 7).p == 2 && gram_tail_slot(8 + 5).kind == 3 &&
               gram_tail_slot(8 + 5).p == 3 && gram_tail_slot(8 + 6).kind == 0 && gram_tail_slot(16 + 5).kind == 0 && gram_tail_slot(32 + 8 + 5).kind == 0, "tail slots");
 
-// The exact head sums u[t][ct] = A[ct] x B[t] (v_mfma_f32_16x16x16_f16, C = 0) of the 2 x 2 tiles, as ONE asm block that ends in
-// five wait states.  gfx950 does NOT interlock a 16x16x32 MFMA that accumulates onto the result of a 16x16x16 one, and hipcc does
-// not pad the pair: with fewer than 5 wait states (or one other MFMA) between the two the second reads a stale accumulator --
+// K2g's exact head sums (v_mfma_f32_16x16x16_f16, C = 0), each as ONE asm block that ends in five wait states.  gfx950 does NOT
+// interlock a 16x16x32 MFMA that accumulates onto the result of a 16x16x16 one, and hipcc does not pad the pair: with fewer than 5 wait states (or one other MFMA) between the two the second reads a stale accumulator --
 // half of its outputs wrong, tools/probe_mfma_dependent.hip (16x16x32 -> 16x16x32, 16x16x16 -> 16x16x16 and MFMA -> VALU are
 // interlocked).  The compiler's schedule had kept the pairs apart in the shipped kernels and put them back to back in faster
 // variants of K2g (four waves per SIMD: all 24 instances wrong), which is how this was found.
-__device__ __forceinline__ void gram_heads(const h4_t (&a)[2], const h4_t (&b)[2], f4_t (&u)[2][2]) {
-  asm("v_mfma_f32_16x16x16_f16 %0, %4, %6, 0\n v_mfma_f32_16x16x16_f16 %1, %5, %6, 0\n v_mfma_f32_16x16x16_f16 %2, %4, %7, 0\n "
-      "v_mfma_f32_16x16x16_f16 %3, %5, %7, 0\n s_nop 4"
-      : "=&v"(u[0][0]), "=&v"(u[0][1]), "=&v"(u[1][0]), "=&v"(u[1][1])
-      : "v"(a[0]), "v"(a[1]), "v"(b[0]), "v"(b[1]));
-}
-// the same for one query half against two centre tiles (K2g): u[ct] = A x B[ct]
+// one query half against two centre tiles: u[ct] = A x B[ct]
 __device__ __forceinline__ void gram_heads2(const h4_t& a, const h4_t (&b)[2], f4_t (&u)[2]) {
   asm("v_mfma_f32_16x16x16_f16 %0, %2, %3, 0\n v_mfma_f32_16x16x16_f16 %1, %2, %4, 0\n s_nop 4"
       : "=&v"(u[0]), "=&v"(u[1])
@@ -324,31 +448,28 @@ __device__ __forceinline__ void gram_heads2c(const h4_t& a, const h4_t (&b)[2], 
       : "v"(a), "v"(b[0]), "v"(b[1]), "v"(c));
 }
 
-// the argument of the transcendental for the 2 x 2 tiles (query tile t, centre tile ct) of the chunk image at `buf`: head sum
-// (exact), then the tails
-// (`l8`, `l16`: the lane's 8 and 16 bytes at the start of the image, buf + lane * 8 and buf + lane * 16)
-__device__ __forceinline__ void gram_distances_at(const unsigned char* l8, const unsigned char* l16, const h4_t (&bhd)[2],
-                                                  const h8_t (&btl)[2][2], f4_t (&u)[2][2]) {
-  h4_t ahd[2];
-  h8_t atl[2][2];
+// the argument of the transcendental for the 2 x 2 tiles (query tile t, centre tile ct) of the chunk image at `buf`: operand 0
+// (C = 0: the exact head sum, then its 16 tails), then operand 1 -- the four independent MFMAs first, so that no MFMA follows
+// the one it accumulates onto (16x16x32 onto 16x16x32 is interlocked either way: tools/probe_mfma_dependent.hip)
+// (`l16`: the lane's 16 bytes at the start of the image, buf + lane * 16)
+__device__ __forceinline__ void gram_distances_at(const unsigned char* l16, const h8_t (&bq)[2][2], f4_t (&u)[2][2]) {
+  h8_t aq[2][2];
 #pragma unroll
-  for (int ct = 0; ct < 2; ++ct) {
-    ahd[ct] = *reinterpret_cast<const h4_t*>(l8 + ct * 512);
-    atl[ct][0] = *reinterpret_cast<const h8_t*>(l16 + kGramHeadBytes + (ct * 2 + 0) * 1024);
-    atl[ct][1] = *reinterpret_cast<const h8_t*>(l16 + kGramHeadBytes + (ct * 2 + 1) * 1024);
-  }
-  gram_heads(ahd, bhd, u);                                     // exact head sums
+  for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-  for (int hf = 0; hf < 2; ++hf)
+    for (int o = 0; o < 2; ++o) aq[ct][o] = *reinterpret_cast<const h8_t*>(l16 + (ct * 2 + o) * 1024);
+  const f4_t z = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+  for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-        u[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(atl[ct][hf], btl[t][hf], u[t][ct], 0, 0, 0);
+    for (int ct = 0; ct < 2; ++ct) u[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aq[ct][0], bq[t][0], z, 0, 0, 0);
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) u[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aq[ct][1], bq[t][1], u[t][ct], 0, 0, 0);
 }
-__device__ __forceinline__ void gram_distances(const unsigned char* buf, int lane, const h4_t (&bhd)[2], const h8_t (&btl)[2][2],
-                                               f4_t (&u)[2][2]) {
-  gram_distances_at(buf + lane * 8, buf + lane * 16, bhd, btl, u);
+__device__ __forceinline__ void gram_distances(const unsigned char* buf, int lane, const h8_t (&bq)[2][2], f4_t (&u)[2][2]) {
+  gram_distances_at(buf + lane * 16, bq, u);
 }
 
 // The same arguments on the VALU from K1h's centre records `recs` of the chunk (a wave with a query outside the box): t16[t * 8 + j] for

@@ -21,7 +21,8 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
   static_assert(DC <= kGramDims, "eight coordinate slots");
   const F16Args& a = ga.f;
   constexpr int CBL = f16_chunk_bytes(DC);                   // K1h's chunk image (the VALU path reads its records)
-  constexpr int CB = kGramChunkBytes;
+  constexpr int CB = kGramChunkBytes;                        // what a ring slot holds of a chunk image
+  constexpr int CST = gram_chunk_stride(1);                  // chunk image to chunk image in memory (K2g's records lie between)
   const int tid = threadIdx.x, lane = tid & 63;
   IRBFN_GRAM_PHASE(GP_ENTRY);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -69,13 +70,12 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
       }
     }
   }
-  h4_t bhd[2];
-  h8_t btl[2][2];
-  const bool bad = gram_query_operands<DC>(a, hp, xop, rop, g, bhd, btl);
+  h8_t bq[2][2];
+  const bool bad = gram_query_operands_fold<DC>(a, hp, xop, rop, g, bq);
   // wave-uniform: the VALU distances for these 32 queries (through readfirstlane, which tells the compiler so)
   const bool wave_bad = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_ballot_w64(bad) != 0ull ? 1 : 0) != 0;
 #ifdef IRBFN_GRAM_STAMPS
-  asm volatile("" ::"s"((int)wave_bad), "v"(bhd[1]), "v"(btl[1][1]));
+  asm volatile("" ::"s"((int)wave_bad), "v"(bq[1][0]), "v"(bq[1][1]));
 #endif
   IRBFN_GRAM_PHASE(GP_OPERANDS);
 
@@ -87,7 +87,7 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
   // Ring of kGramRing chunk images per slice: during step i the waves read the distance operands of chunk i + 1 and the W
   // operands of chunk i while later chunks land (end_of_step below).
   unsigned char* ring = lds + (size_t)slice * kGramRing * CB;
-  constexpr int NVI = CB / 1024;                             // 7 wave-instructions per chunk image
+  constexpr int NVI = CB / 1024;                             // 6 wave-instructions per chunk image
   // The one-region instances carry the address of their refills: a wave requests pieces qg, qg + QG, ... of every chunk image of
   // its slice, and the chunks are staged in order (k = 0, 1, 2, ... from the prologue on), so gnext is the lane's 16 bytes of piece
   // qg of the NEXT chunk to stage, advanced by one image per staged chunk: one 64-bit add per chunk where the address built from k
@@ -96,17 +96,17 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
   [[maybe_unused]] int npc = 0;                              // pieces of a chunk image this wave requests
 #pragma unroll
   for (int p = 0; p < NVI; ++p) npc += qg + p * QG < NVI ? 1 : 0;
-  [[maybe_unused]] const unsigned char* gnext = ga.gimg + (size_t)c0 * CB + qg * 1024 + lane * 16;
+  [[maybe_unused]] const unsigned char* gnext = ga.gimg + (size_t)c0 * CST + qg * 1024 + lane * 16;
   auto stage = [&](int k, int buf) __attribute__((always_inline)) {   // chunk c0 + k of the slice -> ring slot buf; the QG waves share the copy
     if (k >= na) return;
     unsigned char* dst = ring + buf * CB;
     if constexpr (GAMMA) {
-      const unsigned char* gp = ga.gimg + (size_t)(c0 + k) * CB + lane * 16;
+      const unsigned char* gp = ga.gimg + (size_t)(c0 + k) * CST + lane * 16;
       for (int v = qg; v < NVI; v += QG)
         __builtin_amdgcn_global_load_lds((gptr_t)(gp + v * 1024), (lptr_t)(dst + v * 1024), 16, 0, 0);
     } else {
-      // piece qg from the pointer itself; QG < 7: the further pieces in a rolled loop, one add each as before (unrolled to
-      // seven pieces with their LDS addresses as constants the ten-step trip wants 70 scalar registers and spills them)
+      // piece qg from the pointer itself; QG < 6: the further pieces in a rolled loop, one add each as before (unrolled to
+      // all pieces with their LDS addresses as constants the ten-step trip wants 70 scalar registers and spills them)
       if (npc > 0) {
         const unsigned char* gp = gnext;
         unsigned char* lp = dst + qg * 1024;
@@ -117,7 +117,7 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
           __builtin_amdgcn_global_load_lds((gptr_t)gp, (lptr_t)lp, 16, 0, 0);
         }
       }
-      gnext += CB;
+      gnext += CST;
     }
   };
   auto step_barrier = [&]() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
@@ -224,24 +224,23 @@ __device__ __forceinline__ void gram_body(const GramArgs& ga, const F16Roll& rl,
   if (!wave_bad) {
     // the distances of chunk i + 1 are issued in front of the VALU work on chunk i: ua / ub hold them in turn
     f4_t ua[2][2], ub[2][2];
-    if (na > 0) gram_distances(ring, lane, bhd, btl, ua);
-    // trans16 is inline asm: the hazard recogniser does not see it read MFMA results.  In the loop the 12 distance MFMAs of the
+    if (na > 0) gram_distances(ring, lane, bq, ua);
+    // trans16 is inline asm: the hazard recogniser does not see it read MFMA results.  In the loop the 8 distance MFMAs of the
     // next chunk lie in front of it; a slice of ONE chunk reads them right away: explicit wait states, once
     asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
     [[maybe_unused]] unsigned long long tph[5] = {0, 0, 0, 0, 0};
-    // The lane's two bases into the slice's ring (8-byte head records; 16-byte tail and W records).  The one-region instances
-    // hold them as registers the compiler takes as given: with the slot a constant (below) every LDS read of a step is one of the
-    // two plus an immediate, at most (kGramRing - 1) x 7168 + 6144 -- no vector add per read group.
-    unsigned o8 = (unsigned)(slice * kGramRing * CB) + lane * 8, o16 = (unsigned)(slice * kGramRing * CB) + lane * 16;
-    if constexpr (!GAMMA) asm volatile("" : "+v"(o8), "+v"(o16));
-    const unsigned char* const r8 = lds + o8;
+    // The lane's base into the slice's ring (16-byte operand and W records).  The one-region instances hold it as a register the
+    // compiler takes as given: with the slot a constant (below) every LDS read of a step is the base plus an immediate, at most
+    // (kGramRing - 1) x 6144 + 5120 -- no vector add per read group.
+    unsigned o16 = (unsigned)(slice * kGramRing * CB) + lane * 16;
+    if constexpr (!GAMMA) asm volatile("" : "+v"(o16));
     const unsigned char* const r16 = lds + o16;
     static_assert((kGramRing - 1) * CB + kGramOpBytes + kF16WBytes + 16 <= 65536, "the offset field of ds_read has 16 bits");
     // step i: chunk i in ring slot b0, chunk i + 1 in the next slot; par = i % kGramPer; all: the caller knows i + 1 < na
     auto one_step = [&](int i, int b0, int par, f4_t (&ucur)[2][2], f4_t (&unxt)[2][2], bool all = false) __attribute__((always_inline)) {
       const int b1 = next3(b0);
       [[maybe_unused]] const unsigned long long t0 = IRBFN_GRAM_T();
-      if (all || i + 1 < na) gram_distances_at(r8 + b1 * CB, r16 + b1 * CB, bhd, btl, unxt);   // issued in front of the VALU work on chunk i
+      if (all || i + 1 < na) gram_distances_at(r16 + b1 * CB, bq, unxt);   // issued in front of the VALU work on chunk i
       if (all || i < na) {
         gamma_read(i);
         float t16[16];

@@ -57,7 +57,7 @@ int gram_gamma_select(irbfn_net* net) {
   if (net->gram_img) return IRBFN_OK;
   const size_t nchunks = (size_t)net->R * gram_gamma_cpr(net);
   void* bufs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  const size_t bytes[5] = {nchunks * f16_chunk_bytes(net->DC, 1), 128 * sizeof(float), nchunks * kGramChunkBytes, sizeof(GramHdr),
+  const size_t bytes[5] = {nchunks * f16_chunk_bytes(net->DC, 1), 128 * sizeof(float), nchunks * gram_chunk_stride(1), sizeof(GramHdr),
                            pack_partials_bytes(net)};
   for (int i = 0; i < 5; ++i) {
     const hipError_t e = hipMalloc(&bufs[i], bytes[i]);

@@ -1,11 +1,11 @@
 // K1g for wide outputs (16 < O <= 128): the body of rbf_fwd_f16gram_wide (rbf_forward_gram_wide.hip) and of the one-launch
 // planning tick rbf_tick_f16gram_wide (plan_tick_wide.hip).  The squared distances of a 32-centre chunk come from the matrix
-// cores as the exactly-cancelling Gram expansion of rbf_forward_gram.hip (12 MFMAs for the wave's 32 queries instead of
+// cores as the exactly-cancelling Gram expansion of rbf_forward_gram.hip (8 MFMAs for the wave's 32 queries instead of
 // 16 x 15 VALU instructions), the transcendental and the (hi, lo) split stay on the VALU, and the 6 NT MFMAs of Phi x W follow as
 // in K1h's wide kernel (rbf_forward_f16_wide.h) -- whose epilogue (slice sums per column tile, gate, scale, bias, optional
 // roll-out of the block's trajectories) is shared.
 //
-// Chunk image: 5 KiB of distance operands (rbf_forward_gram.h) + NT x (W hi, W lo) with the W rows in the k order the distance
+// Chunk image: 4 KiB of distance operands (rbf_forward_gram.h) + NT x (W hi, W lo) with the W rows in the k order the distance
 // MFMAs leave the basis values in (centre 16 ct + 4 g + r <-> k = 8 g + 4 ct + r).  The QG waves of a centre slice share an
 // LDS ring of three images filled by LDS-DMA; during step i a wave turns the arguments of chunk i into (hi, lo) basis operands,
 // issues the distance MFMAs of chunk i + 1 and, behind them, the Phi x W products of chunk i; one barrier per step.
@@ -19,7 +19,8 @@ template <int DC, int BC, int NT, int MODE>
 __device__ __forceinline__ void wide_gram_body(const GramArgs& ga, const F16Roll& rl, unsigned char* lds) {
   const F16Args& a = ga.f;
   constexpr int CBL = f16_chunk_bytes(DC, NT);               // K1h's chunk image (the VALU path reads its records)
-  constexpr int CB = gram_chunk_bytes(NT);
+  constexpr int CB = gram_chunk_bytes(NT);                   // what a ring slot holds of a chunk image
+  constexpr int CST = gram_chunk_stride(NT);                 // chunk image to chunk image in memory (K2g's records lie between)
   constexpr int NVI = CB / 1024;                             // wave-instructions per chunk image
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -34,9 +35,8 @@ __device__ __forceinline__ void wide_gram_body(const GramArgs& ga, const F16Roll
     q = q < a.B ? q : a.B - 1;
     qrow[t] = q < 0 ? 0 : q;
   }
-  h4_t bhd[2];
-  h8_t btl[2][2];
-  const bool bad = gram_query_operands<DC>(a, ga.hdr, qrow, g, bhd, btl);
+  h8_t bq[2][2];
+  const bool bad = gram_query_operands_fold<DC>(a, ga.hdr, qrow, g, bq);
   const bool wave_bad = __builtin_amdgcn_ballot_w64(bad) != 0ull;     // wave-uniform: the VALU distances for these 32 queries
 
   const int nsteps = (a.nchunks + SW - 1) / SW;              // chunks per slice (the last slice may have fewer)
@@ -46,7 +46,7 @@ __device__ __forceinline__ void wide_gram_body(const GramArgs& ga, const F16Roll
   unsigned char* ring = lds + (size_t)slice * 3 * CB;
   auto stage = [&](int k, int buf) {                         // chunk c0 + k of the slice -> ring slot buf; the QG waves share the copy
     if (k >= na) return;
-    const unsigned char* gp = ga.gimg + (size_t)(c0 + k) * CB + lane * 16;
+    const unsigned char* gp = ga.gimg + (size_t)(c0 + k) * CST + lane * 16;
     unsigned char* dst = ring + buf * CB;
     for (int v = qg; v < NVI; v += QG)
       __builtin_amdgcn_global_load_lds((gptr_t)(gp + v * 1024), (lptr_t)(dst + v * 1024), 16, 0, 0);
@@ -103,7 +103,7 @@ __device__ __forceinline__ void wide_gram_body(const GramArgs& ga, const F16Roll
     // per step: basis values and operand split of chunk i (VALU), then the distance MFMAs of chunk i + 1 -- issued once the
     // arguments of chunk i are consumed: one set of 16 argument registers -- and the Phi x W MFMAs of chunk i behind them
     f4_t u[2][2];
-    if (na > 0) gram_distances(ring, lane, bhd, btl, u);
+    if (na > 0) gram_distances(ring, lane, bq, u);
     // trans16 is inline asm: the hazard recogniser does not see it read MFMA results.  In the loop 6 NT MFMAs lie between the
     // distance MFMAs and the transcendentals that read them; here, once, explicit wait states do
     asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
@@ -117,7 +117,7 @@ __device__ __forceinline__ void wide_gram_body(const GramArgs& ga, const F16Roll
           trans16<BC>(u, t16);
           split16(t16, ah, al);
         }
-        if (i + 1 < na) gram_distances(ring + b1 * CB, lane, bhd, btl, u);
+        if (i + 1 < na) gram_distances(ring + b1 * CB, lane, bq, u);
         products(ah, al, ring + b0 * CB);
       }
       step_barrier();                                        // chunk i + 2 is there; everybody has left chunk i

@@ -606,11 +606,15 @@ static int launch_vjp_gram_mode(irbfn_net* net, const float* x, const float* gou
   });
   if (rc != IRBFN_OK) return rc;
   VjpGArgs a;
-  a.qblk = qblk; a.scales = scales; a.gimg = net->gram_img; a.hdr = hdr; a.flag = flag; a.gen = gen; a.rec = net->rec; a.sig2 = net->sig2;
+  a.qblk = qblk; a.scales = scales; a.hdr = hdr; a.flag = flag; a.gen = gen; a.rec = net->rec; a.sig2 = net->sig2;
   a.oscale = net->f16_oscale; a.part = part;
   a.nqb = nqb; a.O = net->O; a.OP = net->OP; a.N = net->N; a.S = net->S; a.Npad = Npad;
   a.bpb = (int)((nqb + QSB - 1) / QSB);
-  a.cstride = gram_chunk_bytes((net->O + 15) / 16);
+  {
+    const int nt = (net->O + 15) / 16;                       // the unfolded centre-side records lie behind each chunk image of K1g
+    a.gimg = net->gram_img + gram_chunk_bytes(nt);
+    a.cstride = gram_chunk_stride(nt);
+  }
   a.nchunks = (net->N + 31) / 32;
   a.gscale = gauss_scale(net->basis);
   if (gtile != nullptr) {
