@@ -543,6 +543,30 @@ int irbfn_kmeans_step(const float* x_dev /*[N,D]*/, const float* centers_dev /*[
                       int64_t* counts_dev /*[K] or NULL*/, double* stats_dev /*[4]*/, int64_t N, int K, int D,
                       void* workspace_dev, int64_t workspace_bytes, void* stream);
 
+/* Closed-form fit of the output layer (rbf_hidden.hip, syrk_f64.hip; irbfn_amd/linear_fit.py).  With the centres and widths held
+ * fixed a net is linear in linear/kernel and linear/bias: the classical RBF construction takes them from linear least squares in
+ * one pass over the table.  The reference has no counterpart (it reaches these weights by Adam alone): parity is unpinned; each
+ * stage is pinned against a float64 statement of it.
+ * irbfn_net_hidden: x_dev [B,D] -> h_dev[b * ldh + k] = sum_r gamma[b,r] phi(|x_b - c_rk| / sigma_rk), k < K, ldh >= K; columns
+ *   >= K of a row are not written.  gamma is the net's own tanh gate; the bound linear leaves are ignored.  All-float32 VALU
+ *   arithmetic as irbfn_net_forward's K1 (direct differences, the same basis and gate forms, the gate's exact zero); any net
+ *   irbfn_net_create accepts.  Rows are independent (a NaN query stays in its row); no workspace; deterministic.  B = 0:
+ *   IRBFN_OK, no launch.  IRBFN_ERR_BAD_ARG: NULL net, B < 0, and with B > 0 a NULL x / h or ldh < K; IRBFN_ERR_NO_PARAMS
+ *   before irbfn_net_set_params.  irbfn_net_last_launch names it rbf_hidden<...>.
+ * irbfn_syrk_f64: g[i][j] (+)= sum_n z[n * ldz + i] z[n * ldz + j], i, j < M: the float64 Gram matrix of float32 rows, both
+ *   triangles of the full row-major [M][M] matrix, symmetric bit for bit.  accumulate = 0 overwrites g and never reads it (rows = 0
+ *   zeroes it); accumulate = 1 adds onto it (rows = 0 leaves it untouched).  Every product is float32 x float32, exact in
+ *   float64, and every sum is float64 (v_mfma_f64_16x16x4_f64): |g - exact| <= rows 2^-53 sum_n |z_ni z_nj|.  Rows past
+ *   `rows` and columns in [M, ldz) are never read.  Non-finite values of z propagate by IEEE rules into the entries they touch.
+ *   No atomics: bit-identical across repeats.  The workspace (irbfn_syrk_f64_workspace_bytes(rows, M) bytes, below 1 GiB, 8-byte
+ *   aligned) need not be cleared.  IRBFN_ERR_BAD_ARG: M < 1, M > 8192, ldz < M, rows < 0, a NULL g, a NULL z with rows > 0, a
+ *   workspace that is NULL, misaligned or too small; all decided before any HIP call.  irbfn_syrk_f64_workspace_bytes returns
+ *   the same negative code for sizes it refuses. */
+int irbfn_net_hidden(irbfn_net* net, const float* x_dev /*[B,D]*/, float* h_dev /*[B,ldh]*/, int64_t ldh, int64_t B, void* stream);
+int64_t irbfn_syrk_f64_workspace_bytes(int64_t rows, int M);
+int irbfn_syrk_f64(const float* z_dev /*[rows,ldz]*/, int64_t ldz, int64_t rows, int M, double* g_dev /*[M,M]*/, int accumulate,
+                   void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* Diagnostics */
 int irbfn_abi_version(void);
 int irbfn_device_count(void);

@@ -86,6 +86,9 @@ SIGNATURES = {
     "irbfn_f64_vjp_x": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _vp, _i64, _vp]),
     "irbfn_kmeans_workspace_bytes": (_i64, [_i64, _i, _i]),
     "irbfn_kmeans_step": (_i, [_fp, _fp, _ip, _fp, _fp, _ip, _fp, _i64, _i, _i, _vp, _i64, _vp]),
+    "irbfn_net_hidden": (_i, [_vp, _fp, _fp, _i64, _i64, _vp]),
+    "irbfn_syrk_f64_workspace_bytes": (_i64, [_i64, _i]),
+    "irbfn_syrk_f64": (_i, [_fp, _i64, _i64, _i, _fp, _i, _vp, _i64, _vp]),
     "irbfn_abi_version": (_i, []),
     "irbfn_device_count": (_i, []),
     "irbfn_last_hip_error": (_i, []),

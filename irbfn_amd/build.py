@@ -61,6 +61,8 @@ UNITS = [
     ("train_step.hip", "train_step.o", []),
     ("eval_errors.hip", "eval_errors.o", []),          # K6: roll-out error statistics of a table (rolled step loop)
     ("kmeans.hip", "kmeans.o", []),                    # K7: one Lloyd iteration of k-means on a table
+    ("rbf_hidden.hip", "rbf_hidden.o", []),            # the hidden layer h[B][K] of a net: the design matrix of the closed-form fit
+    ("syrk_f64.hip", "syrk_f64.o", []),                # K8: float64 Gram matrix of float32 rows on the f64 matrix instruction
     ("mlp_head.hip", "mlp_head.o", []),
     ("planner_front.hip", "planner_front.o", []),
 ]

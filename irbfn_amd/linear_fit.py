@@ -1,0 +1,187 @@
+"""The output layer in closed form: float64 normal equations on the device (``irbfn_net_hidden``, ``irbfn_syrk_f64``).
+
+With the centres and widths held fixed a ``WCRBFNet`` is linear in ``linear/kernel`` and ``linear/bias``, so the classical RBF
+construction -- centres from clustering, then the output layer from linear least squares -- needs one pass over the table
+where Adam needs thousands of epochs.  The reference has no counterpart (it trains these weights by Adam alone), so parity is
+unpinned; what is pinned is each stage against a float64 statement of it (tests/_linear_fit_util.py).
+
+    res = kmeans.fit(table.x, k=1000)
+    net = WCRBFNet(..., centers=res.as_centers(net0), fixed_centers=True, fixed_width=True)
+    params, fit = linear_fit.fit_linear(net, net.init(), table.x, table.y)         # -> evaluate_table(net, params, table)
+
+One chunk of rows is one hidden-layer launch into Z = [h | 1 | y] and one float64 Gram launch G += Z^T Z; nothing synchronises
+with the host until ``solve``.  G is accumulated in float64 because RBF design matrices are ill-conditioned and the normal
+equations square the condition number; the products of float32 values are exact in float64, so G is the Gram matrix of the
+kernel's own float32 hidden layer up to rows * 2^-53 relative per entry.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+from .model import _grown_ws, _inner, _ptr, _stream_ptr, to_device_f32
+
+_SYRK_WS: dict = {}
+
+
+def syrk(z, out=None, accumulate: bool = False):
+    """z [rows, M] float32 on the device (rows may be strided: ``z.stride(0) >= M``) -> G = z^T z [M, M] float64, both
+    triangles (``irbfn_syrk_f64``).  ``out``: a contiguous float64 [M, M] cuda tensor to write, or with ``accumulate`` to add onto."""
+    torch = _lib.require_gpu()
+    lib = _lib.load()
+    if not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != torch.float32 or z.dim() != 2 or (z.shape[0] > 1 and z.stride(1) != 1):
+        z = to_device_f32(z, torch)
+        if z.dim() != 2:
+            raise ValueError(f"syrk needs z [rows, M], got {tuple(z.shape)}")
+    rows, M = z.shape
+    ldz = z.stride(0) if rows > 1 else max(z.stride(0), M)
+    if out is None:
+        if accumulate:
+            raise ValueError("syrk: accumulate=True needs out=")
+        out = torch.empty((M, M), dtype=torch.float64, device=z.device)
+    elif tuple(out.shape) != (M, M) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"syrk: out must be a contiguous float64 cuda tensor of shape ({M}, {M})")
+    need = lib.irbfn_syrk_f64_workspace_bytes(rows, M)
+    if need < 0:
+        _lib.check(int(need), "irbfn_syrk_f64_workspace_bytes")
+    ws = _grown_ws(_SYRK_WS, z.device.index, need, torch, z.device)
+    st = lib.irbfn_syrk_f64(_ptr(z), ldz, rows, M, _ptr(out), 1 if accumulate else 0, _ptr(ws), ws.numel(), _stream_ptr(torch))
+    _lib.check(st, "irbfn_syrk_f64")
+    return out
+
+
+class LinearFit:
+    """The solution of ``NormalEquations.solve``: ``kernel`` [K,O] and ``bias`` [O] in float64 (on G's device), the number of
+    rows ``n``, ``rss`` [O] = the residual sum of squares per output computed from G alone, ``mse`` = sum(rss) / (n O), and
+    ``ridge_abs`` = the absolute ridge lambda that was added to the diagonal of H^T H."""
+
+    def __init__(self, kernel, bias, n, rss, ridge_abs):
+        self.kernel, self.bias, self.n, self.rss, self.ridge_abs = kernel, bias, n, rss, float(ridge_abs)
+
+    @property
+    def mse(self) -> float:
+        return float(self.rss.sum().item()) / (max(self.n, 1) * max(self.rss.numel(), 1))
+
+
+class NormalEquations:
+    """G = Z^T Z in float64, Z = [h_0 .. h_{K-1}, 1, y_0 .. y_{O-1}] (M = K + 1 + O columns): H^T H, the column sums H^T 1, H^T Y,
+    n = G[K,K], 1^T Y and Y^T Y at once.  ``add`` accumulates rows on the device; ``merge`` / ``all_reduce`` combine
+    accumulators; ``solve`` returns the ridge-regularised least-squares output layer."""
+
+    def __init__(self, net, G=None):
+        if getattr(net, "use_float64", False):
+            raise ValueError("NormalEquations: the float64 mode has no hidden-layer kernel (construct the net with use_float64=False)")
+        self.net = net
+        self.K, self.O = int(net.num_kernels), int(net.out_features)
+        self.M = self.K + 1 + self.O
+        if G is not None and (tuple(G.shape) != (self.M, self.M) or str(G.dtype) != "torch.float64"):
+            raise ValueError(f"G must be a float64 tensor of shape ({self.M}, {self.M})")
+        self.G = G
+        self._Z = None
+
+    def add(self, params: dict, x, y, batch_size: int = 65536) -> "NormalEquations":
+        """Adds the rows (x [N,D], y [N,O]) under ``params``: per chunk of ``batch_size`` rows one ``irbfn_net_hidden`` into the
+        reused buffer Z [chunk, M], the ones column and y by two slice assignments, then ``irbfn_syrk_f64(accumulate=1)``."""
+        torch = _lib.require_gpu()
+        net, K, O, M = self.net, self.K, self.O, self.M
+        xs, ys = tuple(x.shape), tuple(y.shape)
+        if len(xs) != 2 or xs[1] != net.in_features:
+            raise ValueError(f"x must have shape (N, {net.in_features}), got {xs}")
+        if len(ys) != 2 or ys[1] != O:
+            raise ValueError(f"y must have shape (N, {O}), got {ys}")
+        if xs[0] != ys[0]:
+            raise ValueError(f"x has {xs[0]} rows, y has {ys[0]}")
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        net._warn_if_float64(params)
+        net.bind(params)
+        xd = to_device_f32(x, torch)
+        yd = to_device_f32(y, torch, device=xd.device)
+        if self.G is None:
+            self.G = torch.zeros((M, M), dtype=torch.float64, device=xd.device)
+        N = xs[0]
+        chunk = min(int(batch_size), max(N, 1))
+        if self._Z is None or self._Z.shape[0] < chunk or self._Z.device != xd.device:
+            self._Z = torch.empty((chunk, M), dtype=torch.float32, device=xd.device)
+        for i in range(0, N, chunk):
+            n = min(chunk, N - i)
+            Z = self._Z[:n]
+            net._hidden_into(xd[i:i + n], Z, torch)
+            Z[:, K] = 1.0
+            Z[:, K + 1:] = yd[i:i + n]
+            syrk(Z, out=self.G, accumulate=True)
+        return self
+
+    def merge(self, other: "NormalEquations") -> "NormalEquations":
+        """Adds another accumulator of the same net shape (e.g. of another part of the table)."""
+        if (other.K, other.O) != (self.K, self.O):
+            raise ValueError(f"merge: accumulators of K={other.K}, O={other.O} and K={self.K}, O={self.O}")
+        if other.G is not None:
+            self.G = other.G.clone() if self.G is None else self.G + other.G.to(self.G.device)
+        return self
+
+    def all_reduce(self) -> "NormalEquations":
+        """Sums G over the ranks when ``torch.distributed`` is initialised (identity otherwise), as ``ErrorStats.all_reduce``."""
+        from . import distributed
+        if distributed.is_dist() and self.G is not None:
+            import torch.distributed as dist
+            dist.all_reduce(self.G, op=dist.ReduceOp.SUM)
+        return self
+
+    def solve(self, ridge: float = 1e-8, fit_bias: bool = True) -> LinearFit:
+        """(A + lambda diag(1, .., 1, 0)) [W; b] = [H^T Y; 1^T Y] with A = [[H^T H, H^T 1], [1^T H, n]] and
+        lambda = ridge * trace(H^T H) / K (none on the bias), in float64 on G's device: symmetric Jacobi scaling by
+        1 / sqrt(diag) (a zero diagonal entry is scaled by 1), ``torch.linalg.cholesky_ex``, two triangular solves.
+        ``fit_bias=False`` drops the ones column and returns bias = 0.  O(K^3), once per fit."""
+        import torch
+        if self.G is None:
+            raise ValueError("solve: no rows were added")
+        G, K, O = self.G, self.K, self.O
+        bad = int((~torch.isfinite(G)).sum().item())
+        if bad:
+            raise ValueError(f"normal equations hold {bad} non-finite entries of {G.numel()} (non-finite rows in x or y?)")
+        n = int(round(float(G[K, K].item())))
+        m = K + 1 if fit_bias else K
+        A0 = G[:m, :m]
+        rhs = torch.cat([G[:K, K + 1:], G[K:K + 1, K + 1:]]) if fit_bias else G[:K, K + 1:]
+        lam = float(ridge) * float(torch.diagonal(G)[:K].sum().item()) / K
+        A = A0.clone()
+        torch.diagonal(A)[:K] += lam
+        d = torch.diagonal(A)
+        s = torch.where(d > 0, torch.rsqrt(torch.where(d > 0, d, torch.ones_like(d))), torch.ones_like(d))
+        As = A * s[:, None] * s[None, :]
+        try:
+            L, info = torch.linalg.cholesky_ex(As)
+        except RuntimeError:           # a torch build without the device factorisation: the O(K^3) step on the host
+            L, info = (t.to(As.device) for t in torch.linalg.cholesky_ex(As.cpu()))
+        # the scaled matrix has a unit diagonal: a pivot below m 2^-52 is rounding noise of a singular system
+        if int(info.item()) != 0 or not bool((torch.diagonal(L) ** 2 > m * 2.0 ** -52).all().item()):
+            raise ValueError(f"normal equations not positive definite at ridge={ridge:g}; raise ridge")
+        t = torch.linalg.solve_triangular(L, rhs * s[:, None], upper=False)
+        sol = torch.linalg.solve_triangular(L.mT, t, upper=True) * s[:, None]
+        W = sol[:K].contiguous()
+        b = sol[K].contiguous() if fit_bias else torch.zeros(O, dtype=G.dtype, device=G.device)
+        yty = torch.diagonal(G)[K + 1:]
+        rss = (yty - 2.0 * (sol * rhs).sum(0) + (sol * (A0 @ sol)).sum(0)).clamp_min(0.0)
+        return LinearFit(W, b, n, rss, lam)
+
+
+def _like_leaf(t64, old):
+    """The float32 leaf that replaces ``old``: a torch tensor on old's device, else a NumPy array."""
+    import torch
+    if isinstance(old, torch.Tensor):
+        return t64.to(device=old.device, dtype=torch.float32)
+    return t64.detach().cpu().numpy().astype(np.float32)
+
+
+def fit_linear(net, params: dict, x, y, ridge: float = 1e-8, fit_bias: bool = True, batch_size: int = 65536):
+    """-> (new_params, LinearFit): ``linear/kernel`` and ``linear/bias`` of ``params`` replaced by the ridge least-squares fit
+    of y [N,O] on the net's hidden layer of x [N,D] (centres, widths and gate as in ``params`` / the net), cast to float32;
+    every other leaf and the tree's shape are the input's, so a fixed-centre or fixed-width net gets its reduced tree back.
+    x, y: arrays or tensors on any device (a ``DeviceTable``'s ``.x``, ``.y``)."""
+    fit = NormalEquations(net).add(params, x, y, batch_size=batch_size).solve(ridge=ridge, fit_bias=fit_bias)
+    p = _inner(params)
+    new = {g: dict(v) for g, v in p.items()}
+    new["linear"]["kernel"] = _like_leaf(fit.kernel, p["linear"]["kernel"])
+    new["linear"]["bias"] = _like_leaf(fit.bias, p["linear"]["bias"])
+    return ({"params": new} if "params" in params else new), fit

@@ -503,6 +503,31 @@ class WCRBFNet:
                        "irbfn_net_gate")
         return like_input(g, x, torch)
 
+    def hidden(self, params: dict, x):
+        """The hidden layer h[b,k] = sum_r gamma[b,r] phi[b,r,k] of x[B,D] -> [B,K] float32 (``irbfn_net_hidden``): what
+        ``apply`` multiplies by ``linear/kernel``, so ``apply(params, x) == hidden(params, x) @ kernel + bias`` up to float32
+        rounding.  The design matrix of ``linear_fit.fit_linear``; the reference has no counterpart.  The float64 mode has
+        no hidden-layer kernel: a ``use_float64`` net raises ``ValueError``."""
+        if self.use_float64:
+            raise ValueError("WCRBFNet.hidden: the float64 mode has no hidden-layer kernel (construct the net with use_float64=False)")
+        torch = _lib.require_gpu()
+        self._warn_if_float64(params)
+        self.bind(params)
+        shape = tuple(x.shape)
+        if len(shape) != 2 or shape[1] != self.in_features:
+            raise ValueError(f"x must have shape (B, {self.in_features}), got {shape}")
+        xd = to_device_f32(x, torch)
+        h = torch.empty((shape[0], self.num_kernels), dtype=torch.float32, device=xd.device)
+        self._hidden_into(xd, h, torch)
+        return like_input(h, x, torch)
+
+    def _hidden_into(self, xd, h, torch):
+        """irbfn_net_hidden of the bound parameters into the first K columns of the float32 cuda matrix h [B, ldh >= K]."""
+        B = xd.shape[0]
+        if B:
+            st = _lib.load().irbfn_net_hidden(self._handle(torch), _ptr(xd), _ptr(h), h.stride(0), B, _stream_ptr(torch))
+            _lib.check(st, "irbfn_net_hidden")
+
     # ------------------------------------------------------------------ backward
     def vjp(self, params: dict, x, gout, out: Optional[dict] = None) -> dict:
         """Parameter VJP: cotangent gout[B,O] -> gradient pytree (same structure as ``params``).
