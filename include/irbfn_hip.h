@@ -567,6 +567,35 @@ int64_t irbfn_syrk_f64_workspace_bytes(int64_t rows, int M);
 int irbfn_syrk_f64(const float* z_dev /*[rows,ldz]*/, int64_t ldz, int64_t rows, int M, double* g_dev /*[M,M]*/, int accumulate,
                    void* ws_dev, int64_t ws_bytes, void* stream);
 
+/* The p nearest centres of every row (knn.hip; irbfn_amd/widths.py): the core of the width rules that stand between k-means and
+ * the closed-form fit.  The reference leaves its widths to Adam from log_sig = 0 and has no width rule: parity is unpinned; the
+ * arithmetic below is pinned against a float64 statement.
+ *   d2[n,k]  = the float32 chain d2 = fmaf(t, t, d2), t = q[n,d] - c[k,d], d = 0 .. D-1, from 0 (no Gram expansion): the chain of
+ *              irbfn_kmeans_step, so p = 1 reproduces its label and d2 bit for bit.
+ *   Row n gets its p smallest candidates in ascending order of the pair (d2, k): equal d2 goes to the lower k, and a centre at
+ *   distance 0 is a neighbour like any other.  d2_dev[n,j] and idx_dev[n,j] (optional) are the j-th of them.
+ *   A candidate whose d2 is NaN or Inf is never taken (a centre or a row with a non-finite component, an overflow).  self0 >= 0:
+ *   row n never takes centre self0 + n (the rows are centres self0 .. self0 + N - 1 of the same set; an index >= K excludes
+ *   nothing); self0 = -1: no exclusion.
+ *   Slots for which no candidate is left (K minus the exclusions < p, non-finite centres, a non-finite row) get d2 = NaN and
+ *   idx = -1, the k-means convention.
+ *   split: the centres are cut into segments of whole tiles whose lists a second launch merges; 0 = the library chooses from N
+ *   and K, s >= 1 = s segments (clamped to the number of tiles).  The order is total, so every output is bit-identical across
+ *   repeats and across every value of split.  No atomics.
+ * Supported: 1 <= D <= 16, 1 <= K <= 65536, 1 <= p <= 16, any N >= 0 (grid-stride); outside it IRBFN_ERR_UNSUPPORTED.  K < 1,
+ * D < 1, p < 1, N < 0, self0 < -1, split < 0, a NULL q / c / d2 with N > 0, or a workspace that is NULL, not 8-byte aligned or
+ * smaller than irbfn_knn_workspace_bytes(N, K, D, p, split): IRBFN_ERR_BAD_ARG, which wins over an unsupported size -- but for the
+ * workspace that is too small: a size exists for supported shapes only, so that one test comes after the size limits.  All of
+ * these are decided before any HIP call.  N = 0: IRBFN_OK, no launch, the outputs untouched.  The workspace need not be cleared.
+ * Both launches are grid-stride loops: no N is refused for the grid it would need.
+ * irbfn_knn_workspace_bytes returns the same negative codes for sizes it refuses; it grows with N, K, p and with split >= 1
+ * (split = 0 lies between split = 1 and the number of tiles). */
+int64_t irbfn_knn_workspace_bytes(int64_t N, int K, int D, int p, int split);
+int irbfn_knn_d2(const float* q_dev /*[N,D]*/, const float* c_dev /*[K,D]*/, int64_t N, int K, int D, int p,
+                 int64_t self0 /* -1: none; >= 0: row n never takes centre self0 + n */,
+                 int split /* 0: the library chooses; s >= 1: the centres in s segments (clamped to the number of tiles) */,
+                 float* d2_dev /*[N,p]*/, int32_t* idx_dev /*[N,p] or NULL*/, void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* Diagnostics */
 int irbfn_abi_version(void);
 int irbfn_device_count(void);

@@ -7,6 +7,7 @@ is pinned is one Lloyd iteration against a float64 statement of it (tests/_kmean
 
     res = kmeans.fit(table_inputs, k=1000)                       # plain Lloyd, k-means++ start
     net = WCRBFNet(..., centers=res.as_centers(net0), fixed_centers=True)
+    w = widths.nearest_neighbour(res.centers, p=2)               # the widths from the centres: w.log_sigs(net) is the log_sigs leaf
     table = tables.DeviceTable(inputs, outputs, labels=res.labels, num_classes=500)   # -> train_epoch(ClusterTrainState)
 
 One iteration is one library call that reads the rows once (nearest centre, the per-cluster sums and counts, the step

@@ -6,8 +6,11 @@ where Adam needs thousands of epochs.  The reference has no counterpart (it trai
 unpinned; what is pinned is each stage against a float64 statement of it (tests/_linear_fit_util.py).
 
     res = kmeans.fit(table.x, k=1000)
-    net = WCRBFNet(..., centers=res.as_centers(net0), fixed_centers=True, fixed_width=True)
+    w = widths.nearest_neighbour(res.centers, p=2).scaled(2.0)                     # or widths.select_scale for the multiplier
+    net = WCRBFNet(..., centers=res.as_centers(net0), fixed_centers=True, fixed_width=True, log_sigs=w.log_sigs(net0))
     params, fit = linear_fit.fit_linear(net, net.init(), table.x, table.y)         # -> evaluate_table(net, params, table)
+
+Without ``log_sigs=`` a fixed-width net runs at sigma = 1 in the units of the table's columns, whatever the centres.
 
 One chunk of rows is one hidden-layer launch into Z = [h | 1 | y] and one float64 Gram launch G += Z^T Z; nothing synchronises
 with the host until ``solve``.  G is accumulated in float64 because RBF design matrices are ill-conditioned and the normal
@@ -53,10 +56,15 @@ def syrk(z, out=None, accumulate: bool = False):
 class LinearFit:
     """The solution of ``NormalEquations.solve``: ``kernel`` [K,O] and ``bias`` [O] in float64 (on G's device), the number of
     rows ``n``, ``rss`` [O] = the residual sum of squares per output computed from G alone, ``mse`` = sum(rss) / (n O), and
-    ``ridge_abs`` = the absolute ridge lambda that was added to the diagonal of H^T H."""
+    ``ridge_abs`` = the absolute ridge lambda that was added to the diagonal of H^T H; ``fit_bias`` as ``solve`` was called.
+    ``sol`` = the stacked solution [W; b] ([W] without the ones column), the very tensor ``solve`` took ``rss`` from.  ``rss_of``
+    prices it where it is there, so that for a fit made by ``solve`` ``rss_of`` on the solving accumulator equals ``rss`` bit for
+    bit.  A ``LinearFit`` built by hand (``sol=None``) is stacked from ``kernel`` and ``bias``; the matrix product may then take
+    another path and agree only to rounding."""
 
-    def __init__(self, kernel, bias, n, rss, ridge_abs):
+    def __init__(self, kernel, bias, n, rss, ridge_abs, fit_bias: bool = True, sol=None):
         self.kernel, self.bias, self.n, self.rss, self.ridge_abs = kernel, bias, n, rss, float(ridge_abs)
+        self.fit_bias, self.sol = bool(fit_bias), sol
 
     @property
     def mse(self) -> float:
@@ -161,9 +169,33 @@ class NormalEquations:
         sol = torch.linalg.solve_triangular(L.mT, t, upper=True) * s[:, None]
         W = sol[:K].contiguous()
         b = sol[K].contiguous() if fit_bias else torch.zeros(O, dtype=G.dtype, device=G.device)
+        return LinearFit(W, b, n, self._rss(sol, fit_bias), lam, fit_bias, sol)
+
+    def _rss(self, sol, fit_bias: bool):
+        """y^T y - 2 sol^T rhs + sol^T A0 sol per output, clamped at 0: the residual sum of squares of sol = [W; b] ([W] without
+        the ones column) on this accumulator's rows, from G alone."""
+        import torch
+        G, K = self.G, self.K
+        m = K + 1 if fit_bias else K
+        A0 = G[:m, :m]
+        rhs = torch.cat([G[:K, K + 1:], G[K:K + 1, K + 1:]]) if fit_bias else G[:K, K + 1:]
         yty = torch.diagonal(G)[K + 1:]
-        rss = (yty - 2.0 * (sol * rhs).sum(0) + (sol * (A0 @ sol)).sum(0)).clamp_min(0.0)
-        return LinearFit(W, b, n, rss, lam)
+        return (yty - 2.0 * (sol * rhs).sum(0) + (sol * (A0 @ sol)).sum(0)).clamp_min(0.0)
+
+    def rss_of(self, fit: LinearFit):
+        """The residual sum of squares per output [O] of a given ``LinearFit`` on this accumulator's rows, from G alone (no pass
+        over the rows): how a fit solved on one part of a table is priced on another.  On the accumulator the fit was solved on
+        it is ``fit.rss``."""
+        import torch
+        if self.G is None:
+            raise ValueError("rss_of: no rows were added")
+        if tuple(fit.kernel.shape) != (self.K, self.O):
+            raise ValueError(f"rss_of: a fit of shape {tuple(fit.kernel.shape)} on an accumulator of K={self.K}, O={self.O}")
+        if fit.sol is not None:            # the very tensor solve priced: the matrix product then takes the same path, bit for bit
+            return self._rss(fit.sol.to(device=self.G.device, dtype=self.G.dtype), fit.fit_bias)
+        W = fit.kernel.to(device=self.G.device, dtype=self.G.dtype)
+        b = fit.bias.to(device=self.G.device, dtype=self.G.dtype)
+        return self._rss(torch.cat([W, b[None]]) if fit.fit_bias else W, fit.fit_bias)
 
 
 def _like_leaf(t64, old):
