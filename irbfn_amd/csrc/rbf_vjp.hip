@@ -428,11 +428,13 @@ int launch_vjp_reduce(const irbfn_net* net, float* part, float* g_centers, float
 // d bias[o] = sum_b g[b,o]: per-block column sums, then one block finishes (fixed order)
 __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ g, float* __restrict__ part,
                                                               long B, int O, long rows_per_block,
-                                                              float* __restrict__ bmax) {
+                                                              float* __restrict__ bmax, const float* __restrict__ oscale) {
   extern __shared__ float sm[];                // [256]
   __shared__ float smax[256];
   float mx = 0.0f;                             // max FINITE |g| of this block's rows: the K2h / K2g operand scale (a NaN or Inf
                                                // reaches the f16 operands as such whatever the scale; split_cotangent_f16)
+  float mo = 0.0f;                             // max finite |g[q,o]| s_o of these rows (bmax + gridDim.x + 8): the largest term of hbar
+                                               // that is there -- K2g's scale of hbar's operands (rbf_vjp_gram.hip)
   const long r0 = (long)blockIdx.x * rows_per_block;
   long r1 = r0 + rows_per_block;
   r1 = r1 < B ? r1 : B;
@@ -444,13 +446,15 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
     const int stride = per * O;
     const int t = threadIdx.x;
     float s = 0.0f;
-    if (t < stride)
+    if (t < stride) {
       for (long i = t; i < total; i += stride) {
         const float v = base[i];
         s += v;
         const float av = fabsf(v);
         mx = (av > mx && av <= 3.402823466e38f) ? av : mx;
       }
+      if (bmax) mo = mx * oscale[t % O];         // one column per thread, its scale a power of two
+    }
     sm[t] = t < stride ? s : 0.0f;
     __syncthreads();
     if (t < O) {
@@ -466,6 +470,7 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
         s += v;
         const float av = fabsf(v);
         mx = (av > mx && av <= 3.402823466e38f) ? av : mx;
+        if (bmax) mo = fmaxf(mo, (av <= 3.402823466e38f ? av : 0.0f) * oscale[o]);
       }
       part[(size_t)blockIdx.x * O + o] = s;
     }
@@ -481,6 +486,17 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
       __syncthreads();
     }
     if (threadIdx.x == 0) bmax[blockIdx.x] = smax[0];
+    __syncthreads();
+    smax[threadIdx.x] = mo;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (threadIdx.x < w) {
+        const float o2 = smax[threadIdx.x + w], m2 = smax[threadIdx.x];
+        smax[threadIdx.x] = o2 > m2 ? o2 : m2;
+      }
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) bmax[gridDim.x + 8 + blockIdx.x] = smax[0];
   }
 }
 
@@ -523,7 +539,8 @@ static VjpLayout vjp_layout(const irbfn_net* net, int64_t B) {
   const size_t blkb = vjph_block_bytes(net) > vjpg_block_bytes() ? vjph_block_bytes(net) : vjpg_block_bytes();
   const bool gam = vjpgg_eligible(net) && net->gram_img != nullptr;
   p.off_qblk = off;  off += al(vjph_eligible(net) ? (size_t)((B + 31) / 32) * blkb : (gam ? (size_t)((B + 31) / 32) * vjpg_block_bytes() : 0));
-  p.off_misc = off;  off += al((size_t)(p.bias_blocks + 8) * sizeof(float));
+  // [bias_blocks] max |g| per block, [8] (s_g, s_h, ...), [bias_blocks] max |g[q,o]| s_o per block (colsum_partial_kernel)
+  p.off_misc = off;  off += al((size_t)(2 * p.bias_blocks + 8) * sizeof(float));
   p.SL = 0;
   p.off_sp = p.off_sp_part = off;
   if (sparse_vjp_eligible(net)) {
@@ -895,10 +912,11 @@ struct VjpCall {
   template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }
 };
 
-// the bias column sums per block; bmax: the block maxima of |g| as well (K2h / K2g pack g to f16 with them)
+// the bias column sums per block; bmax: the block maxima of |g|, and behind them and the scales those of |g| s_o, as well (K2h / K2g
+// pack g to f16 with them)
 static int bias_partials(const VjpCall& c, const VjpLayout& L, float* bmax) {
   hipLaunchKernelGGL(colsum_partial_kernel, dim3(L.bias_blocks), dim3(256), 256 * sizeof(float), c.s, c.gout, c.at<float>(L.off_bias),
-                     (long)c.B, c.net->O, L.rows_per_block, bmax);
+                     (long)c.B, c.net->O, L.rows_per_block, bmax, bmax ? c.net->f16_oscale : nullptr);
   IRBFN_HIP_CHECK(hipGetLastError());
   return IRBFN_OK;
 }

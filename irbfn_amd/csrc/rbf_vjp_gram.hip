@@ -41,6 +41,14 @@ constexpr int kVgOC = 10;                                // up to this many outp
 // weight side 2^-17 (<= 1/4) on top of the 2^15 of split_static_f16 -- small entries sink into the f16 subnormals, which the
 // matrix cores honour: a (hi, lo) pair then keeps 2^-36 ABSOLUTE against operands of size 2^-2, beyond float32.  The gaussian
 // (ET = 33) needs no multiplication of hbar at all any more, the other bases one by 2^-(ET - 33).
+// An absolute accuracy is only as good as the scale it is relative to.  The cotangent side is gamma_q g[q,o] s_o / s_h with the
+// weights' column scales s_o folded in; s_h is the power of two above max_{q,o} |g[q,o]| s_o over the FINITE elements of the batch
+// (colsum_partial_kernel's second per-block maximum), so the largest cotangent-side operand that is there lies in [1/2, 1) of its
+// range and every term of hbar keeps 2^-36 (O <= 10: 2^-30, the cross terms' scaled copies) of the batch's largest.  Range: weight
+// columns and cotangent rows may spread over 2^+-10 and more (tests/test_gpu_k2g.py, the wcols and grows cases); what a term loses
+// is relative to the largest term of the batch, which is what a gradient is judged against.  (Until then s_h was s_g max_o s_o:
+// with the cotangent in a column 2^20 below the widest one every operand sat 2^-20 lower, and d centers / d log_sigs missed the
+// 5e-5 bound by a factor 5 (gaussians) to 90 (the other bases) on inputs K2h handles at 1e-6.)
 // (The gaussian's basis value is taken as phi itself here -- see kVgShift in the kernel -- so its factor is 2^-19: 2^-9 and 2^-10.)
 // rbf_vjp_f16gram_gamma multiplies the region weight onto P in front of the ungained (hi, lo) split of the dW operand, which is good
 // to 2^-25 ABSOLUTE below 2^-4: with gamma ~ 1 / R that is every term of a net of 500 regions (dW then misses float32 by two orders
@@ -125,9 +133,13 @@ __global__ __launch_bounds__(192) void vjp_pack_blocks_gram_kernel(const float* 
     mx = (o2 > mx || o2 != o2) ? o2 : mx;
   }
   const float sg = vg_pow2_ceil_scale(mx);
-  float somax = 0.0f;
-  for (int o = 0; o < O; ++o) somax = fmaxf(somax, oscale[o]);
-  const float sh = sg * somax;
+  // s_h: the power of two above the largest |g[q,o]| s_o that is there (per-block maxima behind bmax and the scales), not s_g max_o
+  // s_o: the absolute accuracy of hbar's operand pairs is then relative to the largest term of hbar in the batch (header)
+  float mo = 0.0f;
+  for (int i = lane; i < nbmax; i += 64) mo = fmaxf(mo, bmax[nbmax + 8 + i]);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) mo = fmaxf(mo, __shfl_xor(mo, off));
+  const float sh = vg_pow2_ceil_scale(mo);
   if (blockIdx.x == 0 && role == 1 && lane == 0) { scales[0] = sg; scales[1] = sh; }
   // gate of the single region (model.py:42-95) of query q0 + lane (lanes >= 32: 0)
   float gm = 0.0f;
