@@ -596,6 +596,44 @@ int irbfn_knn_d2(const float* q_dev /*[N,D]*/, const float* c_dev /*[K,D]*/, int
                  int split /* 0: the library chooses; s >= 1: the centres in s segments (clamped to the number of tiles) */,
                  float* d2_dev /*[N,p]*/, int32_t* idx_dev /*[N,p] or NULL*/, void* ws_dev, int64_t ws_bytes, void* stream);
 
+/* Orthogonal least squares forward selection on a Gram matrix (ols.hip; irbfn_amd/ols.py): from a pool of M candidate centres,
+ * repeatedly the one whose hidden-layer column removes the most of what is still unexplained in y (Chen, Cowan & Grant 1991).  The
+ * reference places no centre by what it explains: parity is unpinned; the arithmetic below is pinned against a float64 statement.
+ *   g_dev [Mg][Mg], Mg = M + 1 + O: G = Z^T Z of Z = [h | 1 | y] as irbfn_syrk_f64 leaves it (symmetric bit for bit; only read).
+ *   A = G[:M+1,:M+1] with ridge_abs added to its first M diagonal entries, B = G[:M+1, M+1:]; n = M + 1 columns, or n = M with
+ *   fit_bias = 0 (column M is then never read).  npad = M + 1 rounded up to a multiple of 64.
+ *   State: d_dev [2][npad] = the running diagonal d and the first one d0; c_dev [npad][O] = the running right-hand side;
+ *   l_dev [kmax + 1][npad] = the factor, one row per step; sel_dev [kmax + 1], gain_dev [kmax + 1][O], count_dev [1].
+ *   irbfn_ols_begin: d = d0 = diag(A), c = B, count = 0, and the pivot of step 0.  Entries n .. npad - 1 of a row of d, c and l
+ *   are never read or written.
+ *   irbfn_ols_steps takes `steps` further pivots.  Step t = count:
+ *     pivot   j = M in step 0 with fit_bias (the ones column), else the argmax over the columns i < M not yet taken with
+ *             d[i] > tol d0[i] of score[i] = (sum_o c[i,o]^2) / d[i], ties to the lowest i; a NaN score never wins.  Without
+ *             such a column, or with a best score that is not positive (or a ones column with d[M] <= 0), selection has ended:
+ *             this and every later step is a no-op that writes nothing.  So is every step once count = kmax + fit_bias.
+ *     column  l[t][i] = (A[i,j] - sum_{s<t} l[s][i] l[s][j]) / sqrt(d[j]) for the columns not yet taken, l[t][j] = sqrt(d[j]),
+ *             0 for the columns taken earlier.
+ *     update  ly = c[j,:] / sqrt(d[j]); gain[t,:] = ly^2; d[i] -= l[t][i]^2 and c[i,:] -= l[t][i] ly for every column not taken
+ *             earlier, j included; sel[t] = j; count = t + 1.
+ *   G_yy[o,o] - sum_{s<=t} gain[s,o] is the least of rss + ridge_abs |w|^2 over the weights of the first t + 1 pivots.
+ *   All float64 on the vector pipe; the sum over s runs in a fixed order that depends on t alone, so every output is
+ *   bit-identical across repeats and across how the steps are divided over calls.  A step is two launches (the column, update
+ *   and per-block best scores; the pivot); no block waits for another, no atomics, and the pivot stays on the device.
+ *   The workspace (irbfn_ols_workspace_bytes(M, O, kmax) bytes, 8-byte aligned) need not be cleared before irbfn_ols_begin and
+ *   carries the selection's state from call to call, like the other buffers.
+ * Supported: 1 <= M, 1 <= O, M + 1 + O <= 8192 (the limit of irbfn_syrk_f64), 1 <= kmax <= M.  Outside it, and for a NULL
+ * pointer, a negative or NaN ridge_abs or tol, steps < 0, or a workspace that is not 8-byte aligned or too small:
+ * IRBFN_ERR_BAD_ARG, decided before any HIP call.  steps = 0: IRBFN_OK, no launch.  irbfn_ols_workspace_bytes returns the same
+ * negative code for sizes it refuses. */
+int64_t irbfn_ols_workspace_bytes(int M, int O, int kmax);
+int irbfn_ols_begin(const double* g_dev /*[Mg,Mg]*/, int M, int O, int fit_bias, double ridge_abs, double tol, int kmax,
+                    double* l_dev /*[kmax+1][npad]*/, double* d_dev /*[2][npad]: d, d0*/, double* c_dev /*[npad][O]*/,
+                    int32_t* sel_dev /*[kmax+1]*/, double* gain_dev /*[kmax+1][O]*/, int32_t* count_dev /*[1]*/, void* ws_dev,
+                    int64_t ws_bytes, void* stream);
+int irbfn_ols_steps(const double* g_dev /*[Mg,Mg]*/, int M, int O, int fit_bias, double tol, int kmax, double* l_dev, double* d_dev,
+                    double* c_dev, int32_t* sel_dev, double* gain_dev, int32_t* count_dev, void* ws_dev, int64_t ws_bytes,
+                    int steps, void* stream);
+
 /* Diagnostics */
 int irbfn_abi_version(void);
 int irbfn_device_count(void);

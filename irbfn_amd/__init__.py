@@ -11,6 +11,7 @@ Host side is Python (like the reference) over a C-ABI shared library of hand-wri
 * ``irbfn_amd.kmeans``        ``fit`` / ``assign``: centres and cluster labels from a table (k-means on the device)
 * ``irbfn_amd.widths``        ``nearest_neighbour`` / ``cluster_spread`` / ``select_scale``: RBF widths from the centres and the table
 * ``irbfn_amd.linear_fit``    ``fit_linear``: the output layer in closed form (float64 normal equations on the device)
+* ``irbfn_amd.ols``           ``select`` / ``fit_ols``: centres chosen by what they explain (OLS forward selection on the Gram matrix)
 * ``irbfn_amd.autograd``      ``torch.autograd`` wrappers (the ``jax.grad`` surface)
 * ``irbfn_amd.distributed``   one-process-per-GPU sharding, RCCL broadcast of the parameters
 
@@ -21,5 +22,6 @@ __version__ = "0.1.0"
 from . import flax_rbf  # noqa: F401
 from . import kmeans  # noqa: F401
 from . import linear_fit  # noqa: F401
+from . import ols  # noqa: F401
 from . import widths  # noqa: F401
 from .model import WCRBFNet, pred_step  # noqa: F401

@@ -64,6 +64,7 @@ UNITS = [
     ("rbf_hidden.hip", "rbf_hidden.o", []),            # the hidden layer h[B][K] of a net: the design matrix of the closed-form fit
     ("syrk_f64.hip", "syrk_f64.o", []),                # K8: float64 Gram matrix of float32 rows on the f64 matrix instruction
     ("knn.hip", "knn.o", []),                          # K9: the p nearest centres of every row (the width rules)
+    ("ols.hip", "ols.o", []),                          # K10: OLS forward selection of centres on the Gram matrix (f64 VALU)
     ("mlp_head.hip", "mlp_head.o", []),
     ("planner_front.hip", "planner_front.o", []),
 ]

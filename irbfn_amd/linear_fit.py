@@ -128,6 +128,23 @@ class NormalEquations:
             self.G = other.G.clone() if self.G is None else self.G + other.G.to(self.G.device)
         return self
 
+    def subset(self, indices, net_k) -> "NormalEquations":
+        """The accumulator of the sub-net ``net_k`` that keeps the kernels ``indices`` (in that order) of this one: the rows and
+        columns [indices, K, K + 1 ...] of G, so that ``solve`` / ``rss_of`` give and price the fit of any selection without
+        another pass over the rows (``ols.select``).  indices: an integer array or tensor of ``net_k.num_kernels`` entries."""
+        import torch
+        if self.G is None:
+            raise ValueError("subset: no rows were added")
+        idx = torch.as_tensor(indices).to(device=self.G.device, dtype=torch.long).reshape(-1)
+        out = NormalEquations(net_k)
+        if out.K != idx.numel() or out.O != self.O:
+            raise ValueError(f"subset: {idx.numel()} indices and O={self.O} for a net of num_kernels={out.K}, out_features={out.O}")
+        if idx.numel() and not bool(((idx >= 0) & (idx < self.K)).all().item()):
+            raise ValueError(f"subset: indices outside [0, {self.K})")
+        full = torch.cat([idx, torch.arange(self.K, self.M, device=idx.device)])
+        out.G = self.G.index_select(0, full).index_select(1, full).contiguous()
+        return out
+
     def all_reduce(self) -> "NormalEquations":
         """Sums G over the ranks when ``torch.distributed`` is initialised (identity otherwise), as ``ErrorStats.all_reduce``."""
         from . import distributed
