@@ -634,6 +634,29 @@ int irbfn_ols_steps(const double* g_dev /*[Mg,Mg]*/, int M, int O, int fit_bias,
                     double* c_dev, int32_t* sel_dev, double* gain_dev, int32_t* count_dev, void* ws_dev, int64_t ws_bytes,
                     int steps, void* stream);
 
+/* Leverages and predictions of the closed-form fit, row by row (rows_quad_f64.hip; irbfn_amd/loo.py): the pass over the rows behind
+ * leave-one-out residuals, PRESS, GCV and the predictive variance factor of a query.  The reference has no counterpart: parity is
+ * unpinned; the arithmetic below is pinned against integer and extended-precision statements of it.
+ *   q[n]    = sum_{j<m} ( sum_{k<=j} z[n * ldz + k] p[k * ldp + j] )^2: the first m columns of p are an upper triangle (the host
+ *             passes T^T, T = L^-1 diag(s) of the Cholesky factor of the scaled normal equations: q[n] = |T z_n|^2, the leverage).
+ *   v[n,o]  = sum_{k<m} z[n * ldz + k] p[k * ldp + m + o], o < nd: nd dense columns (the host passes [W; b]: the prediction).
+ *   Entries p[k][j] with k > j and j < m are never read, whatever they hold; neither are the columns [m, ldz) of z, the columns
+ *   [m + nd, ldp) of p and the rows past `rows`.
+ *   z is converted float32 -> float64 (exact); every product and sum is float64 (v_mfma_f64_16x16x4_f64).  Any-order bounds:
+ *   |v - exact| <= (m + 1) 2^-53 sum_k |z_k p_ko| and |q - exact| <= (4 m + 8) 2^-53 sum_j (sum_k |z_k p_kj|)^2; integer data
+ *   whose sums stay below 2^53 come out bit for bit.
+ *   A block owns whole rows: no workspace, no atomics, one launch.  The order of every sum is fixed and the same for every row, so
+ *   a row's q and v depend on that row's values, m, nd and p alone -- not on `rows`, on where the row sits in the call or on its
+ *   neighbours: bit-identical across repeats and across any division of the rows over calls.  A non-finite value of z gives a
+ *   non-finite q in its own row and touches no other row.
+ * Supported: 1 <= m <= 8192 (the limit of irbfn_syrk_f64), 0 <= nd <= 256, ldz >= m, ldp >= m + nd, rows >= 0 (grid-stride: no row
+ * count is refused for the grid it would need).  Outside it, and with rows > 0 for a NULL z, p or q or, with nd > 0, a NULL v:
+ * IRBFN_ERR_BAD_ARG as irbfn_syrk_f64, decided before any HIP call.  rows = 0: IRBFN_OK, no launch, nothing is read or written.
+ * nd = 0: v_dev is not used and may be NULL. */
+int irbfn_rows_quad_f64(const float* z_dev /*[rows,ldz]*/, int64_t ldz, int64_t rows, int m, const double* p_dev /*[m,ldp]*/,
+                        int64_t ldp, int nd, double* q_dev /*[rows]*/, double* v_dev /*[rows,nd] or NULL with nd = 0*/,
+                        void* stream);
+
 /* Diagnostics */
 int irbfn_abi_version(void);
 int irbfn_device_count(void);

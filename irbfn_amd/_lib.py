@@ -94,6 +94,7 @@ SIGNATURES = {
     "irbfn_ols_workspace_bytes": (_i64, [_i, _i, _i]),
     "irbfn_ols_begin": (_i, [_fp, _i, _i, _i, _d, _d, _i, _fp, _fp, _fp, _ip, _fp, _ip, _vp, _i64, _vp]),
     "irbfn_ols_steps": (_i, [_fp, _i, _i, _i, _d, _i, _fp, _fp, _fp, _ip, _fp, _ip, _vp, _i64, _i, _vp]),
+    "irbfn_rows_quad_f64": (_i, [_fp, _i64, _i64, _i, _fp, _i64, _i, _fp, _fp, _vp]),
     "irbfn_abi_version": (_i, []),
     "irbfn_device_count": (_i, []),
     "irbfn_last_hip_error": (_i, []),

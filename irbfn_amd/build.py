@@ -65,6 +65,7 @@ UNITS = [
     ("syrk_f64.hip", "syrk_f64.o", []),                # K8: float64 Gram matrix of float32 rows on the f64 matrix instruction
     ("knn.hip", "knn.o", []),                          # K9: the p nearest centres of every row (the width rules)
     ("ols.hip", "ols.o", []),                          # K10: OLS forward selection of centres on the Gram matrix (f64 VALU)
+    ("rows_quad_f64.hip", "rows_quad_f64.o", []),      # K11: per-row leverages and predictions of the closed-form fit (f64 MFMA)
     ("mlp_head.hip", "mlp_head.o", []),
     ("planner_front.hip", "planner_front.o", []),
 ]
