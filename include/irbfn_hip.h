@@ -239,10 +239,21 @@ int irbfn_rollout_forward(int mode, const float* x0u_dev, const float* dyn_param
  * :356-374; scripts/train_nmpc_frenet.py:408-409; deprecated/train_newlut.py:194-199).
  * clip() passes gradient 1 strictly inside its bounds, 0 strictly outside and `clip_tie` (0, 0.5 or
  * 1) exactly on a bound.  ST_SELECT returns IRBFN_ERR_UNSUPPORTED: the reference never
- * differentiates integrate_st_mult, and jax.grad through its lax.select is NaN at V = 0. */
+ * differentiates integrate_st_mult, and jax.grad through its lax.select is NaN at V = 0.  This project's
+ * own adjoint of that mode, under the convention stated there, is irbfn_rollout_vjp_select. */
 int irbfn_rollout_vjp(int mode, const float* x0u_dev, const float* dyn_params_host,
                       const float* gstates_dev, float* g_x0u_dev, int64_t B, int T, float clip_tie,
                       void* stream);
+
+/* VJP of the ST_SELECT roll-out (integrate_st_mult, dynamics.py:94-100): gstates_dev[B,T,7] -> g_x0u_dev[B, 7+2T].  No
+ * reference counterpart.  Convention: one step is x' = x + select(V > 3, f, f_ks) dt with V the clipped speed, and the adjoint
+ * holds the mask V > 3 constant -- a step taken on the dynamic branch back-propagates through f (dynamics.py:49-76), a step
+ * taken on the kinematic branch through f_ks (:78-88), V = 3 exactly is kinematic as in the forward; the derivative of the
+ * branch a step did not take is never evaluated, so a kinematic step at V = 0 gives finite gradients.  Clips as in
+ * irbfn_rollout_vjp (clip_tie).  float32 only, like the forward.  T = 0 zeroes g_x0u_dev, B = 0 is a no-op, T > 120 returns
+ * IRBFN_ERR_UNSUPPORTED; deterministic, rows are independent. */
+int irbfn_rollout_vjp_select(const float* x0u_dev, const float* dyn_params_host, const float* gstates_dev, float* g_x0u_dev,
+                             int64_t B, int T, float clip_tie, void* stream);
 
 /* Fused planning tick: net forward + roll-out in one launch, the predicted controls never leave
  * the chip.  Batched form of IRBFNPlanner.plan's `pred_step` -> `hstack` -> `integrate_st_mult`
@@ -290,10 +301,20 @@ int irbfn_train_seeds_fullint(const float* x_dev, const float* y_pred_dev, const
 int irbfn_train_seeds_frenet_fullint(const float* x_dev, const float* y_pred_dev, const float* y_dev,
                                      const float* dyn_params_host, float clip_tie, float* gy_dev, float* loss_dev,
                                      float* partials_dev, int64_t B, int D, int T, void* stream);
+/* irbfn_train_seeds_st_fullint: a full-integration loss through the single-track roll-out, mode = IRBFN_ROLLOUT_ST_SELECT (the
+ *   planner's model, differentiated as irbfn_rollout_vjp_select does) or IRBFN_ROLLOUT_ST_KS.  No reference counterpart: L1 as
+ *   in its two full-integration losses, the state components of its one-step loss.
+ *   x [B, D >= 7] as for irbfn_train_seeds_oneint, initial state [0,0,0, x[:,0], 0, x[:,6], x[:,5]]; O = 2T, T <= 16;
+ *   loss = mean|y_pred - y| + mean|S_pred[:, :, [0,1,3,4]] - S_act[:, :, [0,1,3,4]]| with S_pred, S_act the T-step roll-outs of
+ *   the predicted and of the label controls (the second mean over B * T * 4 entries).  Writes gy [B,2T] and the scalar loss. */
+int irbfn_train_seeds_st_fullint(int mode, const float* x_dev, const float* y_pred_dev, const float* y_dev,
+                                 const float* dyn_params_host, float clip_tie, float* gy_dev, float* loss_dev,
+                                 float* partials_dev, int64_t B, int D, int T, void* stream);
 int irbfn_adam_clip_step(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev, int64_t n,
                          int* step_dev, float lr, float beta1, float beta2, float eps, float max_grad_norm,
                          float* partials_dev, void* stream);
-/* float64 twins of the four calls above, for a net trained under --use_float64 (scripts/train_nmpc.py:41-42: jax_enable_x64):
+/* float64 twins of four of the calls above (the select model is float32 only: irbfn_train_seeds_st_fullint has none),
+ * for a net trained under --use_float64 (scripts/train_nmpc.py:41-42: jax_enable_x64):
  * double buffers and double dynamics parameters, the same argument rules and status codes.  partials_dev holds
  * irbfn_train_loss_partials() doubles.
  * irbfn_train_seeds_oneint_f64: loss_fn of train_step_oneint in float64 (scripts/train_nmpc.py:268-295).

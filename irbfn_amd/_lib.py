@@ -45,11 +45,13 @@ SIGNATURES = {
     "irbfn_rollout_input_dim": (_i, [_i, _i]),
     "irbfn_rollout_forward": (_i, [_i, _fp, _fp, _fp, _i64, _i, _vp]),
     "irbfn_rollout_vjp": (_i, [_i, _fp, _fp, _fp, _fp, _i64, _i, _f, _vp]),
+    "irbfn_rollout_vjp_select": (_i, [_fp, _fp, _fp, _fp, _i64, _i, _f, _vp]),
     "irbfn_net_forward_rollout": (_i, [_vp, _i, _fp, _fp, _fp, _fp, _fp, _i64, _i, _vp]),
     "irbfn_train_loss_partials": (_i, []),
     "irbfn_train_seeds_oneint": (_i, [_fp, _fp, _fp, _fp, _f, _fp, _fp, _fp, _i64, _i, _i, _vp]),
     "irbfn_train_seeds_fullint": (_i, [_fp, _fp, _fp, _f, _fp, _fp, _fp, _i64, _i, _i, _vp]),
     "irbfn_train_seeds_frenet_fullint": (_i, [_fp, _fp, _fp, _fp, _f, _fp, _fp, _fp, _i64, _i, _i, _vp]),
+    "irbfn_train_seeds_st_fullint": (_i, [_i, _fp, _fp, _fp, _fp, _f, _fp, _fp, _fp, _i64, _i, _i, _vp]),
     "irbfn_adam_clip_step": (_i, [_fp, _fp, _fp, _fp, _i64, _vp, _f, _f, _f, _f, _f, _fp, _vp]),
     "irbfn_train_seeds_oneint_f64": (_i, [_fp, _fp, _fp, _fp, _d, _fp, _fp, _fp, _i64, _i, _i, _vp]),
     "irbfn_train_seeds_fullint_f64": (_i, [_fp, _fp, _fp, _d, _fp, _fp, _fp, _i64, _i, _i, _vp]),

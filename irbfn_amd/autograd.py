@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .dynamics import rollout_forward, rollout_vjp, _infer_T
+from .dynamics import rollout_forward, rollout_vjp, rollout_vjp_select, _infer_T
 
 
 class _WCRBFApply(torch.autograd.Function):
@@ -49,8 +49,18 @@ class _Rollout(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gstates):
         (x0u,) = ctx.saved_tensors
-        g = rollout_vjp(ctx.mode, x0u, ctx.dyn, gstates.contiguous(), ctx.T, ctx.tie)
+        if ctx.mode == _lib.ROLLOUT_ST_SELECT:       # this project's own adjoint: the branch each step took (dynamics.rollout_vjp_select)
+            g = rollout_vjp_select(x0u, ctx.dyn, gstates.contiguous(), ctx.T, ctx.tie)
+        else:
+            g = rollout_vjp(ctx.mode, x0u, ctx.dyn, gstates.contiguous(), ctx.T, ctx.tie)
         return g, None, None, None, None
+
+
+def integrate_st_mult(x_and_pred_u, dyn_params, clip_tie: float = 0.5):
+    """Differentiable dynamics.py:94-100, the planner's roll-out.  The reference never takes this gradient (its jax.grad is NaN
+    at V = 0); the backward pass differentiates the branch each step took, the mask V > 3 held constant."""
+    T = _infer_T(_lib.ROLLOUT_ST_SELECT, x_and_pred_u.shape[1])
+    return _Rollout.apply(x_and_pred_u, _lib.ROLLOUT_ST_SELECT, dyn_params, T, clip_tie)
 
 
 def integrate_st_ks_mult(x_and_pred_u, dyn_params, clip_tie: float = 0.5):

@@ -335,6 +335,17 @@ int irbfn_rollout_vjp(int mode, const float* x0u_dev, const float* dyn_params_ho
   return launch_rollout_vjp(mode, x0u_dev, dp, gstates_dev, g_x0u_dev, B, T, clip_tie, as_stream(stream));
 }
 
+int irbfn_rollout_vjp_select(const float* x0u_dev, const float* dyn_params_host, const float* gstates_dev, float* g_x0u_dev,
+                             int64_t B, int T, float clip_tie, void* stream) {
+  if (B < 0 || T < 0) return IRBFN_ERR_BAD_ARG;
+  if (B == 0) return IRBFN_OK;
+  if (!x0u_dev || !g_x0u_dev || (T > 0 && !gstates_dev)) return IRBFN_ERR_BAD_ARG;
+  DynParams dp;
+  int rc = load_dyn(IRBFN_ROLLOUT_ST_SELECT, dyn_params_host, &dp);
+  if (rc != IRBFN_OK) return rc;
+  return launch_rollout_vjp_select(x0u_dev, dp, gstates_dev, g_x0u_dev, B, T, clip_tie, as_stream(stream));
+}
+
 int irbfn_net_forward_rollout(irbfn_net* net, int mode, const float* x_dev, const float* state0_dev,
                               const float* dyn_params_host, float* controls_dev, float* states_dev,
                               int64_t B, int T, void* stream) {

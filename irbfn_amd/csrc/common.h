@@ -292,6 +292,8 @@ int launch_rollout_forward_split(int mode, const float* state0, const float* con
                                  float* states, int64_t B, int T, hipStream_t s);
 int launch_rollout_vjp(int mode, const float* x0u, const DynParams& dp, const float* gstates,
                        float* g_x0u, int64_t B, int T, float clip_tie, hipStream_t s);
+int launch_rollout_vjp_select(const float* x0u, const DynParams& dp, const float* gstates, float* g_x0u, int64_t B, int T,
+                              float clip_tie, hipStream_t s);
 // roll-out error statistics of a table (eval_errors.hip): M = S + 2 metrics per row, < 0 for a mode without controls
 int eval_num_metrics(int mode);
 int64_t eval_workspace_bytes(int mode);

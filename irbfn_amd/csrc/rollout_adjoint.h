@@ -5,6 +5,8 @@
 // tie rule is 1/2).
 // clipgrad, vjp_park and vjp_back_step<ST_KS / FULLINT / FRENET_LS> take their scalar type S as a template parameter (float
 // by default; S = double with TrigF64 and DynParams64: the float64 training steps).
+// ST_SELECT (float only, like its forward): the adjoint of the branch each step TOOK, the mask V > 3 a constant -- see
+// vjp_back_step<ST_SELECT>.  Its NumPy statement is tests/_st_select_util.py: vjp_st_select.
 #pragma once
 
 #include "rollout_step.h"
@@ -19,6 +21,7 @@ __device__ __forceinline__ S clipgrad(S v, S lo, S hi, S tie) {
 template <int MODE, typename S>
 __device__ __forceinline__ void vjp_park(const S* s, S* p) {
   if constexpr (MODE == IRBFN_ROLLOUT_FRENET_LS) { p[0] = s[1]; p[1] = s[2]; p[2] = s[3]; p[3] = s[6]; }
+  else if constexpr (MODE == IRBFN_ROLLOUT_ST_SELECT) { p[0] = s[2]; p[1] = s[3]; p[2] = s[4]; p[3] = s[5]; p[4] = s[6]; }
   else { p[0] = s[2]; p[1] = s[3]; p[2] = s[4]; }
 }
 
@@ -43,6 +46,53 @@ __device__ __forceinline__ void vjp_back_step(const S* p, S a_in, S sv_in, S* la
     const S l3 = lam[3] + mv * dt * (lam[0] * cp + lam[1] * sp + lam[4] * td / Lw);
     const S l4 = lam[4] + dt * V * (-lam[0] * sp + lam[1] * cp);
     lam[2] = l2; lam[3] = l3; lam[4] = l4;
+  } else if constexpr (MODE == IRBFN_ROLLOUT_ST_SELECT) {
+    // x' = x + select(V > 3, f, f_ks) dt with the mask held constant: a step taken on the dynamic branch goes back through f
+    // (dynamics.py:49-76), one taken on the kinematic branch through f_ks with ST_KS's expressions above, V = 3 is kinematic as
+    // in the forward.  Branch-free like st_step<true>: ONE sincos of the selected angle, both sets of coefficients as
+    // straight-line code, then selects.  At V = 0 the dynamic quantities (psi_dot / V, mu / (V L)) are inf / nan on a lane
+    // that never took that branch: they are dropped by the selects, never multiplied by 0.  No reference counterpart (its
+    // jax.grad through lax.select is NaN at V = 0); pinned by torch.autograd of a float64 restatement.
+    static_assert(std::is_same<S, float>::value, "the select model runs in float32 only");
+    const S g = S(9.81);
+    const S mu = dp.p[0], m = dp.p[1], I = dp.p[2], lf = dp.p[3], lr = dp.p[4], C_Sf = dp.p[5], C_Sr = dp.p[6], h = dp.p[7],
+            dt = dp.p[8], sv_max = dp.p[9], a_max = dp.p[10], s_max = dp.p[11], v_max = dp.p[12];
+    const S Lw = lr + lf;
+    const S d_raw = p[0], v_raw = p[1], psi = p[2], pd = p[3], beta = p[4];
+    const S DELTA = clipf(d_raw, -s_max, s_max), V = clipf(v_raw, -v_max, v_max);
+    const S A = clipf(a_in, -a_max, a_max);
+    const S md = clipgrad(d_raw, -s_max, s_max, tie), mv = clipgrad(v_raw, -v_max, v_max, tie);
+    const S ma = clipgrad(a_in, -a_max, a_max, tie), ms = clipgrad(sv_in, -sv_max, sv_max, tie);
+    const bool dyn = V > S(3.0);
+    S cp, sp, td;
+    trig.sincos_tan(dyn ? psi + beta : psi, DELTA, s_max < 4194304.0f, sp, cp, td);
+    // kinematic lanes: ST_KS
+    const S gak = ma * dt * lam[3];
+    const S l2k = lam[2] + md * lam[4] * (V / Lw) * (S(1.0) + td * td) * dt;
+    const S l3k = lam[3] + mv * dt * (lam[0] * cp + lam[1] * sp + lam[4] * td / Lw);
+    const S head = dt * V * (-lam[0] * sp + lam[1] * cp);      // the cotangent both f0 and f1 put on their angle
+    // dynamic lanes
+    const S glr = g * lr - A * h, glf = g * lf + A * h;
+    const S E = C_Sf * glr, F = C_Sr * glf;
+    const S P = lf * E, Q = lr * F, R = lf * lf * E + lr * lr * F, M = F * lr - E * lf;
+    const S rV = S(1.0) / V, pv = pd * rV;
+    const S c5 = (mu * m) / (I * Lw), c6 = (mu * rV) / Lw;
+    const S U = E * DELTA - (F + E) * beta + M * pv;
+    const S Ea = -C_Sf * h, Fa = C_Sr * h;                      // dE/dA, dF/dA
+    const S f5A = c5 * (lf * Ea * DELTA + (lr * Fa - lf * Ea) * beta - (lf * lf * Ea + lr * lr * Fa) * pv);
+    const S f6A = c6 * (Ea * DELTA - (Fa + Ea) * beta + (Fa * lr - Ea * lf) * pv);
+    const S f5V = c5 * R * pv * rV, f6V = -c6 * (U + M * pv) * rV;
+    const S f5W = -c5 * R * rV, f6W = c6 * M * rV - S(1.0);     // d/d psi_dot
+    const S gad = ma * dt * (lam[3] + lam[5] * f5A + lam[6] * f6A);
+    const S l2d = lam[2] + md * dt * (lam[5] * (c5 * P) + lam[6] * (c6 * E));
+    const S l3d = lam[3] + mv * dt * (lam[0] * cp + lam[1] * sp + lam[5] * f5V + lam[6] * f6V);
+    const S l5d = lam[5] + dt * (lam[4] + lam[5] * f5W + lam[6] * f6W);
+    const S l6d = lam[6] + head + dt * (lam[5] * (c5 * (Q - P)) - lam[6] * (c6 * (F + E)));
+    ga = dyn ? gad : gak;
+    gsv = ms * dt * lam[2];
+    const S l4 = lam[4] + head;
+    lam[2] = dyn ? l2d : l2k; lam[3] = dyn ? l3d : l3k; lam[4] = l4;
+    lam[5] = dyn ? l5d : lam[5]; lam[6] = dyn ? l6d : lam[6];
   } else if constexpr (MODE == IRBFN_ROLLOUT_FULLINT) {
     const S DT = S(0.1), WB = S(0.33), VMAX = S(7.0), VMIN = S(0.0), SMAX = S(0.4189);
     const S d0 = p[0], v0 = p[1], psi = p[2];

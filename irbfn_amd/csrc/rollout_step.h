@@ -283,7 +283,7 @@ __device__ __forceinline__ void spiral_step(float (&st)[6], const float (&c)[4],
 template <int MODE>
 struct ModeTraits;
 template <>
-struct ModeTraits<IRBFN_ROLLOUT_ST_SELECT> { static constexpr int S = 7, S0 = 7, NU = 2; };
+struct ModeTraits<IRBFN_ROLLOUT_ST_SELECT> { static constexpr int S = 7, S0 = 7, NU = 2, NP = 5; };
 template <>
 struct ModeTraits<IRBFN_ROLLOUT_ST_KS> { static constexpr int S = 7, S0 = 7, NU = 2, NP = 3; };
 template <>

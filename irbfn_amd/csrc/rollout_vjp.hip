@@ -299,9 +299,14 @@ __global__ __launch_bounds__(64 * kVjpWaves, 2) void rollout_vjp_regs_kernel(con
   auto request = [&](int gq, float* dst) {       // seeds of group gq -> dst (asynchronous; retired by vmcnt)
     const int tq = gq * G;
     const int nq = (T - tq) < G ? (T - tq) : G;
+    int ln = lane;
+    // NP = 5 (ST_SELECT): the NPC piece addresses, loop-invariant up to tq, were hoisted out of pass 2 into 34 VGPRs the sweeps
+    // have no room for, and came back from scratch in every group.  Opaque lane: they are computed where they are used
+    // (a dozen integer instructions per piece and group).
+    if constexpr (NP > 4) asm volatile("" : "+v"(ln));
 #pragma unroll
     for (int j = 0; j < NPC; ++j) {
-      const int idx = j * kWave + lane;
+      const int idx = j * kWave + (NP > 4 ? ln : lane);      // the other modes: `lane` itself, their code as it was
       const int r = idx / NPC, part = idx - r * NPC;
       const int C = (g4 + (int)((r * rs + (long)tq * S) & 3)) & 3;
       const float* src = gs_tile + r * rs + (long)tq * S - C + 4 * part;        // 16-byte aligned, inside the tile
@@ -376,6 +381,7 @@ __global__ __launch_bounds__(64 * kVjpWaves, 2) void rollout_vjp_regs_kernel(con
 #pragma unroll
       for (int i = 0; i < S; ++i) ss[i] = 0.0f;
       if constexpr (MODE == IRBFN_ROLLOUT_FRENET_LS) { ss[1] = pk[0]; ss[2] = pk[1]; ss[3] = pk[2]; ss[6] = pk[3]; ss[7] = cur; }
+      else if constexpr (MODE == IRBFN_ROLLOUT_ST_SELECT) { ss[2] = pk[0]; ss[3] = pk[1]; ss[4] = pk[2]; ss[5] = pk[3]; ss[6] = pk[4]; }
       else { ss[2] = pk[0]; ss[3] = pk[1]; ss[4] = pk[2]; }
 #pragma unroll
       for (int tt = 0; tt < G; ++tt) {
@@ -484,10 +490,26 @@ static int launch_vjp_mode(const RollVjpArgs& a, hipStream_t s) {
   return launch_vjp_park<MODE>(a, s);
 }
 
+// ST_SELECT with the mask V > 3 held constant (rollout_adjoint.h): the same two kernels; the park kernel's LDS bound gives
+// T <= 120 at NP = 5
+int launch_rollout_vjp_select(const float* x0u, const DynParams& dp, const float* gstates, float* g_x0u, int64_t B, int T,
+                              float clip_tie, hipStream_t s) {
+  constexpr int MODE = IRBFN_ROLLOUT_ST_SELECT;
+  if (B == 0) return IRBFN_OK;
+  if (T == 0) {
+    IRBFN_HIP_CHECK(hipMemsetAsync(g_x0u, 0, (size_t)B * ModeTraits<MODE>::S0 * sizeof(float), s));
+    return IRBFN_OK;
+  }
+  RollVjpArgs a;
+  a.x0u = x0u; a.gstates = gstates; a.gx0u = g_x0u; a.B = (long)B; a.T = T;
+  a.L = rollout_input_dim(MODE, T); a.tie = clip_tie; a.dp = dp;
+  return launch_vjp_mode<MODE>(a, s);
+}
+
 int launch_rollout_vjp(int mode, const float* x0u, const DynParams& dp, const float* gstates,
                        float* g_x0u, int64_t B, int T, float clip_tie, hipStream_t s) {
   if (B == 0) return IRBFN_OK;
-  // ST_SELECT: the reference never differentiates it (SURVEY B-5)
+  // ST_SELECT: the reference never differentiates it (SURVEY B-5); launch_rollout_vjp_select is this project's own adjoint
   if (mode == IRBFN_ROLLOUT_ST_SELECT || rollout_state_dim(mode) < 0) return IRBFN_ERR_UNSUPPORTED;
   if (T == 0) {                                  // no step: the rows are the initial states, and nothing depends on them
     IRBFN_HIP_CHECK(hipMemsetAsync(g_x0u, 0, (size_t)B * mode_dims(mode).S0 * sizeof(float), s));

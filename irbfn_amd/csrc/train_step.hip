@@ -6,6 +6,7 @@
 //   seeds_oneint  : loss_fn of train_step_oneint  (scripts/train_nmpc.py:268-295)
 //   seeds_fullint : loss_fn of train_step_fullint (scripts/train_nmpc.py:306-390)
 //   seeds_frenet_fullint : loss_fn of the Frenet train_step_fullint (scripts/train_nmpc_frenet.py:394-421)
+//   seeds_st_fullint : a full-integration loss through integrate_st_mult / the kinematic scan (this project's own)
 //   adam_clip     : optax.chain(clip_by_global_norm(max_norm), adam(lr)) + apply_gradients
 //                   (scripts/train_nmpc.py:231-233, :299)
 // All reductions are two-stage with a fixed order (deterministic).
@@ -325,6 +326,64 @@ __global__ __launch_bounds__(256) void seeds_frenet_fullint_kernel(const S* __re
   if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
 }
 
+// ---- single-track full integration (no reference counterpart; include/irbfn_hip.h: irbfn_train_seeds_st_fullint) --------
+// x[B,D>=7] and the initial state as seeds_oneint; SELECT: integrate_st_mult's model (select(V > 3, dynamic, kinematic), the
+// planner's roll-out) with the adjoint of the branch each step took (rollout_adjoint.h), else the kinematic model alone.
+// loss = mean|y_pred - y| + mean|S_pred[:, :, [0,1,3,4]] - S_act[:, :, [0,1,3,4]]| over all T states.  O = 2T.  float32 only.
+// Shaped like seeds_frenet_fullint_kernel<TMAX, float>: both sweeps unrolled to TMAX under t < T, park and seeds in registers.
+template <int TMAX, bool SELECT>
+__global__ __launch_bounds__(256) void seeds_st_fullint_kernel(const float* __restrict__ x, const float* __restrict__ yp,
+                                                               const float* __restrict__ y, float* __restrict__ gy,
+                                                               float* __restrict__ loss_part, long B, int D, int T,
+                                                               DynParams dp, float tie) {
+  constexpr int MODE = SELECT ? IRBFN_ROLLOUT_ST_SELECT : IRBFN_ROLLOUT_ST_KS;
+  constexpr int NP = ModeTraits<MODE>::NP;
+  __shared__ float sm[256];
+  const int O = 2 * T;
+  const float inv_y = 1.0f / ((float)B * (float)O), inv_s = 1.0f / ((float)B * (float)T * 4.0f);
+  float lsum = 0.0f;
+  for (long b = (long)blockIdx.x * 256 + threadIdx.x; b < B; b += (long)gridDim.x * 256) {
+    const float* xb = x + b * D;
+    float sa[7] = {0.0f, 0.0f, 0.0f, xb[0], 0.0f, xb[6], xb[5]};
+    float sp[7] = {0.0f, 0.0f, 0.0f, xb[0], 0.0f, xb[6], xb[5]};
+    float park[TMAX][NP], seed[TMAX][4];
+    const int idx[4] = {0, 1, 3, 4};
+#pragma unroll
+    for (int t = 0; t < TMAX; ++t) {
+      if (t < T) {
+        st_step<SELECT>(sa, y[b * O + t], y[b * O + T + t], dp);
+        vjp_park<MODE>(sp, park[t]);
+        st_step<SELECT>(sp, yp[b * O + t], yp[b * O + T + t], dp);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float d = sp[idx[k]] - sa[idx[k]];
+          lsum += fabsf(d) * inv_s;
+          seed[t][k] = sgn(d) * inv_s;
+        }
+      }
+    }
+    float lam[7] = {0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int t = TMAX - 1; t >= 0; --t) {
+      if (t < T) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) lam[idx[k]] += seed[t][k];
+        float ga, gsv;
+        vjp_back_step<MODE>(park[t], yp[b * O + t], yp[b * O + T + t], lam, 0.0f, tie, dp, ga, gsv);
+        gy[b * O + t] = ga;
+        gy[b * O + T + t] = gsv;
+      }
+    }
+    for (int o = 0; o < O; ++o) {
+      const float d = yp[b * O + o] - y[b * O + o];
+      lsum += fabsf(d) * inv_y;
+      gy[b * O + o] += sgn(d) * inv_y;
+    }
+  }
+  const float tot = block_sum_256(lsum, sm);
+  if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
+}
+
 template <typename S>
 __global__ __launch_bounds__(256) void final_sum_kernel(const S* __restrict__ part, int n, S* __restrict__ out) {
   __shared__ S sm[256];
@@ -448,6 +507,27 @@ static int train_seeds_frenet_fullint(const S* x_dev, const S* y_pred_dev, const
   return finish_loss(partials_dev, loss_dev, B, s);
 }
 
+static int train_seeds_st_fullint(int mode, const float* x_dev, const float* y_pred_dev, const float* y_dev,
+                                  const float* dyn_params_host, float clip_tie, float* gy_dev, float* loss_dev,
+                                  float* partials_dev, int64_t B, int D, int T, void* stream) {
+  if (mode != IRBFN_ROLLOUT_ST_SELECT && mode != IRBFN_ROLLOUT_ST_KS) return IRBFN_ERR_BAD_ARG;
+  if (B < 0 || D < 7 || T < 1 || T > 16 || !dyn_params_host) return IRBFN_ERR_BAD_ARG;
+  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
+  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
+  DynParams dp;
+  memcpy(dp.p, dyn_params_host, sizeof(dp.p));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid(seed_blocks(B)), block(256);
+#define IRBFN_SEEDS_ST(TMAX, SELECT) \
+  hipLaunchKernelGGL((seeds_st_fullint_kernel<TMAX, SELECT>), grid, block, 0, s, x_dev, y_pred_dev, y_dev, gy_dev, partials_dev, \
+                     (long)B, D, T, dp, clip_tie)
+  const bool select = mode == IRBFN_ROLLOUT_ST_SELECT;
+  if (T <= 5) { if (select) IRBFN_SEEDS_ST(5, true); else IRBFN_SEEDS_ST(5, false); }
+  else { if (select) IRBFN_SEEDS_ST(16, true); else IRBFN_SEEDS_ST(16, false); }
+#undef IRBFN_SEEDS_ST
+  return finish_loss(partials_dev, loss_dev, B, s);
+}
+
 template <typename S>
 static int adam_clip_step(S* params_dev, const S* grads_dev, S* m_dev, S* v_dev, int64_t n, int* step_dev, S lr, S beta1,
                           S beta2, S eps, S max_grad_norm, S* partials_dev, void* stream) {
@@ -490,6 +570,13 @@ int irbfn_train_seeds_frenet_fullint(const float* x_dev, const float* y_pred_dev
                                      float* partials_dev, int64_t B, int D, int T, void* stream) {
   return train_seeds_frenet_fullint(x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev, partials_dev, B, D, T,
                                     stream);
+}
+
+int irbfn_train_seeds_st_fullint(int mode, const float* x_dev, const float* y_pred_dev, const float* y_dev,
+                                 const float* dyn_params_host, float clip_tie, float* gy_dev, float* loss_dev,
+                                 float* partials_dev, int64_t B, int D, int T, void* stream) {
+  return train_seeds_st_fullint(mode, x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev, partials_dev, B, D, T,
+                                stream);
 }
 
 int irbfn_adam_clip_step(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev, int64_t n,

@@ -65,6 +65,26 @@ def rollout_vjp(mode: int, x0u, params, gstates, T: int, clip_tie: float = 0.5):
     return like_input(g, x0u, torch)
 
 
+def rollout_vjp_select(x0u, params, gstates, T: int, clip_tie: float = 0.5):
+    """Cotangent of ``integrate_st_mult``'s all_states [B,T,7] -> cotangent of the input rows [B, 7+2T].  The reference never
+    differentiates this model; the convention is this project's own (include/irbfn_hip.h, irbfn_rollout_vjp_select): each step
+    back-propagates through the branch it took -- dynamic where the clipped speed V > 3, kinematic otherwise -- with the mask held
+    constant, so a standing trajectory (V = 0) has finite gradients.  float32 only, T <= 120."""
+    torch = _lib.require_gpu()
+    lib = _lib.load()
+    xd, gd = to_device_f32(x0u, torch), to_device_f32(gstates, torch)
+    if xd.dim() != 2 or xd.shape[1] != 7 + 2 * T:
+        raise ValueError(f"roll-out input must be [B, {7 + 2 * T}] for T={T}, got {tuple(xd.shape)}")
+    B = xd.shape[0]
+    if tuple(gd.shape) != (B, T, 7):
+        raise ValueError(f"gstates must have shape ({B}, {T}, 7), got {tuple(gd.shape)}")
+    keep, pp = _dyn(params)
+    g = torch.empty_like(xd)
+    st = lib.irbfn_rollout_vjp_select(_ptr(xd), pp, _ptr(gd), _ptr(g), B, T, float(clip_tie), _stream_ptr(torch))
+    _lib.check(st, "irbfn_rollout_vjp_select")
+    return like_input(g, x0u, torch)
+
+
 def integrate_st_mult(x_and_pred_u, params):
     """src/irbfn_mpc/dynamics.py:94-100: [B, 7+2T] -> all_states [B, T, 7]; select(V > 3, dynamic, kinematic)."""
     return rollout_forward(_lib.ROLLOUT_ST_SELECT, x_and_pred_u, params,

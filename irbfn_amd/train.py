@@ -261,6 +261,36 @@ def train_step_frenet_fullint(state: TrainState, x, y, dyn_params, clip_tie: flo
     return state, _backward_and_update(state, xd, gy, torch, lib, **vjp_kw)
 
 
+def train_step_st_fullint(state: TrainState, x, y, dyn_params, mode: int = _lib.ROLLOUT_ST_SELECT,
+                          clip_tie: float = 0.5) -> Tuple[TrainState, "object"]:
+    """A full-integration step through the single-track roll-out the planner uses (``integrate_st_mult``, ``mode`` =
+    ``ROLLOUT_ST_SELECT``) or its kinematic part alone (``ROLLOUT_ST_KS``); the reference has no such step.  x [B, D >= 7] as
+    for ``train_step_oneint``, y [B, 2T] (T <= 16) -> (state, loss[1] on device);
+    loss = mean|y_pred - y| + mean|S_pred[:, :, [0,1,3,4]] - S_act[:, :, [0,1,3,4]]| over the T states of both roll-outs.
+    The select model is differentiated branch by branch (``dynamics.rollout_vjp_select``).  float32 states of a ``WCRBFNet`` or
+    a ``DeeperWCRBFNet`` only."""
+    torch = _lib.require_gpu()
+    lib = _lib.load()
+    if isinstance(state, ClusterTrainState):
+        raise ValueError("train_step_st_fullint has no cluster form: a ClusterTrainState trains with train_step_fullint_withcluster")
+    if _is_f64(state, torch):
+        raise ValueError("train_step_st_fullint runs in float32 only (the select model has no float64 form)")
+    if mode not in (_lib.ROLLOUT_ST_SELECT, _lib.ROLLOUT_ST_KS):
+        raise ValueError("train_step_st_fullint: mode must be ROLLOUT_ST_SELECT or ROLLOUT_ST_KS")
+    xd, yd = _step_inputs(state, x, y, torch)
+    B, O = yd.shape
+    if xd.shape[1] < 7 or O != state.net.out_features or O % 2 or not 1 <= O // 2 <= 16:
+        raise ValueError("train_step_st_fullint needs x [B, D >= 7] and y [B, out_features = 2T], 1 <= T <= 16")
+    y_pred, vjp_kw = _forward(state, xd)
+    gy = torch.empty_like(y_pred)
+    keep, pp = _dyn(dyn_params)
+    _fresh_loss(state, torch)
+    st = lib.irbfn_train_seeds_st_fullint(int(mode), _ptr(xd), _ptr(y_pred), _ptr(yd), pp, float(clip_tie), _ptr(gy),
+                                          _ptr(state.loss), _ptr(state.partials), B, xd.shape[1], O // 2, _stream_ptr(torch))
+    _lib.check(st, "irbfn_train_seeds_st_fullint")
+    return state, _backward_and_update(state, xd, gy, torch, lib, **vjp_kw)
+
+
 def train_step_fullint_withcluster(state: ClusterTrainState, x, y, cluster_ids, dyn_params, clip_tie: float = 0.5):
     """``train_step_fullint_withcluster`` (scripts/train_nmpc_frenet.py:424-453): the Frenet full-integration loss plus
     ``optax.softmax_cross_entropy(logits, cluster_ids).mean()`` on the gate of a ClusterWCRBFNet.  x [B,8], y [B,2T],
