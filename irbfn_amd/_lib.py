@@ -151,6 +151,14 @@ def check(status: int, where: str) -> None:
         raise IrbfnError(status, where, detail)
 
 
+def workspace_bytes(name: str, *args) -> int:
+    """The byte count a ``*_workspace_bytes`` function of the library returns; a negative one is a status and raises as in ``check``."""
+    need = int(getattr(load(), name)(*args))
+    if need < 0:
+        check(need, name)
+    return need
+
+
 def require_gpu():
     import torch
     if not torch.cuda.is_available():

@@ -32,11 +32,8 @@ def _step(lib, torch, x, centers, labels, d2, new_centers, counts, stats, ws):
     _lib.check(st, "irbfn_kmeans_step")
 
 
-def _workspace(lib, torch, N, K, D, device):
-    need = lib.irbfn_kmeans_workspace_bytes(N, K, D)
-    if need < 0:
-        _lib.check(int(need), "irbfn_kmeans_workspace_bytes")
-    return torch.empty(max(int(need), 8), dtype=torch.uint8, device=device)
+def _workspace(torch, N, K, D, device):
+    return torch.empty(max(_lib.workspace_bytes("irbfn_kmeans_workspace_bytes", N, K, D), 8), dtype=torch.uint8, device=device)
 
 
 def _rows_and_centers(x, centers, torch):
@@ -58,7 +55,7 @@ def assign(x, centers):
     d2 = torch.empty(N, dtype=torch.float32, device=xd.device)
     if N:
         stats = torch.empty(4, dtype=torch.float64, device=xd.device)
-        _step(lib, torch, xd, cd, labels, d2, None, None, stats, _workspace(lib, torch, N, cd.shape[0], D, xd.device))
+        _step(lib, torch, xd, cd, labels, d2, None, None, stats, _workspace(torch, N, cd.shape[0], D, xd.device))
     return labels, d2
 
 
@@ -112,7 +109,7 @@ def init_kmeanspp(xd, k, gen):
     first = order[:1]
     centers = torch.empty((k, D), dtype=torch.float32, device=xd.device)
     centers[0:1] = xd.index_select(0, first)
-    ws = _workspace(lib, torch, N, 1, D, xd.device)
+    ws = _workspace(torch, N, 1, D, xd.device)
     labels = torch.full((N,), -1, dtype=torch.int32, device=xd.device)
     d2 = torch.empty(N, dtype=torch.float32, device=xd.device)
     stats = torch.empty(4, dtype=torch.float64, device=xd.device)
@@ -157,7 +154,7 @@ def fit(x, k: int, max_iter: int = 100, init="kmeans++", seed: int = 0, tol: flo
         cur = to_device_f32(init, torch, device=xd.device).clone()
         if tuple(cur.shape) != (k, D):
             raise ValueError(f"init has shape {tuple(cur.shape)}, expected ({k}, {D})")
-    ws = _workspace(lib, torch, N, k, D, xd.device)
+    ws = _workspace(torch, N, k, D, xd.device)
     nxt = torch.empty_like(cur)
     labels = torch.full((N,), -1, dtype=torch.int32, device=xd.device)
     counts = torch.zeros(k, dtype=torch.int64, device=xd.device)

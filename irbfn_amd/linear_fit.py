@@ -22,9 +22,20 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .model import _grown_ws, _inner, _ptr, _stream_ptr, to_device_f32
+from .model import NO_F64_HIDDEN, _grown_ws, _inner, _ptr, _stream_ptr, to_device_f32
 
 _SYRK_WS: dict = {}
+
+
+def _rows_f32(z, what: str, torch):
+    """-> (z, ld): the float32 matrix argument ``what`` of a kernel that reads rows of any stride, and its leading dimension; a
+    float32 cuda matrix with unit column stride is read in place, anything else goes through ``to_device_f32``."""
+    if not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != torch.float32 or z.dim() != 2 or (z.shape[0] > 1 and z.stride(1) != 1):
+        z = to_device_f32(z, torch)
+        if z.dim() != 2:
+            raise ValueError(f"{what}, got {tuple(z.shape)}")
+    rows, cols = z.shape
+    return z, (z.stride(0) if rows > 1 else max(z.stride(0), cols))
 
 
 def syrk(z, out=None, accumulate: bool = False):
@@ -32,25 +43,56 @@ def syrk(z, out=None, accumulate: bool = False):
     triangles (``irbfn_syrk_f64``).  ``out``: a contiguous float64 [M, M] cuda tensor to write, or with ``accumulate`` to add onto."""
     torch = _lib.require_gpu()
     lib = _lib.load()
-    if not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != torch.float32 or z.dim() != 2 or (z.shape[0] > 1 and z.stride(1) != 1):
-        z = to_device_f32(z, torch)
-        if z.dim() != 2:
-            raise ValueError(f"syrk needs z [rows, M], got {tuple(z.shape)}")
+    z, ldz = _rows_f32(z, "syrk needs z [rows, M]", torch)
     rows, M = z.shape
-    ldz = z.stride(0) if rows > 1 else max(z.stride(0), M)
     if out is None:
         if accumulate:
             raise ValueError("syrk: accumulate=True needs out=")
         out = torch.empty((M, M), dtype=torch.float64, device=z.device)
     elif tuple(out.shape) != (M, M) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
         raise ValueError(f"syrk: out must be a contiguous float64 cuda tensor of shape ({M}, {M})")
-    need = lib.irbfn_syrk_f64_workspace_bytes(rows, M)
-    if need < 0:
-        _lib.check(int(need), "irbfn_syrk_f64_workspace_bytes")
-    ws = _grown_ws(_SYRK_WS, z.device.index, need, torch, z.device)
+    ws = _grown_ws(_SYRK_WS, z.device.index, _lib.workspace_bytes("irbfn_syrk_f64_workspace_bytes", rows, M), torch, z.device)
     st = lib.irbfn_syrk_f64(_ptr(z), ldz, rows, M, _ptr(out), 1 if accumulate else 0, _ptr(ws), ws.numel(), _stream_ptr(torch))
     _lib.check(st, "irbfn_syrk_f64")
     return out
+
+
+def _rows_of(net, x) -> int:
+    """N of x [N, in_features]; any other shape raises."""
+    xs = tuple(x.shape)
+    if len(xs) != 2 or xs[1] != net.in_features:
+        raise ValueError(f"x must have shape (N, {net.in_features}), got {xs}")
+    return xs[0]
+
+
+def hidden_rows(net, params, x, width: int, ones_col, batch_size: int, what: str, buf=None):
+    """The one pass over the rows of x [N,D] that every closed-form stage makes -> (xd, Z, chunks).  ``chunks`` yields (i, n, Z[:n])
+    per chunk of ``batch_size`` rows: ``irbfn_net_hidden`` of x[i:i + n] under ``params`` in the first K columns of the reused
+    float32 buffer Z [chunk, width], 1 in column ``ones_col`` (None: no column is written); every other column is the caller's.
+    ``xd`` = x on the device, where y can follow it; Z = ``buf`` where that has the rows and the device, else a new buffer.
+    ``what`` names the caller where a float64 net is refused.  No host read."""
+    torch = _lib.require_gpu()
+    if getattr(net, "use_float64", False):
+        raise ValueError(f"{what}: {NO_F64_HIDDEN}")
+    N = _rows_of(net, x)
+    if int(batch_size) < 1:
+        raise ValueError("batch_size must be >= 1")
+    net._warn_if_float64(params)
+    net.bind(params)
+    xd = to_device_f32(x, torch)
+    chunk = min(int(batch_size), max(N, 1))
+    if buf is None or buf.shape[0] < chunk or buf.device != xd.device:
+        buf = torch.empty((chunk, int(width)), dtype=torch.float32, device=xd.device)
+
+    def chunks():
+        for i in range(0, N, chunk):
+            n = min(chunk, N - i)
+            Z = buf[:n]
+            net._hidden_into(xd[i:i + n], Z, torch)
+            if ones_col is not None:
+                Z[:, ones_col] = 1.0
+            yield i, n, Z
+    return xd, buf, chunks()
 
 
 class LinearFit:
@@ -78,7 +120,7 @@ class NormalEquations:
 
     def __init__(self, net, G=None):
         if getattr(net, "use_float64", False):
-            raise ValueError("NormalEquations: the float64 mode has no hidden-layer kernel (construct the net with use_float64=False)")
+            raise ValueError(f"NormalEquations: {NO_F64_HIDDEN}")
         self.net = net
         self.K, self.O = int(net.num_kernels), int(net.out_features)
         self.M = self.K + 1 + self.O
@@ -91,31 +133,17 @@ class NormalEquations:
         """Adds the rows (x [N,D], y [N,O]) under ``params``: per chunk of ``batch_size`` rows one ``irbfn_net_hidden`` into the
         reused buffer Z [chunk, M], the ones column and y by two slice assignments, then ``irbfn_syrk_f64(accumulate=1)``."""
         torch = _lib.require_gpu()
-        net, K, O, M = self.net, self.K, self.O, self.M
-        xs, ys = tuple(x.shape), tuple(y.shape)
-        if len(xs) != 2 or xs[1] != net.in_features:
-            raise ValueError(f"x must have shape (N, {net.in_features}), got {xs}")
+        K, O, M = self.K, self.O, self.M
+        N, ys = _rows_of(self.net, x), tuple(y.shape)
         if len(ys) != 2 or ys[1] != O:
             raise ValueError(f"y must have shape (N, {O}), got {ys}")
-        if xs[0] != ys[0]:
-            raise ValueError(f"x has {xs[0]} rows, y has {ys[0]}")
-        if int(batch_size) < 1:
-            raise ValueError("batch_size must be >= 1")
-        net._warn_if_float64(params)
-        net.bind(params)
-        xd = to_device_f32(x, torch)
+        if N != ys[0]:
+            raise ValueError(f"x has {N} rows, y has {ys[0]}")
+        xd, self._Z, chunks = hidden_rows(self.net, params, x, M, K, batch_size, "NormalEquations", buf=self._Z)
         yd = to_device_f32(y, torch, device=xd.device)
         if self.G is None:
             self.G = torch.zeros((M, M), dtype=torch.float64, device=xd.device)
-        N = xs[0]
-        chunk = min(int(batch_size), max(N, 1))
-        if self._Z is None or self._Z.shape[0] < chunk or self._Z.device != xd.device:
-            self._Z = torch.empty((chunk, M), dtype=torch.float32, device=xd.device)
-        for i in range(0, N, chunk):
-            n = min(chunk, N - i)
-            Z = self._Z[:n]
-            net._hidden_into(xd[i:i + n], Z, torch)
-            Z[:, K] = 1.0
+        for i, n, Z in chunks:
             Z[:, K + 1:] = yd[i:i + n]
             syrk(Z, out=self.G, accumulate=True)
         return self
@@ -158,18 +186,40 @@ class NormalEquations:
         lambda = ridge * trace(H^T H) / K (none on the bias), in float64 on G's device: symmetric Jacobi scaling by
         1 / sqrt(diag) (a zero diagonal entry is scaled by 1), ``torch.linalg.cholesky_ex``, two triangular solves.
         ``fit_bias=False`` drops the ones column and returns bias = 0.  O(K^3), once per fit."""
+        return self._factorise(ridge, fit_bias)[2]
+
+    def finite_G(self, what: str):
+        """G, after the two refusals every consumer of it shares: no rows were added, or an entry is not finite (one host read)."""
         import torch
         if self.G is None:
-            raise ValueError("solve: no rows were added")
-        G, K, O = self.G, self.K, self.O
-        bad = int((~torch.isfinite(G)).sum().item())
+            raise ValueError(f"{what}: no rows were added")
+        bad = int((~torch.isfinite(self.G)).sum().item())
         if bad:
-            raise ValueError(f"normal equations hold {bad} non-finite entries of {G.numel()} (non-finite rows in x or y?)")
+            raise ValueError(f"normal equations hold {bad} non-finite entries of {self.G.numel()} (non-finite rows in x or y?)")
+        return self.G
+
+    def ridge_abs(self, ridge: float) -> float:
+        """The absolute ridge lambda = ridge * trace(H^T H) / K (one host read)."""
+        import torch
+        return float(ridge) * float(torch.diagonal(self.G)[:self.K].sum().item()) / self.K
+
+    def _system(self, fit_bias: bool):
+        """(A0 [m,m], rhs [m,O]) of G: [[H^T H, H^T 1], [1^T H, n]] and [H^T Y; 1^T Y], without the ones column m = K."""
+        import torch
+        G, K = self.G, self.K
+        if fit_bias:
+            return G[:K + 1, :K + 1], torch.cat([G[:K, K + 1:], G[K:K + 1, K + 1:]])
+        return G[:K, :K], G[:K, K + 1:]
+
+    def _factorise(self, ridge: float, fit_bias: bool):
+        """``solve``, keeping what ``loo.factor`` builds on -> (L [m,m] the lower Cholesky factor of the scaled matrix
+        diag(s) (A0 + Lambda) diag(s), s [m] the scaling, the ``LinearFit``)."""
+        import torch
+        G, K, O = self.finite_G("solve"), self.K, self.O
         n = int(round(float(G[K, K].item())))
-        m = K + 1 if fit_bias else K
-        A0 = G[:m, :m]
-        rhs = torch.cat([G[:K, K + 1:], G[K:K + 1, K + 1:]]) if fit_bias else G[:K, K + 1:]
-        lam = float(ridge) * float(torch.diagonal(G)[:K].sum().item()) / K
+        A0, rhs = self._system(fit_bias)
+        m = A0.shape[0]
+        lam = self.ridge_abs(ridge)
         A = A0.clone()
         torch.diagonal(A)[:K] += lam
         d = torch.diagonal(A)
@@ -186,17 +236,14 @@ class NormalEquations:
         sol = torch.linalg.solve_triangular(L.mT, t, upper=True) * s[:, None]
         W = sol[:K].contiguous()
         b = sol[K].contiguous() if fit_bias else torch.zeros(O, dtype=G.dtype, device=G.device)
-        return LinearFit(W, b, n, self._rss(sol, fit_bias), lam, fit_bias, sol)
+        return L, s, LinearFit(W, b, n, self._rss(sol, fit_bias), lam, fit_bias, sol)
 
     def _rss(self, sol, fit_bias: bool):
         """y^T y - 2 sol^T rhs + sol^T A0 sol per output, clamped at 0: the residual sum of squares of sol = [W; b] ([W] without
         the ones column) on this accumulator's rows, from G alone."""
         import torch
-        G, K = self.G, self.K
-        m = K + 1 if fit_bias else K
-        A0 = G[:m, :m]
-        rhs = torch.cat([G[:K, K + 1:], G[K:K + 1, K + 1:]]) if fit_bias else G[:K, K + 1:]
-        yty = torch.diagonal(G)[K + 1:]
+        A0, rhs = self._system(fit_bias)
+        yty = torch.diagonal(self.G)[self.K + 1:]
         return (yty - 2.0 * (sol * rhs).sum(0) + (sol * (A0 @ sol)).sum(0)).clamp_min(0.0)
 
     def rss_of(self, fit: LinearFit):
@@ -223,14 +270,21 @@ def _like_leaf(t64, old):
     return t64.detach().cpu().numpy().astype(np.float32)
 
 
+def with_fit(params: dict, fit: LinearFit) -> dict:
+    """The tree of ``params`` (with its ``{"params": ...}`` wrapper or without) with ``linear/kernel`` and ``linear/bias`` from the
+    fit, cast to float32 in the flavour of the leaves they replace; every other leaf is the input's own, the groups are new dicts
+    and ``params`` is left as it was."""
+    p = _inner(params)
+    new = {g: dict(v) for g, v in p.items()}
+    new["linear"]["kernel"] = _like_leaf(fit.kernel, p["linear"]["kernel"])
+    new["linear"]["bias"] = _like_leaf(fit.bias, p["linear"]["bias"])
+    return {"params": new} if "params" in params else new
+
+
 def fit_linear(net, params: dict, x, y, ridge: float = 1e-8, fit_bias: bool = True, batch_size: int = 65536):
     """-> (new_params, LinearFit): ``linear/kernel`` and ``linear/bias`` of ``params`` replaced by the ridge least-squares fit
     of y [N,O] on the net's hidden layer of x [N,D] (centres, widths and gate as in ``params`` / the net), cast to float32;
     every other leaf and the tree's shape are the input's, so a fixed-centre or fixed-width net gets its reduced tree back.
     x, y: arrays or tensors on any device (a ``DeviceTable``'s ``.x``, ``.y``)."""
     fit = NormalEquations(net).add(params, x, y, batch_size=batch_size).solve(ridge=ridge, fit_bias=fit_bias)
-    p = _inner(params)
-    new = {g: dict(v) for g, v in p.items()}
-    new["linear"]["kernel"] = _like_leaf(fit.kernel, p["linear"]["kernel"])
-    new["linear"]["bias"] = _like_leaf(fit.bias, p["linear"]["bias"])
-    return ({"params": new} if "params" in params else new), fit
+    return with_fit(params, fit), fit

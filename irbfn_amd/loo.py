@@ -15,8 +15,9 @@ of row n under the fit of all *other* rows is exactly e_n / (1 - l_n) (Sherman-M
     res = loo.loo(net, params, table.x, table.y, fac, per_row=True)   # res.press, res.gcv, res.trace, res.loo_residual ...
     search = loo.select_ridge(net, params, table.x, table.y)          # the ridge by PRESS; loo.select_scale: the width multiplier
 
-``factor`` repeats the steps of ``NormalEquations.solve`` and keeps the Cholesky factor L of the scaled system: with
-T = L^-1 diag(s), l_n = |T z_n|^2.  The pass over the rows is one hidden-layer launch and one K11 launch per chunk; the
+``factor`` is ``NormalEquations.solve`` itself (one factorisation serves both) and keeps the Cholesky factor L of the scaled
+system: with T = L^-1 diag(s), l_n = |T z_n|^2.  The pass over the rows is the one of ``NormalEquations.add``
+(``linear_fit.hidden_rows``): one hidden-layer launch and one K11 launch per chunk; the
 rows x m x m / 2 product in float64 is never stored.  The reference has no counterpart (its "table cleaning" notebooks are not in
 its snapshot): parity is unpinned; each stage is pinned against a float64 statement of it (tests/_loo_util.py).
 
@@ -28,8 +29,9 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .linear_fit import LinearFit, NormalEquations, _like_leaf
-from .model import _inner, _ptr, _stream_ptr, to_device_f32
+from .linear_fit import NormalEquations, _rows_f32, hidden_rows, with_fit
+from .model import _ptr, _stream_ptr, to_device_f32
+from .widths import finite_lists, search_scales
 
 
 class Factor:
@@ -51,41 +53,14 @@ class Factor:
 
 
 def factor(ne: NormalEquations, ridge: float = 1e-8, fit_bias: bool = True) -> Factor:
-    """``NormalEquations.solve``'s steps with its refusals (no rows, non-finite entries of G, ``info != 0``, a pivot of the
-    unit-diagonal matrix below m 2^-52), keeping the factor.  The same operations on the same values in the same order as ``solve``:
-    ``fit`` equals ``ne.solve(ridge, fit_bias)`` bit for bit.  On top of it one triangular solve against diag(s), O(m^3), once
-    per factor."""
+    """``NormalEquations.solve`` with its refusals (no rows, non-finite entries of G, ``info != 0``, a pivot of the unit-diagonal
+    matrix below m 2^-52), keeping the factor: ``fit`` is the ``LinearFit`` of the one factorisation ``solve`` returns, so it equals
+    ``ne.solve(ridge, fit_bias)`` bit for bit.  On top of it one triangular solve against diag(s), O(m^3), once per factor."""
     import torch
-    if ne.G is None:
-        raise ValueError("solve: no rows were added")
-    G, K, O = ne.G, ne.K, ne.O
-    bad = int((~torch.isfinite(G)).sum().item())
-    if bad:
-        raise ValueError(f"normal equations hold {bad} non-finite entries of {G.numel()} (non-finite rows in x or y?)")
-    n = int(round(float(G[K, K].item())))
-    m = K + 1 if fit_bias else K
-    A0 = G[:m, :m]
-    rhs = torch.cat([G[:K, K + 1:], G[K:K + 1, K + 1:]]) if fit_bias else G[:K, K + 1:]
-    lam = float(ridge) * float(torch.diagonal(G)[:K].sum().item()) / K
-    A = A0.clone()
-    torch.diagonal(A)[:K] += lam
-    d = torch.diagonal(A)
-    s = torch.where(d > 0, torch.rsqrt(torch.where(d > 0, d, torch.ones_like(d))), torch.ones_like(d))
-    As = A * s[:, None] * s[None, :]
-    try:
-        L, info = torch.linalg.cholesky_ex(As)
-    except RuntimeError:           # a torch build without the device factorisation: the O(K^3) step on the host
-        L, info = (t.to(As.device) for t in torch.linalg.cholesky_ex(As.cpu()))
-    if int(info.item()) != 0 or not bool((torch.diagonal(L) ** 2 > m * 2.0 ** -52).all().item()):
-        raise ValueError(f"normal equations not positive definite at ridge={ridge:g}; raise ridge")
-    t = torch.linalg.solve_triangular(L, rhs * s[:, None], upper=False)
-    sol = torch.linalg.solve_triangular(L.mT, t, upper=True) * s[:, None]
-    W = sol[:K].contiguous()
-    b = sol[K].contiguous() if fit_bias else torch.zeros(O, dtype=G.dtype, device=G.device)
-    fit = LinearFit(W, b, n, ne._rss(sol, fit_bias), lam, fit_bias, sol)
+    L, s, fit = ne._factorise(ridge, fit_bias)
     T = torch.linalg.solve_triangular(L, torch.diag(s), upper=False)               # L^-1 diag(s): lower triangular
-    P = torch.cat([T.mT, sol], dim=1).contiguous()
-    return Factor(L, s, lam, n, fit_bias, fit, P)
+    P = torch.cat([T.mT, fit.sol], dim=1).contiguous()
+    return Factor(L, s, fit.ridge_abs, fit.n, fit_bias, fit, P)
 
 
 def rows_quad(z, P, nd: int):
@@ -96,15 +71,11 @@ def rows_quad(z, P, nd: int):
     torch = _lib.require_gpu()
     lib = _lib.load()
     nd = int(nd)
-    if not isinstance(z, torch.Tensor) or not z.is_cuda or z.dtype != torch.float32 or z.dim() != 2 or (z.shape[0] > 1 and z.stride(1) != 1):
-        z = to_device_f32(z, torch)
-        if z.dim() != 2:
-            raise ValueError(f"rows_quad needs z [rows, m], got {tuple(z.shape)}")
+    z, ldz = _rows_f32(z, "rows_quad needs z [rows, m]", torch)
     rows, m = z.shape
     if (not isinstance(P, torch.Tensor) or P.dtype != torch.float64 or P.device != z.device or P.dim() != 2 or nd < 0
             or tuple(P.shape) != (m, m + nd) or (m + nd > 1 and P.stride(1) != 1) or (m > 1 and P.stride(0) < m + nd)):
         raise ValueError(f"rows_quad: P must be a float64 tensor of shape ({m}, {m} + nd) with unit column stride on z's device")
-    ldz = z.stride(0) if rows > 1 else max(z.stride(0), m)
     ldp = P.stride(0) if m > 1 else max(P.stride(0), m + nd)
     q = torch.empty((rows,), dtype=torch.float64, device=z.device)
     v = torch.empty((rows, nd), dtype=torch.float64, device=z.device)
@@ -115,38 +86,16 @@ def rows_quad(z, P, nd: int):
 
 
 def _chunks(net, params, x, fac: Factor, batch_size: int, nd: int):
-    """Yields (i, n, q [n], v [n, nd]) per chunk of ``batch_size`` rows of x: ``net._hidden_into`` into a reused Z [chunk, m], the ones
-    column, one ``irbfn_rows_quad_f64``.  -> (generator, xd)."""
-    torch = _lib.require_gpu()
-    if getattr(net, "use_float64", False):
-        raise ValueError("loo: the float64 mode has no hidden-layer kernel (construct the net with use_float64=False)")
+    """-> (chunks, xd): ``chunks`` yields (i, n, q [n], v [n, nd]) per chunk of ``batch_size`` rows of x, one ``irbfn_rows_quad_f64`` on
+    each Z = [h | 1] of ``linear_fit.hidden_rows`` (no ones column for a factor without ``fit_bias``)."""
     K = int(net.num_kernels)
     if fac.m != K + (1 if fac.fit_bias else 0):
         raise ValueError(f"a factor of {fac.m} columns on a net of num_kernels={K} (fit_bias={fac.fit_bias})")
-    xs = tuple(x.shape)
-    if len(xs) != 2 or xs[1] != net.in_features:
-        raise ValueError(f"x must have shape (N, {net.in_features}), got {xs}")
-    if int(batch_size) < 1:
-        raise ValueError("batch_size must be >= 1")
-    net._warn_if_float64(params)
-    net.bind(params)
-    xd = to_device_f32(x, torch)
+    xd, _, rows = hidden_rows(net, params, x, fac.m, K if fac.fit_bias else None, batch_size, "loo")
     if fac.P.device != xd.device:
         raise ValueError(f"the factor lives on {fac.P.device}, the rows on {xd.device}")
-    N = xs[0]
-    chunk = min(int(batch_size), max(N, 1))
     P = fac.P if nd else fac.P[:, :fac.m]
-
-    def gen():
-        Z = torch.empty((chunk, fac.m), dtype=torch.float32, device=xd.device)
-        for i in range(0, N, chunk):
-            n = min(chunk, N - i)
-            Zn = Z[:n]
-            net._hidden_into(xd[i:i + n], Zn, torch)
-            if fac.fit_bias:
-                Zn[:, K] = 1.0
-            yield (i, n, *rows_quad(Zn, P, nd))
-    return gen(), xd
+    return ((i, n, *rows_quad(Z, P, nd)) for i, n, Z in rows), xd
 
 
 def leverage(net, params: dict, x, fac: Factor, batch_size: int = 65536):
@@ -230,15 +179,6 @@ def loo(net, params: dict, x, y, fac: Factor, batch_size: int = 65536, per_row: 
     return LooResult(N, rss, press, trace, qmax, qrow, ndeg, lev, res, lres)
 
 
-def _with_fit(params: dict, fit: LinearFit) -> dict:
-    """The tree of ``params`` with the fit's linear leaves, as ``fit_linear`` builds it."""
-    p = _inner(params)
-    new = {g: dict(v) for g, v in p.items()}
-    new["linear"]["kernel"] = _like_leaf(fit.kernel, p["linear"]["kernel"])
-    new["linear"]["bias"] = _like_leaf(fit.bias, p["linear"]["bias"])
-    return {"params": new} if "params" in params else new
-
-
 class RidgeSearch:
     """``ridges``; ``press`` [R][O], ``gcv`` [R][O] and ``trace`` [R] per ridge as host lists (``inf`` where the system was refused
     or a row was degenerate); ``best`` = the index of the smallest summed PRESS (ties: the smaller ridge); ``fit`` and ``params`` =
@@ -280,13 +220,12 @@ def select_ridge(net, params: dict, x, y, ridges=(1e-10, 1e-8, 1e-6, 1e-4, 1e-2)
         press.append(res.press)
         gcv.append(res.gcv)
         trace.append(res.trace)
-    clean = lambda t: torch.nan_to_num(t, nan=float("inf"), posinf=float("inf")).tolist()
-    press, gcv, trace = clean(torch.stack(press)), clean(torch.stack(gcv)), clean(torch.stack(trace))
+    press, gcv, trace = finite_lists(torch.stack(press)), finite_lists(torch.stack(gcv)), finite_lists(torch.stack(trace))
     total = [float(np.sum(p)) for p in press]
     best = min(range(len(ridges)), key=lambda i: (total[i], ridges[i]))
     if fits[best] is None or not np.isfinite(total[best]):
         raise ValueError("select_ridge: no ridge gave a positive definite system with a finite PRESS")
-    return RidgeSearch(ridges, press, gcv, trace, best, fits[best], _with_fit(params, fits[best]))
+    return RidgeSearch(ridges, press, gcv, trace, best, fits[best], with_fit(params, fits[best]))
 
 
 def select_scale(net, widths, x, y, scales=(0.5, 1, 2, 4, 8), ridge: float = 1e-8, batch_size: int = 65536):
@@ -295,38 +234,13 @@ def select_scale(net, widths, x, y, scales=(0.5, 1, 2, 4, 8), ridge: float = 1e-
     fifth of the table and runs two Gram passes.  -> ``widths.ScaleSearch`` with ``train_mse`` = rss / (n O) and ``holdout_mse``
     holding the leave-one-out MSE; a scale whose system is refused gets ``inf``."""
     torch = _lib.require_gpu()
-    from .widths import ScaleSearch, Widths
-    if not (net.fixed_width and net.centers is not None):
-        raise ValueError("select_scale needs a fixed-width net: WCRBFNet(..., centers=C, fixed_width=True)")
-    scales = tuple(float(s) for s in scales)
-    if not scales:
-        raise ValueError("select_scale needs at least one scale")
     xd = to_device_f32(x, torch)
     yd = to_device_f32(y, torch, device=xd.device)
     N, O = xd.shape[0], net.out_features
     if N < 1:
         raise ValueError("select_scale needs rows")
-    inf = torch.full((), float("inf"), dtype=torch.float64, device=xd.device)
-    tried, mse_t, mse_l = [], [], []
-    host = Widths(widths.sigma.detach().cpu(), widths.replaced)      # the one read of the widths
-    for s in scales:
-        net_s = type(net).from_config(dict(net.config(), log_sigs=host.scaled(s).log_sigs(net)), centers=net.centers)
-        p = net_s.init()
-        ne = NormalEquations(net_s).add(p, xd, yd, batch_size=batch_size)
-        try:
-            fac = factor(ne, ridge=ridge)
-        except ValueError:             # not positive definite, or non-finite entries: this scale is out
-            tried.append((net_s, None))
-            mse_t.append(inf)
-            mse_l.append(inf)
-            continue
-        res = loo(net_s, p, xd, yd, fac, batch_size=batch_size)
-        tried.append((net_s, fac.fit))
-        mse_t.append(fac.fit.rss.sum() / (N * O))
-        mse_l.append(res.press.sum() / (N * O))
-    both = torch.nan_to_num(torch.stack([torch.stack(mse_t), torch.stack(mse_l)]), nan=float("inf"), posinf=float("inf")).tolist()
-    best = int(np.argmin(both[1]))
-    net_b, fit_b = tried[best]
-    if fit_b is None or not np.isfinite(both[1][best]):
-        raise ValueError("select_scale: no scale gave a positive definite system with a finite leave-one-out error")
-    return ScaleSearch(scales, both[0], both[1], best, net_b, _with_fit(net_b.init(), fit_b), fit_b)
+
+    def press(net_s, p, ne):
+        fac = factor(ne, ridge=ridge)
+        return fac.fit, loo(net_s, p, xd, yd, fac, batch_size=batch_size).press.sum() / (N * O)
+    return search_scales(net, widths, xd, yd, scales, batch_size, press, "leave-one-out error")

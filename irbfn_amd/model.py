@@ -20,6 +20,9 @@ _CFG_FIELDS = ("in_features", "out_features", "num_kernels", "basis_func", "num_
                "upper_bounds", "dimension_ranges", "activation_idx", "delta")
 
 
+NO_F64_HIDDEN = "the float64 mode has no hidden-layer kernel (construct the net with use_float64=False)"      # after the caller's prefix
+
+
 def _inner(params: dict) -> dict:
     return params["params"] if "params" in params else params
 
@@ -509,7 +512,7 @@ class WCRBFNet:
         rounding.  The design matrix of ``linear_fit.fit_linear``; the reference has no counterpart.  The float64 mode has
         no hidden-layer kernel: a ``use_float64`` net raises ``ValueError``."""
         if self.use_float64:
-            raise ValueError("WCRBFNet.hidden: the float64 mode has no hidden-layer kernel (construct the net with use_float64=False)")
+            raise ValueError(f"WCRBFNet.hidden: {NO_F64_HIDDEN}")
         torch = _lib.require_gpu()
         self._warn_if_float64(params)
         self.bind(params)

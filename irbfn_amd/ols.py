@@ -20,8 +20,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .linear_fit import NormalEquations, _like_leaf
-from .model import WCRBFNet, _inner, _ptr, _stream_ptr
+from .linear_fit import NormalEquations, with_fit
+from .model import NO_F64_HIDDEN, WCRBFNet, _inner, _ptr, _stream_ptr
 
 
 def npad(M: int) -> int:
@@ -58,10 +58,7 @@ class OLSResult:
         idx = self.indices[:k]
         net_k, new = slice_net(net, params, idx.cpu().numpy())
         fit = self.ne.subset(idx, net_k).solve(ridge=self.ridge, fit_bias=self.fit_bias)
-        p = _inner(params)
-        new["linear"]["kernel"] = _like_leaf(fit.kernel, p["linear"]["kernel"])
-        new["linear"]["bias"] = _like_leaf(fit.bias, p["linear"]["bias"])
-        return net_k, ({"params": new} if "params" in params else new), fit
+        return net_k, with_fit({"params": new} if "params" in params else new, fit), fit      # slice_net keeps the leaves' flavour
 
 
 def _take(leaf, idx: np.ndarray, axis: int):
@@ -78,7 +75,7 @@ def slice_net(net, params: dict, idx):
     if type(net) is not WCRBFNet:
         raise ValueError(f"selection of centres is built for WCRBFNet, not {type(net).__name__}")
     if net.use_float64:
-        raise ValueError("NormalEquations: the float64 mode has no hidden-layer kernel (construct the net with use_float64=False)")
+        raise ValueError(f"NormalEquations: {NO_F64_HIDDEN}")
     idx = np.asarray(idx, dtype=np.int64).reshape(-1)
     if idx.size < 1 or idx.min() < 0 or idx.max() >= net.num_kernels:
         raise ValueError(f"kernel indices must be a non-empty subset of [0, {net.num_kernels})")
@@ -110,10 +107,7 @@ class _State:
         self.sel = torch.full((kmax + 1,), -1, dtype=torch.int32, device=dev)
         self.gain = torch.zeros((kmax + 1, O), dtype=torch.float64, device=dev)
         self.count = torch.zeros(1, dtype=torch.int32, device=dev)
-        need = lib.irbfn_ols_workspace_bytes(M, O, kmax)
-        if need < 0:
-            _lib.check(int(need), "irbfn_ols_workspace_bytes")
-        self.ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
+        self.ws = torch.empty(_lib.workspace_bytes("irbfn_ols_workspace_bytes", M, O, kmax), dtype=torch.uint8, device=dev)
         st = lib.irbfn_ols_begin(_ptr(G), M, O, self.args[2], float(ridge_abs), self.tol, self.kmax, *self._bufs(), _stream_ptr(torch))
         _lib.check(st, "irbfn_ols_begin")
 
@@ -137,19 +131,14 @@ def select(ne: NormalEquations, k: int, ridge: float = 1e-8, fit_bias: bool = Tr
     read until the result is built.  Raises ``ValueError`` where ``solve`` does: no rows, non-finite entries in G."""
     torch = _lib.require_gpu()
     lib = _lib.load()
-    if ne.G is None:
-        raise ValueError("select: no rows were added")
-    G, M, O = ne.G.contiguous(), ne.K, ne.O
+    G, M, O = ne.finite_G("select").contiguous(), ne.K, ne.O
     k = int(k)
     if not 1 <= k <= M:
         raise ValueError(f"select: k = {k} of a pool of {M}")
     if not float(ridge) >= 0.0 or int(check_every) < 0:
         raise ValueError("select needs ridge >= 0 and check_every >= 0")
-    bad = int((~torch.isfinite(G)).sum().item())
-    if bad:
-        raise ValueError(f"normal equations hold {bad} non-finite entries of {G.numel()} (non-finite rows in x or y?)")
     diag = torch.diagonal(G)
-    lam = float(ridge) * float(diag[:M].sum().item()) / M
+    lam = ne.ridge_abs(ridge)
     tol = default_tol(M, fit_bias) if tol is None else float(tol)
     b = 1 if fit_bias else 0
     with torch.cuda.device(G.device):

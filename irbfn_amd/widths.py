@@ -18,8 +18,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib, kmeans
-from .linear_fit import NormalEquations, _like_leaf
-from .model import _grown_ws, _inner, _ptr, _stream_ptr, to_device_f32
+from .linear_fit import NormalEquations, with_fit
+from .model import _grown_ws, _ptr, _stream_ptr, to_device_f32
 
 _KNN_WS: dict = {}
 
@@ -40,9 +40,7 @@ def knn(q, c, p: int, exclude_self: bool = False, row0: int = 0, split: int = 0)
         raise ValueError("row0 must be >= 0")
     N, D = qd.shape
     K = cd.shape[0]
-    need = lib.irbfn_knn_workspace_bytes(N, K, D, p, split)
-    if need < 0:
-        _lib.check(int(need), "irbfn_knn_workspace_bytes")
+    need = _lib.workspace_bytes("irbfn_knn_workspace_bytes", N, K, D, p, split)
     d2 = torch.empty((N, p), dtype=torch.float32, device=qd.device)
     idx = torch.empty((N, p), dtype=torch.int32, device=qd.device)
     ws = _grown_ws(_KNN_WS, qd.device.index, need, torch, qd.device)
@@ -156,21 +154,59 @@ class ScaleSearch:
         return self.scales[self.best]
 
 
+def finite_lists(t):
+    """A device tensor of errors as nested host lists, NaN and +inf both as ``inf`` (one host read)."""
+    import torch
+    return torch.nan_to_num(t, nan=float("inf"), posinf=float("inf")).tolist()
+
+
+def search_scales(net, widths: Widths, x, y, scales, batch_size: int, price, what: str) -> ScaleSearch:
+    """The search of this module's ``select_scale`` and of ``loo.select_scale``.  x [n,D], y [n,O]: the rows every scale is fitted
+    on, float32 on the device.  Per scale s: net_s, its ``init()`` tree p, ``ne = NormalEquations(net_s).add(p, x, y)`` (a wrong
+    shape of x or y raises there) and ``price(net_s, p, ne) -> (LinearFit, second error)``, the error a float64 device scalar;
+    a ``ValueError`` from ``price`` (a system ``solve`` refuses) puts the scale out with ``inf`` for both errors.  ``train_mse`` =
+    rss / (n O) of the fit, ``holdout_mse`` = the second error, which ``what`` names where no scale has a finite one.  Host
+    reads: those of ``price``, the widths once before the first scale (``log_sigs`` is a host array; the scales are applied to
+    the host copy) and one read of both paths at the end."""
+    torch = _lib.require_gpu()
+    if not (net.fixed_width and net.centers is not None):
+        raise ValueError("select_scale needs a fixed-width net: WCRBFNet(..., centers=C, fixed_width=True)")
+    scales = tuple(float(s) for s in scales)
+    if not scales:
+        raise ValueError("select_scale needs at least one scale")
+    inf = torch.full((), float("inf"), dtype=torch.float64, device=x.device)
+    tried, mse_t, mse_x = [], [], []
+    host = Widths(widths.sigma.detach().cpu(), widths.replaced)      # the one read of the widths
+    for s in scales:
+        net_s = type(net).from_config(dict(net.config(), log_sigs=host.scaled(s).log_sigs(net)), centers=net.centers)
+        p = net_s.init()
+        ne = NormalEquations(net_s).add(p, x, y, batch_size=batch_size)
+        try:
+            fit, second = price(net_s, p, ne)
+        except ValueError:             # not positive definite, or non-finite entries: this scale is out
+            fit, second = None, inf
+        tried.append((net_s, fit))
+        mse_t.append(inf if fit is None else fit.rss.sum() / (x.shape[0] * net.out_features))
+        mse_x.append(second)
+    both = finite_lists(torch.stack([torch.stack(mse_t), torch.stack(mse_x)]))
+    best = int(np.argmin(both[1]))
+    net_b, fit_b = tried[best]
+    if fit_b is None or not np.isfinite(both[1][best]):
+        raise ValueError(f"select_scale: no scale gave a positive definite system with a finite {what}")
+    return ScaleSearch(scales, both[0], both[1], best, net_b, with_fit(net_b.init(), fit_b), fit_b)
+
+
 def select_scale(net, widths: Widths, x, y, scales=(0.5, 1, 2, 4, 8), holdout_every: int = 5, ridge: float = 1e-8,
                  batch_size: int = 65536) -> ScaleSearch:
     """The multiplier of a width rule from held-out rows.  net: a fixed-width ``WCRBFNet`` with ``centers=``.  For every scale s
     the same net with ``log_sigs = widths.scaled(s).log_sigs(net)``, one ``NormalEquations`` over the rows with
     index % holdout_every != 0 and one over the rest; the first is solved, and the solution is priced on the second from its Gram
-    matrix alone (``NormalEquations.rss_of``): no second pass over the held-out rows.  Host reads: those of ``solve`` per scale,
-    the widths once before the first scale (``log_sigs`` is a host array; the scales are applied to the host copy) and one read
-    of the MSEs at the end.  A scale whose system ``solve`` refuses gets ``inf``; wrong shapes of x or y raise as in ``add``."""
+    matrix alone (``NormalEquations.rss_of``): no second pass over the held-out rows.  The search, its host reads (here those of
+    ``solve`` per scale) and its refusals are ``search_scales``'."""
     torch = _lib.require_gpu()
-    if not (net.fixed_width and net.centers is not None):
-        raise ValueError("select_scale needs a fixed-width net: WCRBFNet(..., centers=C, fixed_width=True)")
-    scales = tuple(float(s) for s in scales)
     holdout_every = int(holdout_every)
-    if not scales or holdout_every < 2:
-        raise ValueError("select_scale needs at least one scale and holdout_every >= 2")
+    if holdout_every < 2:
+        raise ValueError("select_scale needs holdout_every >= 2")
     xd = to_device_f32(x, torch)
     yd = to_device_f32(y, torch, device=xd.device)
     N = xd.shape[0]
@@ -179,32 +215,10 @@ def select_scale(net, widths: Widths, x, y, scales=(0.5, 1, 2, 4, 8), holdout_ev
     ho = torch.from_numpy(rows[rows % holdout_every == 0]).to(xd.device)
     if tr.numel() == 0 or ho.numel() == 0:
         raise ValueError(f"{N} rows leave nothing to fit on or to hold out at holdout_every={holdout_every}")
-    xt, yt, xh, yh = xd[tr], yd[tr], xd[ho], yd[ho]
-    O = net.out_features
-    inf = torch.full((), float("inf"), dtype=torch.float64, device=xd.device)
-    tried, mse_t, mse_h = [], [], []
-    host = Widths(widths.sigma.detach().cpu(), widths.replaced)      # the one read of the widths
-    for s in scales:
-        net_s = type(net).from_config(dict(net.config(), log_sigs=host.scaled(s).log_sigs(net)), centers=net.centers)
-        p = net_s.init()
-        train = NormalEquations(net_s).add(p, xt, yt, batch_size=batch_size)
-        try:
-            fit = train.solve(ridge=ridge)
-        except ValueError:             # not positive definite, or non-finite entries: this scale is out
-            tried.append((net_s, None))
-            mse_t.append(inf)
-            mse_h.append(inf)
-            continue
+    xh, yh = xd[ho], yd[ho]
+
+    def held_out(net_s, p, train):
+        fit = train.solve(ridge=ridge)               # a refused scale ends here: no pass over its held-out rows
         held = NormalEquations(net_s).add(p, xh, yh, batch_size=batch_size)
-        tried.append((net_s, fit))
-        mse_t.append(fit.rss.sum() / (tr.numel() * O))
-        mse_h.append(held.rss_of(fit).sum() / (ho.numel() * O))
-    both = torch.nan_to_num(torch.stack([torch.stack(mse_t), torch.stack(mse_h)]), nan=float("inf"), posinf=float("inf")).tolist()
-    best = int(np.argmin(both[1]))
-    net_b, fit_b = tried[best]
-    if fit_b is None or not np.isfinite(both[1][best]):
-        raise ValueError("select_scale: no scale gave a positive definite system with a finite held-out error")
-    params = net_b.init()
-    lin = _inner(params)["linear"]
-    lin["kernel"], lin["bias"] = _like_leaf(fit_b.kernel, lin["kernel"]), _like_leaf(fit_b.bias, lin["bias"])
-    return ScaleSearch(scales, both[0], both[1], best, net_b, params, fit_b)
+        return fit, held.rss_of(fit).sum() / (ho.numel() * net.out_features)
+    return search_scales(net, widths, xd[tr], yd[tr], scales, batch_size, held_out, "held-out error")

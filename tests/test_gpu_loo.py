@@ -363,3 +363,48 @@ def test_loo_of_a_two_region_gated_net(gpu):
     fac = loo.factor(linear_fit.NormalEquations(net).add(p, x, y, batch_size=97), ridge=1e-6)
     res = loo.loo(net, p, x, y, fac, batch_size=97, per_row=True)
     hold_to_statement(net, p, x, y, fac, res)
+
+
+# ------------------------------------------------------------------ the shared pass over the rows
+@functools.lru_cache(maxsize=None)
+def _tiny():
+    """K = 4, D = 3, O = 2, gaussian, one region: (net, params, 5 rows x, y, a factor with the ones column and one without)."""
+    rng = np.random.default_rng(3)
+    net = WCRBFNet.from_config(lu.synthetic_cfg(3, 4, "gaussian"))
+    p = net.init()
+    p["params"]["rbf_list"]["centers"] = rng.uniform(0.5, 3.5, size=(1, 4, 3)).astype(np.float32)
+    p["params"]["rbf_list"]["log_sigs"] = rng.uniform(0.0, 1.0, size=(1, 4)).astype(np.float32)
+    xs = rng.uniform(0.3, 3.7, size=(40, 3)).astype(np.float32)           # the rows the factors are solved on
+    ne = linear_fit.NormalEquations(net).add(p, xs, rng.normal(size=(40, 2)).astype(np.float32))
+    x, y = rng.uniform(0.3, 3.7, size=(5, 3)).astype(np.float32), rng.normal(size=(5, 2)).astype(np.float32)
+    return net, p, x, y, loo.factor(ne, ridge=1e-6), loo.factor(ne, ridge=1e-6, fit_bias=False)
+
+
+def test_the_shared_row_pass_at_its_edges(gpu):
+    """N = 0, 1, 5 in chunks of 1, 2, 5, 8 through ``NormalEquations.add`` and ``loo.leverage``: one answer however the rows are
+    cut, nothing for no rows, and no ones column for a factor without one."""
+    net, p, x, y, fac, flat = _tiny()
+    assert (fac.m, flat.m, fac.O) == (5, 4, 2)
+    h = net.hidden(p, x)
+    Z32 = np.hstack([h, np.ones((5, 1), np.float32), y])
+    for N in (0, 1, 5):
+        Gs, levs, flats = [], [], []
+        for bs in (1, 2, 5, 8):
+            ne = linear_fit.NormalEquations(net).add(p, x[:N], y[:N], batch_size=bs)
+            assert tuple(ne.G.shape) == (7, 7) and ne.G.dtype == torch.float64 and ne.G.is_cuda
+            Gs.append(ne.G)
+            levs.append(loo.leverage(net, p, x[:N], fac, batch_size=bs))
+            flats.append(loo.leverage(net, p, x[:N], flat, batch_size=bs))
+            assert tuple(levs[-1].shape) == tuple(flats[-1].shape) == (N,) and levs[-1].dtype == torch.float64
+        print(f"N = {N}: largest |G - G(batch_size=1)| over the batch sizes {max(float((G - Gs[0]).abs().max()) for G in Gs):.3e}")
+        assert all(torch.equal(G, Gs[0]) for G in Gs) and all(torch.equal(q, levs[0]) for q in levs) and all(torch.equal(q, flats[0]) for q in flats)
+        if N == 0:
+            assert not bool(Gs[0].any())                                  # no rows: G stays at zero, and an empty leverage tensor
+            continue
+        z = Z32[:N].astype(np.float64)
+        assert (np.abs(Gs[0].cpu().numpy() - z.T @ z) <= lu.gram_bound(Z32[:N])).all()
+        for f, q in ((fac, levs[0]), (flat, flats[0])):                   # flat: z = h alone, column K is never written
+            m = f.m
+            U = f.P[:, :m].cpu().numpy()                                  # (L^-1 diag(s))^T, upper triangular
+            ref = ((z[:, :m] @ np.triu(U)) ** 2).sum(1)
+            assert (np.abs(q.cpu().numpy() - ref) <= lo.leverage_bound(z[:, :m], U.T) + 1e-15 * ref).all()

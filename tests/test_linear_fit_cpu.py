@@ -186,3 +186,71 @@ def test_fit_case_is_well_conditioned():
     cfg, centers, log_sigs, x, y, h64, gsum = lu.fit_case()
     assert h64.shape == (1500, 48) and y.shape == (1500, 3)
     assert np.linalg.cond(np.hstack([h64, np.ones((1500, 1))])) < 100
+
+
+def _small_fit(K=4, O=2):
+    rng = np.random.default_rng(11)
+    W, b = torch.from_numpy(rng.normal(size=(K, O))), torch.from_numpy(rng.normal(size=O))
+    return linear_fit.LinearFit(W, b, 10, torch.zeros(O, dtype=torch.float64), 0.0)
+
+
+def _as_torch(tree):
+    return {g: {k: torch.from_numpy(np.array(v)) for k, v in grp.items()} for g, grp in tree.items()}
+
+
+@pytest.mark.parametrize("wrapped", (True, False))
+@pytest.mark.parametrize("flavour", ("numpy", "torch"))
+def test_with_fit_replaces_the_linear_leaves_and_nothing_else(flavour, wrapped):
+    from irbfn_amd.model import WCRBFNet
+    cfg = lu.synthetic_cfg(3, 4, "gaussian")
+    centers = np.random.default_rng(0).uniform(0.0, 4.0, size=(4, 3)).astype(np.float32)
+    fit = _small_fit()
+    fixed = WCRBFNet.from_config(dict(cfg, fixed_centers=True, fixed_width=True), centers=centers)
+    assert set(fixed.init()["params"]) == {"linear"}                     # the reduced tree of a fixed-centre net
+    for net in (WCRBFNet.from_config(cfg), fixed):
+        tree = net.init()["params"]
+        if flavour == "torch":
+            tree = _as_torch(tree)
+        params = {"params": tree} if wrapped else tree
+        leaves = {(g, k): (v, np.array(v.numpy() if flavour == "torch" else v)) for g, grp in tree.items() for k, v in grp.items()}
+        new = linear_fit.with_fit(params, fit)
+        assert set(new) == set(params) and ("params" in new) == wrapped
+        inner = new["params"] if wrapped else new
+        assert {g: set(v) for g, v in inner.items()} == {g: set(v) for g, v in tree.items()}          # the tree keeps its shape
+        assert new is not params and inner is not tree and inner["linear"] is not tree["linear"]
+        for (g, k), (leaf, copy) in leaves.items():                       # the input is as it was, and every other leaf is shared
+            assert tree[g][k] is leaf and np.array_equal(np.asarray(leaf), copy)
+            assert g == "linear" or inner[g][k] is leaf
+        for name, t in (("kernel", fit.kernel), ("bias", fit.bias)):
+            leaf = inner["linear"][name]
+            if flavour == "torch":
+                assert isinstance(leaf, torch.Tensor) and leaf.dtype == torch.float32 and leaf.device == tree["linear"][name].device
+                assert torch.equal(leaf, t.to(torch.float32))
+            else:
+                assert isinstance(leaf, np.ndarray) and leaf.dtype == np.float32 and np.array_equal(leaf, t.numpy().astype(np.float32))
+
+
+@pytest.mark.parametrize("wrapped", (True, False))
+@pytest.mark.parametrize("flavour", ("numpy", "torch"))
+def test_subnet_gives_the_sliced_tree_the_fit_in_the_flavour_of_the_callers_leaves(flavour, wrapped):
+    from irbfn_amd import ols
+    from irbfn_amd.model import WCRBFNet
+    rng = np.random.default_rng(5)
+    net = WCRBFNet.from_config(lu.synthetic_cfg(3, 4, "gaussian"))
+    ne = linear_fit.NormalEquations(net, G=torch.from_numpy(lu.stacked_gram(rng.uniform(size=(50, 4)), rng.normal(size=(50, 2)))))
+    res = ols.OLSResult(ne, torch.tensor([2, 0, 3], dtype=torch.int32), None, None, 1e-8, 0.0, True)
+    tree = net.init()["params"]
+    tree["linear"]["kernel"] = rng.normal(size=(4, 2)).astype(np.float32)
+    if flavour == "torch":
+        tree = _as_torch(tree)
+    net_k, new, fit = res.subnet(net, {"params": tree} if wrapped else tree, k=2)
+    assert ("params" in new) == wrapped and net_k.num_kernels == 2
+    inner = new["params"] if wrapped else new
+    want = ne.subset([2, 0], net_k).solve(ridge=1e-8)
+    assert fit.kernel.numpy().tobytes() == want.kernel.numpy().tobytes() and tuple(tree["linear"]["kernel"].shape) == (4, 2)
+    for name, t in (("kernel", want.kernel), ("bias", want.bias)):
+        leaf = inner["linear"][name]
+        assert type(leaf) is type(tree["linear"][name]) and tuple(leaf.shape) == tuple(t.shape)
+        assert np.asarray(leaf).dtype == np.float32 and np.array_equal(np.asarray(leaf), t.numpy().astype(np.float32))
+    c = inner["rbf_list"]["centers"]
+    assert type(c) is type(tree["rbf_list"]["centers"]) and np.array_equal(np.asarray(c), np.asarray(tree["rbf_list"]["centers"])[:, [2, 0]])
