@@ -24,7 +24,7 @@ constexpr int kSeedBlocksMax = 1024;
 // basis classes the hot loops are specialised on
 enum BasisClass : int { BC_GAUSS = 0, BC_IQ = 1, BC_IMQ = 2, BC_GENERIC = 3 };
 
-inline int basis_class(int basis) {
+__host__ __device__ inline int basis_class(int basis) {
   switch (basis) {
     case IRBFN_GAUSSIAN:
     case IRBFN_GAUSSIAN_WIDE:

@@ -64,7 +64,7 @@ __device__ __forceinline__ void records_body(const PackArgs& a, int vb) {
   for (int j = 0; j < a.DC; ++j) r[j] = j < a.D ? a.centers[(size_t)n * a.D + j] : 0.0f;
   const float s2 = expf(-2.0f * a.log_sigs[n]);              // 1/sigma^2, sigma = exp(log_sig) (flax_rbf.py:280)
   a.sig2[n] = s2;
-  r[a.DC] = a.bclass == BC_GAUSS ? -a.gscale * 1.4426950408889634f * s2 : s2;
+  r[a.DC] = folded_scale(a.bclass, a.gscale, s2);
   for (int o = 0; o < a.OP; ++o) r[a.DC + 1 + o] = o < a.O ? a.kernel[(size_t)k * a.O + o] : 0.0f;
   for (int j = a.DC + 1 + a.OP; j < a.S; ++j) r[j] = 0.0f;
 }
@@ -84,7 +84,7 @@ __device__ __forceinline__ void mfma_records_body(const PackArgs& a, int vb) {
   const int k = n % a.K;
   for (int j = 0; j < a.CW; ++j) r[j] = j < a.D ? a.centers[(size_t)n * a.D + j] : 0.0f;
   const float s2 = expf(-2.0f * a.log_sigs[n]);
-  r[a.D] = a.bclass == BC_GAUSS ? -a.gscale * 1.4426950408889634f * s2 : s2;
+  r[a.D] = folded_scale(a.bclass, a.gscale, s2);
   for (int o = 0; o < a.OW; ++o) r[a.CW + o] = o < a.O ? a.kernel[(size_t)k * a.O + o] : 0.0f;
 }
 
@@ -130,7 +130,7 @@ __device__ __forceinline__ void colscale_body(const PackArgs& a, int vb, float (
 }
 
 __device__ inline void gram_alpha_beta(int bclass, double s2, double gscale, double& alpha, double& beta) {
-  if (bclass == BC_GAUSS) { alpha = -gscale * 1.4426950408889634 * s2; beta = (double)kPhiExp; }     // P = 2^(alpha d2 + 14)
+  if (bclass == BC_GAUSS) { alpha = folded_scale(BC_GAUSS, gscale, s2); beta = (double)kPhiExp; }     // P = 2^(alpha d2 + 14)
   else { alpha = s2 * (double)kPhiInv; beta = (double)kPhiInv; }   // IQ: P = 1 / (2^-14 (1 + d2 s2)); IMQ: P = rsqrt(same) = 2^7 phi
 }
 
@@ -182,7 +182,7 @@ __device__ __forceinline__ void sparse_tables_body(const PackArgs& a, int vb) {
   float* dst = a.sp_ctab + (size_t)r * a.sp_RS + (size_t)k * a.sp_EW;
   for (int j = 0; j < a.sp_EW; ++j) dst[j] = (j < a.D) ? a.centers[(size_t)n * a.D + j] : 0.0f;
   const float s2 = expf(-2.0f * a.log_sigs[n]);
-  dst[a.DC] = a.bclass == BC_GAUSS ? -a.gscale * 1.4426950408889634f * s2 : s2;
+  dst[a.DC] = folded_scale(a.bclass, a.gscale, s2);
 }
 
 __global__ __launch_bounds__(kPackBlock) void pack_level0_kernel(const PackArgs a) {
@@ -217,7 +217,7 @@ __device__ __forceinline__ void f16_image_body(const PackArgs& a, int vb) {
   float sc = 0.0f;                                           // padding centre: P = 2^kPhiExp exactly, W = 0
   if (real) {
     const float s2 = expf(-2.0f * a.log_sigs[n]);            // 1/sigma^2 (flax_rbf.py:280)
-    if (a.bclass == BC_GAUSS) sc = -a.gscale * 1.4426950408889634f * s2;   // P = 2^(r2*sc + kPhiExp)
+    if (a.bclass == BC_GAUSS) sc = folded_scale(BC_GAUSS, a.gscale, s2);   // P = 2^(r2*sc + kPhiExp)
     else if (a.bclass == BC_IQ) sc = s2 * kPhiInv;                         // P = 1 / (2^-kPhiExp (1 + d2))
     else sc = s2 * kPhiInv * kPhiInv;                                      // P = rsqrt(2^-2kPhiExp (1 + d2))
   }

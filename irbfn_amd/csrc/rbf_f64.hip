@@ -9,7 +9,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "common.h"
+#include "rbf_basis.h"
 
 namespace irbfn {
 
@@ -21,55 +21,41 @@ struct F64Card {                                 // device copy of irbfn_f64_car
   const int* dim_ranges;
 };
 
-__device__ __forceinline__ double basis_f64(double d2, int basis) {      // flax_rbf.py:34-111 as functions of d^2 = (d)^2
-  const double d = sqrt(d2);
+// The formulas are rbf_basis.h's with T = double; the basis classes the float32 kernels are specialised on are run-time cases here.
+__device__ __forceinline__ double basis_f64(double d2, int basis) { return basis_value<double, true>(d2, basis); }
+
+// d phi / d(d^2) of a fast-class basis from phi (a in double: gauss_scale's 0.1f is not 0.1)
+__device__ __forceinline__ double slope_fast_f64(double phi, int basis) {
   switch (basis) {
-    case IRBFN_GAUSSIAN: return exp(-1.0 * d2);
-    case IRBFN_GAUSSIAN_WIDE: return exp(-0.1 * d2);
-    case IRBFN_GAUSSIAN_WIDER: return exp(-0.01 * d2);
-    case IRBFN_INVERSE_QUADRATIC: return 1.0 / (1.0 + d2);
-    case IRBFN_LINEAR: return d;
-    case IRBFN_QUADRATIC: return d2;
-    case IRBFN_MULTIQUADRIC: return sqrt(1.0 + d2);
-    case IRBFN_INVERSE_MULTIQUADRIC: return 1.0 / sqrt(1.0 + d2);
-    case IRBFN_SPLINE: return d2 * log(d + 1.0);
-    case IRBFN_POISSON_ONE: return (d - 1.0) * exp(-d);
-    case IRBFN_POISSON_TWO: return ((d - 2.0) / 2.0) * d * exp(-d);
-    case IRBFN_MATERN32: return (1.0 + 1.7320508075688772 * d) * exp(-1.7320508075688772 * d);
-    case IRBFN_MATERN52: return (1.0 + 2.23606797749979 * d + (5.0 / 3.0) * d2) * exp(-2.23606797749979 * d);
-    default: return 0.0;
+    case IRBFN_GAUSSIAN: return basis_slope_fast<BC_GAUSS>(phi, 1.0);
+    case IRBFN_GAUSSIAN_WIDE: return basis_slope_fast<BC_GAUSS>(phi, 0.1);
+    case IRBFN_GAUSSIAN_WIDER: return basis_slope_fast<BC_GAUSS>(phi, 0.01);
+    case IRBFN_INVERSE_QUADRATIC: return basis_slope_fast<BC_IQ>(phi, 0.0);
+    default: return basis_slope_fast<BC_IMQ>(phi, 0.0);
   }
 }
 
-// d phi / d(d^2) and the log_sig factor (units of dphi_dd2 * r2; the caller multiplies by -2 s2): as rbf_vjp.hip
+// parameter-VJP slope and the log_sig factor (units of slope * r2; the caller multiplies by -2 s2)
 __device__ __forceinline__ double dphi_dd2_f64(double phi, double d2, double r2, double s2, int basis, double& ls_term) {
   double t;
   switch (basis) {
-    case IRBFN_GAUSSIAN: t = -phi; break;
-    case IRBFN_GAUSSIAN_WIDE: t = -0.1 * phi; break;
-    case IRBFN_GAUSSIAN_WIDER: t = -0.01 * phi; break;
-    case IRBFN_INVERSE_QUADRATIC: t = -(phi * phi); break;
-    case IRBFN_INVERSE_MULTIQUADRIC: t = -0.5 * phi * phi * phi; break;
-    case IRBFN_MULTIQUADRIC: t = 0.5 / phi; break;
-    case IRBFN_QUADRATIC: t = 1.0; break;
-    default: {
-      const double d = sqrt(d2);
-      double dp;
-      switch (basis) {
-        case IRBFN_LINEAR: dp = 1.0; break;
-        case IRBFN_SPLINE: dp = 2.0 * d * log(d + 1.0) + d2 / (d + 1.0); break;
-        case IRBFN_POISSON_ONE: dp = (2.0 - d) * exp(-d); break;
-        case IRBFN_POISSON_TWO: dp = (2.0 * d - 1.0 - 0.5 * d2) * exp(-d); break;
-        case IRBFN_MATERN32: dp = -3.0 * d * exp(-1.7320508075688772 * d); break;
-        case IRBFN_MATERN52: dp = -(5.0 / 3.0) * d * (1.0 + 2.23606797749979 * d) * exp(-2.23606797749979 * d); break;
-        default: dp = 0.0; break;
-      }
-      ls_term = 0.5 * dp * d / s2;               // width path does not go through the sqrt: finite at d = 0
-      return dp * (0.5 / d);                     // centre path: NaN on a centre, like jax.grad of (sum sq) ** 0.5
-    }
+    case IRBFN_GAUSSIAN:
+    case IRBFN_GAUSSIAN_WIDE:
+    case IRBFN_GAUSSIAN_WIDER:
+    case IRBFN_INVERSE_QUADRATIC:
+    case IRBFN_INVERSE_MULTIQUADRIC: t = slope_fast_f64(phi, basis); break;
+    default: return basis_slope_generic(phi, d2, r2, s2, basis, ls_term);
   }
   ls_term = t * r2;
   return t;
+}
+
+// phi and the x-VJP slope
+__device__ __forceinline__ double basis_value_slope_x_f64(double d2, int basis, double& fprime) {
+  if (basis_class(basis) == BC_GENERIC) return basis_value_slope_finite(d2, basis, fprime);
+  const double phi = basis_f64(d2, basis);
+  fprime = slope_fast_f64(phi, basis);
+  return phi;
 }
 
 __device__ __forceinline__ double gate_factor_f64(double xv, double lo, double hi, double delta) {   // model.py:83-85
@@ -144,28 +130,6 @@ __global__ __launch_bounds__(64) void f64_forward_kernel(const F64Card c, const 
   }
 }
 
-// d phi / d(d^2) for the x-VJP, in the forms that stay finite where the limit is; linear / poisson_one / poisson_two diverge at
-// d = 0 and return 0 there (the convention of the float32 kernels, rbf_vjpx.h)
-__device__ __forceinline__ double dphi_dd2_x_f64(double phi, double d2, int basis) {
-  const double d = sqrt(d2);
-  switch (basis) {
-    case IRBFN_GAUSSIAN: return -phi;
-    case IRBFN_GAUSSIAN_WIDE: return -0.1 * phi;
-    case IRBFN_GAUSSIAN_WIDER: return -0.01 * phi;
-    case IRBFN_INVERSE_QUADRATIC: return -(phi * phi);
-    case IRBFN_INVERSE_MULTIQUADRIC: return -0.5 * phi * phi * phi;
-    case IRBFN_MULTIQUADRIC: return 0.5 / phi;
-    case IRBFN_QUADRATIC: return 1.0;
-    case IRBFN_LINEAR: return d > 0.0 ? 0.5 / d : (d == 0.0 ? 0.0 : d);
-    case IRBFN_SPLINE: return log(d + 1.0) + 0.5 * d / (d + 1.0);
-    case IRBFN_POISSON_ONE: return d > 0.0 ? (2.0 - d) * exp(-d) * (0.5 / d) : (d == 0.0 ? 0.0 : d);
-    case IRBFN_POISSON_TWO: return d > 0.0 ? (2.0 * d - 1.0 - 0.5 * d2) * exp(-d) * (0.5 / d) : (d == 0.0 ? 0.0 : d);
-    case IRBFN_MATERN32: return -1.5 * exp(-1.7320508075688772 * d);
-    case IRBFN_MATERN52: return -(5.0 / 6.0) * (1.0 + 2.23606797749979 * d) * exp(-2.23606797749979 * d);
-    default: return 0.0;
-  }
-}
-
 // x-VJP (rbf_vjpx.h for the formula): one lane per query, centres / widths / weights wave-uniform; the gate and its logarithmic
 // derivative are evaluated per region in the tanh form of the reference (model.py:83-85)
 __global__ __launch_bounds__(64) void vjpx_f64(const F64Card c, const double* __restrict__ centers, const double* __restrict__ log_sigs,
@@ -214,7 +178,8 @@ __global__ __launch_bounds__(64) void vjpx_f64(const F64Card c, const double* __
       }
       const double s2 = exp(-2.0 * log_sigs[n]);
       const double d2 = r2 * s2;
-      const double phi = basis_f64(d2, c.basis);
+      double fp;
+      const double phi = basis_value_slope_x_f64(d2, c.basis, fp);
       const double* wr = kernel + (size_t)k * c.O;
       double hb = 0.0;
       if (greg) {
@@ -225,7 +190,7 @@ __global__ __launch_bounds__(64) void vjpx_f64(const F64Card c, const double* __
         for (int o = 0; o < c.O; ++o) hb = fma(grow[o], wr[o], hb);
       }
       q = fma(hb, phi, q);
-      const double s = 2.0 * hb * dphi_dd2_x_f64(phi, d2, c.basis) * s2;
+      const double s = 2.0 * hb * fp * s2;
 #pragma unroll
       for (int j = 0; j < kMaxD; ++j) racc[j] = fma(s, df[j], racc[j]);
     }

@@ -15,7 +15,7 @@
 // are applied and the tile is written with coalesced stores.
 #pragma once
 
-#include "common.h"
+#include "rbf_basis.h"
 
 namespace irbfn {
 
@@ -45,34 +45,20 @@ __device__ __forceinline__ float fast_exp2(float v) { return __builtin_amdgcn_ex
 __device__ __forceinline__ float fast_rcp(float v) { return __builtin_amdgcn_rcpf(v); }
 __device__ __forceinline__ float fast_rsq(float v) { return __builtin_amdgcn_rsqf(v); }
 
-// phi from the squared distance r2 and the record's folded scale sc.
-//   BC_GAUSS : sc = -a*log2(e)*exp(-2 log_sig)  -> phi = 2^(r2*sc) = exp(-a d^2)   (flax_rbf.py:35-47)
-//   others   : sc = exp(-2 log_sig)             -> d^2 = r2*sc
+// The record's folded width scale sc from 1/sigma^2 = exp(-2 log_sig) (pack_all.hip), and phi from the squared distance r2 and sc:
+//   BC_GAUSS : sc = -a*log2(e)/sigma^2  -> phi = 2^(r2*sc) = exp(-a d^2)   (flax_rbf.py:35-47)
+//   others   : sc = 1/sigma^2           -> d^2 = r2*sc
+template <class T>
+__device__ __forceinline__ T folded_scale(int bclass, T gscale, T s2) {
+  return bclass == BC_GAUSS ? -gscale * kLog2e<T> * s2 : s2;
+}
 template <int BC>
 __device__ __forceinline__ float basis_from_r2(float r2, float sc, int basis) {
   const float t = r2 * sc;
-  if constexpr (BC == BC_GAUSS) {
-    return fast_exp2(t);
-  } else if constexpr (BC == BC_IQ) {
-    return fast_rcp(1.0f + t);                 // flax_rbf.py:50-52
-  } else if constexpr (BC == BC_IMQ) {
-    return fast_rsq(1.0f + t);                 // flax_rbf.py:73-75
-  } else {
-    const float d2 = t;
-    const float d = sqrtf(d2);                 // flax_rbf.py:280
-    switch (basis) {
-      case IRBFN_LINEAR: return d;                                         // :55-57
-      case IRBFN_QUADRATIC: return d2;                                     // :61-63
-      case IRBFN_MULTIQUADRIC: return sqrtf(1.0f + d2);                    // :67-69
-      case IRBFN_SPLINE: return d2 * logf(d + 1.0f);                       // :79-81
-      case IRBFN_POISSON_ONE: return (d - 1.0f) * expf(-d);                // :85-87
-      case IRBFN_POISSON_TWO: return ((d - 2.0f) / 2.0f) * d * expf(-d);   // :91-97
-      case IRBFN_MATERN32: return (1.0f + 1.7320508075688772f * d) * expf(-1.7320508075688772f * d);
-      case IRBFN_MATERN52:
-        return (1.0f + 2.23606797749979f * d + (5.0f / 3.0f) * d2) * expf(-2.23606797749979f * d);
-      default: return 0.0f;
-    }
-  }
+  if constexpr (BC == BC_GAUSS) return fast_exp2(t);
+  else if constexpr (BC == BC_IQ) return fast_rcp(1.0f + t);                 // flax_rbf.py:50-52
+  else if constexpr (BC == BC_IMQ) return fast_rsq(1.0f + t);                // flax_rbf.py:73-75
+  else return basis_value(t, basis);
 }
 
 // ---- batched transcendentals ----------------------------------------------------------------------------
@@ -131,7 +117,7 @@ __device__ __forceinline__ void trans_block(float (&v)[NT]) {
 // Saturates to exactly 1 by itself (1 + 2^-26 rounds to 1) and propagates NaN like the tanh form.
 constexpr float kGateSatZ = 9.0109133f;                              // 13 ln 2
 __device__ __forceinline__ float half_tanh_plus_one(float z) {
-  const float v = fast_rcp(1.0f + fast_exp2(-2.8853900817779268f * z));      // 2*log2(e)
+  const float v = fast_rcp(1.0f + fast_exp2(-2.0f * kLog2e<float> * z));
   return z < -kGateSatZ ? 0.0f : v;                                    // NaN: comparison false -> v = NaN
 }
 __device__ __forceinline__ float gate_factor(float xv, float lo, float hi, float delta) {

@@ -1088,7 +1088,7 @@ __global__ __launch_bounds__(kWave) void rbf_vjp_sparse(const SpVjpArgs a) {
           hb = __builtin_fmaf(gq[p][o], rp[D + 1 + o], hb);
           vals[D + 1 + o] = __builtin_fmaf(gphi, gq[p][o], vals[D + 1 + o]);
         }
-        const float t = hb * gam[p] * dphi_dd2_h<BC>(phi, a.gscale);
+        const float t = hb * gam[p] * basis_slope_fast<BC>(phi, a.gscale);
         vals[D] = __builtin_fmaf(t, r2, vals[D]);
 #pragma unroll
         for (int j = 0; j < D; ++j) vals[j] = __builtin_fmaf(t, diff[j], vals[j]);

@@ -36,42 +36,6 @@ struct VjpArgs {
   int gen;
 };
 
-// d phi / d(d2) from phi and d2.  The fast classes need phi only; the generic class covers the bases that depend on
-// d = sqrt(d2) itself (flax_rbf.py:55-111): d phi / d(d2) = phi'(d) * (0.5 / d), evaluated literally so that a query ON a
-// centre (d = 0) gives what jax.grad gives there -- sqrt has no derivative at 0: inf, and inf * 0 = NaN.
-// `ls_term` is the factor of the log_sig sum, in the units of `dphi_dd2 * r2` (the caller multiplies the finished sums by
-// -2 / sigma^2): for the d-dependent bases it is phi'(d) * d / (2 s2), i.e. d log_sig = phi'(d) * (-d) -- the width does
-// NOT go through the sqrt in the reference (flax_rbf.py:280: sqrt(sum sq) / exp(log_sig)), so its gradient is finite (0)
-// for a query on a centre, where only the centre path is NaN.
-template <int BC>
-__device__ __forceinline__ float dphi_dd2(float phi, float d2, float r2, float s2, float gscale, int basis, float& ls_term) {
-  float t;
-  if constexpr (BC == BC_GAUSS) t = -gscale * phi;             // exp(-a d2)
-  else if constexpr (BC == BC_IQ) t = -(phi * phi);            // 1/(1+d2)
-  else if constexpr (BC == BC_IMQ) t = -0.5f * phi * phi * phi;      // (1+d2)^-1/2
-  else {
-    if (basis == IRBFN_MULTIQUADRIC) { t = 0.5f / phi; ls_term = t * r2; return t; }   // sqrt(1+d2)
-    if (basis == IRBFN_QUADRATIC) { ls_term = r2; return 1.0f; }                          // d2
-    const float d = sqrtf(d2);
-    float dp;                                                  // phi'(d)
-    switch (basis) {
-      case IRBFN_LINEAR: dp = 1.0f; break;                                                    // d
-      case IRBFN_SPLINE: dp = 2.0f * d * logf(d + 1.0f) + d2 / (d + 1.0f); break;             // d^2 log(d + 1)
-      case IRBFN_POISSON_ONE: dp = (2.0f - d) * expf(-d); break;                              // (d - 1) exp(-d)
-      case IRBFN_POISSON_TWO: dp = (2.0f * d - 1.0f - 0.5f * d2) * expf(-d); break;           // ((d - 2) / 2) d exp(-d)
-      case IRBFN_MATERN32: dp = -3.0f * d * expf(-1.7320508075688772f * d); break;            // (1 + sqrt3 d) exp(-sqrt3 d)
-      case IRBFN_MATERN52:                                                                    // (1 + sqrt5 d + 5/3 d^2) exp(-sqrt5 d)
-        dp = -(5.0f / 3.0f) * d * (1.0f + 2.23606797749979f * d) * expf(-2.23606797749979f * d);
-        break;
-      default: dp = 0.0f; break;
-    }
-    ls_term = 0.5f * dp * d / s2;
-    return dp * (0.5f / d);
-  }
-  ls_term = t * r2;
-  return t;
-}
-
 // Pre-pass: one packed, zero-padded record per query so that the hot loop reads ONE contiguous scalar
 // stream (s_load_dwordx16 + x4) without per-element bounds branches:
 //   qrec[b] = { x[b, 0..D) (padded to DC), gamma[b] (R == 1; model.py:42-95), g[b, 0..O) (padded to OP) }.
@@ -204,7 +168,7 @@ __global__ __launch_bounds__(256) void rbf_vjp_kernel(const VjpArgs a) {
     // d log_sig += t * (-2 d2) = (-2 s2) * t * r2,   d centre += (-2 t s2) * diff = (-2 s2) * t * diff
     float lsf;
     const float hg = hbar * gam;
-    const float t = hg * dphi_dd2<BC>(phi, d2, r2, s2, a.gscale, a.basis, lsf);
+    const float t = hg * basis_slope<BC>(phi, d2, r2, s2, a.gscale, a.basis, lsf);
     if constexpr (BC == BC_GAUSS || BC == BC_IQ || BC == BC_IMQ) gls = __builtin_fmaf(t, r2, gls);
     else gls = __builtin_fmaf(hg, lsf, gls);
 #pragma unroll

@@ -6,14 +6,6 @@ namespace irbfn {
 
 constexpr int vjph_rfq(int DC) { return DC <= 3 ? 4 : (DC <= 7 ? 8 : 12); }   // floats per packed query row (x, gamma)
 
-// d phi / d(d2) from phi for the fast basis classes
-template <int BC>
-__device__ __forceinline__ float dphi_dd2_h(float phi, float gscale) {
-  if constexpr (BC == BC_GAUSS) return -gscale * phi;
-  else if constexpr (BC == BC_IQ) return -(phi * phi);
-  else return -0.5f * phi * phi * phi;
-}
-
 bool vjph_eligible(const irbfn_net* net);
 size_t vjph_block_bytes(const irbfn_net* net);
 size_t vjph_lds_bytes(const irbfn_net* net);

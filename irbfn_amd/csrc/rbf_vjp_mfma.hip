@@ -26,13 +26,6 @@ namespace irbfn {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <int BC>
-__device__ __forceinline__ float dphi_dd2_fast(float phi, float gscale) {     // rbf_vjp.hip dphi_dd2, the fast classes
-  if constexpr (BC == BC_GAUSS) return -gscale * phi;                          // exp(-a d2)
-  else if constexpr (BC == BC_IQ) return -(phi * phi);                         // 1/(1+d2)
-  else return -0.5f * phi * phi * phi;                                         // (1+d2)^-1/2
-}
-
 __host__ __device__ constexpr int vjpm_xw(int DC) { return (DC + 1 + 3) & ~3; }   // x[DC], gamma, padding
 
 static int vjpm_ow(int O) { return O <= 32 ? 32 : (O <= 64 ? 64 : 128); }
@@ -202,7 +195,7 @@ __global__ __launch_bounds__(256) void rbf_vjp_mfma(const VjpmArgs a) {
         }
         const float phi = basis_from_r2<BC>(r2, scv[c], a.basis);
         // K2's factoring: the centre's -2 / sigma^2 multiplies the finished sums
-        const float tt = hb[c][r] * gam * dphi_dd2_fast<BC>(phi, a.gscale);
+        const float tt = hb[c][r] * gam * basis_slope_fast<BC>(phi, a.gscale);
         gls[c] = __builtin_fmaf(tt, r2, gls[c]);
 #pragma unroll
         for (int d = 0; d < D; ++d) gc[c][d] = __builtin_fmaf(tt, diff[d], gc[c][d]);

@@ -27,9 +27,7 @@
 // With caller-provided region weights (ClusterWCRBFNet) the kernel returns the RBF term and, on request, dgamma[b,r] = q[b,r];
 // the waves then split whole regions, so that one wave owns all of q[b,r].
 //
-// A query exactly ON a centre: the pair's RBF term is 0.  For the bases in d^2 and for spline / matern32 / matern52 that is
-// the limit (f' is finite there); for linear, poisson_one and poisson_two, whose f'(u) = phi'(d) / (2 d) diverges at d = 0,
-// it is a convention -- jax.grad gives NaN there.
+// A query exactly ON a centre: the pair's RBF term is 0, the limit or a convention (basis_value_slope_finite, rbf_basis.h).
 #pragma once
 
 #include "rbf_forward.h"
@@ -64,7 +62,7 @@ struct VjpxPlan {
 //   BC_GAUSS: f' = -a phi, sc = -a log2(e) sigma^-2   ->  2 ln 2 * phi * sc
 //   BC_IQ:    f' = -phi^2                              -> -2 * phi^2 * sc
 //   BC_IMQ:   f' = -phi^3 / 2                          -> -1 * phi^3 * sc
-//   generic:  f' below                                 ->  2 * f' * sc
+//   generic:  basis_value_slope_finite (rbf_basis.h)   ->  2 * f' * sc
 template <int BC>
 __host__ __device__ constexpr float vjpx_scale() {
   return BC == BC_GAUSS ? 1.3862943611198906f : (BC == BC_IQ ? -2.0f : (BC == BC_IMQ ? -1.0f : 2.0f));
@@ -78,53 +76,12 @@ __device__ __forceinline__ float vjpx_fast_factor(float phi) {
   else return phi * phi * phi;
 }
 
-// generic class: phi and f'(u) = d phi / d(d^2) from u = d^2, in the forms that stay finite where the limit is
-// (flax_rbf.py:55-111); linear / poisson_one / poisson_two diverge at d = 0 and return 0 there (header comment)
-__device__ __forceinline__ float vjpx_generic(float u, int basis, float& fprime) {
-  const float d = sqrtf(u);
-  switch (basis) {
-    case IRBFN_LINEAR: fprime = d > 0.0f ? 0.5f / d : (d == 0.0f ? 0.0f : d); return d;
-    case IRBFN_QUADRATIC: fprime = 1.0f; return u;
-    case IRBFN_MULTIQUADRIC: {
-      const float p = sqrtf(1.0f + u);
-      fprime = 0.5f / p;
-      return p;
-    }
-    case IRBFN_SPLINE: {
-      const float l = logf(d + 1.0f);
-      fprime = l + 0.5f * d / (d + 1.0f);
-      return u * l;
-    }
-    case IRBFN_POISSON_ONE: {
-      const float e = expf(-d);
-      fprime = d > 0.0f ? (2.0f - d) * e * (0.5f / d) : (d == 0.0f ? 0.0f : d);
-      return (d - 1.0f) * e;
-    }
-    case IRBFN_POISSON_TWO: {
-      const float e = expf(-d);
-      fprime = d > 0.0f ? (2.0f * d - 1.0f - 0.5f * u) * e * (0.5f / d) : (d == 0.0f ? 0.0f : d);
-      return ((d - 2.0f) / 2.0f) * d * e;
-    }
-    case IRBFN_MATERN32: {
-      const float e = expf(-1.7320508075688772f * d);
-      fprime = -1.5f * e;
-      return (1.0f + 1.7320508075688772f * d) * e;
-    }
-    case IRBFN_MATERN52: {
-      const float e = expf(-2.23606797749979f * d);
-      fprime = -(5.0f / 6.0f) * (1.0f + 2.23606797749979f * d) * e;
-      return (1.0f + 2.23606797749979f * d + (5.0f / 3.0f) * u) * e;
-    }
-    default: fprime = 0.0f; return 0.0f;
-  }
-}
-
 // one factor pair of the gate and its logarithmic derivative: *fac = a b with float64's zero (header comment),
 // returns d log(a b) / d x = 2 delta ((1 - a) - (1 - b)).  NaN propagates (every comparison is false).
 constexpr float kGateSatZ64 = 18.368f;           // 53/2 ln 2
 __device__ __forceinline__ float gate_factor_dlog(float xv, float lo, float hi, float delta, float* fac) {
   const float z1 = delta * (xv - lo), z2 = delta * (hi - xv);
-  const float e1 = fast_exp2(-2.8853900817779268f * z1), e2 = fast_exp2(-2.8853900817779268f * z2);
+  const float e1 = fast_exp2(-2.0f * kLog2e<float> * z1), e2 = fast_exp2(-2.0f * kLog2e<float> * z2);
   const float a = fast_rcp(1.0f + e1), b = fast_rcp(1.0f + e2);
   const float fa = z1 < -kGateSatZ64 ? 0.0f : a, fb = z2 < -kGateSatZ64 ? 0.0f : b;
   const float na = z1 < 0.0f ? 1.0f - a : e1 * a, nb = z2 < 0.0f ? 1.0f - b : e2 * b;

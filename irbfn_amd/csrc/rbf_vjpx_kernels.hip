@@ -41,7 +41,7 @@ __device__ __forceinline__ void vjpx_pair(const float* __restrict__ rp_, const f
   const float hb = vjpx_hbar<D, OP>(rp, gq);
   float phi, fac;
   if constexpr (BC == BC_GENERIC) {
-    phi = vjpx_generic(r2 * sc, basis, fac);
+    phi = basis_value_slope_finite(r2 * sc, basis, fac);
   } else {
     phi = basis_from_r2<BC>(r2, sc, basis);
     fac = vjpx_fast_factor<BC>(phi);

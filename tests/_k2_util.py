@@ -60,23 +60,25 @@ def k2_plan(N, B, D, O, basis, gated):
 
 
 # ------------------------------------------------------------------------------------------------ the formulas
-def basis_and_slope(name, d2):
-    """(phi, d phi / d(d2)) at d2 = |x - c|^2 / sigma^2, in d2's dtype.  The bases that depend on d = sqrt(d2) itself go through
-    phi'(d) * (0.5 / d), as the kernel's generic class does."""
+def basis_terms(name, d2):
+    """(phi, d phi / d(d2), None) at d2 = |x - c|^2 / sigma^2, in d2's dtype, for the bases in d2 alone.  The bases that depend on d = sqrt(d2) itself go through
+    phi'(d) * (0.5 / d), as the kernel's generic class does, and return phi'(d) * d as the third value: the width reaches d without
+    the sqrt (d = sqrt(sum sq) / exp(log_sig), flax_rbf.py:280), so d phi / d log_sig = -phi'(d) d is finite for a query ON a centre,
+    where the slope in d2 is not."""
     if name in GAUSS_A:
         phi = np.exp(-GAUSS_A[name] * d2)
-        return phi, -GAUSS_A[name] * phi
+        return phi, -GAUSS_A[name] * phi, None
     if name == "inverse_quadratic":
         phi = 1 / (1 + d2)
-        return phi, -phi * phi
+        return phi, -phi * phi, None
     if name == "inverse_multiquadric":
         phi = (1 + d2) ** -0.5
-        return phi, -0.5 * phi ** 3
+        return phi, -0.5 * phi ** 3, None
     if name == "multiquadric":
         phi = (1 + d2) ** 0.5
-        return phi, 0.5 / phi
+        return phi, 0.5 / phi, None
     if name == "quadratic":
-        return d2, np.ones_like(d2)
+        return d2, np.ones_like(d2), None
     d = np.sqrt(d2)
     if name == "linear":
         phi, dp = d, np.ones_like(d)
@@ -94,7 +96,11 @@ def basis_and_slope(name, d2):
         phi, dp = (1 + s5 * d + (5 / 3) * d2) * np.exp(-s5 * d), -(5 / 3) * d * (1 + s5 * d) * np.exp(-s5 * d)
     else:
         raise ValueError(name)
-    return phi, dp * (0.5 / d)
+    return phi, dp * (0.5 / d), dp * d
+
+
+def basis_and_slope(name, d2):
+    return basis_terms(name, d2)[:2]
 
 
 def tanh_gate(cfg, x, dtype=np.float64):
@@ -141,10 +147,11 @@ def _terms(basis, params, x, g, gamma, dtype):
     r2 = (diff * diff).sum(-1)
     s2 = np.exp(-2 * ls)[None]
     d2 = r2 * s2
-    phi, dphi = basis_and_slope(basis, d2)
+    phi, dphi, dpd = basis_terms(basis, d2)
     hbar = g @ W.T
-    t = hbar[:, None, :] * gamma[:, :, None] * dphi
-    return (t * s2)[..., None] * -2 * diff, t * (-2 * d2), gamma[:, :, None] * phi, g
+    G = hbar[:, None, :] * gamma[:, :, None]
+    t = G * dphi
+    return (t * s2)[..., None] * -2 * diff, t * (-2 * d2) if dpd is None else -(G * dpd), gamma[:, :, None] * phi, g
 
 
 def vjp_reference(basis, params, x, g, gamma):
@@ -228,7 +235,8 @@ class Case:
         self.g = np.ascontiguousarray(rng.normal(size=(nb, O))[:self.B].astype(np.float32))
         if spec.get("on_centres"):           # three queries that ARE centres
             cc = self.params["params"]["rbf_list"]["centers"]
-            self.x[5], self.x[20], self.x[self.B - 1] = cc[0, 3], cc[0, 17], cc[0, K - 1]
+            k0, k1 = (0, 1) if K == 3 else (3, 17)
+            self.x[5], self.x[20], self.x[self.B - 1] = cc[0, k0], cc[0, k1], cc[0, K - 1]
         poison = spec.get("poison")
         if poison == "nan_g":
             self.g[17, 1] = np.nan
@@ -313,7 +321,10 @@ BIAS = [_one(f"bias_b{B}", 3, 5, 10, "gaussian_wide", B, net="bias", draw=16385)
 REUSE = [_one("reuse_b65", 4, 10, 150, "gaussian", 65, net="reuse", draw=4096)]
 NONFINITE = [_one(f"nonfinite_{p}", 5, 3, 70, "gaussian_wide", 130, ns=2, net="nonfinite", poison=p) for p in ("nan_g", "nan_x", "inf_g")]
 ON_CENTRES = [_one(f"on_centres_{b}", 3, 5, 40, b, 64, ns=1, on_centres=True) for b in ("gaussian", "inverse_quadratic", "inverse_multiquadric")]
-TABLE = SHAPES + WIDE + REGIONS + CLUSTER + BATCH + BIAS + REUSE + NONFINITE + ON_CENTRES
+# the bases in d itself, every centre under a query: d centers is NaN (sqrt has no derivative at 0), d log_sigs finite
+D_BASES = ("linear", "spline", "poisson_one", "poisson_two", "matern32", "matern52")
+ON_CENTRES_D = [_one(f"on_centres_{b}", 3, 2, 3, b, 65, ns=1, on_centres=True) for b in D_BASES]
+TABLE = SHAPES + WIDE + REGIONS + CLUSTER + BATCH + BIAS + REUSE + NONFINITE + ON_CENTRES + ON_CENTRES_D
 
 
 # ------------------------------------------------------------------------------------------------ the bounds

@@ -65,6 +65,32 @@ def test_float64_forward_and_vjp_all_bases(gpu, basis):
             assert _rel(got[grp][name], r) <= 1e-11, (basis, B, name, _rel(got[grp][name], r))
 
 
+@pytest.mark.parametrize("basis", ["linear", "spline", "poisson_one", "poisson_two", "matern32", "matern52"])
+def test_float64_vjp_with_queries_on_centres(gpu, basis):
+    """The bases that depend on d = sqrt(d2) itself, three of 65 queries ON the three centres: NaN exactly where torch.autograd of
+    the restatement has it (d centers: sqrt has no derivative at 0; d log_sigs stays finite, the width does not go through the
+    sqrt), the finite elements to the bound of the other tests."""
+    import torch
+    cfg = dict(configs.model_card(1), basis_func=basis, num_kernels=3, out_features=2)
+    rng = np.random.default_rng(11)
+    P = {"params": {"rbf_list": {"centers": rng.uniform([1, -6, -1.3], [30, 6, 1.3], size=(1, 3, 3)), "log_sigs": rng.uniform(0, 1.5, size=(1, 3))},
+                    "linear": {"kernel": rng.normal(size=(3, 2)), "bias": rng.normal(size=(2,)) * 0.1}}}
+    x = rng.uniform([1, -6, -1.3], [30, 6, 1.3], size=(65, 3))
+    x[[5, 20, 64]] = P["params"]["rbf_list"]["centers"][0]
+    g = rng.normal(size=(65, 2))
+    got = WCRBFNet.from_config(cfg, use_float64=True).vjp(P, x, g)["params"]
+    tp = orc.torch_params(P, torch.float64, requires_grad=True)
+    (orc.wcrbfnet_apply(cfg, tp, torch.tensor(x)) * torch.tensor(g)).sum().backward()
+    ref = {(grp, name): tp["params"][grp][name].grad.numpy() for grp, name in LEAVES}
+    if not (np.isnan(ref["rbf_list", "centers"]).all() and np.isfinite(ref["rbf_list", "log_sigs"]).all()):
+        pytest.fail("test inputs, not the code under test: the reference's NaN are not where the case wants them")
+    for (grp, name), r in ref.items():
+        fin = np.isfinite(r)
+        assert np.array_equal(np.isnan(got[grp][name]), np.isnan(r)) and np.array_equal(np.isinf(got[grp][name]), np.isinf(r)), (basis, name)
+        if fin.any():
+            assert _rel(got[grp][name][fin], r[fin]) <= 1e-11, (basis, name, _rel(got[grp][name][fin], r[fin]))
+
+
 def test_float64_vjp_on_the_float64_checkpoint_and_the_float32_path_says_so(gpu):
     """dnmpc_128regions was trained with --use_float64 (float64 centers / log_sigs in the checkpoint): the float64 mode agrees
     with torch.autograd of the restatement to 1e-11; handing the same leaves to the float32 path warns once."""

@@ -175,3 +175,16 @@ def test_queries_on_centres(gpu, tag):
     if not all((case.x[b] == cc[0, k]).all() for b, k in ((5, 3), (20, 17), (case.B - 1, case.K - 1))):
         pytest.fail("test inputs, not the code under test: the three queries are not centres")
     assert all(np.isfinite(got[leaf]).all() for leaf in k2.LEAVES)
+
+
+@pytest.mark.parametrize("tag", [s["tag"] for s in k2.ON_CENTRES_D])
+def test_queries_on_centres_of_a_basis_in_d(gpu, tag):
+    """The bases that depend on d = sqrt(d2) itself, three of 65 queries ON the three centres: d centers is NaN as jax.grad's (sqrt
+    has no derivative at 0), d log_sigs finite (the width does not go through the sqrt); check() holds the non-finite elements to
+    the reference's and the finite ones to the bounds."""
+    case, got, ref = run_case(gpu, tag)
+    cc = case.params["params"]["rbf_list"]["centers"]
+    if not (all((case.x[b] == cc[0, k]).all() for b, k in ((5, 0), (20, 1), (64, 2))) and np.isnan(ref["centers"][0]).all()
+            and np.isfinite(ref["log_sigs"][0]).all()):
+        pytest.fail("test inputs, not the code under test: the three queries are not centres, or the reference's NaN are elsewhere")
+    assert np.isnan(got["centers"]).all() and np.isfinite(got["log_sigs"]).all()

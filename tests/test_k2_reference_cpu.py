@@ -50,6 +50,20 @@ def test_reference_agrees_with_the_oracle_and_autograd(tag):
             assert (np.abs(grad - other[leaf]) <= 1e-11 * S).all(), (tag, leaf, name, worst)
 
 
+@pytest.mark.parametrize("tag", [s["tag"] for s in k2.ON_CENTRES_D])
+def test_reference_has_autograds_non_finite_elements_on_centres(tag):
+    """A basis in d itself with a query on every centre: NaN in d centers, a finite d log_sigs (the width does not go through the
+    sqrt) -- the reference element for element where torch.autograd of the oracle's forward has them, the finite ones to 1e-11 S."""
+    case = k2.Case(BY_TAG[tag])
+    ref, auto = case.reference(), _autograd(case)
+    assert np.isnan(auto["centers"]).all() and np.isfinite(auto["log_sigs"]).all()
+    for leaf in k2.LEAVES:
+        grad, S = ref[leaf]
+        assert k2.same_nonfinite(grad, auto[leaf]), (tag, leaf)
+        fin = np.isfinite(grad)
+        assert (np.abs(grad[fin] - auto[leaf][fin]) <= 1e-11 * S[fin]).all(), (tag, leaf)
+
+
 def test_regions_without_a_range_and_tiny_weights_are_what_the_cases_say():
     case = k2.Case(BY_TAG["r6_rows4"])
     ref = case.reference()
