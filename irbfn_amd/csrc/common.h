@@ -78,6 +78,29 @@ int launch_kernel(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&.
   return IRBFN_OK;
 }
 
+// One value per thread of a 256-thread block, combined in a fixed tree through sm[256] (deterministic); every thread gets the
+// result.  RESYNC: a barrier behind the read of sm[0], for a caller that writes sm again.
+struct TreeSum { template <typename S> __device__ static S of(S a, S b) { return a + b; } };
+struct TreeMax { template <typename S> __device__ static S of(S a, S b) { return b > a ? b : a; } };
+template <typename Op, bool RESYNC, typename S>
+__device__ __forceinline__ S block_tree_256(S v, S* sm) {
+  const int t = threadIdx.x;
+  sm[t] = v;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) {
+      const S o = sm[t + w];
+      sm[t] = Op::of(sm[t], o);
+    }
+    __syncthreads();
+  }
+  const S r = sm[0];
+  if constexpr (RESYNC) __syncthreads();
+  return r;
+}
+template <typename S>
+__device__ __forceinline__ S block_sum_256(S v, S* sm) { return block_tree_256<TreeSum, true>(v, sm); }
+
 struct GateTables {        // device pointers owned by the descriptor
   const float* lo;         // [nsplit][max_ranges]
   const float* hi;         // [nsplit][max_ranges]

@@ -309,13 +309,8 @@ __global__ __launch_bounds__(256) void f64_colsum_kernel(const double* __restric
   const int o = blockIdx.x, t = threadIdx.x;
   double s = 0.0;
   for (long b = t; b < B; b += 256) s += g[b * O + o];
-  sm[t] = s;
-  __syncthreads();
-  for (int w2 = 128; w2 > 0; w2 >>= 1) {
-    if (t < w2) sm[t] += sm[t + w2];
-    __syncthreads();
-  }
-  if (t == 0) g_bias[o] = sm[0];
+  s = block_tree_256<TreeSum, false>(s, sm);
+  if (t == 0) g_bias[o] = s;
 }
 
 static int f64_slices(const F64Card& c, int64_t B) {

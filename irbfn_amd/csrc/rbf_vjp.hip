@@ -205,93 +205,78 @@ __global__ __launch_bounds__(256) void rbf_vjp_kernel(const VjpArgs a) {
 // output value in ONE thread: 100 threads x 128 regions x 24 slices of dependent loads = 2.2 ms of the 2.6 ms training
 // step of the reference's 128-region net at its batch size of 80000.)
 // Row V of the grid (blockIdx.y == V) is the second stage of the bias gradient: block o sums the per-block column sums of g
-// (colsum_partial_kernel) -- a launch of its own until round 3.  vjp_reduce_live_kernel repeats that row: as one
-// __forceinline__ device function (three spellings tried) the last tree step of both kernels compiles to two ds_read_b32
-// instead of one ds_read2_b32 (275 -> 277 and 341 -> 343 instructions; registers, LDS, scratch equal).  The folded form was not timed
-// on the device, so it is not taken on an instruction count alone: the 12 lines stay written twice.
-__global__ __launch_bounds__(256) void vjp_reduce_kernel(float* __restrict__ part, float* __restrict__ g_centers,
-                                                         float* __restrict__ g_log_sigs, float* __restrict__ g_kernel, int QSB,
-                                                         int V, int Npad, int N, int K, int R, int D, int DC, int O,
-                                                         const float* __restrict__ bpart, float* __restrict__ g_bias, int bias_blocks) {
+// (colsum_partial_kernel) -- a launch of its own until round 3.
+//
+// Where the slabs of a call live.  The primary buffer holds [slices][Vs][pitch]: the rows of K2g's live-leaf mode (rbf_vjp_gram.hip,
+// VgMode: [d centers (0)] [d log_sigs (0, 1)] d kernel), full rows (mode 0) from every other kernel,
+//     mode   crows   lrow   kb       Vs = kb + OP        (centre rows [0, crows), the width row, the first Dense row)
+//     0      DC      DC     DC + 1   DC + 1 + OP = V
+//     1      0       0      1        1 + OP
+//     2      0       -1     0        OP
+// and centre n in column n, or (cpr > 0: rbf_vjp_f16gram_gamma's padded chunk order) centre k of region r in column 32 cpr r + k,
+// whose padding columns are never read.  Which kernel wrote the slabs can be known on the device only: where the flag holds `gen`
+// the kernel in front handed the call over (it returned at once) and the one behind it wrote full rows in the plain order -- K2h
+// behind a frozen-leaf K2g into the same buffer with the same slices, the gated K2 behind rbf_vjp_f16gram_gamma into `alt`, K2's own.
+struct VjpSlabs {
+  float* part;
+  int slices, pitch, cpr, mode;
+  float* alt;                       // cpr > 0: [alt_slices][V][alt_pitch]
+  int alt_slices, alt_pitch;
+  const int* flag;                  // null: no hand-over (never null with cpr > 0)
+  int gen;
+};
+
+// grid row V of the slab reduce: block o sums the column sums of colsum_partial_kernel's blocks.  As a device function the last
+// tree step compiles to two ds_read_b32 where the row written into the kernel had one ds_read2_b32 (+2 instructions); timed against
+// that form on an MI355X (parent, parent again, this form; medians, us): 1000 centres at B = 80000 87.8 / 86.2 / 86.0, config 3
+// 156.2 / 156.3 / 156.5, 128 regions 71.4 / 71.8 / 72.0 -- differences of the size two runs of one form show, so the row is
+// stated once (profiles/vjp_reduce_fold.txt)
+__device__ __forceinline__ void vjp_bias_row(const float* __restrict__ bpart, float* __restrict__ g_bias, int bias_blocks, int O,
+                                             float* sm) {
+  const int o = blockIdx.x, t = threadIdx.x;
+  if (o >= O || bpart == nullptr) return;
+  float sacc = 0.0f;
+  for (int b = t; b < bias_blocks; b += 256) sacc += bpart[(size_t)b * O + o];
+  sacc = block_tree_256<TreeSum, false>(sacc, sm);
+  if (t == 0) g_bias[o] = sacc;
+}
+
+// What differs between the calls is compile-time: COLMAP the padded chunk order with its flag and second buffer, LIVE rows of a
+// live-leaf mode, perhaps a flag, and leaves that may be null (a null g_centers / g_log_sigs is not written).  <false, false> runs
+// in every training step: no load of a flag, no division.  The order of the sums is the contract: a handed-over call returns the
+// bits of the kernel behind it run alone, a frozen call those of the all-live one.
+template <bool COLMAP, bool LIVE>
+__global__ __launch_bounds__(256) void vjp_reduce_kernel(const VjpSlabs sl, float* __restrict__ g_centers,
+                                                         float* __restrict__ g_log_sigs, float* __restrict__ g_kernel, int V, int N,
+                                                         int K, int R, int D, int DC, int O, int OP, const float* __restrict__ bpart,
+                                                         float* __restrict__ g_bias, int bias_blocks) {
   // block = (value v, 64 consecutive centres) x 4 slice groups: thread (sg, l) sums slices sg, sg + 4, ... in order, the
   // four partial sums are added in a fixed order (small nets have few centre groups and hundreds of slices)
   __shared__ float sm[4][kWave];
   const int l = threadIdx.x & (kWave - 1), sg = threadIdx.x >> 6;
-  if (blockIdx.y == (unsigned)V) {
-    const int o = blockIdx.x, t = threadIdx.x;
-    if (o >= O || bpart == nullptr) return;
-    float* sb = &sm[0][0];
-    float sacc = 0.0f;
-    for (int b = t; b < bias_blocks; b += 256) sacc += bpart[(size_t)b * O + o];
-    sb[t] = sacc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {             // fixed tree -> deterministic
-      if (t < w) sb[t] += sb[t + w];
-      __syncthreads();
-    }
-    if (t == 0) g_bias[o] = sb[0];
-    return;
-  }
+  if (blockIdx.y == (unsigned)V) return vjp_bias_row(bpart, g_bias, bias_blocks, O, &sm[0][0]);
   const int v = blockIdx.y, n = blockIdx.x * kWave + l;
-  if ((v >= D && v < DC) || v > DC + O) return;            // padded coordinate / output slots (whole block)
-  float s = 0.0f;
-  if (n < N)
-    for (int q = sg; q < QSB; q += 4) s += part[((size_t)q * V + v) * Npad + n];
-  sm[sg][l] = s;
-  __syncthreads();
-  if (sg != 0 || n >= N) return;
-  s = (sm[0][l] + sm[1][l]) + (sm[2][l] + sm[3][l]);
-  if (v < D) g_centers[(size_t)n * D + v] = s;
-  else if (v == DC) g_log_sigs[n] = s;
-  else if (R == 1) g_kernel[(size_t)n * O + (v - DC - 1)] = s;
-  else part[(size_t)v * Npad + n] = s;                      // slab 0
-}
-
-__global__ __launch_bounds__(64) void vjp_reduce_regions_kernel(const float* __restrict__ part, float* __restrict__ g_kernel,
-                                                                int Npad, int K, int R, int DC, int O) {
-  const int k = blockIdx.x, o = blockIdx.y, lane = threadIdx.x;
-  float s = 0.0f;
-  for (int r = lane; r < R; r += kWave) s += part[(size_t)(DC + 1 + o) * Npad + (size_t)r * K + k];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);      // fixed tree: deterministic
-  if (lane == 0) g_kernel[(size_t)k * O + o] = s;
-}
-
-// vjp_reduce_kernel for irbfn_net_vjp_frozen; a null g_centers / g_log_sigs is not written.  The slabs hold the rows of K2g's
-// live-leaf mode `mode` (rbf_vjp_gram.hip, VgMode: [d centers (0)] [d log_sigs (0, 1)] d kernel) -- full rows (mode 0) where
-// another kernel wrote them, and where K2g handed this call to K2h: the flag holds `gen` then (K2g returned at once).  V: the
-// full row count, the grid's bias row.  The sums run in the order of vjp_reduce_kernel, which the all-live path keeps.
-__global__ __launch_bounds__(256) void vjp_reduce_live_kernel(float* __restrict__ part, float* __restrict__ g_centers,
-                                                              float* __restrict__ g_log_sigs, float* __restrict__ g_kernel, int QSB,
-                                                              int V, int mode, const int* __restrict__ flag, int gen, int Npad, int N,
-                                                              int R, int D, int DC, int O, int OP, const float* __restrict__ bpart,
-                                                              float* __restrict__ g_bias, int bias_blocks) {
-  __shared__ float sm[4][kWave];
-  const int l = threadIdx.x & (kWave - 1), sg = threadIdx.x >> 6;
-  if (blockIdx.y == (unsigned)V) {
-    const int o = blockIdx.x, t = threadIdx.x;
-    if (o >= O || bpart == nullptr) return;
-    float* sb = &sm[0][0];
-    float sacc = 0.0f;
-    for (int b = t; b < bias_blocks; b += 256) sacc += bpart[(size_t)b * O + o];
-    sb[t] = sacc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {             // fixed tree -> deterministic
-      if (t < w) sb[t] += sb[t + w];
-      __syncthreads();
-    }
-    if (t == 0) g_bias[o] = sb[0];
-    return;
-  }
-  const int v = blockIdx.y, n = blockIdx.x * kWave + l;
-  const int m = (flag != nullptr && *flag == gen) ? 0 : mode;
+  bool handed = false;                                      // the kernel behind the flag wrote the slabs
+  if constexpr (COLMAP) handed = *sl.flag == sl.gen;
+  else if constexpr (LIVE) handed = sl.flag != nullptr && *sl.flag == sl.gen;
+  const int m = LIVE && !handed ? sl.mode : 0;
   const int crows = m == 0 ? DC : 0, lrow = m == 0 ? DC : (m == 1 ? 0 : -1), kb = m == 0 ? DC + 1 : (m == 1 ? 1 : 0);
-  const int Vs = kb + OP;                                    // slab stride of this layout
-  const bool want = v < crows ? (v < D && g_centers != nullptr) : (v == lrow ? g_log_sigs != nullptr : (v >= kb && v < kb + O));
-  if (!want) return;                                        // frozen leaf / padded slot (whole block)
+  const int Vs = LIVE ? kb + OP : V;                         // slab stride of this layout
+  // whole blocks leave: padded coordinate and output slots, and with LIVE a frozen leaf
+  if constexpr (!LIVE) {
+    if ((v >= D && v < DC) || v > DC + O) return;
+  } else {
+    if (!(v < crows ? (v < D && g_centers != nullptr) : (v == lrow ? g_log_sigs != nullptr : (v >= kb && v < kb + O)))) return;
+  }
+  const bool alt = COLMAP && handed;
+  float* part = alt ? sl.alt : sl.part;
+  const int QS = alt ? sl.alt_slices : sl.slices, Np = alt ? sl.alt_pitch : sl.pitch;
+  int col = n;
+  if constexpr (COLMAP)
+    if (!alt) col = (n / K) * sl.cpr * 32 + n % K;
   float s = 0.0f;
   if (n < N)
-    for (int q = sg; q < QSB; q += 4) s += part[((size_t)q * Vs + v) * Npad + n];
+    for (int q = sg; q < QS; q += 4) s += part[((size_t)q * Vs + v) * Np + col];
   sm[sg][l] = s;
   __syncthreads();
   if (sg != 0 || n >= N) return;
@@ -299,94 +284,23 @@ __global__ __launch_bounds__(256) void vjp_reduce_live_kernel(float* __restrict_
   if (v < crows) g_centers[(size_t)n * D + v] = s;
   else if (v == lrow) g_log_sigs[n] = s;
   else if (R == 1) g_kernel[(size_t)n * O + (v - kb)] = s;
-  else part[(size_t)v * Npad + n] = s;                      // slab 0 (R > 1: full slab rows, kb = DC + 1)
+  else part[(size_t)v * Np + col] = s;                      // slab 0 of the buffer that was read (R > 1: full rows, kb = DC + 1)
 }
 
-// The slab reduce behind rbf_vjp_f16gram_gamma.  Which kernel wrote slabs is known on the device only: the matrix-core kernel its
-// own [QSG][V][NpadG] in the padded chunk order (centre k of region r in column 32 cpr r + k; padding columns are never read), or,
-// where the flag holds `gen`, the gated K2 behind it K2's [QSB][V][Npad].  The sums run in the order of vjp_reduce_kernel, so a
-// handed-over call returns the bits of a forced K2 call.
-struct VjpGammaSlabs {
-  float *gpart, *kpart;
-  int QSG, QSB, NpadG, Npad, cpr;
-  const int* flag;
-  int gen;
-};
-__global__ __launch_bounds__(256) void vjp_reduce_gamma_kernel(const VjpGammaSlabs sl, float* __restrict__ g_centers,
-                                                               float* __restrict__ g_log_sigs, float* __restrict__ g_kernel, int V,
-                                                               int N, int K, int R, int D, int DC, int O,
-                                                               const float* __restrict__ bpart, float* __restrict__ g_bias, int bias_blocks) {
-  __shared__ float sm[4][kWave];
-  const int l = threadIdx.x & (kWave - 1), sg = threadIdx.x >> 6;
-  if (blockIdx.y == (unsigned)V) {
-    const int o = blockIdx.x, t = threadIdx.x;
-    if (o >= O || bpart == nullptr) return;
-    float* sb = &sm[0][0];
-    float sacc = 0.0f;
-    for (int b = t; b < bias_blocks; b += 256) sacc += bpart[(size_t)b * O + o];
-    sb[t] = sacc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {             // fixed tree -> deterministic
-      if (t < w) sb[t] += sb[t + w];
-      __syncthreads();
-    }
-    if (t == 0) g_bias[o] = sb[0];
-    return;
-  }
-  const int v = blockIdx.y, n = blockIdx.x * kWave + l;
-  if ((v >= D && v < DC) || v > DC + O) return;            // padded coordinate / output slots (whole block)
-  const bool k2 = *sl.flag == sl.gen;
-  float* part = k2 ? sl.kpart : sl.gpart;
-  const int QS = k2 ? sl.QSB : sl.QSG, Np = k2 ? sl.Npad : sl.NpadG;
-  const int col = k2 ? n : (n / K) * sl.cpr * 32 + n % K;
-  float s = 0.0f;
-  if (n < N)
-    for (int q = sg; q < QS; q += 4) s += part[((size_t)q * V + v) * Np + col];
-  sm[sg][l] = s;
-  __syncthreads();
-  if (sg != 0 || n >= N) return;
-  s = (sm[0][l] + sm[1][l]) + (sm[2][l] + sm[3][l]);
-  if (v < D) g_centers[(size_t)n * D + v] = s;
-  else if (v == DC) g_log_sigs[n] = s;
-  else if (R == 1) g_kernel[(size_t)n * O + (v - DC - 1)] = s;
-  else part[(size_t)v * Np + col] = s;                      // slab 0
-}
-
-__global__ __launch_bounds__(64) void vjp_reduce_regions_gamma_kernel(const VjpGammaSlabs sl, float* __restrict__ g_kernel, int K, int R,
-                                                                      int DC, int O) {
+// R > 1: d kernel[k, o] = the per-centre values of slab 0 summed over the regions, lanes over r and a fixed tree.  Only the padded
+// order needs the flag here: a live-leaf call's two writers share buffer and pitch.
+template <bool COLMAP>
+__global__ __launch_bounds__(64) void vjp_reduce_regions_kernel(const VjpSlabs sl, float* __restrict__ g_kernel, int K, int R, int DC,
+                                                                int O) {
   const int k = blockIdx.x, o = blockIdx.y, lane = threadIdx.x;
-  const bool k2 = *sl.flag == sl.gen;
-  const float* part = k2 ? sl.kpart : sl.gpart;
-  const int Np = k2 ? sl.Npad : sl.NpadG, rs = k2 ? K : sl.cpr * 32;
+  const bool alt = COLMAP && *sl.flag == sl.gen;
+  const float* part = alt ? sl.alt : sl.part;
+  const int Np = alt ? sl.alt_pitch : sl.pitch, rs = COLMAP && !alt ? sl.cpr * 32 : K;
   float s = 0.0f;
   for (int r = lane; r < R; r += kWave) s += part[(size_t)(DC + 1 + o) * Np + (size_t)r * rs + k];
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);      // fixed tree: deterministic
   if (lane == 0) g_kernel[(size_t)k * O + o] = s;
-}
-
-// vg_mode: -1 the all-live path (vjp_reduce_kernel); else vjp_reduce_live_kernel with the slabs' layout (K2g's VgMode; 0 = the
-// full rows of every other kernel) -- and, behind a frozen-leaf K2g, the hand-over flag that says K2h wrote full rows instead
-int launch_vjp_reduce(const irbfn_net* net, float* part, float* g_centers, float* g_log_sigs, float* g_kernel, int QSB, int V,
-                      int Npad, hipStream_t s, const float* bpart, float* g_bias, int bias_blocks, int vg_mode = -1,
-                      const int* flag = nullptr, int gen = 0) {
-  unsigned gx = (unsigned)((net->N + kWave - 1) / kWave);
-  if (bpart != nullptr && gx < (unsigned)net->O) gx = (unsigned)net->O;
-  if (vg_mode < 0) {
-    hipLaunchKernelGGL(vjp_reduce_kernel, dim3(gx, V + (bpart != nullptr ? 1 : 0)), dim3(256), 0, s, part, g_centers,
-                       g_log_sigs, g_kernel, QSB, V, Npad, net->N, net->K, net->R, net->D, net->DC, net->O, bpart, g_bias, bias_blocks);
-  } else {
-    hipLaunchKernelGGL(vjp_reduce_live_kernel, dim3(gx, V + (bpart != nullptr ? 1 : 0)), dim3(256), 0, s, part, g_centers,
-                       g_log_sigs, g_kernel, QSB, V, vg_mode, flag, gen, Npad, net->N, net->R, net->D, net->DC, net->O, net->OP, bpart,
-                       g_bias, bias_blocks);
-  }
-  IRBFN_HIP_CHECK(hipGetLastError());
-  if (net->R > 1) {
-    hipLaunchKernelGGL(vjp_reduce_regions_kernel, dim3(net->K, net->O), dim3(kWave), 0, s, part, g_kernel, Npad, net->K, net->R,
-                       net->DC, net->O);
-    IRBFN_HIP_CHECK(hipGetLastError());
-  }
-  return IRBFN_OK;
 }
 
 // d bias[o] = sum_b g[b,o]: per-block column sums, then one block finishes (fixed order)
@@ -440,27 +354,12 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
     }
   }
   if (bmax) {                                  // block-uniform
-    smax[threadIdx.x] = mx;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if (threadIdx.x < w) {
-        const float o2 = smax[threadIdx.x + w], m2 = smax[threadIdx.x];
-        smax[threadIdx.x] = o2 > m2 ? o2 : m2;
-      }
-      __syncthreads();
+    mx = block_tree_256<TreeMax, true>(mx, smax);
+    mo = block_tree_256<TreeMax, false>(mo, smax);
+    if (threadIdx.x == 0) {
+      bmax[blockIdx.x] = mx;
+      bmax[gridDim.x + 8 + blockIdx.x] = mo;
     }
-    if (threadIdx.x == 0) bmax[blockIdx.x] = smax[0];
-    __syncthreads();
-    smax[threadIdx.x] = mo;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if (threadIdx.x < w) {
-        const float o2 = smax[threadIdx.x + w], m2 = smax[threadIdx.x];
-        smax[threadIdx.x] = o2 > m2 ? o2 : m2;
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) bmax[gridDim.x + 8 + blockIdx.x] = smax[0];
   }
 }
 
@@ -826,26 +725,16 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
       glogits[b * R + r] = (expf(lp) * sl - labels[b * R + r]) * invB;
     }
   }
-  sm[threadIdx.x] = lsum;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) sm[threadIdx.x] += sm[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss_part[blockIdx.x] = sm[0];
+  lsum = block_tree_256<TreeSum, false>(lsum, sm);
+  if (threadIdx.x == 0) loss_part[blockIdx.x] = lsum;
 }
 
 __global__ __launch_bounds__(256) void xent_final_kernel(const float* __restrict__ part, int n, float* __restrict__ out, int accumulate) {
   __shared__ float sm[256];
   float v = 0.0f;
   for (int i = threadIdx.x; i < n; i += 256) v += part[i];
-  sm[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) sm[threadIdx.x] += sm[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = accumulate ? out[0] + sm[0] : sm[0];
+  v = block_tree_256<TreeSum, false>(v, sm);
+  if (threadIdx.x == 0) out[0] = accumulate ? out[0] + v : v;
 }
 
 int launch_softmax_xent(const float* logits, const float* labels, float* glogits, float* loss, float* partials, int accumulate,
@@ -872,7 +761,6 @@ struct VjpCall {
   int64_t B;
   char* ws;
   hipStream_t s;
-  int red_mode;                                  // launch_vjp_reduce: -1 the all-live kernel, 0 the live-leaf kernel of every frozen call
   template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }
 };
 
@@ -885,15 +773,38 @@ static int bias_partials(const VjpCall& c, const VjpLayout& L, float* bmax) {
   return IRBFN_OK;
 }
 
-static int slab_reduce(const VjpCall& c, const VjpLayout& L, float* slabs, int slices, int mode, const int* flag = nullptr, int gen = 0) {
-  return launch_vjp_reduce(c.net, slabs, c.g_centers, c.g_log_sigs, c.g_kernel, slices, L.V, L.Npad, c.s, c.at<float>(L.off_bias), c.g_bias,
-                           L.bias_blocks, mode, flag, gen);
+// The slab reduce of every call: V value rows and the bias row over max(centre groups, O) blocks, then for R > 1 the region stage.
+// The instance follows from the slabs and the leaves; full rows of one buffer with every leaf live take the one without a flag load.
+static int launch_vjp_reduce(const VjpCall& c, const VjpLayout& L, const VjpSlabs& sl) {
+  const irbfn_net* net = c.net;
+  unsigned gx = (unsigned)((net->N + kWave - 1) / kWave);
+  if (gx < (unsigned)net->O) gx = (unsigned)net->O;
+  const bool colmap = sl.cpr > 0, live = sl.flag != nullptr || sl.mode != 0 || !c.g_centers || !c.g_log_sigs;
+  auto stage1 = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(gx, L.V + 1), dim3(256), 0, c.s, sl, c.g_centers, c.g_log_sigs, c.g_kernel, L.V, net->N, net->K, net->R,
+                       net->D, net->DC, net->O, net->OP, c.at<float>(L.off_bias), c.g_bias, L.bias_blocks);
+  };
+  if (colmap) stage1(vjp_reduce_kernel<true, false>);
+  else if (live) stage1(vjp_reduce_kernel<false, true>);
+  else stage1(vjp_reduce_kernel<false, false>);
+  IRBFN_HIP_CHECK(hipGetLastError());
+  if (net->R > 1) {
+    auto stage2 = colmap ? vjp_reduce_regions_kernel<true> : vjp_reduce_regions_kernel<false>;
+    hipLaunchKernelGGL(stage2, dim3(net->K, net->O), dim3(kWave), 0, c.s, sl, c.g_kernel, net->K, net->R, net->DC, net->O);
+    IRBFN_HIP_CHECK(hipGetLastError());
+  }
+  return IRBFN_OK;
+}
+
+// full rows [slices][V][Npad] of one writer in the plain order
+static VjpSlabs plain_slabs(const VjpLayout& L, float* slabs, int slices) {
+  return {slabs, slices, L.Npad, 0, 0, nullptr, 0, 0, nullptr, 0};
 }
 
 // the tail of K2m, K2r and K2: the bias column sums (no block maxima: nobody packs g to f16 there), then the slab reduce
 static int bias_and_reduce(const VjpCall& c, const VjpLayout& L, float* slabs, int slices) {
   const int rc = bias_partials(c, L, nullptr);
-  return rc != IRBFN_OK ? rc : slab_reduce(c, L, slabs, slices, c.red_mode);
+  return rc != IRBFN_OK ? rc : launch_vjp_reduce(c, L, plain_slabs(L, slabs, slices));
 }
 
 // K2h, or K2g with K2h behind it
@@ -924,8 +835,9 @@ static int launch_vjp_k2h(const VjpCall& c, const VjpLayout& L, const LaunchPlan
   }
   rc = launch_vjp_f16(net, c.x, c.gout, c.B, qblk, bmax, L.bias_blocks, scales, part, p.S, L.Npad, c.s, run_if, run_gen);
   if (rc != IRBFN_OK) return rc;
-  // live: which of K2g and K2h wrote the slabs is known on the device only: the flag
-  return live ? slab_reduce(c, L, part, p.S, p.mode, run_if, run_gen) : slab_reduce(c, L, part, p.S, c.red_mode);
+  VjpSlabs sl = plain_slabs(L, part, p.S);
+  if (live) { sl.mode = p.mode; sl.flag = run_if; sl.gen = run_gen; }   // K2g's live rows, or K2h's full ones where the flag holds gen
+  return launch_vjp_reduce(c, L, sl);
 }
 
 static int launch_vjp_k2m(const VjpCall& c, const VjpLayout& L, const LaunchPlan& p) {
@@ -994,18 +906,8 @@ static int launch_vjp_k2g_gamma(const VjpCall& c, const VjpLayout& L, const Laun
   if (rc != IRBFN_OK) return rc;
   rc = launch_vjp_k2_main(c, L, pk, flag, gen);
   if (rc != IRBFN_OK) return rc;
-  const VjpGammaSlabs sl = {c.at<float>(L.off_gpart), c.at<float>(L.off_part), p.S, pk.S, L.NpadG, L.Npad, gram_gamma_cpr(net), flag, gen};
-  unsigned gx = (unsigned)((net->N + kWave - 1) / kWave);
-  if (gx < (unsigned)net->O) gx = (unsigned)net->O;
-  hipLaunchKernelGGL(vjp_reduce_gamma_kernel, dim3(gx, L.V + 1), dim3(256), 0, c.s, sl, c.g_centers, c.g_log_sigs, c.g_kernel, L.V, net->N,
-                     net->K, net->R, net->D, net->DC, net->O, c.at<float>(L.off_bias), c.g_bias, L.bias_blocks);
-  IRBFN_HIP_CHECK(hipGetLastError());
-  if (net->R > 1) {
-    hipLaunchKernelGGL(vjp_reduce_regions_gamma_kernel, dim3(net->K, net->O), dim3(kWave), 0, c.s, sl, c.g_kernel, net->K, net->R, net->DC,
-                       net->O);
-    IRBFN_HIP_CHECK(hipGetLastError());
-  }
-  return IRBFN_OK;
+  // the matrix-core kernel's slabs in the padded chunk order, or K2's own where the flag holds gen
+  return launch_vjp_reduce(c, L, {c.at<float>(L.off_gpart), p.S, L.NpadG, gram_gamma_cpr(net), 0, c.at<float>(L.off_part), pk.S, L.Npad, flag, gen});
 }
 
 int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_centers, float* g_log_sigs, float* g_kernel,
@@ -1022,7 +924,7 @@ int launch_vjp(irbfn_net* net, const float* x, const float* gout, float* g_cente
   const int vg_mode = !frozen || g_centers ? 0 : (g_log_sigs ? 1 : 2);
   const VjpLayout L = vjp_layout(net, B);
   const LaunchPlan p = plan_vjp(net, B, net->opt[IRBFN_OPT_VJP_KERNEL], gamma_ext != nullptr, vg_mode, L);
-  const VjpCall c = {net, x, gout, gamma_ext, g_centers, g_log_sigs, g_kernel, g_bias, B, static_cast<char*>(ws), s, frozen ? 0 : -1};
+  const VjpCall c = {net, x, gout, gamma_ext, g_centers, g_log_sigs, g_kernel, g_bias, B, static_cast<char*>(ws), s};
   switch (p.kind) {
     case LK_K2G:
     case LK_K2H: return launch_vjp_k2h(c, L, p);

@@ -28,20 +28,6 @@ template <> struct TrigOf<double> { using type = TrigF64; };
 template <typename S>
 __device__ __forceinline__ S sgn(S d) { return d > S(0) ? S(1) : (d < S(0) ? S(-1) : S(0)); }   // d|.| = sign
 
-template <typename S>
-__device__ __forceinline__ S block_sum_256(S v, S* sm) {
-  const int t = threadIdx.x;
-  sm[t] = v;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) sm[t] += sm[t + w];
-    __syncthreads();
-  }
-  const S r = sm[0];
-  __syncthreads();
-  return r;
-}
-
 // ---- train_step_oneint ----------------------------------------------------------------------------
 // x[B,D>=7] = [v_c, x_g, y_g, t_g, v_g, beta, angv]; y_pred, y [B,O>=2] = (accel, steer-vel) in cols 0,1.
 // initial_state = [0,0,0, x[:,0], 0, x[:,6], x[:,5]]                       (train_nmpc.py:260-266)
@@ -265,122 +251,107 @@ __global__ __launch_bounds__(256) void seeds_fullint_f64_kernel(const double* __
   if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
 }
 
-// ---- Frenet train_step_fullint (scripts/train_nmpc_frenet.py:394-421) -------------------------------------------
-// x[B,8] = [ey, delta, vx_car, vy_car, vx_goal, wz, epsi, curv]; initial_state = x[:, [0,0,1,2,3,5,6,7]] (:398);
-// loss = mean|y_pred - y| + mean|integrate_frenet_mult([init, y_pred]) - integrate_frenet_mult([init, y])|
-// (:402-412; all T states, all 8 components).  gy = d loss / d y_pred through the T-step Frenet roll-out
-// (rollout_adjoint.h: the adjoint of dynamics.py:190-290, low-speed RHS).  O = 2T.
+// ---- the multi-step losses: every state of a T-step roll-out against the label's roll-out --------------------------------
+// loss = mean|y_pred - y| + mean|roll([init, y_pred])[:, :, comps] - roll([init, y])[:, :, comps]| over all T states; gy = d loss /
+// d y_pred through the roll-out's adjoint (rollout_adjoint.h).  O = 2T.  What a mode adds to ModeTraits (rollout_step.h) for it:
+// the initial state from a query row, the NSEED seeded state components comp(0 .. NSEED), the curvature vjp_back_step takes,
+// the step, and whether a float64 form exists.
+template <int MODE>
+struct SeedTraits;
+// Frenet train_step_fullint (scripts/train_nmpc_frenet.py:394-421): x[B,8] = [ey, delta, vx_car, vy_car, vx_goal, wz, epsi, curv];
+// initial_state = x[:, [0,0,1,2,3,5,6,7]] (:398); integrate_frenet_mult (:402-412; all 8 components; the adjoint of
+// dynamics.py:190-290, low-speed RHS)
+template <>
+struct SeedTraits<IRBFN_ROLLOUT_FRENET_LS> {
+  static constexpr int NSEED = 8;
+  static constexpr bool F64 = true;
+  __device__ static constexpr int comp(int k) { return k; }
+  template <typename S>
+  __device__ static void init(const S* xb, S (&s)[8]) {
+    const S s0[8] = {xb[0], xb[0], xb[1], xb[2], xb[3], xb[5], xb[6], xb[7]};
+    for (int i = 0; i < 8; ++i) s[i] = s0[i];
+  }
+  template <typename S>
+  __device__ static S cur(const S (&s)[8]) { return s[7]; }
+  template <typename Trig, typename S>
+  __device__ static void step(S (&s)[8], S a, S sv, const typename DynOf<S>::type& dp) { frenet_step<Trig>(s, a, sv, dp); }
+};
+// single-track full integration (no reference counterpart; include/irbfn_hip.h: irbfn_train_seeds_st_fullint): x[B,D>=7] and the
+// initial state as seeds_oneint; SELECT: integrate_st_mult's model (select(V > 3, dynamic, kinematic), the planner's roll-out) with
+// the adjoint of the branch each step took, else the kinematic model alone; components [0,1,3,4].  float32 only.
+template <bool SELECT>
+struct SeedTraitsSt {
+  static constexpr int NSEED = 4;
+  static constexpr bool F64 = false;
+  __device__ static constexpr int comp(int k) { return k < 2 ? k : k + 1; }
+  template <typename S>
+  __device__ static void init(const S* xb, S (&s)[7]) {
+    const S s0[7] = {S(0), S(0), S(0), xb[0], S(0), xb[6], xb[5]};
+    for (int i = 0; i < 7; ++i) s[i] = s0[i];
+  }
+  template <typename S>
+  __device__ static S cur(const S (&)[7]) { return S(0); }
+  template <typename Trig, typename S>
+  __device__ static void step(S (&s)[7], S a, S sv, const typename DynOf<S>::type& dp) { st_step<SELECT, Trig>(s, a, sv, dp); }
+};
+template <> struct SeedTraits<IRBFN_ROLLOUT_ST_SELECT> : SeedTraitsSt<true> {};
+template <> struct SeedTraits<IRBFN_ROLLOUT_ST_KS> : SeedTraitsSt<false> {};
+
 // The loop shape follows S.  float: both sweeps unrolled to TMAX under a t < T guard, so park / seed stay in registers.
-// double: rolled loops over T (ROLLED); unrolled, that kernel grows from 1768 to 6719 instructions at TMAX = 5 (22 364 at 16).
-template <int TMAX, typename S>
-__global__ __launch_bounds__(256) void seeds_frenet_fullint_kernel(const S* __restrict__ x, const S* __restrict__ yp,
-                                                                   const S* __restrict__ y, S* __restrict__ gy,
-                                                                   S* __restrict__ loss_part, long B, int D, int T,
-                                                                   typename DynOf<S>::type dp, S tie) {
+// double: rolled loops over T (ROLLED); unrolled, the Frenet kernel grows from 1768 to 6719 instructions at TMAX = 5 (22 364 at 16).
+template <int MODE, int TMAX, typename S>
+__global__ __launch_bounds__(256) void seeds_multistep_kernel(const S* __restrict__ x, const S* __restrict__ yp,
+                                                              const S* __restrict__ y, S* __restrict__ gy,
+                                                              S* __restrict__ loss_part, long B, int D, int T,
+                                                              typename DynOf<S>::type dp, S tie) {
   using Trig = typename TrigOf<S>::type;
+  using M = SeedTraits<MODE>;
   constexpr bool ROLLED = std::is_same<S, double>::value;
-  constexpr int UNROLL = ROLLED ? 1 : TMAX;
+  static_assert(M::F64 || !ROLLED, "this mode has no float64 form");
+  constexpr int UNROLL = ROLLED ? 1 : TMAX, NS = ModeTraits<MODE>::S, NSEED = M::NSEED;
   __shared__ S sm[256];
   const int O = 2 * T, TN = ROLLED ? T : TMAX;                                // trip count of the two sweeps
-  const S inv_y = S(1) / ((S)B * (S)O), inv_s = S(1) / ((S)B * (S)T * S(8));
+  const S inv_y = S(1) / ((S)B * (S)O), inv_s = S(1) / ((S)B * (S)T * S(NSEED));
   S lsum = S(0);
   for (long b = (long)blockIdx.x * 256 + threadIdx.x; b < B; b += (long)gridDim.x * 256) {
-    const S* xb = x + b * D;
-    S sa[8] = {xb[0], xb[0], xb[1], xb[2], xb[3], xb[5], xb[6], xb[7]};
-    S sp[8] = {xb[0], xb[0], xb[1], xb[2], xb[3], xb[5], xb[6], xb[7]};
-    const S cur = sp[7];
-    S park[TMAX][ModeTraits<IRBFN_ROLLOUT_FRENET_LS>::NP], seed[TMAX][8];
+    S sa[NS], sp[NS];
+    M::init(x + b * D, sa);
+    M::init(x + b * D, sp);
+    const S cur = M::cur(sp);
+    S park[TMAX][ModeTraits<MODE>::NP], seed[TMAX][NSEED];
 #pragma unroll UNROLL
     for (int t = 0; t < TN; ++t) {
       if (ROLLED || t < T) {
-        frenet_step<Trig>(sa, y[b * O + t], y[b * O + T + t], dp);        // actual_states (:407)
-        vjp_park<IRBFN_ROLLOUT_FRENET_LS>(sp, park[t]);
-        frenet_step<Trig>(sp, yp[b * O + t], yp[b * O + T + t], dp);      // pred_states   (:408)
+        M::template step<Trig>(sa, y[b * O + t], y[b * O + T + t], dp);       // the label's states
+        vjp_park<MODE>(sp, park[t]);
+        M::template step<Trig>(sp, yp[b * O + t], yp[b * O + T + t], dp);     // the prediction's
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const S d = sp[i] - sa[i];
+        for (int k = 0; k < NSEED; ++k) {
+          const S d = sp[M::comp(k)] - sa[M::comp(k)];
           lsum += fabs(d) * inv_s;
-          seed[t][i] = sgn(d) * inv_s;
+          seed[t][k] = sgn(d) * inv_s;
         }
       }
     }
-    S lam[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    S lam[NS] = {};
 #pragma unroll UNROLL
     for (int t = TN - 1; t >= 0; --t) {
       if (ROLLED || t < T) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) lam[i] += seed[t][i];
+        for (int k = 0; k < NSEED; ++k) lam[M::comp(k)] += seed[t][k];
         S ga, gsv;
-        vjp_back_step<IRBFN_ROLLOUT_FRENET_LS, Trig>(park[t], yp[b * O + t], yp[b * O + T + t], lam, cur, tie, dp, ga, gsv);
+        vjp_back_step<MODE, Trig>(park[t], yp[b * O + t], yp[b * O + T + t], lam, cur, tie, dp, ga, gsv);
         gy[b * O + t] = ga;
         gy[b * O + T + t] = gsv;
       }
     }
-    for (int o = 0; o < O; ++o) {                             // pred_loss = |y_pred - y|.mean()  (:401)
+    for (int o = 0; o < O; ++o) {                             // pred_loss = |y_pred - y|.mean()
       const S d = yp[b * O + o] - y[b * O + o];
       lsum += fabs(d) * inv_y;
       gy[b * O + o] += sgn(d) * inv_y;
     }
   }
   const S tot = block_sum_256(lsum, sm);
-  if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
-}
-
-// ---- single-track full integration (no reference counterpart; include/irbfn_hip.h: irbfn_train_seeds_st_fullint) --------
-// x[B,D>=7] and the initial state as seeds_oneint; SELECT: integrate_st_mult's model (select(V > 3, dynamic, kinematic), the
-// planner's roll-out) with the adjoint of the branch each step took (rollout_adjoint.h), else the kinematic model alone.
-// loss = mean|y_pred - y| + mean|S_pred[:, :, [0,1,3,4]] - S_act[:, :, [0,1,3,4]]| over all T states.  O = 2T.  float32 only.
-// Shaped like seeds_frenet_fullint_kernel<TMAX, float>: both sweeps unrolled to TMAX under t < T, park and seeds in registers.
-template <int TMAX, bool SELECT>
-__global__ __launch_bounds__(256) void seeds_st_fullint_kernel(const float* __restrict__ x, const float* __restrict__ yp,
-                                                               const float* __restrict__ y, float* __restrict__ gy,
-                                                               float* __restrict__ loss_part, long B, int D, int T,
-                                                               DynParams dp, float tie) {
-  constexpr int MODE = SELECT ? IRBFN_ROLLOUT_ST_SELECT : IRBFN_ROLLOUT_ST_KS;
-  constexpr int NP = ModeTraits<MODE>::NP;
-  __shared__ float sm[256];
-  const int O = 2 * T;
-  const float inv_y = 1.0f / ((float)B * (float)O), inv_s = 1.0f / ((float)B * (float)T * 4.0f);
-  float lsum = 0.0f;
-  for (long b = (long)blockIdx.x * 256 + threadIdx.x; b < B; b += (long)gridDim.x * 256) {
-    const float* xb = x + b * D;
-    float sa[7] = {0.0f, 0.0f, 0.0f, xb[0], 0.0f, xb[6], xb[5]};
-    float sp[7] = {0.0f, 0.0f, 0.0f, xb[0], 0.0f, xb[6], xb[5]};
-    float park[TMAX][NP], seed[TMAX][4];
-    const int idx[4] = {0, 1, 3, 4};
-#pragma unroll
-    for (int t = 0; t < TMAX; ++t) {
-      if (t < T) {
-        st_step<SELECT>(sa, y[b * O + t], y[b * O + T + t], dp);
-        vjp_park<MODE>(sp, park[t]);
-        st_step<SELECT>(sp, yp[b * O + t], yp[b * O + T + t], dp);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float d = sp[idx[k]] - sa[idx[k]];
-          lsum += fabsf(d) * inv_s;
-          seed[t][k] = sgn(d) * inv_s;
-        }
-      }
-    }
-    float lam[7] = {0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int t = TMAX - 1; t >= 0; --t) {
-      if (t < T) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) lam[idx[k]] += seed[t][k];
-        float ga, gsv;
-        vjp_back_step<MODE>(park[t], yp[b * O + t], yp[b * O + T + t], lam, 0.0f, tie, dp, ga, gsv);
-        gy[b * O + t] = ga;
-        gy[b * O + T + t] = gsv;
-      }
-    }
-    for (int o = 0; o < O; ++o) {
-      const float d = yp[b * O + o] - y[b * O + o];
-      lsum += fabsf(d) * inv_y;
-      gy[b * O + o] += sgn(d) * inv_y;
-    }
-  }
-  const float tot = block_sum_256(lsum, sm);
   if (threadIdx.x == 0) loss_part[blockIdx.x] = tot;
 }
 
@@ -488,43 +459,19 @@ static int train_seeds_fullint(const S* x_dev, const S* y_pred_dev, const S* y_d
   return finish_loss(partials_dev, loss_dev, B, s);
 }
 
-template <typename S>
-static int train_seeds_frenet_fullint(const S* x_dev, const S* y_pred_dev, const S* y_dev, const S* dyn_params_host,
-                                      S clip_tie, S* gy_dev, S* loss_dev, S* partials_dev, int64_t B, int D, int T,
-                                      void* stream) {
-  if (B < 0 || D < 8 || T < 1 || T > 16 || !dyn_params_host) return IRBFN_ERR_BAD_ARG;
+// the instances unroll to 5 steps (the reference's horizon) or to 16
+template <int MODE, typename S>
+static int train_seeds_multistep(const S* x_dev, const S* y_pred_dev, const S* y_dev, const S* dyn_params_host, S clip_tie,
+                                 S* gy_dev, S* loss_dev, S* partials_dev, int64_t B, int D, int T, void* stream) {
+  if (B < 0 || D < ModeTraits<MODE>::S0 || T < 1 || T > 16 || !dyn_params_host) return IRBFN_ERR_BAD_ARG;
   if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
   if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
   typename DynOf<S>::type dp;
   memcpy(dp.p, dyn_params_host, sizeof(dp.p));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (T <= 5)
-    hipLaunchKernelGGL((seeds_frenet_fullint_kernel<5, S>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev,
-                       gy_dev, partials_dev, (long)B, D, T, dp, clip_tie);
-  else
-    hipLaunchKernelGGL((seeds_frenet_fullint_kernel<16, S>), dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev,
-                       gy_dev, partials_dev, (long)B, D, T, dp, clip_tie);
-  return finish_loss(partials_dev, loss_dev, B, s);
-}
-
-static int train_seeds_st_fullint(int mode, const float* x_dev, const float* y_pred_dev, const float* y_dev,
-                                  const float* dyn_params_host, float clip_tie, float* gy_dev, float* loss_dev,
-                                  float* partials_dev, int64_t B, int D, int T, void* stream) {
-  if (mode != IRBFN_ROLLOUT_ST_SELECT && mode != IRBFN_ROLLOUT_ST_KS) return IRBFN_ERR_BAD_ARG;
-  if (B < 0 || D < 7 || T < 1 || T > 16 || !dyn_params_host) return IRBFN_ERR_BAD_ARG;
-  if (B > 0 && (!x_dev || !y_pred_dev || !y_dev || !gy_dev)) return IRBFN_ERR_BAD_ARG;
-  if (!loss_dev || !partials_dev) return IRBFN_ERR_BAD_ARG;
-  DynParams dp;
-  memcpy(dp.p, dyn_params_host, sizeof(dp.p));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const dim3 grid(seed_blocks(B)), block(256);
-#define IRBFN_SEEDS_ST(TMAX, SELECT) \
-  hipLaunchKernelGGL((seeds_st_fullint_kernel<TMAX, SELECT>), grid, block, 0, s, x_dev, y_pred_dev, y_dev, gy_dev, partials_dev, \
-                     (long)B, D, T, dp, clip_tie)
-  const bool select = mode == IRBFN_ROLLOUT_ST_SELECT;
-  if (T <= 5) { if (select) IRBFN_SEEDS_ST(5, true); else IRBFN_SEEDS_ST(5, false); }
-  else { if (select) IRBFN_SEEDS_ST(16, true); else IRBFN_SEEDS_ST(16, false); }
-#undef IRBFN_SEEDS_ST
+  auto kernel = T <= 5 ? seeds_multistep_kernel<MODE, 5, S> : seeds_multistep_kernel<MODE, 16, S>;
+  hipLaunchKernelGGL(kernel, dim3(seed_blocks(B)), dim3(256), 0, s, x_dev, y_pred_dev, y_dev, gy_dev, partials_dev, (long)B, D, T, dp,
+                     clip_tie);
   return finish_loss(partials_dev, loss_dev, B, s);
 }
 
@@ -568,15 +515,20 @@ int irbfn_train_seeds_fullint(const float* x_dev, const float* y_pred_dev, const
 int irbfn_train_seeds_frenet_fullint(const float* x_dev, const float* y_pred_dev, const float* y_dev,
                                      const float* dyn_params_host, float clip_tie, float* gy_dev, float* loss_dev,
                                      float* partials_dev, int64_t B, int D, int T, void* stream) {
-  return train_seeds_frenet_fullint(x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev, partials_dev, B, D, T,
-                                    stream);
+  return train_seeds_multistep<IRBFN_ROLLOUT_FRENET_LS>(x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev,
+                                                        partials_dev, B, D, T, stream);
 }
 
 int irbfn_train_seeds_st_fullint(int mode, const float* x_dev, const float* y_pred_dev, const float* y_dev,
                                  const float* dyn_params_host, float clip_tie, float* gy_dev, float* loss_dev,
                                  float* partials_dev, int64_t B, int D, int T, void* stream) {
-  return train_seeds_st_fullint(mode, x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev, partials_dev, B, D, T,
-                                stream);
+  if (mode == IRBFN_ROLLOUT_ST_SELECT)
+    return train_seeds_multistep<IRBFN_ROLLOUT_ST_SELECT>(x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev,
+                                                          partials_dev, B, D, T, stream);
+  if (mode == IRBFN_ROLLOUT_ST_KS)
+    return train_seeds_multistep<IRBFN_ROLLOUT_ST_KS>(x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev,
+                                                      partials_dev, B, D, T, stream);
+  return IRBFN_ERR_BAD_ARG;
 }
 
 int irbfn_adam_clip_step(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev, int64_t n,
@@ -601,8 +553,8 @@ int irbfn_train_seeds_fullint_f64(const double* x_dev, const double* y_pred_dev,
 int irbfn_train_seeds_frenet_fullint_f64(const double* x_dev, const double* y_pred_dev, const double* y_dev,
                                          const double* dyn_params_host, double clip_tie, double* gy_dev, double* loss_dev,
                                          double* partials_dev, int64_t B, int D, int T, void* stream) {
-  return train_seeds_frenet_fullint(x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev, partials_dev, B, D, T,
-                                    stream);
+  return train_seeds_multistep<IRBFN_ROLLOUT_FRENET_LS>(x_dev, y_pred_dev, y_dev, dyn_params_host, clip_tie, gy_dev, loss_dev,
+                                                        partials_dev, B, D, T, stream);
 }
 
 int irbfn_adam_clip_step_f64(double* params_dev, const double* grads_dev, double* m_dev, double* v_dev, int64_t n,

@@ -1,5 +1,5 @@
 """The statements behind the ST_SELECT adjoint (irbfn_amd/csrc/rollout_adjoint.h: vjp_back_step<ST_SELECT>) and the single-track
-full-integration seeds (train_step.hip: seeds_st_fullint_kernel), shared by test_st_select_reference_cpu.py (which holds them to
+full-integration seeds (train_step.hip: seeds_multistep_kernel), shared by test_st_select_reference_cpu.py (which holds them to
 torch.autograd) and test_gpu_st_select_vjp.py / test_gpu_train_st.py (which hold the kernels to them).  A plain module.
 
 The convention.  One step is x' = x + select(V > 3, f, f_ks) dt, V the clipped speed (oracle.dynamic_st_onestep).  The adjoint

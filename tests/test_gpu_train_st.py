@@ -1,4 +1,4 @@
-"""irbfn_train_seeds_st_fullint (train_step.hip: seeds_st_fullint_kernel<5 / 16, select>) through its C ABI, y_pred given as data,
+"""irbfn_train_seeds_st_fullint (train_step.hip: seeds_multistep_kernel<ST_SELECT / ST_KS, 5 / 16, float>) through its C ABI, y_pred given as data,
 against the float64 statement of _st_select_util.py under the project's float32 rule (_train_step_util.ratio32 <= 1 with the
 float32 statement as twin), and one train_step_st_fullint on a small net.  gy, the loss and `partials` are NaN before every call.
 Rows the float64 statement flags as ambiguous (within MARGIN = 1e-5 of a kink or of the switch at V = 3) are checked for finiteness

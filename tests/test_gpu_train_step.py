@@ -9,7 +9,8 @@ statement's error is measured in the test.  float64 bounds are those of tests/te
 max |gy_ref|, Adam 1e-13 max |p|).  Rows the float64 statement flags as ambiguous (within 1e-5 of a kink without sitting on it:
 _train_step_util) are checked for finiteness only in float32, and their share is capped at 5 % in every case.
 
-The test ids name the kernel instance a case runs; each prints its largest err / bound (pytest -s; profiles/train_step_parity.txt)."""
+The test ids name the kernel instance a case runs (the Frenet seeds under the name they had before they became instances of
+seeds_multistep_kernel, see instance()); each prints its largest err / bound (pytest -s; profiles/train_step_parity.txt)."""
 import ctypes as C
 import functools
 
@@ -38,7 +39,8 @@ def _dp(f64):
 
 
 def instance(kind, n, f64):
-    """the kernel instance the launchers of train_step.hip pick"""
+    """the kernel instance the launchers of train_step.hip pick (frenet: seeds_multistep_kernel<FRENET_LS, 5 / 16, S>, under the
+    name the test ids have carried since before it was folded with the single-track seeds)"""
     if kind == "oneint":
         return "seeds_oneint_kernel<%s>" % ("double" if f64 else "float")
     if kind == "frenet":

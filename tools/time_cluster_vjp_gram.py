@@ -12,7 +12,8 @@ and K = 10, B = 80 000 and 65 536.
 One warm-up pass over every variant of a shape, then ROUNDS interleaved rounds (every variant once per round, INNER calls between
 two device events); median over the rounds with min / max (the spread between repeats).  ``--profile`` runs the VJP of one shape
 (``--k 50`` / ``--k 10``) on one kernel (``--kernel k2`` / ``--kernel k2g``) a few times only, for a
-``rocprofv3 --kernel-trace --stats`` pass in a run of its own.  GPU box; output kept as profiles/cluster_vjp_gram.txt."""
+``rocprofv3 --kernel-trace --stats`` pass in a run of its own.  ``--vjp-only`` stops each shape after the first block (to compare
+builds of the library, IRBFN_LIB, process by process), ``--outside`` puts one query outside K1g's box (the hand-over to the gated K2).  GPU box; output kept as profiles/cluster_vjp_gram.txt."""
 import os
 import sys
 
@@ -28,6 +29,7 @@ from irbfn_amd import _lib, configs, train  # noqa: E402
 from irbfn_amd.model import ClusterWCRBFNet, _ptr, _stream_ptr  # noqa: E402
 
 PROFILE = "--profile" in sys.argv
+VJP_ONLY, OUTSIDE = "--vjp-only" in sys.argv, "--outside" in sys.argv
 ROUNDS, INNER = (1, 3) if PROFILE else (10, 5)
 R, D, O, T = 500, 8, 10, 5
 KERNELS = (("K2", _lib.VJP_K2), ("K2g", _lib.VJP_K2G_GAMMA))
@@ -106,6 +108,8 @@ def leaves(K, B):
 
 def shape(K, B, kernels=KERNELS):
     rng, cfg, params, x, nets = cluster_net(K, B, kernels)
+    if OUTSIDE:
+        x[123, 4] = 50.0                         # outside K1g's box: the matrix-core kernel hands the call to the gated K2 behind it
     xt = torch.from_numpy(x).cuda()
     gd = torch.from_numpy(rng.normal(size=(B, O)).astype(np.float32)).cuda()
     gld = torch.from_numpy(rng.normal(size=(B, R)).astype(np.float32)).cuda()
@@ -122,6 +126,8 @@ def shape(K, B, kernels=KERNELS):
     for k in outs["K2"]:
         a, b = outs["K2g"][k], outs["K2"][k]
         print(f"   max |K2g - K2| / max |K2| {k:9s} {float((a - b).abs().max() / b.abs().max()):.2e}")
+    if VJP_ONLY:
+        return
     res = measure("ClusterWCRBFNet.vjp, " + title,
                   [(f"model {n}", (lambda net: lambda: net.vjp(params, xt, gd, glogits=gld))(nets[n])) for n in nets])
     verdict(res, "model")
@@ -175,7 +181,7 @@ def main():
     for K in (50, 10):
         for B in (80000, 65536):
             shape(K, B)
-    for K in (50, 10):
+    for K in () if VJP_ONLY else (50, 10):
         errors(K)
 
 
