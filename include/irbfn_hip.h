@@ -678,6 +678,65 @@ int irbfn_rows_quad_f64(const float* z_dev /*[rows,ldz]*/, int64_t ldz, int64_t 
                         int64_t ldp, int nd, double* q_dev /*[rows]*/, double* v_dev /*[rows,nd] or NULL with nd = 0*/,
                         void* stream);
 
+/* Closed-loop simulation of B cars on one race line (sim_advance.hip; irbfn_amd/simulate.py): plan, apply the first control,
+ * move, plan again from where the car went.  One planning tick is irbfn_plan_tick (no roll-out) and ONE irbfn_sim_advance:
+ * plant step(s), way-point search in a window around the car's last segment, look-ahead goal (the f1tenth pure-pursuit rule
+ * of the reference's planners), statistics, and the next query with its mirror flag.  The reference runs this loop in the
+ * gym (scripts/eval_dnmpc.py); parity of the loop is unpinned, every stage repeats, bit for bit, an entry point above.
+ *
+ * Per-car arrays that persist between calls (device, all in/out): state_dev [B,7] float32 (single-track state
+ * [x, y, delta, v, psi, psi_dot, beta]), seg_dev [B] int32 (last nearest segment), status_dev [B] int32 (irbfn_sim_status),
+ * record_dev [B, irbfn_sim_record_doubles()] float64 = [ticks, sum_d2, max_d, sum_dv, progress, s_last, fail_tick].  A fresh
+ * record is all zero with fail_tick = -1.  A car whose status is not IRBFN_SIM_OK is FROZEN: the call reads and writes nothing
+ * of its rows in any array.  Per call and car b:
+ *  1. Plant, skipped when controls_dev is NULL (the call that prepares tick 0).  a = controls[b, 0], sv = controls[b, T]
+ *     (rows [a_0..a_{T-1}, sv_0..sv_{T-1}]); n_sub >= 1 steps of the single-track step of `mode` (IRBFN_ROLLOUT_ST_SELECT or
+ *     IRBFN_ROLLOUT_ST_KS) with the controls held and dt' = p[8] / n_sub (a float32 division); p = dyn_params_dev[b, 0:13]
+ *     where that pointer is given (one parameter row per car), else dyn_params_host[13].  The new state has the bits of
+ *     irbfn_rollout_forward(mode, [state, a x n_sub, sv x n_sub], p with p[8] = dt', T = n_sub)[:, -1, :].  A non-finite
+ *     component: the state is stored, status = IRBFN_SIM_NONFINITE, fail_tick = tick, and the car stops here.
+ *  2. Nearest segment i, parameter t and distance d of (double)state[0:2] on the polyline waypoints[:, 0:2], with the
+ *     arithmetic of irbfn_nearest_point per segment (NaN distances skipped), over the segments seg[b] - win_back ..
+ *     seg[b] + win_fwd: taken modulo N - 1 on a `wrap` track, else clipped to [0, N - 2] (seg[b] itself is clipped into that
+ *     range first); each segment at most once, however large the window.  win_back = win_fwd = -1: every segment.  The
+ *     smallest distance wins, ties go to the lowest segment index; nothing below infinity: d = inf, t = 0, i = 0.
+ *  3. Statistics, float64, unfused, in this order: ticks += 1; sum_d2 += d * d; max_d = max(max_d, d);
+ *     sum_dv += |(double)state[3] - waypoints[i,3]|; s = cum[i] + t * len[i]; unless this is the car's first call (ticks was
+ *     0), e = s - s_last, on a wrap track e -= length if e > length / 2, else e += length if e <= -length / 2, and
+ *     progress += e; then s_last = s.
+ *  4. half_width > 0 and d > half_width: status = IRBFN_SIM_OFF_TRACK, fail_tick = tick, the car stops here.
+ *  5. Goal.  d < lookahead: the search of irbfn_intersect_point from t_start = i + t with radius = (float)lookahead and the
+ *     track's wrap, over the whole track in that function's order, first hit wins: goal = waypoints[(first_i + N) % N, :]; no
+ *     hit: IRBFN_SIM_LOST.  Else d < max_reacquire: goal = waypoints[i, :].  Else IRBFN_SIM_LOST.  LOST sets fail_tick = tick
+ *     and stops the car.
+ *  6. x_dev[b, 0:7] and mirror_dev[b] = irbfn_plan_queries_cartesian of pose = (double)state[b] and this goal; seg[b] = i;
+ *     goal_dev [B,4], dist_dev [B], t_dev [B] (float64, each optional) get the goal row, d and t.
+ * A car that stops in steps 1, 4 or 5 has its state (and, from step 4 on, its record) stored, and nothing of step 6.
+ * `tick` is only stored: simulate.closed_loop passes the number of plant steps taken so far, this call's included.
+ * A car's result depends on that car alone: bit-identical across repeats and however the cars are divided over calls.  No atomics, no workspace; every loop is bounded by N.
+ * IRBFN_ERR_BAD_ARG, decided before any HIP call: a NULL track, B < 0, N < 2, n_sub < 1, a window side below -1 or one side
+ * -1 and the other not, T < 1 with controls given, a mode other than the two, a negative or NaN lookahead or max_reacquire,
+ * a NaN half_width; and, with B > 0, a NULL waypoints / cum / len / state / seg / status / record / x / mirror pointer, or
+ * controls without either dyn_params pointer.  B = 0: IRBFN_OK, no launch. */
+typedef enum irbfn_sim_status {
+  IRBFN_SIM_OK = 0,
+  IRBFN_SIM_NONFINITE = 1,   /* the plant produced a non-finite state */
+  IRBFN_SIM_OFF_TRACK = 2,   /* farther than half_width from the line */
+  IRBFN_SIM_LOST = 3         /* no look-ahead goal: no intersection, or farther than max_reacquire */
+} irbfn_sim_status;
+typedef struct irbfn_sim_track {
+  const double* waypoints_dev;   /* [N,4] x, y, theta, v */
+  const double* cum_dev;         /* [N-1] arc length at the start of each segment */
+  const double* len_dev;         /* [N-1] segment lengths */
+  double length;                 /* of the whole line, the closing segment of a wrap track included */
+  double lookahead, max_reacquire, half_width;
+  int N, wrap, win_back, win_fwd;
+} irbfn_sim_track;
+int irbfn_sim_record_doubles(void);
+int irbfn_sim_advance(const irbfn_sim_track* track, int mode, int tick, const float* controls_dev /*[B,2T] or NULL*/, int T,
+                      const float* dyn_params_host /*[13]*/, const float* dyn_params_dev /*[B,13] or NULL*/, int n_sub,
+                      float* state_dev, int32_t* seg_dev, int32_t* status_dev, double* record_dev, float* x_dev,
+                      int32_t* mirror_dev, double* goal_dev, double* dist_dev, double* t_dev, int64_t B, void* stream);
 /* Diagnostics */
 int irbfn_abi_version(void);
 int irbfn_device_count(void);

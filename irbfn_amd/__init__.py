@@ -13,6 +13,7 @@ Host side is Python (like the reference) over a C-ABI shared library of hand-wri
 * ``irbfn_amd.linear_fit``    ``fit_linear``: the output layer in closed form (float64 normal equations on the device)
 * ``irbfn_amd.ols``           ``select`` / ``fit_ols``: centres chosen by what they explain (OLS forward selection on the Gram matrix)
 * ``irbfn_amd.loo``           ``factor`` / ``loo`` / ``leverage`` / ``select_ridge``: leave-one-out errors and leverages of the closed-form fit
+* ``irbfn_amd.simulate``      ``Track`` / ``closed_loop``: B cars driven by a net along a race line, plant and way-point search on the device
 * ``irbfn_amd.autograd``      ``torch.autograd`` wrappers (the ``jax.grad`` surface)
 * ``irbfn_amd.distributed``   one-process-per-GPU sharding, RCCL broadcast of the parameters
 
@@ -26,4 +27,5 @@ from . import linear_fit  # noqa: F401
 from . import ols  # noqa: F401
 from . import widths  # noqa: F401
 from . import loo  # noqa: F401
+from . import simulate  # noqa: F401
 from .model import WCRBFNet, pred_step  # noqa: F401

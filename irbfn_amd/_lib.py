@@ -97,12 +97,25 @@ SIGNATURES = {
     "irbfn_ols_begin": (_i, [_fp, _i, _i, _i, _d, _d, _i, _fp, _fp, _fp, _ip, _fp, _ip, _vp, _i64, _vp]),
     "irbfn_ols_steps": (_i, [_fp, _i, _i, _i, _d, _i, _fp, _fp, _fp, _ip, _fp, _ip, _vp, _i64, _i, _vp]),
     "irbfn_rows_quad_f64": (_i, [_fp, _i64, _i64, _i, _fp, _i64, _i, _fp, _fp, _vp]),
+    "irbfn_sim_record_doubles": (_i, []),
+    "irbfn_sim_advance": (_i, [_vp, _i, _i, _fp, _i, _fp, _fp, _i, _fp, _ip, _ip, _fp, _fp, _ip, _fp, _fp, _fp, _i64, _vp]),
     "irbfn_abi_version": (_i, []),
     "irbfn_device_count": (_i, []),
     "irbfn_last_hip_error": (_i, []),
     "irbfn_strerror": (C.c_char_p, [_i]),
     "irbfn_net_last_launch": (_i, [_vp, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_i)]),
 }
+
+SIM_OK, SIM_NONFINITE, SIM_OFF_TRACK, SIM_LOST = 0, 1, 2, 3          # irbfn_sim_status
+SIM_STATUS_NAMES = {SIM_OK: "ok", SIM_NONFINITE: "nonfinite", SIM_OFF_TRACK: "off_track", SIM_LOST: "lost"}
+
+
+class SimTrack(C.Structure):
+    """irbfn_sim_track (include/irbfn_hip.h): device pointers and constants of one race line."""
+    _fields_ = [("waypoints_dev", C.c_void_p), ("cum_dev", C.c_void_p), ("len_dev", C.c_void_p), ("length", C.c_double),
+                ("lookahead", C.c_double), ("max_reacquire", C.c_double), ("half_width", C.c_double), ("N", C.c_int),
+                ("wrap", C.c_int), ("win_back", C.c_int), ("win_fwd", C.c_int)]
+
 
 class F64Card(C.Structure):
     """irbfn_f64_card (include/irbfn_hip.h): sizes + device pointers of the float64 gate tables."""

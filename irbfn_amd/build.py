@@ -68,6 +68,9 @@ UNITS = [
     ("rows_quad_f64.hip", "rows_quad_f64.o", []),      # K11: per-row leverages and predictions of the closed-form fit (f64 MFMA)
     ("mlp_head.hip", "mlp_head.o", []),
     ("planner_front.hip", "planner_front.o", []),
+    # the closed-loop tick around the net: plant step, windowed way-point search, goal, statistics, next query (no SLP: the plant
+    # step is the roll-out's)
+    ("sim_advance.hip", "sim_advance.o", ["-fno-slp-vectorize"]),
 ]
 
 

@@ -10,43 +10,26 @@
 #include <string.h>
 
 #include "common.h"
+#include "planner_geom.h"
 
 namespace irbfn {
-
-// Python's float modulo: result has the sign of the divisor (b > 0 here)
-__device__ __forceinline__ double py_mod(double a, double b) {
-  double r = fmod(a, b);
-  if (r == 0.0) return copysign(0.0, b);          // fmod keeps the sign of a: -0.0 % pi is +0.0 in Python and NumPy
-  if ((r < 0.0) != (b < 0.0)) r += b;
-  return r;
-}
 
 __global__ __launch_bounds__(256) void plan_queries_cartesian_kernel(const double* __restrict__ pose,
                                                                      const double* __restrict__ goal,
                                                                      float* __restrict__ x_out,
                                                                      float* __restrict__ state0_out,
                                                                      int* __restrict__ mirror_out, long B) {
-#pragma clang fp contract(off)                   // NumPy rounds each product: a fused s*dx + c*dy flips the sign of an exact 0
   const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const double* p = pose + b * 7;                // [x, y, delta, v, theta, angv, beta]  (:240)
-  const double* g = goal + b * 4;                // ref_point [x, y, theta, v]            (:170-171)
-  const double x = p[0], y = p[1], v = p[3], theta = p[4], angv = p[5], beta = p[6];
-  const double c = cos(-theta), s = sin(-theta); // rot = [[c, -s], [s, c]]               (:181-183)
-  const double dx = g[0] - x, dy = g[1] - y;
-  const double gl0 = c * dx + (-s) * dy;         // np.dot(rot, d): products then one add, no FMA
-  const double gl1 = s * dx + c * dy;
-  const double gt = g[2] - theta;
-  const bool m = gl1 < 0.0;                      // goal_needs_mirror                     (:188)
-  const double pi = 3.141592653589793;
-  float* xo = x_out + b * 7;                     // [v, x_g, y_g, t_g, v_g, beta, angv]   (:189-201)
-  xo[0] = (float)v;
-  xo[1] = (float)gl0;
-  xo[2] = (float)(m ? -gl1 : gl1);
-  xo[3] = (float)(m ? py_mod(-gt, pi) : py_mod(gt, pi));
-  xo[4] = (float)g[3];
-  xo[5] = (float)beta;
-  xo[6] = (float)angv;
+  double p[7], g[4];
+  float xo[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) p[i] = pose[b * 7 + i];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) g[i] = goal[b * 4 + i];
+  const bool m = cartesian_query(p, g, xo);
+#pragma unroll
+  for (int i = 0; i < 7; ++i) x_out[b * 7 + i] = xo[i];
   if (state0_out) {
 #pragma unroll
     for (int i = 0; i < 7; ++i) state0_out[b * 7 + i] = (float)p[i];
@@ -249,16 +232,8 @@ __global__ __launch_bounds__(256) void nearest_point_kernel(const WayArgs a, dou
   double best = INFINITY, bt = 0.0, bx = 0.0, by = 0.0;
   int bi = 0x7fffffff;
   for (int i = lane; i + 1 < a.N; i += 64) {
-    const double x0 = wp[2 * i], y0 = wp[2 * i + 1];
-    const float dx = (float)(wp[2 * i + 2] - x0), dy = (float)(wp[2 * i + 3] - y0);       // diffs.astype(float32) :125
-    const float l2 = dx * dx + dy * dy;                                                  // :126
-    const float lx = (float)(px - x0), ly = (float)(py - y0);                            // :129
-    const float dot = lx * dx + ly * dy;                                                 // np.dot of two float32 pairs :130
-    double t = (double)dot / (double)l2;                                                 // :131
-    t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);                                             // :132-133 (nan stays)
-    const double qx = x0 + t * (double)dx, qy = y0 + t * (double)dy;                     // :134
-    const double ex = px - qx, ey = py - qy;
-    const double d = sqrt(ex * ex + ey * ey);                                            // :137-138
+    double d, t, qx, qy;
+    segment_distance<2>(wp, i, px, py, d, t, qx, qy);
     if (d < best) { best = d; bt = t; bx = qx; by = qy; bi = i; }                        // first minimum of this lane's segments
   }
   double gbest = best;
@@ -277,37 +252,6 @@ __global__ __launch_bounds__(256) void nearest_point_kernel(const WayArgs a, dou
   }
 }
 
-__device__ __forceinline__ bool circle_hit(const double* wp, int N, int i, double px, double py, float radius,
-                                           bool first, float start_t, float& t_out, float& qx, float& qy) {
-#pragma clang fp contract(off)
-  const int i0 = ((i % N) + N) % N, i1 = (((i + 1) % N) + N) % N;
-  const float sx = (float)wp[2 * i0], sy = (float)wp[2 * i0 + 1];                         // trajectory.astype(float32) :160
-  const float ex = (float)wp[2 * i1] + 1e-6f, ey = (float)wp[2 * i1 + 1] + 1e-6f;         // :163
-  const float vx = ex - sx, vy = ey - sy;
-  const float av = vx * vx + vy * vy;                                                    // :166
-  const double bq = 2.0 * ((double)vx * ((double)sx - px) + (double)vy * ((double)sy - py));   // :167
-  const double cq = (double)(sx * sx + sy * sy) + (px * px + py * py) - 2.0 * ((double)sx * px + (double)sy * py) -
-                    (double)radius * (double)radius;                                     // :168-173
-  double disc = bq * bq - 4.0 * (double)av * cq;                                         // :174
-  if (disc < 0.0 || disc != disc) return false;
-  disc = sqrt(disc);
-  const double t1 = (-bq - disc) / (2.0 * (double)av), t2 = (-bq + disc) / (2.0 * (double)av);   // :182-183
-  double t;
-  if (first) {                                                                           // :184-193
-    if (t1 >= 0.0 && t1 <= 1.0 && t1 >= (double)start_t) t = t1;
-    else if (t2 >= 0.0 && t2 <= 1.0 && t2 >= (double)start_t) t = t2;
-    else return false;
-  } else {                                                                               // :194-203
-    if (t1 >= 0.0 && t1 <= 1.0) t = t1;
-    else if (t2 >= 0.0 && t2 <= 1.0) t = t2;
-    else return false;
-  }
-  t_out = (float)t;
-  qx = (float)((double)sx + t * (double)vx);
-  qy = (float)((double)sy + t * (double)vy);
-  return true;
-}
-
 // One wave per point: the search order of the reference (segments start_i .. N - 2, then, with wrap, -1 .. start_i - 1) is
 // walked 64 segments at a time; the first round with a hit ends the search and its lowest lane is the first intersection.
 __global__ __launch_bounds__(256) void intersect_point_kernel(const WayArgs a, const double* __restrict__ t0, float radius,
@@ -320,23 +264,12 @@ __global__ __launch_bounds__(256) void intersect_point_kernel(const WayArgs a, c
   const double* __restrict__ wp = a.traj;
   const double px = a.pts[2 * b], py = a.pts[2 * b + 1];
   const double ts = t0 ? t0[b] : 0.0;
-  const int start_i = (int)ts;                                                           // :155
-  const float start_t = (float)fmod(ts, 1.0);                                            // :156
-  const int nfwd = a.N - 1 - start_i > 0 ? a.N - 1 - start_i : 0;                        // i = start_i .. N - 2
-  const int nwrap = wrap ? (start_i + 1 > 0 ? start_i + 1 : 0) : 0;                      // i = -1 .. start_i - 1   :205-231
+  const HitOrder order(ts, a.N, wrap);
   float t = NAN, qx = NAN, qy = NAN;                                                     // (None, None, None)
   int fi = 0, hit = 0;
-  for (int base = 0; base < nfwd + nwrap; base += 64) {
-    const int ord = base + lane;
-    bool h = false;
-    int i = 0;
-    if (ord < nfwd) {
-      i = start_i + ord;
-      h = circle_hit(wp, a.N, i, px, py, radius, ord == 0, start_t, t, qx, qy);
-    } else if (ord < nfwd + nwrap) {
-      i = ord - nfwd - 1;
-      h = circle_hit(wp, a.N, i, px, py, radius, false, 0.0f, t, qx, qy);
-    }
+  for (int base = 0; base < order.total(); base += 64) {
+    int i;
+    const bool h = order.probe<2>(wp, a.N, base + lane, px, py, radius, i, t, qx, qy);
     const unsigned long long m = __ballot(h);
     if (m != 0ull) {
       const int src = __ffsll((long long)m) - 1;                                         // the first hit in search order
