@@ -737,6 +737,50 @@ int irbfn_sim_advance(const irbfn_sim_track* track, int mode, int tick, const fl
                       const float* dyn_params_host /*[13]*/, const float* dyn_params_dev /*[B,13] or NULL*/, int n_sub,
                       float* state_dev, int32_t* seg_dev, int32_t* status_dev, double* record_dev, float* x_dev,
                       int32_t* mirror_dev, double* goal_dev, double* dist_dev, double* t_dev, int64_t B, void* stream);
+
+/* Batched NMPC solver (nmpc_solve.hip, K13; irbfn_amd/nmpc.py): for B independent (state, goal) pairs the control sequence
+ * u [2T] = [a_0..a_{T-1}, sv_0..sv_{T-1}] that minimises a tracking cost through the roll-out model of `mode`
+ * (IRBFN_ROLLOUT_ST_KS or IRBFN_ROLLOUT_ST_SELECT) inside the box |a_t| <= p[10], |sv_t| <= p[9].  The reference's labels come
+ * from CasADi / IPOPT solvers that cannot be run here: parity is unpinned, the rule below is pinned against a float64 statement
+ * of itself (tests/_nmpc_util.py).  One problem per lane, everything float32, no atomics, no workspace.
+ *   States s_1..s_T: T steps of the model's one-step map from state0 -- the bits of irbfn_rollout_forward(mode, [state0 | u]).
+ *   e_t = (x_t - g_x, y_t - g_y, wrap(psi_t - g_h), v_t - g_v), wrap(e) = e - 2 pi rint(e / 2 pi), slope 1.
+ *   cost(u) = 1/2 [ sum_{t<T} q . e_t^2 + qf . e_T^2 + sum_t (r_a a_t^2 + r_sv sv_t^2)
+ *                   + sum_{t<T-1} (rd_a (a_{t+1} - a_t)^2 + rd_sv (sv_{t+1} - sv_t)^2) ],
+ *   the terms summed in this order (per step x, y, heading, speed).  With r the residuals (each term = r_i^2) and J = dr/du:
+ *   g = J^T r, H = J^T J; J holds the mask V > 3 of ST_SELECT constant and gives the clips of delta and V slope 1/2 on a bound.
+ *   u = clip(u0) (0 without u0), lambda = lambda0, c = cost(u).  Each of at most max_iter iterations: a variable is FIXED if
+ *   (u <= lo and g > 0) or (u >= hi and g < 0); on the others (H + diag(lambda H_jj + eps max_j H_jj)) d = -g by Cholesky (a
+ *   pivot <= 0 gives d = 0 in its variable), d = 0 on the fixed ones; u+ = clip(u + d).  cost(u+) < c: accept, lambda <-
+ *   max(lambda / 10, lambda_min).  CONVERGED if |c - c+| <= tol c, accepted or not (a float32 cost at its minimum moves by
+ *   rounding alone; a step that every bound stops leaves it where it is), or if c+ = 0.  Else, if not accepted, reject:
+ *   lambda <- min(10 lambda, lambda_max), STALLED once lambda = lambda_max.  A start with c = 0 is CONVERGED with 0 iterations; a NaN / Inf in a row's state, goal,
+ *   start, parameters or first cost is NONFINITE: u = the clipped start, both costs NaN, 0 iterations.
+ *   Outputs: u_dev [B,2T]; cost_dev [B,2] = (cost of the clipped start, cost of u); info_dev [B,2] = (irbfn_nmpc_status,
+ *   iterations); grad_dev [B,2T] (optional) = J^T r at u.  max_iter = 0: cost and gradient at the clipped start, status
+ *   IRBFN_NMPC_MAX_ITER, nothing else.  A row's result depends on that row alone: bit-identical across repeats and however the
+ *   rows are divided over calls.
+ * p = dyn_params_dev[b, 0:13] where that pointer is given, else dyn_params_host[13] (as irbfn_sim_advance).
+ * IRBFN_ERR_BAD_ARG, decided before any HIP call: B < 0, a mode other than the two, a NULL options pointer, a weight, lambda,
+ * tol or eps that is negative or not finite, lambda_min > lambda_max, max_iter < 0; and, with B > 0, a NULL state0 / goal / u /
+ * cost / info pointer or neither dyn_params pointer.  T outside 1..8: IRBFN_ERR_UNSUPPORTED.  B = 0: IRBFN_OK, no launch. */
+typedef enum irbfn_nmpc_status {
+  IRBFN_NMPC_CONVERGED = 0,
+  IRBFN_NMPC_MAX_ITER = 1,
+  IRBFN_NMPC_STALLED = 2,
+  IRBFN_NMPC_NONFINITE = 3
+} irbfn_nmpc_status;
+typedef struct irbfn_nmpc_options {
+  float q[4], qf[4];         /* stage and terminal weights of (x, y, heading, speed) */
+  float r[2], rd[2];         /* weights of (a, sv) and of their differences */
+  float lambda0, lambda_min, lambda_max, tol, eps;
+  int max_iter;
+} irbfn_nmpc_options;
+int irbfn_nmpc_solve(int mode, int T, const float* state0_dev /*[B,7]*/, const float* goal_dev /*[B,4]*/,
+                     const float* u0_dev /*[B,2T] or NULL*/, const float* dyn_params_host /*[13]*/,
+                     const float* dyn_params_dev /*[B,13] or NULL*/, const irbfn_nmpc_options* opt, float* u_dev /*[B,2T]*/,
+                     float* cost_dev /*[B,2]*/, int32_t* info_dev /*[B,2]*/, float* grad_dev /*[B,2T] or NULL*/, int64_t B,
+                     void* stream);
 /* Diagnostics */
 int irbfn_abi_version(void);
 int irbfn_device_count(void);

@@ -99,6 +99,7 @@ SIGNATURES = {
     "irbfn_rows_quad_f64": (_i, [_fp, _i64, _i64, _i, _fp, _i64, _i, _fp, _fp, _vp]),
     "irbfn_sim_record_doubles": (_i, []),
     "irbfn_sim_advance": (_i, [_vp, _i, _i, _fp, _i, _fp, _fp, _i, _fp, _ip, _ip, _fp, _fp, _ip, _fp, _fp, _fp, _i64, _vp]),
+    "irbfn_nmpc_solve": (_i, [_i, _i, _fp, _fp, _fp, _fp, _fp, _vp, _fp, _fp, _ip, _fp, _i64, _vp]),
     "irbfn_abi_version": (_i, []),
     "irbfn_device_count": (_i, []),
     "irbfn_last_hip_error": (_i, []),
@@ -115,6 +116,16 @@ class SimTrack(C.Structure):
     _fields_ = [("waypoints_dev", C.c_void_p), ("cum_dev", C.c_void_p), ("len_dev", C.c_void_p), ("length", C.c_double),
                 ("lookahead", C.c_double), ("max_reacquire", C.c_double), ("half_width", C.c_double), ("N", C.c_int),
                 ("wrap", C.c_int), ("win_back", C.c_int), ("win_fwd", C.c_int)]
+
+
+NMPC_CONVERGED, NMPC_MAX_ITER, NMPC_STALLED, NMPC_NONFINITE = 0, 1, 2, 3          # irbfn_nmpc_status
+NMPC_STATUS_NAMES = {NMPC_CONVERGED: "converged", NMPC_MAX_ITER: "max_iter", NMPC_STALLED: "stalled", NMPC_NONFINITE: "nonfinite"}
+
+
+class NmpcOptions(C.Structure):
+    """irbfn_nmpc_options (include/irbfn_hip.h): weights and iteration constants of irbfn_nmpc_solve."""
+    _fields_ = [("q", C.c_float * 4), ("qf", C.c_float * 4), ("r", C.c_float * 2), ("rd", C.c_float * 2), ("lambda0", C.c_float),
+                ("lambda_min", C.c_float), ("lambda_max", C.c_float), ("tol", C.c_float), ("eps", C.c_float), ("max_iter", C.c_int)]
 
 
 class F64Card(C.Structure):

@@ -132,6 +132,116 @@ __device__ __forceinline__ void vjp_back_step(const S* p, S a_in, S sv_in, S* la
   }
 }
 
+// The same one-step Jacobians in forward (JVP) form, for the two single-track modes (nmpc_solve.hip advances the sensitivities
+// S_t = d s_t / d u with them).  jvp_coeffs evaluates, from the state a step STARTS from, the dt-scaled entries of
+// F_x = d s' / d s and of d s' / d a that are neither 0 nor 1 -- the coefficient expressions of vjp_back_step above, entry for
+// entry; jvp_carry applies them to one tangent, jvp_fresh gives the tangents of this step's own two controls.  The controls are
+// taken to lie inside their box (slope 1: the solver keeps them there by projection); the clips of delta and V have
+// clipgrad's slope.  ST_KS never moves psi_dot and beta: its tangents have NS = 5 components [x, y, delta, v, psi]; ST_SELECT
+// carries all 7 and holds the mask V > 3 constant, a coefficient of the branch not taken being 0 by select (never by a product
+// with 0: at V = 0 the dynamic ones are inf / nan).  The NumPy statement is tests/_nmpc_util.py: step_jacobian.
+template <int MODE>
+struct StepJac;
+template <>
+struct StepJac<IRBFN_ROLLOUT_ST_KS> {
+  static constexpr int NS = 5;
+  float x3, x4, y3, y4, p2, p3;
+};
+template <>
+struct StepJac<IRBFN_ROLLOUT_ST_SELECT> {
+  static constexpr int NS = 7;
+  float x3, x4, x6, y3, y4, y6, p2, p3, p5;   // rows x', y', psi'
+  float w2, w3, w5, w6, wa;                   // row psi_dot' (wa: d / d a)
+  float b2, b3, b5, b6, ba;                   // row beta'
+};
+
+template <int MODE, typename Trig = TrigDirect>
+__device__ __forceinline__ void jvp_coeffs(const float* s, float a_in, float tie, const DynParams& dp, StepJac<MODE>& J,
+                                           const Trig trig = Trig()) {
+  static_assert(MODE == IRBFN_ROLLOUT_ST_KS || MODE == IRBFN_ROLLOUT_ST_SELECT, "single-track modes only");
+  const float lf = dp.p[3], lr = dp.p[4], dt = dp.p[8], s_max = dp.p[11], v_max = dp.p[12];
+  const float Lw = lr + lf;
+  const float d_raw = s[2], v_raw = s[3], psi = s[4];
+  const float DELTA = clipf(d_raw, -s_max, s_max), V = clipf(v_raw, -v_max, v_max);
+  const float md = clipgrad(d_raw, -s_max, s_max, tie), mv = clipgrad(v_raw, -v_max, v_max, tie);
+  float cp, sp, td;
+  if constexpr (MODE == IRBFN_ROLLOUT_ST_KS) {
+    trig.sincos_tan(psi, DELTA, s_max < 4194304.0f, sp, cp, td);
+    J.x3 = mv * dt * cp;
+    J.x4 = -(dt * V * sp);
+    J.y3 = mv * dt * sp;
+    J.y4 = dt * V * cp;
+    J.p2 = md * (V / Lw) * (1.0f + td * td) * dt;
+    J.p3 = mv * dt * (td / Lw);
+  } else {
+    const float g = 9.81f;
+    const float mu = dp.p[0], m = dp.p[1], I = dp.p[2], C_Sf = dp.p[5], C_Sr = dp.p[6], h = dp.p[7], a_max = dp.p[10];
+    const float pd = s[5], beta = s[6];
+    const float A = clipf(a_in, -a_max, a_max);
+    const bool dyn = V > 3.0f;
+    trig.sincos_tan(dyn ? psi + beta : psi, DELTA, s_max < 4194304.0f, sp, cp, td);
+    const float head_x = -(dt * V * sp), head_y = dt * V * cp;   // what f0 and f1 put on their angle
+    const float glr = g * lr - A * h, glf = g * lf + A * h;
+    const float E = C_Sf * glr, F = C_Sr * glf;
+    const float P = lf * E, Q = lr * F, R = lf * lf * E + lr * lr * F, M = F * lr - E * lf;
+    const float rV = 1.0f / V, pv = pd * rV;
+    const float c5 = (mu * m) / (I * Lw), c6 = (mu * rV) / Lw;
+    const float U = E * DELTA - (F + E) * beta + M * pv;
+    const float Ea = -C_Sf * h, Fa = C_Sr * h;
+    const float f5A = c5 * (lf * Ea * DELTA + (lr * Fa - lf * Ea) * beta - (lf * lf * Ea + lr * lr * Fa) * pv);
+    const float f6A = c6 * (Ea * DELTA - (Fa + Ea) * beta + (Fa * lr - Ea * lf) * pv);
+    const float f5V = c5 * R * pv * rV, f6V = -c6 * (U + M * pv) * rV;
+    const float f5W = -c5 * R * rV, f6W = c6 * M * rV - 1.0f;
+    J.x3 = mv * dt * cp;
+    J.x4 = head_x;
+    J.x6 = dyn ? head_x : 0.0f;
+    J.y3 = mv * dt * sp;
+    J.y4 = head_y;
+    J.y6 = dyn ? head_y : 0.0f;
+    J.p2 = dyn ? 0.0f : md * (V / Lw) * (1.0f + td * td) * dt;
+    J.p3 = dyn ? 0.0f : mv * dt * (td / Lw);
+    J.p5 = dyn ? dt : 0.0f;
+    J.w2 = dyn ? md * dt * (c5 * P) : 0.0f;
+    J.w3 = dyn ? mv * dt * f5V : 0.0f;
+    J.w5 = dyn ? dt * f5W : 0.0f;
+    J.w6 = dyn ? dt * (c5 * (Q - P)) : 0.0f;
+    J.wa = dyn ? dt * f5A : 0.0f;
+    J.b2 = dyn ? md * dt * (c6 * E) : 0.0f;
+    J.b3 = dyn ? mv * dt * f6V : 0.0f;
+    J.b5 = dyn ? dt * f6W : 0.0f;
+    J.b6 = dyn ? -(dt * (c6 * (F + E))) : 0.0f;
+    J.ba = dyn ? dt * f6A : 0.0f;
+  }
+}
+
+// d <- F_x d: the tangent of an earlier control through this step
+template <int MODE>
+__device__ __forceinline__ void jvp_carry(const StepJac<MODE>& J, float* d) {
+  if constexpr (MODE == IRBFN_ROLLOUT_ST_KS) {
+    const float n0 = d[0] + (J.x3 * d[3] + J.x4 * d[4]);
+    const float n1 = d[1] + (J.y3 * d[3] + J.y4 * d[4]);
+    const float n4 = d[4] + (J.p2 * d[2] + J.p3 * d[3]);
+    d[0] = n0; d[1] = n1; d[4] = n4;
+  } else {
+    const float n0 = d[0] + (J.x3 * d[3] + J.x4 * d[4] + J.x6 * d[6]);
+    const float n1 = d[1] + (J.y3 * d[3] + J.y4 * d[4] + J.y6 * d[6]);
+    const float n4 = d[4] + (J.p2 * d[2] + J.p3 * d[3] + J.p5 * d[5]);
+    const float n5 = d[5] + (J.w2 * d[2] + J.w3 * d[3] + J.w5 * d[5] + J.w6 * d[6]);
+    const float n6 = d[6] + (J.b2 * d[2] + J.b3 * d[3] + J.b5 * d[5] + J.b6 * d[6]);
+    d[0] = n0; d[1] = n1; d[4] = n4; d[5] = n5; d[6] = n6;
+  }
+}
+
+// the tangents d s' / d a_t and d s' / d sv_t of the step's own controls
+template <int MODE>
+__device__ __forceinline__ void jvp_fresh(const StepJac<MODE>& J, float dt, float* da, float* dsv) {
+#pragma unroll
+  for (int i = 0; i < StepJac<MODE>::NS; ++i) { da[i] = 0.0f; dsv[i] = 0.0f; }
+  da[3] = dt;
+  dsv[2] = dt;
+  if constexpr (MODE == IRBFN_ROLLOUT_ST_SELECT) { da[5] = J.wa; da[6] = J.ba; }
+}
+
 // cotangent of an input row's first S0 columns (roll_init) from the cotangent `lam` of the initial state
 template <int MODE>
 __device__ __forceinline__ void roll_init_grad(const float* row, const float* lam, float tie, float (&g)[ModeTraits<MODE>::S0]) {
