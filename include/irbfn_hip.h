@@ -738,6 +738,53 @@ int irbfn_sim_advance(const irbfn_sim_track* track, int mode, int tick, const fl
                       float* state_dev, int32_t* seg_dev, int32_t* status_dev, double* record_dev, float* x_dev,
                       int32_t* mirror_dev, double* goal_dev, double* dist_dev, double* t_dev, int64_t B, void* stream);
 
+/* Closed loop with the Frenet planner's 8-input nets (K14; the same kernel as above with one more template flag): the plant
+ * stays the Cartesian single-track model, and the tick changes frame before it builds the query.  The reference takes the
+ * Frenet pose from the gym's spline track, which is not available: parity is unpinned, the rule below is pinned against a
+ * float64 statement of itself (tests/_frenet_sim_util.py), and the fused tick against the two stand-alone entry points.
+ *
+ * Track curvature curv_dev [N] float64, one value per way-point, from the caller (simulate.Track computes it once on the
+ * host).  With wrap(e) = e - 2 pi rint(e / 2 pi), theta = waypoints[:, 2] and len the segment lengths, Track's rule is
+ * kappa_i = wrap(theta_{i+1} - theta_{i-1}) / (len_{i-1} + len_i) at interior way-points; on a `wrap` track the two end
+ * way-points use their neighbours across the seam and the closing segment's length; on an open track the ends are one-sided,
+ * kappa_0 = wrap(theta_1 - theta_0) / len_0 and kappa_{N-1} = wrap(theta_{N-1} - theta_{N-2}) / len_{N-2}.
+ *
+ * Frenet pose of one car, state [x, y, delta, v, psi, psi_dot, beta] float32, from the nearest segment i, the parameter t
+ * and the distance d of step 2 above.  Everything float64, no product fused into a sum:
+ *   (dx, dy) = waypoints[i+1, 0:2] - waypoints[i, 0:2];  c = dx * (y - y_i) - dy * (x - x_i)
+ *   ey = c >= 0 ? d : -d  (left of the line is positive; d = 0 gives +0 or -0, neither of which is mirrored)
+ *   s = cum[i] + t * len[i]  (the value of step 3)
+ *   theta_line = theta_i + t * wrap(theta_{i+1} - theta_i);  epsi = wrap(psi - theta_line)
+ *   curv = kappa_i + t * (kappa_{i+1} - kappa_i)
+ *   vx = v cos(beta), vy = v sin(beta), wz = psi_dot, delta = delta
+ *   row = [s, ey, delta, vx, vy, wz, epsi, curv], the layout irbfn_plan_queries_frenet takes.
+ * Way-point i + 1 never wraps: the polyline has N - 1 segments.  The frame is that of a polyline, not of a spline: crossing
+ * a vertex at lateral offset ey, s jumps by about ey * dtheta and epsi by about ey * kappa * dtheta.
+ *
+ * irbfn_cartesian_to_frenet: the search of step 2 and the pose, nothing else (no status: every row is converted).  seg_dev
+ * given: the track's window around seg_dev[b], exactly as step 2; NULL: every segment.  frenet_dev [B,8]; seg_out_dev [B], dist_dev
+ * [B], t_dev [B] optional, get i, d, t.  seg_out_dev must not overlap seg_dev.  Nothing comparable (d = inf, i = 0) gives
+ * ey = +-inf.
+ *
+ * irbfn_sim_advance_frenet: steps 1-5 of irbfn_sim_advance word for word; step 6 becomes: the pose above from the new state;
+ * vx_goal = goal[3] (the goal way-point's speed); x_dev[b, 0:8] and mirror_dev[b] = irbfn_plan_queries_frenet of that pose and
+ * vx_goal; seg[b] = i; frenet_dev [B,8] (optional) gets the pose, goal_dev / dist_dev / t_dev as above.  The record keeps its
+ * 7 doubles.  A NaN curvature makes a NaN query, and the plant reports IRBFN_SIM_NONFINITE one tick later; there is no new
+ * status.  state, seg, status, record, goal, dist and t have the bits irbfn_sim_advance gives them; frenet_dev has the bits of
+ * irbfn_cartesian_to_frenet(new state, old seg); x and mirror those of irbfn_plan_queries_frenet(frenet_dev, goal[:, 3]).
+ * IRBFN_ERR_BAD_ARG, decided before any HIP call: as irbfn_sim_advance (the conversion: the track's conditions and B < 0
+ * only), and with B > 0 a NULL curv_dev (the conversion: or a NULL waypoints / cum / len / state / frenet pointer).  B = 0:
+ * IRBFN_OK, no launch. */
+int irbfn_cartesian_to_frenet(const irbfn_sim_track* track, const double* curv_dev /*[N]*/, const float* state_dev /*[B,7]*/,
+                              const int32_t* seg_dev /*[B] or NULL = every segment*/, double* frenet_dev /*[B,8]*/,
+                              int32_t* seg_out_dev /*[B] or NULL*/, double* dist_dev /*or NULL*/, double* t_dev /*or NULL*/,
+                              int64_t B, void* stream);
+int irbfn_sim_advance_frenet(const irbfn_sim_track* track, const double* curv_dev, int mode, int tick,
+                             const float* controls_dev, int T, const float* dyn_params_host, const float* dyn_params_dev,
+                             int n_sub, float* state_dev, int32_t* seg_dev, int32_t* status_dev, double* record_dev,
+                             float* x_dev /*[B,8]*/, int32_t* mirror_dev, double* frenet_dev /*[B,8] or NULL*/, double* goal_dev,
+                             double* dist_dev, double* t_dev, int64_t B, void* stream);
+
 /* Batched NMPC solver (nmpc_solve.hip, K13; irbfn_amd/nmpc.py): for B independent (state, goal) pairs the control sequence
  * u [2T] = [a_0..a_{T-1}, sv_0..sv_{T-1}] that minimises a tracking cost through the roll-out model of `mode`
  * (IRBFN_ROLLOUT_ST_KS or IRBFN_ROLLOUT_ST_SELECT) inside the box |a_t| <= p[10], |sv_t| <= p[9].  The reference's labels come

@@ -99,6 +99,9 @@ SIGNATURES = {
     "irbfn_rows_quad_f64": (_i, [_fp, _i64, _i64, _i, _fp, _i64, _i, _fp, _fp, _vp]),
     "irbfn_sim_record_doubles": (_i, []),
     "irbfn_sim_advance": (_i, [_vp, _i, _i, _fp, _i, _fp, _fp, _i, _fp, _ip, _ip, _fp, _fp, _ip, _fp, _fp, _fp, _i64, _vp]),
+    "irbfn_cartesian_to_frenet": (_i, [_vp, _fp, _fp, _ip, _fp, _ip, _fp, _fp, _i64, _vp]),
+    "irbfn_sim_advance_frenet": (_i, [_vp, _fp, _i, _i, _fp, _i, _fp, _fp, _i, _fp, _ip, _ip, _fp, _fp, _ip, _fp, _fp, _fp, _fp,
+                                      _i64, _vp]),
     "irbfn_nmpc_solve": (_i, [_i, _i, _fp, _fp, _fp, _fp, _fp, _vp, _fp, _fp, _ip, _fp, _i64, _vp]),
     "irbfn_abi_version": (_i, []),
     "irbfn_device_count": (_i, []),

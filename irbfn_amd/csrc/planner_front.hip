@@ -44,17 +44,13 @@ __global__ __launch_bounds__(256) void plan_queries_frenet_kernel(const double* 
                                                                   int* __restrict__ mirror_out, long B) {
   const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const double* p = fr + b * 8;                  // [s, ey, delta, vx, vy, wz, epsi, curv]  (:491-502)
-  const bool m = p[1] < -0.05;                   // goal_needs_mirror = ey < -0.05           (:457)
-  float* xo = x_out + b * 8;                     // [ey, delta, vx, vy, vx_goal, wz, epsi, curv]  (:459-478)
-  xo[0] = (float)(m ? -p[1] : p[1]);
-  xo[1] = (float)p[2];
-  xo[2] = (float)p[3];
-  xo[3] = (float)(m ? -p[4] : p[4]);
-  xo[4] = (float)vx_goal[b];
-  xo[5] = (float)(m ? -p[5] : p[5]);
-  xo[6] = (float)(m ? -p[6] : p[6]);
-  xo[7] = (float)p[7];
+  double p[8];
+  float xo[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) p[i] = fr[b * 8 + i];
+  const bool m = frenet_query(p, vx_goal[b], xo);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) x_out[b * 8 + i] = xo[i];
   if (state0_out) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) state0_out[b * 8 + i] = (float)p[i];

@@ -39,6 +39,51 @@ __device__ __forceinline__ bool cartesian_query(const double (&p)[7], const doub
   return m;
 }
 
+// Query and mirror flag of IRBFNFrenetPlanner.plan (src/irbfn_mpc/irbfn_planner.py:456-478) for one (Frenet pose, goal speed)
+// pair.  p: [s, ey, delta, vx, vy, wz, epsi, curv] (:491-502); xo: [ey, delta, vx, vy, vx_goal, wz, epsi, curv]
+__device__ __forceinline__ bool frenet_query(const double (&p)[8], double vx_goal, float (&xo)[8]) {
+  const bool m = p[1] < -0.05;                   // goal_needs_mirror = ey < -0.05           (:457)
+  xo[0] = (float)(m ? -p[1] : p[1]);             // (:459-478)
+  xo[1] = (float)p[2];
+  xo[2] = (float)p[3];
+  xo[3] = (float)(m ? -p[4] : p[4]);
+  xo[4] = (float)vx_goal;
+  xo[5] = (float)(m ? -p[5] : p[5]);
+  xo[6] = (float)(m ? -p[6] : p[6]);
+  xo[7] = (float)p[7];
+  return m;
+}
+
+// e - 2 pi rint(e / 2 pi): the angle e brought into [-pi, pi]
+__device__ __forceinline__ double wrap_angle(double e) {
+#pragma clang fp contract(off)
+  const double two_pi = 6.283185307179586;
+  return e - two_pi * rint(e / two_pi);
+}
+
+// Frenet pose of a car on a race line wp [N,4] with way-point curvatures curv [N] (include/irbfn_hip.h:
+// irbfn_cartesian_to_frenet): st = [x, y, delta, v, psi, psi_dot, beta]; i, t, d: the nearest segment, its parameter and the
+// distance as segment_distance<4> found them; sarc = cum[i] + t * len[i].  fr: [s, ey, delta, vx, vy, wz, epsi, curv].
+// Way-point i + 1 exists: the polyline's segments end at N - 2.
+__device__ __forceinline__ void frenet_pose(const double* __restrict__ wp, const double* __restrict__ curv, int i, double t,
+                                            double d, double sarc, const float (&st)[7], double (&fr)[8]) {
+#pragma clang fp contract(off)                   // the float64 statement rounds each product before its sum
+  const double x0 = wp[4 * i], y0 = wp[4 * i + 1], th0 = wp[4 * i + 2];
+  const double dx = wp[4 * (i + 1)] - x0, dy = wp[4 * (i + 1) + 1] - y0;
+  const double c = dx * ((double)st[1] - y0) - dy * ((double)st[0] - x0);   // > 0: the car is left of the segment
+  const double th = th0 + t * wrap_angle(wp[4 * (i + 1) + 2] - th0);
+  const double k0 = curv[i];
+  const double v = (double)st[3], beta = (double)st[6];
+  fr[0] = sarc;
+  fr[1] = c >= 0.0 ? d : -d;
+  fr[2] = (double)st[2];
+  fr[3] = v * cos(beta);
+  fr[4] = v * sin(beta);
+  fr[5] = (double)st[5];
+  fr[6] = wrap_angle((double)st[4] - th);
+  fr[7] = k0 + t * (curv[i + 1] - k0);
+}
+
 // nearest_point (src/irbfn_mpc/planner_utils.py:125-138) for segment i of a polyline: the distance d of (px, py) to the
 // segment, the parameter t in [0, 1] of the closest point and that point.  d is NaN for a repeated or NaN way-point.
 template <int LD>

@@ -9,6 +9,12 @@
 // the same values -- in lockstep that costs what one lane costs, and no value has to be handed from the first lane to the
 // others -- and the group's first lane stores.  A group's lanes never diverge from each other: every branch and loop bound
 // below is a function of the car alone, so the shuffles and ballots inside them always find their partner lanes active.
+//
+// The kernel has three forms (SimForm).  SIM_CARTESIAN is the tick of irbfn_sim_advance.  SIM_FRENET (K14,
+// irbfn_sim_advance_frenet) is the same tick with step 6 replaced: the Frenet pose of the car on the polyline, then the
+// 8-input query of the Frenet planner.  SIM_POSE (irbfn_cartesian_to_frenet) is the search and the pose alone: no status, no
+// plant, no record, no goal.  The three share every line they have in common, so the fused Frenet tick repeats the other two
+// entry points bit for bit.
 #include <math.h>
 
 #include "common.h"
@@ -20,8 +26,11 @@ namespace irbfn {
 constexpr int kSimRecord = 7;    // doubles per car: ticks, sum_d2, max_d, sum_dv, progress, s_last, fail_tick
 enum SimRec : int { SR_TICKS = 0, SR_SUM_D2, SR_MAX_D, SR_SUM_DV, SR_PROGRESS, SR_S_LAST, SR_FAIL_TICK };
 
+enum SimForm : int { SIM_CARTESIAN = 0, SIM_FRENET, SIM_POSE };
+
 struct SimArgs {
   irbfn_sim_track tr;
+  const double* __restrict__ curv;      // [N] way-point curvatures (SIM_FRENET, SIM_POSE)
   const float* __restrict__ controls;   // [B][2T] or null
   const float* __restrict__ dyn_dev;    // [B][13] or null
   DynParams dp;                         // the shared row (dyn_dev null)
@@ -30,8 +39,10 @@ struct SimArgs {
   int* __restrict__ seg;
   int* __restrict__ status;
   double* __restrict__ record;
-  float* __restrict__ x;
+  float* __restrict__ x;                // [B][7], SIM_FRENET: [B][8]
   int* __restrict__ mirror;
+  double* __restrict__ frenet;          // [B][8]: optional in SIM_FRENET, the result of SIM_POSE
+  int* __restrict__ seg_out;            // SIM_POSE (which leaves seg as it is), optional
   double* __restrict__ goal;            // optional
   double* __restrict__ dist;            // optional
   double* __restrict__ tt;              // optional
@@ -67,14 +78,16 @@ struct SimWindow {
   }
 };
 
-template <int G, bool SELECT>
+template <int G, bool SELECT, int FORM>
 __global__ __launch_bounds__(256) void sim_advance_kernel(const SimArgs a) {
 #pragma clang fp contract(off)                   // the statistics and every shared body: each product rounded before its sum
   constexpr int CPB = 256 / G;                   // cars per block
   const int gl = threadIdx.x & (G - 1);          // lane of the group
   const long b = (long)blockIdx.x * CPB + threadIdx.x / G;
   if (b >= a.B) return;                          // the whole group
-  if (a.status[b] != IRBFN_SIM_OK) return;       // frozen: nothing read, nothing written
+  if constexpr (FORM != SIM_POSE) {
+    if (a.status[b] != IRBFN_SIM_OK) return;     // frozen: nothing read, nothing written
+  }
   const bool lead = gl == 0;
   const int N = a.tr.N;
   const double* __restrict__ wp = a.tr.waypoints_dev;
@@ -84,7 +97,7 @@ __global__ __launch_bounds__(256) void sim_advance_kernel(const SimArgs a) {
   for (int i = 0; i < 7; ++i) s[i] = a.state[b * 7 + i];
 
   // ---- 1. plant
-  if (a.controls) {
+  if (FORM != SIM_POSE && a.controls) {
     DynParams dp = a.dp;
     if (a.dyn_dev) {
 #pragma unroll
@@ -113,7 +126,7 @@ __global__ __launch_bounds__(256) void sim_advance_kernel(const SimArgs a) {
   // ---- 2. nearest segment of the window: the (distance, index) order of nearest_point_kernel, within the lane too (a window
   // across the seam does not visit its segments in index order)
   const double px = (double)s[0], py = (double)s[1];
-  const SimWindow win(a.tr, a.seg[b]);
+  const SimWindow win(a.tr, a.seg ? a.seg[b] : 0);   // (no seg: SIM_POSE over every segment, the host set the window to -1)
   double best = INFINITY, bt = 0.0;
   int bi = 0x7fffffff;
   for (int ord = gl; ord < win.count; ord += G) {
@@ -132,6 +145,20 @@ __global__ __launch_bounds__(256) void sim_advance_kernel(const SimArgs a) {
   if (bi == 0x7fffffff) { best = INFINITY; bt = 0.0; bi = 0; }   // nothing comparable: the scalar loop's defaults
   const double d = best, t = bt;
   const int i = bi;
+  const double sarc = a.tr.cum_dev[i] + t * a.tr.len_dev[i];
+
+  if constexpr (FORM == SIM_POSE) {
+    double fr[8];
+    frenet_pose(wp, a.curv, i, t, d, sarc, s, fr);
+    if (lead) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) a.frenet[b * 8 + k] = fr[k];
+      if (a.seg_out) a.seg_out[b] = i;
+      if (a.dist) a.dist[b] = d;
+      if (a.tt) a.tt[b] = t;
+    }
+    return;
+  }
 
   // ---- 3. statistics
   double* __restrict__ rec = a.record + b * kSimRecord;
@@ -141,7 +168,6 @@ __global__ __launch_bounds__(256) void sim_advance_kernel(const SimArgs a) {
   const double max_d = d > max0 ? d : max0;      // max(max_d, d) as Python's: a NaN never replaces
   const double dv = (double)s[3] - wp[4 * i + 3];
   const double sum_dv = rec[SR_SUM_DV] + fabs(dv);
-  const double sarc = a.tr.cum_dev[i] + t * a.tr.len_dev[i];
   double progress = rec[SR_PROGRESS];
   if (ticks0 != 0.0) {
     double e = sarc - rec[SR_S_LAST];
@@ -200,16 +226,29 @@ __global__ __launch_bounds__(256) void sim_advance_kernel(const SimArgs a) {
   }
 
   // ---- 6. query
-  double pose[7], g[4];
-  float xo[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) pose[k] = (double)s[k];
+  constexpr int XW = FORM == SIM_FRENET ? 8 : 7;
+  double g[4];
+  float xo[XW];
 #pragma unroll
   for (int k = 0; k < 4; ++k) g[k] = wp[4 * gi + k];
-  const bool m = cartesian_query(pose, g, xo);
+  bool m;
+  if constexpr (FORM == SIM_FRENET) {
+    double fr[8];
+    frenet_pose(wp, a.curv, i, t, d, sarc, s, fr);
+    m = frenet_query(fr, g[3], xo);
+    if (lead && a.frenet) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) a.frenet[b * 8 + k] = fr[k];
+    }
+  } else {
+    double pose[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) pose[k] = (double)s[k];
+    m = cartesian_query(pose, g, xo);
+  }
   if (lead) {
 #pragma unroll
-    for (int k = 0; k < 7; ++k) a.x[b * 7 + k] = xo[k];
+    for (int k = 0; k < XW; ++k) a.x[b * XW + k] = xo[k];
     a.mirror[b] = m ? 1 : 0;
     a.seg[b] = i;
     if (a.goal) {
@@ -223,11 +262,61 @@ __global__ __launch_bounds__(256) void sim_advance_kernel(const SimArgs a) {
 
 constexpr int kSimLanes = 16;
 
-template <int G>
+template <int G, int FORM>
 static int launch_sim(const SimArgs& a, bool select, hipStream_t s) {
   const dim3 grid((unsigned)((a.B + 256 / G - 1) / (256 / G)));
-  if (select) return launch_kernel<sim_advance_kernel<G, true>>(grid, dim3(256), 0, s, a);
-  return launch_kernel<sim_advance_kernel<G, false>>(grid, dim3(256), 0, s, a);
+  if constexpr (FORM != SIM_POSE) {              // (SIM_POSE has no plant: one instance)
+    if (select) return launch_kernel<sim_advance_kernel<G, true, FORM>>(grid, dim3(256), 0, s, a);
+  }
+  return launch_kernel<sim_advance_kernel<G, false, FORM>>(grid, dim3(256), 0, s, a);
+}
+
+// what every entry point asks of a track before any HIP call
+static bool track_ok(const irbfn_sim_track* track) {
+  if (!track || track->N < 2) return false;
+  if (track->win_back < -1 || track->win_fwd < -1 || ((track->win_back == -1) != (track->win_fwd == -1))) return false;
+  if (!(track->lookahead >= 0.0) || !(track->max_reacquire >= 0.0) || track->half_width != track->half_width) return false;
+  return true;
+}
+
+// irbfn_sim_advance (frenet = false: no curvature, x [B,7]) and irbfn_sim_advance_frenet
+static int sim_advance(bool frenet, const irbfn_sim_track* track, const double* curv_dev, int mode, int tick,
+                       const float* controls_dev, int T, const float* dyn_params_host, const float* dyn_params_dev, int n_sub,
+                       float* state_dev, int32_t* seg_dev, int32_t* status_dev, double* record_dev, float* x_dev,
+                       int32_t* mirror_dev, double* frenet_dev, double* goal_dev, double* dist_dev, double* t_dev, int64_t B,
+                       void* stream) {
+  if (B < 0 || n_sub < 1 || !track_ok(track)) return IRBFN_ERR_BAD_ARG;
+  if (mode != IRBFN_ROLLOUT_ST_SELECT && mode != IRBFN_ROLLOUT_ST_KS) return IRBFN_ERR_BAD_ARG;
+  if (controls_dev && T < 1) return IRBFN_ERR_BAD_ARG;
+  if (B == 0) return IRBFN_OK;
+  if (!track->waypoints_dev || !track->cum_dev || !track->len_dev || !state_dev || !seg_dev || !status_dev || !record_dev ||
+      !x_dev || !mirror_dev || (frenet && !curv_dev))
+    return IRBFN_ERR_BAD_ARG;
+  if (controls_dev && !dyn_params_host && !dyn_params_dev) return IRBFN_ERR_BAD_ARG;
+  SimArgs a;
+  a.tr = *track;
+  a.curv = curv_dev;
+  a.controls = controls_dev;
+  a.dyn_dev = dyn_params_dev;
+  for (int i = 0; i < 13; ++i) a.dp.p[i] = dyn_params_host ? dyn_params_host[i] : 0.0f;
+  a.T = T;
+  a.n_sub = n_sub;
+  a.tick = tick;
+  a.state = state_dev;
+  a.seg = seg_dev;
+  a.status = status_dev;
+  a.record = record_dev;
+  a.x = x_dev;
+  a.mirror = mirror_dev;
+  a.frenet = frenet_dev;
+  a.seg_out = nullptr;
+  a.goal = goal_dev;
+  a.dist = dist_dev;
+  a.tt = t_dev;
+  a.B = (long)B;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool select = mode == IRBFN_ROLLOUT_ST_SELECT;
+  return frenet ? launch_sim<kSimLanes, SIM_FRENET>(a, select, s) : launch_sim<kSimLanes, SIM_CARTESIAN>(a, select, s);
 }
 
 }  // namespace irbfn
@@ -242,38 +331,39 @@ int irbfn_sim_advance(const irbfn_sim_track* track, int mode, int tick, const fl
                       const float* dyn_params_host, const float* dyn_params_dev, int n_sub, float* state_dev, int32_t* seg_dev,
                       int32_t* status_dev, double* record_dev, float* x_dev, int32_t* mirror_dev, double* goal_dev,
                       double* dist_dev, double* t_dev, int64_t B, void* stream) {
-  if (!track || B < 0 || track->N < 2 || n_sub < 1) return IRBFN_ERR_BAD_ARG;
-  if (track->win_back < -1 || track->win_fwd < -1 || ((track->win_back == -1) != (track->win_fwd == -1)))
-    return IRBFN_ERR_BAD_ARG;
-  if (mode != IRBFN_ROLLOUT_ST_SELECT && mode != IRBFN_ROLLOUT_ST_KS) return IRBFN_ERR_BAD_ARG;
-  if (controls_dev && T < 1) return IRBFN_ERR_BAD_ARG;
-  if (!(track->lookahead >= 0.0) || !(track->max_reacquire >= 0.0) || track->half_width != track->half_width)
-    return IRBFN_ERR_BAD_ARG;
+  return sim_advance(false, track, nullptr, mode, tick, controls_dev, T, dyn_params_host, dyn_params_dev, n_sub, state_dev,
+                     seg_dev, status_dev, record_dev, x_dev, mirror_dev, nullptr, goal_dev, dist_dev, t_dev, B, stream);
+}
+
+int irbfn_sim_advance_frenet(const irbfn_sim_track* track, const double* curv_dev, int mode, int tick,
+                             const float* controls_dev, int T, const float* dyn_params_host, const float* dyn_params_dev,
+                             int n_sub, float* state_dev, int32_t* seg_dev, int32_t* status_dev, double* record_dev,
+                             float* x_dev, int32_t* mirror_dev, double* frenet_dev, double* goal_dev, double* dist_dev,
+                             double* t_dev, int64_t B, void* stream) {
+  return sim_advance(true, track, curv_dev, mode, tick, controls_dev, T, dyn_params_host, dyn_params_dev, n_sub, state_dev,
+                     seg_dev, status_dev, record_dev, x_dev, mirror_dev, frenet_dev, goal_dev, dist_dev, t_dev, B, stream);
+}
+
+int irbfn_cartesian_to_frenet(const irbfn_sim_track* track, const double* curv_dev, const float* state_dev,
+                              const int32_t* seg_dev, double* frenet_dev, int32_t* seg_out_dev, double* dist_dev,
+                              double* t_dev, int64_t B, void* stream) {
+  if (B < 0 || !track_ok(track)) return IRBFN_ERR_BAD_ARG;
   if (B == 0) return IRBFN_OK;
-  if (!track->waypoints_dev || !track->cum_dev || !track->len_dev || !state_dev || !seg_dev || !status_dev || !record_dev ||
-      !x_dev || !mirror_dev)
+  if (!track->waypoints_dev || !track->cum_dev || !track->len_dev || !curv_dev || !state_dev || !frenet_dev)
     return IRBFN_ERR_BAD_ARG;
-  if (controls_dev && !dyn_params_host && !dyn_params_dev) return IRBFN_ERR_BAD_ARG;
-  SimArgs a;
+  SimArgs a = {};
   a.tr = *track;
-  a.controls = controls_dev;
-  a.dyn_dev = dyn_params_dev;
-  for (int i = 0; i < 13; ++i) a.dp.p[i] = dyn_params_host ? dyn_params_host[i] : 0.0f;
-  a.T = T;
-  a.n_sub = n_sub;
-  a.tick = tick;
-  a.state = state_dev;
-  a.seg = seg_dev;
-  a.status = status_dev;
-  a.record = record_dev;
-  a.x = x_dev;
-  a.mirror = mirror_dev;
-  a.goal = goal_dev;
+  if (!seg_dev) a.tr.win_back = a.tr.win_fwd = -1;           // every segment
+  a.curv = curv_dev;
+  a.state = const_cast<float*>(state_dev);                   // SIM_POSE only reads the state and the segments
+  a.seg = const_cast<int32_t*>(seg_dev);
+  a.frenet = frenet_dev;
+  a.seg_out = seg_out_dev;
   a.dist = dist_dev;
   a.tt = t_dev;
+  a.n_sub = 1;
   a.B = (long)B;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return launch_sim<kSimLanes>(a, mode == IRBFN_ROLLOUT_ST_SELECT, s);
+  return launch_sim<kSimLanes, SIM_POSE>(a, false, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
