@@ -828,6 +828,26 @@ int irbfn_nmpc_solve(int mode, int T, const float* state0_dev /*[B,7]*/, const f
                      const float* dyn_params_dev /*[B,13] or NULL*/, const irbfn_nmpc_options* opt, float* u_dev /*[B,2T]*/,
                      float* cost_dev /*[B,2]*/, int32_t* info_dev /*[B,2]*/, float* grad_dev /*[B,2T] or NULL*/, int64_t B,
                      void* stream);
+/* The same solver through the Frenet low-speed model (K15; IRBFN_ROLLOUT_FRENET_LS, which irbfn_nmpc_solve keeps refusing): the
+ * controller the Frenet planner's 8-input nets imitate -- lateral and heading error on a line of given curvature.  The
+ * reference's CasADi / IPOPT generators cannot be run here: parity is unpinned, the rule is pinned against a float64 statement of
+ * itself (tests/_nmpc_frenet_util.py).  The rule, the options struct, the outputs, the statuses and the meaning of max_iter = 0
+ * are irbfn_nmpc_solve's word for word; what differs:
+ *   State: state0_dev [B,8] = [s, ey, delta, vx, vy, wz, epsi, curv]; s_1..s_T are the bits of
+ *   irbfn_rollout_forward(IRBFN_ROLLOUT_FRENET_LS, [state0 | u]).  vy, wz and curv never move.
+ *   Residuals: e_t = (s_t - g_0, ey_t - g_1, wrap(epsi_t - g_2), vx_t - g_3), state components {0, 1, 6, 3}, weighted by q / qf
+ *   and summed in the same order.
+ *   Frame: the frame ends at the centre of curvature.  A roll-out that starts any of its steps from 1 - ey_t curv <= 0 has cost
+ *   +inf: as the cost of the clipped start it makes the row IRBFN_NMPC_NONFINITE (u = the clipped start, both costs NaN, 0
+ *   iterations); as the cost of a trial step it is rejected and lambda grows.
+ *   Bounds and slopes: the box is |a_t| <= p[10], |sv_t| <= p[9], held by projection; the clip of delta has slope 1/2 on its
+ *   bound; vx has no clip in this model.
+ * IRBFN_ERR_BAD_ARG / IRBFN_ERR_UNSUPPORTED / B = 0: as irbfn_nmpc_solve, decided before any HIP call (there is no mode). */
+int irbfn_nmpc_solve_frenet(int T, const float* state0_dev /*[B,8]*/, const float* goal_dev /*[B,4]*/,
+                            const float* u0_dev /*[B,2T] or NULL*/, const float* dyn_params_host /*[13]*/,
+                            const float* dyn_params_dev /*[B,13] or NULL*/, const irbfn_nmpc_options* opt,
+                            float* u_dev /*[B,2T]*/, float* cost_dev /*[B,2]*/, int32_t* info_dev /*[B,2]*/,
+                            float* grad_dev /*[B,2T] or NULL*/, int64_t B, void* stream);
 /* Diagnostics */
 int irbfn_abi_version(void);
 int irbfn_device_count(void);

@@ -14,7 +14,7 @@ Host side is Python (like the reference) over a C-ABI shared library of hand-wri
 * ``irbfn_amd.ols``           ``select`` / ``fit_ols``: centres chosen by what they explain (OLS forward selection on the Gram matrix)
 * ``irbfn_amd.loo``           ``factor`` / ``loo`` / ``leverage`` / ``select_ridge``: leave-one-out errors and leverages of the closed-form fit
 * ``irbfn_amd.simulate``      ``Track`` / ``closed_loop``: B cars driven by a net along a race line, plant and way-point search on the device
-* ``irbfn_amd.nmpc``          ``solve`` / ``make_table`` / ``closed_loop``: batched NMPC solver (label tables, the MPC baseline of the closed loop)
+* ``irbfn_amd.nmpc``          ``solve`` / ``make_table`` / ``closed_loop`` and their ``_frenet`` forms: batched NMPC solver (label tables, the MPC baseline of the closed loop)
 * ``irbfn_amd.autograd``      ``torch.autograd`` wrappers (the ``jax.grad`` surface)
 * ``irbfn_amd.distributed``   one-process-per-GPU sharding, RCCL broadcast of the parameters
 

@@ -103,6 +103,7 @@ SIGNATURES = {
     "irbfn_sim_advance_frenet": (_i, [_vp, _fp, _i, _i, _fp, _i, _fp, _fp, _i, _fp, _ip, _ip, _fp, _fp, _ip, _fp, _fp, _fp, _fp,
                                       _i64, _vp]),
     "irbfn_nmpc_solve": (_i, [_i, _i, _fp, _fp, _fp, _fp, _fp, _vp, _fp, _fp, _ip, _fp, _i64, _vp]),
+    "irbfn_nmpc_solve_frenet": (_i, [_i, _fp, _fp, _fp, _fp, _fp, _vp, _fp, _fp, _ip, _fp, _i64, _vp]),
     "irbfn_abi_version": (_i, []),
     "irbfn_device_count": (_i, []),
     "irbfn_last_hip_error": (_i, []),

@@ -71,8 +71,8 @@ UNITS = [
     # the closed-loop tick around the net: plant step, windowed way-point search, goal, statistics, next query (no SLP: the plant
     # step is the roll-out's)
     ("sim_advance.hip", "sim_advance.o", ["-fno-slp-vectorize"]),
-    # K13: batched NMPC solver, one problem per lane; every array statically indexed, so the T and 2T loops must unroll fully (the
-    # roll-out's flags: the step inside is the roll-out's)
+    # K13 / K15: batched NMPC solver (single-track and Frenet models), one problem per lane; every array statically indexed, so
+    # the T and 2T loops must unroll fully (the roll-out's flags: the step inside is the roll-out's)
     ("nmpc_solve.hip", "nmpc_solve.o", ["-mllvm", "-pragma-unroll-threshold=100000", "-fno-slp-vectorize"]),
 ]
 

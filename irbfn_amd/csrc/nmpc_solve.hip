@@ -1,5 +1,6 @@
-// K13: batched NMPC solver (include/irbfn_hip.h: irbfn_nmpc_solve; DESIGN.md "K13").  For every row a bounded least-squares
-// problem in 2T <= 16 unknowns through the project's own roll-out step, solved by a projected Levenberg-Marquardt.
+// K13 / K15: batched NMPC solver (include/irbfn_hip.h: irbfn_nmpc_solve, irbfn_nmpc_solve_frenet; DESIGN.md "K13", "K15").  For
+// every row a bounded least-squares problem in 2T <= 16 unknowns through the project's own roll-out step (single-track, or the
+// Frenet low-speed model), solved by a projected Levenberg-Marquardt.
 //
 // One problem per lane, and everything the iteration touches lives in that lane's registers: u, u+, the sensitivities
 // S_t = d s_t / d u (NS x 2T, advanced step by step with the forward form of the roll-out adjoints, rollout_adjoint.h), the
@@ -17,7 +18,7 @@
 namespace irbfn {
 
 struct NmpcArgs {
-  const float* __restrict__ state0;    // [B][7]
+  const float* __restrict__ state0;    // [B][NmpcModel::SW]
   const float* __restrict__ goal;      // [B][4]
   const float* __restrict__ u0;        // [B][2T] or null
   const float* __restrict__ dyn_dev;   // [B][13] or null
@@ -32,6 +33,20 @@ struct NmpcArgs {
 
 constexpr float kNmpcTie = 0.5f;       // slope of the clips of delta and V on a bound (jnp.clip's, as the roll-out VJPs)
 
+// What the solver has to know about a model beside its step and StepJac: SW, the width of a state row; kHeading, the state
+// component behind the heading residual (the residuals are the state components {0, 1, kHeading, 3}, whose tangents are the
+// rows {0, 1, 4, 3} of S in every model); kFrame, whether a step may start only where 1 - ey curv > 0.
+template <int MODE>
+struct NmpcModel {                     // ST_KS, ST_SELECT: [x, y, delta, v, psi, psi_dot, beta]
+  static constexpr int SW = 7, kHeading = 4;
+  static constexpr bool kFrame = false;
+};
+template <>
+struct NmpcModel<IRBFN_ROLLOUT_FRENET_LS> {   // [s, ey, delta, vx, vy, wz, epsi, curv]: the frame ends at the centre of curvature
+  static constexpr int SW = 8, kHeading = 6;
+  static constexpr bool kFrame = true;
+};
+
 // index of (i, j), i <= j, in the packed upper triangle of an N x N matrix
 __host__ __device__ constexpr int tri(int i, int j, int N) { return i * N - (i * (i - 1)) / 2 + (j - i); }
 
@@ -43,15 +58,19 @@ __device__ __forceinline__ float wrap_angle(float e) {
 
 // One pass over the horizon at u: the cost, and with LIN the gradient g [2T] and the packed Gauss-Newton matrix H as well.
 // The cost arithmetic is the same instruction sequence with and without LIN (contraction off), so both give the same bits.
+// A model with a frame (NmpcModel::kFrame): a roll-out that starts any step from 1 - ey curv <= 0 costs +inf.
 template <int MODE, int T, bool LIN>
-__device__ __forceinline__ float nmpc_pass(const float (&u)[2 * T], const float (&s0)[7], const float (&gl)[4], const DynParams& dp,
-                                           const irbfn_nmpc_options& w, float (&g)[2 * T], float (&H)[T * (2 * T + 1)]) {
+__device__ __forceinline__ float nmpc_pass(const float (&u)[2 * T], const float (&s0)[NmpcModel<MODE>::SW], const float (&gl)[4],
+                                           const DynParams& dp, const irbfn_nmpc_options& w, float (&g)[2 * T],
+                                           float (&H)[T * (2 * T + 1)]) {
 #pragma clang fp contract(off)
+  using M = NmpcModel<MODE>;
   constexpr int N = 2 * T, NS = StepJac<MODE>::NS;
-  constexpr int kComp[4] = {0, 1, 4, 3};           // the state component behind residual x, y, heading, speed
-  float s[7];
+  constexpr int kComp[4] = {0, 1, 4, 3};           // the row of S behind residual x, y, heading, speed (s, ey, epsi, vx)
+  float s[M::SW];
 #pragma unroll
-  for (int i = 0; i < 7; ++i) s[i] = s0[i];
+  for (int i = 0; i < M::SW; ++i) s[i] = s0[i];
+  bool inside = true;
   float S[LIN ? NS * N : 1];                       // S[i * N + j] = d s_i / d u_j
   if constexpr (LIN) {
 #pragma unroll
@@ -82,18 +101,20 @@ __device__ __forceinline__ float nmpc_pass(const float (&u)[2 * T], const float 
 #pragma unroll
       for (int i = 0; i < NS; ++i) { S[i * N + t] = da[i]; S[i * N + T + t] = ds[i]; }
     }
+    if constexpr (M::kFrame) inside = inside && (1.0f - s[1] * s[7] > 0.0f);
     roll_step<MODE>(s, u[t], u[T + t], dp);
     float e[4];
     e[0] = s[0] - gl[0];
     e[1] = s[1] - gl[1];
-    e[2] = wrap_angle(s[4] - gl[2]);
+    e[2] = wrap_angle(s[M::kHeading] - gl[2]);
     e[3] = s[3] - gl[3];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float wk = t == T - 1 ? w.qf[k] : w.q[k];
       c = c + wk * (e[k] * e[k]);
       if constexpr (LIN) {
-        // the columns that reach (x, y, psi, v) of s_{t+1}: a_0..a_t and sv_0..sv_{t-1} (sv_t has only moved delta)
+        // the columns that reach the residual components of s_{t+1} -- (x, y, psi, v), or (s, ey, epsi, vx) in the Frenet model:
+        // a_0..a_t and sv_0..sv_{t-1} (sv_t has only moved delta)
         const int L = 2 * t + 1;
         float row[N], wrow[N];
 #pragma unroll
@@ -140,6 +161,7 @@ __device__ __forceinline__ float nmpc_pass(const float (&u)[2 * T], const float 
       H[tri(T + t, T + t, N)] += w.rd[1]; H[tri(T + t + 1, T + t + 1, N)] += w.rd[1]; H[tri(T + t, T + t + 1, N)] -= w.rd[1];
     }
   }
+  if constexpr (M::kFrame) return inside ? 0.5f * c : INFINITY;
   return 0.5f * c;
 }
 
@@ -212,12 +234,13 @@ __global__ __launch_bounds__(64) void nmpc_solve_kernel(const NmpcArgs a) {
 #pragma unroll
     for (int i = 0; i < 13; ++i) dp.p[i] = a.dyn_dev[row * 13 + i];
   }
-  float s0[7], gl[4], u[N], g[N], H[T * (2 * T + 1)];
+  constexpr int SW = NmpcModel<MODE>::SW;
+  float s0[SW], gl[4], u[N], g[N], H[T * (2 * T + 1)];
   bool finite = true;
 #pragma unroll
   for (int i = 0; i < 13; ++i) finite = finite && (fabsf(dp.p[i]) < INFINITY);
 #pragma unroll
-  for (int i = 0; i < 7; ++i) { s0[i] = a.state0[row * 7 + i]; finite = finite && (fabsf(s0[i]) < INFINITY); }
+  for (int i = 0; i < SW; ++i) { s0[i] = a.state0[row * SW + i]; finite = finite && (fabsf(s0[i]) < INFINITY); }
 #pragma unroll
   for (int i = 0; i < 4; ++i) { gl[i] = a.goal[row * 4 + i]; finite = finite && (fabsf(gl[i]) < INFINITY); }
   const float hi_a = dp.p[10], hi_s = dp.p[9];
@@ -315,11 +338,12 @@ static bool weight_ok(float v) { return v >= 0.0f && v < INFINITY; }
 
 using namespace irbfn;
 
-extern "C" int irbfn_nmpc_solve(int mode, int T, const float* state0_dev, const float* goal_dev, const float* u0_dev,
-                                const float* dyn_params_host, const float* dyn_params_dev, const irbfn_nmpc_options* opt,
-                                float* u_dev, float* cost_dev, int32_t* info_dev, float* grad_dev, int64_t B, void* stream) {
+// the checks both entry points share, decided before any HIP call: IRBFN_OK with *launch set when there is work to do
+static int nmpc_check(int T, const float* state0_dev, const float* goal_dev, const float* dyn_params_host, const float* dyn_params_dev,
+                      const irbfn_nmpc_options* opt, const float* u_dev, const float* cost_dev, const int32_t* info_dev, int64_t B,
+                      bool* launch) {
+  *launch = false;
   if (B < 0 || !opt) return IRBFN_ERR_BAD_ARG;
-  if (mode != IRBFN_ROLLOUT_ST_SELECT && mode != IRBFN_ROLLOUT_ST_KS) return IRBFN_ERR_BAD_ARG;
   for (int k = 0; k < 4; ++k)
     if (!weight_ok(opt->q[k]) || !weight_ok(opt->qf[k])) return IRBFN_ERR_BAD_ARG;
   for (int k = 0; k < 2; ++k)
@@ -331,6 +355,13 @@ extern "C" int irbfn_nmpc_solve(int mode, int T, const float* state0_dev, const 
   if (B == 0) return IRBFN_OK;
   if (!state0_dev || !goal_dev || !u_dev || !cost_dev || !info_dev || (!dyn_params_host && !dyn_params_dev))
     return IRBFN_ERR_BAD_ARG;
+  *launch = true;
+  return IRBFN_OK;
+}
+
+static NmpcArgs nmpc_args(const float* state0_dev, const float* goal_dev, const float* u0_dev, const float* dyn_params_host,
+                          const float* dyn_params_dev, const irbfn_nmpc_options* opt, float* u_dev, float* cost_dev,
+                          int32_t* info_dev, float* grad_dev, int64_t B) {
   NmpcArgs a;
   a.state0 = state0_dev;
   a.goal = goal_dev;
@@ -343,7 +374,31 @@ extern "C" int irbfn_nmpc_solve(int mode, int T, const float* state0_dev, const 
   a.info = info_dev;
   a.grad = grad_dev;
   a.B = (long)B;
+  return a;
+}
+
+extern "C" int irbfn_nmpc_solve(int mode, int T, const float* state0_dev, const float* goal_dev, const float* u0_dev,
+                                const float* dyn_params_host, const float* dyn_params_dev, const irbfn_nmpc_options* opt,
+                                float* u_dev, float* cost_dev, int32_t* info_dev, float* grad_dev, int64_t B, void* stream) {
+  if (B < 0 || !opt) return IRBFN_ERR_BAD_ARG;
+  if (mode != IRBFN_ROLLOUT_ST_SELECT && mode != IRBFN_ROLLOUT_ST_KS) return IRBFN_ERR_BAD_ARG;
+  bool launch;
+  const int st = nmpc_check(T, state0_dev, goal_dev, dyn_params_host, dyn_params_dev, opt, u_dev, cost_dev, info_dev, B, &launch);
+  if (!launch) return st;
+  const NmpcArgs a = nmpc_args(state0_dev, goal_dev, u0_dev, dyn_params_host, dyn_params_dev, opt, u_dev, cost_dev, info_dev,
+                               grad_dev, B);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (mode == IRBFN_ROLLOUT_ST_SELECT) return launch_nmpc<IRBFN_ROLLOUT_ST_SELECT>(T, a, s);
   return launch_nmpc<IRBFN_ROLLOUT_ST_KS>(T, a, s);
+}
+
+extern "C" int irbfn_nmpc_solve_frenet(int T, const float* state0_dev, const float* goal_dev, const float* u0_dev,
+                                       const float* dyn_params_host, const float* dyn_params_dev, const irbfn_nmpc_options* opt,
+                                       float* u_dev, float* cost_dev, int32_t* info_dev, float* grad_dev, int64_t B, void* stream) {
+  bool launch;
+  const int st = nmpc_check(T, state0_dev, goal_dev, dyn_params_host, dyn_params_dev, opt, u_dev, cost_dev, info_dev, B, &launch);
+  if (!launch) return st;
+  const NmpcArgs a = nmpc_args(state0_dev, goal_dev, u0_dev, dyn_params_host, dyn_params_dev, opt, u_dev, cost_dev, info_dev,
+                               grad_dev, B);
+  return launch_nmpc<IRBFN_ROLLOUT_FRENET_LS>(T, a, reinterpret_cast<hipStream_t>(stream));
 }

@@ -132,16 +132,25 @@ __device__ __forceinline__ void vjp_back_step(const S* p, S a_in, S sv_in, S* la
   }
 }
 
-// The same one-step Jacobians in forward (JVP) form, for the two single-track modes (nmpc_solve.hip advances the sensitivities
-// S_t = d s_t / d u with them).  jvp_coeffs evaluates, from the state a step STARTS from, the dt-scaled entries of
-// F_x = d s' / d s and of d s' / d a that are neither 0 nor 1 -- the coefficient expressions of vjp_back_step above, entry for
+// The same one-step Jacobians in forward (JVP) form, for the two single-track modes and the Frenet one (nmpc_solve.hip advances
+// the sensitivities S_t = d s_t / d u with them).  jvp_coeffs evaluates, from the state a step STARTS from, the dt-scaled entries
+// of F_x = d s' / d s and of d s' / d a that are neither 0 nor 1 -- the coefficient expressions of vjp_back_step above, entry for
 // entry; jvp_carry applies them to one tangent, jvp_fresh gives the tangents of this step's own two controls.  The controls are
 // taken to lie inside their box (slope 1: the solver keeps them there by projection); the clips of delta and V have
 // clipgrad's slope.  ST_KS never moves psi_dot and beta: its tangents have NS = 5 components [x, y, delta, v, psi]; ST_SELECT
 // carries all 7 and holds the mask V > 3 constant, a coefficient of the branch not taken being 0 by select (never by a product
 // with 0: at V = 0 the dynamic ones are inf / nan).  The NumPy statement is tests/_nmpc_util.py: step_jacobian.
+// FRENET_LS never moves vy, wz and curv: its tangents have NS = 5 components [s, ey, delta, vx, epsi] (state components 0, 1, 2,
+// 3, 6); vx has no clip in this model.  The NumPy statement is tests/_nmpc_frenet_util.py: step_jacobian.
 template <int MODE>
 struct StepJac;
+template <>
+struct StepJac<IRBFN_ROLLOUT_FRENET_LS> {
+  static constexpr int NS = 5;
+  float s1, s3, s4;        // row s': d / d ey, vx, epsi
+  float y3, y4;            // row ey': d / d vx, epsi
+  float e1, e2, e3, e4;    // row epsi': d / d ey, delta, vx, epsi (e4 on top of the diagonal 1)
+};
 template <>
 struct StepJac<IRBFN_ROLLOUT_ST_KS> {
   static constexpr int NS = 5;
@@ -158,59 +167,80 @@ struct StepJac<IRBFN_ROLLOUT_ST_SELECT> {
 template <int MODE, typename Trig = TrigDirect>
 __device__ __forceinline__ void jvp_coeffs(const float* s, float a_in, float tie, const DynParams& dp, StepJac<MODE>& J,
                                            const Trig trig = Trig()) {
-  static_assert(MODE == IRBFN_ROLLOUT_ST_KS || MODE == IRBFN_ROLLOUT_ST_SELECT, "single-track modes only");
+  static_assert(MODE == IRBFN_ROLLOUT_ST_KS || MODE == IRBFN_ROLLOUT_ST_SELECT || MODE == IRBFN_ROLLOUT_FRENET_LS,
+                "single-track and Frenet modes only");
   const float lf = dp.p[3], lr = dp.p[4], dt = dp.p[8], s_max = dp.p[11], v_max = dp.p[12];
   const float Lw = lr + lf;
-  const float d_raw = s[2], v_raw = s[3], psi = s[4];
-  const float DELTA = clipf(d_raw, -s_max, s_max), V = clipf(v_raw, -v_max, v_max);
-  const float md = clipgrad(d_raw, -s_max, s_max, tie), mv = clipgrad(v_raw, -v_max, v_max, tie);
-  float cp, sp, td;
-  if constexpr (MODE == IRBFN_ROLLOUT_ST_KS) {
-    trig.sincos_tan(psi, DELTA, s_max < 4194304.0f, sp, cp, td);
-    J.x3 = mv * dt * cp;
-    J.x4 = -(dt * V * sp);
-    J.y3 = mv * dt * sp;
-    J.y4 = dt * V * cp;
-    J.p2 = md * (V / Lw) * (1.0f + td * td) * dt;
-    J.p3 = mv * dt * (td / Lw);
+  if constexpr (MODE == IRBFN_ROLLOUT_FRENET_LS) {
+    // s = [s, ey, delta, vx, vy, wz, epsi, curv]; with A = dt lam_s - dt curv lam_epsi the total cotangent on d0 = vx ce / den
+    // in vjp_back_step<FRENET_LS>, row epsi' holds -curv times row s' beside its own tan term
+    const float ey = s[1], d_raw = s[2], vx = s[3], epsi = s[6], cur = s[7];
+    const float dc = clipf(d_raw, -s_max, s_max);
+    const float md = clipgrad(d_raw, -s_max, s_max, tie);
+    float ce, se, td;
+    trig.sincos_tan(epsi, dc, s_max < 4194304.0f, se, ce, td);
+    const float den = 1.0f - ey * cur;
+    J.s1 = dt * (vx * ce * cur / (den * den));
+    J.s3 = dt * (ce / den);
+    J.s4 = dt * (-vx * se / den);
+    J.y3 = dt * se;
+    J.y4 = dt * vx * ce;
+    J.e1 = -(cur * J.s1);
+    J.e2 = md * dt * vx * (1.0f + td * td) / Lw;
+    J.e3 = dt * td / Lw - cur * J.s3;
+    J.e4 = -(cur * J.s4);
   } else {
-    const float g = 9.81f;
-    const float mu = dp.p[0], m = dp.p[1], I = dp.p[2], C_Sf = dp.p[5], C_Sr = dp.p[6], h = dp.p[7], a_max = dp.p[10];
-    const float pd = s[5], beta = s[6];
-    const float A = clipf(a_in, -a_max, a_max);
-    const bool dyn = V > 3.0f;
-    trig.sincos_tan(dyn ? psi + beta : psi, DELTA, s_max < 4194304.0f, sp, cp, td);
-    const float head_x = -(dt * V * sp), head_y = dt * V * cp;   // what f0 and f1 put on their angle
-    const float glr = g * lr - A * h, glf = g * lf + A * h;
-    const float E = C_Sf * glr, F = C_Sr * glf;
-    const float P = lf * E, Q = lr * F, R = lf * lf * E + lr * lr * F, M = F * lr - E * lf;
-    const float rV = 1.0f / V, pv = pd * rV;
-    const float c5 = (mu * m) / (I * Lw), c6 = (mu * rV) / Lw;
-    const float U = E * DELTA - (F + E) * beta + M * pv;
-    const float Ea = -C_Sf * h, Fa = C_Sr * h;
-    const float f5A = c5 * (lf * Ea * DELTA + (lr * Fa - lf * Ea) * beta - (lf * lf * Ea + lr * lr * Fa) * pv);
-    const float f6A = c6 * (Ea * DELTA - (Fa + Ea) * beta + (Fa * lr - Ea * lf) * pv);
-    const float f5V = c5 * R * pv * rV, f6V = -c6 * (U + M * pv) * rV;
-    const float f5W = -c5 * R * rV, f6W = c6 * M * rV - 1.0f;
-    J.x3 = mv * dt * cp;
-    J.x4 = head_x;
-    J.x6 = dyn ? head_x : 0.0f;
-    J.y3 = mv * dt * sp;
-    J.y4 = head_y;
-    J.y6 = dyn ? head_y : 0.0f;
-    J.p2 = dyn ? 0.0f : md * (V / Lw) * (1.0f + td * td) * dt;
-    J.p3 = dyn ? 0.0f : mv * dt * (td / Lw);
-    J.p5 = dyn ? dt : 0.0f;
-    J.w2 = dyn ? md * dt * (c5 * P) : 0.0f;
-    J.w3 = dyn ? mv * dt * f5V : 0.0f;
-    J.w5 = dyn ? dt * f5W : 0.0f;
-    J.w6 = dyn ? dt * (c5 * (Q - P)) : 0.0f;
-    J.wa = dyn ? dt * f5A : 0.0f;
-    J.b2 = dyn ? md * dt * (c6 * E) : 0.0f;
-    J.b3 = dyn ? mv * dt * f6V : 0.0f;
-    J.b5 = dyn ? dt * f6W : 0.0f;
-    J.b6 = dyn ? -(dt * (c6 * (F + E))) : 0.0f;
-    J.ba = dyn ? dt * f6A : 0.0f;
+    const float d_raw = s[2], v_raw = s[3], psi = s[4];
+    const float DELTA = clipf(d_raw, -s_max, s_max), V = clipf(v_raw, -v_max, v_max);
+    const float md = clipgrad(d_raw, -s_max, s_max, tie), mv = clipgrad(v_raw, -v_max, v_max, tie);
+    float cp, sp, td;
+    if constexpr (MODE == IRBFN_ROLLOUT_ST_KS) {
+      trig.sincos_tan(psi, DELTA, s_max < 4194304.0f, sp, cp, td);
+      J.x3 = mv * dt * cp;
+      J.x4 = -(dt * V * sp);
+      J.y3 = mv * dt * sp;
+      J.y4 = dt * V * cp;
+      J.p2 = md * (V / Lw) * (1.0f + td * td) * dt;
+      J.p3 = mv * dt * (td / Lw);
+    } else {
+      const float g = 9.81f;
+      const float mu = dp.p[0], m = dp.p[1], I = dp.p[2], C_Sf = dp.p[5], C_Sr = dp.p[6], h = dp.p[7], a_max = dp.p[10];
+      const float pd = s[5], beta = s[6];
+      const float A = clipf(a_in, -a_max, a_max);
+      const bool dyn = V > 3.0f;
+      trig.sincos_tan(dyn ? psi + beta : psi, DELTA, s_max < 4194304.0f, sp, cp, td);
+      const float head_x = -(dt * V * sp), head_y = dt * V * cp;   // what f0 and f1 put on their angle
+      const float glr = g * lr - A * h, glf = g * lf + A * h;
+      const float E = C_Sf * glr, F = C_Sr * glf;
+      const float P = lf * E, Q = lr * F, R = lf * lf * E + lr * lr * F, M = F * lr - E * lf;
+      const float rV = 1.0f / V, pv = pd * rV;
+      const float c5 = (mu * m) / (I * Lw), c6 = (mu * rV) / Lw;
+      const float U = E * DELTA - (F + E) * beta + M * pv;
+      const float Ea = -C_Sf * h, Fa = C_Sr * h;
+      const float f5A = c5 * (lf * Ea * DELTA + (lr * Fa - lf * Ea) * beta - (lf * lf * Ea + lr * lr * Fa) * pv);
+      const float f6A = c6 * (Ea * DELTA - (Fa + Ea) * beta + (Fa * lr - Ea * lf) * pv);
+      const float f5V = c5 * R * pv * rV, f6V = -c6 * (U + M * pv) * rV;
+      const float f5W = -c5 * R * rV, f6W = c6 * M * rV - 1.0f;
+      J.x3 = mv * dt * cp;
+      J.x4 = head_x;
+      J.x6 = dyn ? head_x : 0.0f;
+      J.y3 = mv * dt * sp;
+      J.y4 = head_y;
+      J.y6 = dyn ? head_y : 0.0f;
+      J.p2 = dyn ? 0.0f : md * (V / Lw) * (1.0f + td * td) * dt;
+      J.p3 = dyn ? 0.0f : mv * dt * (td / Lw);
+      J.p5 = dyn ? dt : 0.0f;
+      J.w2 = dyn ? md * dt * (c5 * P) : 0.0f;
+      J.w3 = dyn ? mv * dt * f5V : 0.0f;
+      J.w5 = dyn ? dt * f5W : 0.0f;
+      J.w6 = dyn ? dt * (c5 * (Q - P)) : 0.0f;
+      J.wa = dyn ? dt * f5A : 0.0f;
+      J.b2 = dyn ? md * dt * (c6 * E) : 0.0f;
+      J.b3 = dyn ? mv * dt * f6V : 0.0f;
+      J.b5 = dyn ? dt * f6W : 0.0f;
+      J.b6 = dyn ? -(dt * (c6 * (F + E))) : 0.0f;
+      J.ba = dyn ? dt * f6A : 0.0f;
+    }
   }
 }
 
@@ -221,6 +251,11 @@ __device__ __forceinline__ void jvp_carry(const StepJac<MODE>& J, float* d) {
     const float n0 = d[0] + (J.x3 * d[3] + J.x4 * d[4]);
     const float n1 = d[1] + (J.y3 * d[3] + J.y4 * d[4]);
     const float n4 = d[4] + (J.p2 * d[2] + J.p3 * d[3]);
+    d[0] = n0; d[1] = n1; d[4] = n4;
+  } else if constexpr (MODE == IRBFN_ROLLOUT_FRENET_LS) {
+    const float n0 = d[0] + (J.s1 * d[1] + J.s3 * d[3] + J.s4 * d[4]);
+    const float n1 = d[1] + (J.y3 * d[3] + J.y4 * d[4]);
+    const float n4 = d[4] + (J.e1 * d[1] + J.e2 * d[2] + J.e3 * d[3] + J.e4 * d[4]);
     d[0] = n0; d[1] = n1; d[4] = n4;
   } else {
     const float n0 = d[0] + (J.x3 * d[3] + J.x4 * d[4] + J.x6 * d[6]);

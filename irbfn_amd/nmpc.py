@@ -6,6 +6,10 @@ It closes the two open ends of the pipeline: ``make_table`` writes a label table
 reference's labels come from CasADi / IPOPT solvers, which this project cannot run), and ``closed_loop`` drives the cars of
 ``simulate.closed_loop`` with the solver instead of a net -- the controller a net imitates, on the same line and plant.
 
+``solve_frenet`` (``irbfn_nmpc_solve_frenet``, K15) is the same solver through the Frenet low-speed model: the controller the
+Frenet planner's 8-input nets imitate.  ``make_table_frenet`` writes their label tables, ``closed_loop_frenet`` drives the cars
+of ``simulate.closed_loop_frenet`` with it.
+
 Weights, tolerances and damping constants are this project's own; the reference's are not readable here.
 Everything stays on the device; nothing synchronises with the host until a result is read."""
 from __future__ import annotations
@@ -33,6 +37,14 @@ class Weights:
     qf: Sequence[float] = (10.0, 10.0, 5.0, 1.0)
     r: Sequence[float] = (0.01, 0.1)
     rd: Sequence[float] = (0.01, 0.1)
+
+
+@dataclass(frozen=True)
+class FrenetWeights(Weights):
+    """``Weights`` for ``solve_frenet``: e = (s, ey, heading error, vx) errors.  The defaults are this project's own: the lateral,
+    heading and speed weights of ``Weights``, and none on s -- progress along the line is free."""
+    q: Sequence[float] = (0.0, 1.0, 0.5, 0.1)
+    qf: Sequence[float] = (0.0, 10.0, 5.0, 1.0)
 
 
 @dataclass
@@ -73,18 +85,24 @@ def _options(weights, max_iter, lambda0, lambda_min, lambda_max, tol, eps) -> _l
     return o
 
 
-def _check_problem(state0, goal, u0, dyn_params, T, mode):
-    """shapes and ranges of one solve, checked without a GPU -> (B, "host" | "dev")"""
+_STATE = {False: (7, "[x, y, delta, v, psi, psi_dot, beta]", "(x, y, heading, speed)"),
+          True: (8, "[s, ey, delta, vx, vy, wz, epsi, curv]", "(s, ey, heading error, vx)")}
+
+
+def _check_problem(state0, goal, u0, dyn_params, T, mode, frenet=False):
+    """shapes and ranges of one solve, checked without a GPU -> (B, "host" | "dev").  ``frenet``: the Frenet model's state row
+    (there is no mode to choose)."""
     if int(T) != T or not 1 <= T <= T_MAX:
         raise ValueError(f"the horizon T must be an integer in 1..{T_MAX}")
-    if mode not in (_lib.ROLLOUT_ST_SELECT, _lib.ROLLOUT_ST_KS):
+    if not frenet and mode not in (_lib.ROLLOUT_ST_SELECT, _lib.ROLLOUT_ST_KS):
         raise ValueError("the model is ROLLOUT_ST_SELECT or ROLLOUT_ST_KS")
+    width, names, errors = _STATE[bool(frenet)]
     s = _shape(state0)
-    if len(s) != 2 or s[1] != 7:
-        raise ValueError("state0 must be [B,7] = [x, y, delta, v, psi, psi_dot, beta]")
+    if len(s) != 2 or s[1] != width:
+        raise ValueError(f"state0 must be [B,{width}] = {names}")
     B = s[0]
     if _shape(goal) != (B, 4):
-        raise ValueError(f"goal must be [B,4] = [{B}, 4] = (x, y, heading, speed)")
+        raise ValueError(f"goal must be [B,4] = [{B}, 4] = {errors}")
     if u0 is not None and _shape(u0) != (B, 2 * T):
         raise ValueError(f"u0 must be [B,2T] = [{B}, {2 * T}]")
     if dyn_params is None:
@@ -102,7 +120,23 @@ def solve(state0, goal, dyn_params, T: int = 5, weights: Weights = Weights(), u0
           eps: float = 1e-6, want_grad: bool = False) -> NMPCResult:
     """One ``irbfn_nmpc_solve``: state0 [B,7], goal [B,4], ``dyn_params`` 13 numbers or a [B,13] tensor (one row per problem),
     start ``u0`` [B,2T] (None: zeros).  ``max_iter = 0`` evaluates cost and gradient at the clipped start."""
-    B, kind = _check_problem(state0, goal, u0, dyn_params, T, mode)
+    return _solve(False, state0, goal, dyn_params, T, weights, u0, mode, max_iter, lambda0, lambda_min, lambda_max, tol, eps,
+                  want_grad)
+
+
+def solve_frenet(state0, goal, dyn_params, T: int = 5, weights: Weights = FrenetWeights(), u0=None, max_iter: int = 30,
+                 lambda0: float = 1e-3, lambda_min: float = 1e-9, lambda_max: float = 1e6, tol: float = 1e-6, eps: float = 1e-6,
+                 want_grad: bool = False) -> NMPCResult:
+    """One ``irbfn_nmpc_solve_frenet``: ``solve`` through the Frenet low-speed model.  state0 [B,8] = [s, ey, delta, vx, vy, wz,
+    epsi, curv], goal [B,4] = (s, ey, heading error, vx).  A row that starts outside the frame (1 - ey curv <= 0) comes back
+    ``NMPC_NONFINITE``."""
+    return _solve(True, state0, goal, dyn_params, T, weights, u0, None, max_iter, lambda0, lambda_min, lambda_max, tol, eps,
+                  want_grad)
+
+
+def _solve(frenet, state0, goal, dyn_params, T, weights, u0, mode, max_iter, lambda0, lambda_min, lambda_max, tol, eps, want_grad):
+    """``solve`` (frenet false) and ``solve_frenet``: the checks, the buffers and the call"""
+    B, kind = _check_problem(state0, goal, u0, dyn_params, T, mode, frenet)
     opt = _options(weights, max_iter, lambda0, lambda_min, lambda_max, tol, eps)
     torch = _lib.require_gpu()
     lib = _lib.load()
@@ -119,9 +153,12 @@ def solve(state0, goal, dyn_params, T: int = 5, weights: Weights = Weights(), u0
     info = torch.empty((B, 2), dtype=torch.int32, device=sd.device)
     grad = torch.empty((B, 2 * T), dtype=torch.float32, device=sd.device) if want_grad else None
     opt_p = lambda t: _ptr(t) if t is not None else null
-    st = lib.irbfn_nmpc_solve(int(mode), int(T), _ptr(sd), _ptr(gd), opt_p(ud), host, opt_p(dev), C.byref(opt), _ptr(u),
-                              _ptr(cost), _ptr(info), opt_p(grad), B, _stream_ptr(torch))
-    _lib.check(st, "irbfn_nmpc_solve")
+    rest = (int(T), _ptr(sd), _ptr(gd), opt_p(ud), host, opt_p(dev), C.byref(opt), _ptr(u), _ptr(cost), _ptr(info), opt_p(grad), B,
+            _stream_ptr(torch))
+    if frenet:
+        _lib.check(lib.irbfn_nmpc_solve_frenet(*rest), "irbfn_nmpc_solve_frenet")
+    else:
+        _lib.check(lib.irbfn_nmpc_solve(int(mode), *rest), "irbfn_nmpc_solve")
     return NMPCResult(controls=u, cost0=cost[:, 0], cost=cost[:, 1], status=info[:, 0], iterations=info[:, 1], grad=grad)
 
 
@@ -150,12 +187,47 @@ def solve_queries(x, dyn_params, T: int = 5, **kw) -> NMPCResult:
     return solve(state0, goal, dyn_params, T=T, **kw)
 
 
+def frenet_query_problem(x):
+    """The Frenet planner's query ``[ey, delta, vx, vy, vx_goal, wz, epsi, curv]`` [B,8] (planner_geom.h) -> (state0 [B,8], goal
+    [B,4]): state0 = [0, ey, delta, vx, vy, wz, epsi, curv], goal = (0, 0, 0, vx_goal).  The query is taken literally: mirroring it
+    is the planner's business, not the table's.  NumPy in, NumPy out; tensor in, tensor out."""
+    if len(_shape(x)) != 2 or _shape(x)[1] != 8:
+        raise ValueError("queries must be [B,8] = [ey, delta, vx, vy, vx_goal, wz, epsi, curv]")
+    if hasattr(x, "new_zeros"):
+        state0 = x.new_zeros(x.shape)
+        goal = x.new_zeros((x.shape[0], 4))
+    else:
+        x = np.asarray(x)
+        state0 = np.zeros_like(x)
+        goal = np.zeros((x.shape[0], 4), x.dtype)
+    state0[:, 1:4] = x[:, 0:3]
+    state0[:, 4] = x[:, 3]
+    state0[:, 5:8] = x[:, 5:8]
+    goal[:, 3] = x[:, 4]
+    return state0, goal
+
+
+def solve_queries_frenet(x, dyn_params, T: int = 5, **kw) -> NMPCResult:
+    """``solve_frenet`` on Frenet planner queries x [B,8] (``frenet_query_problem``)."""
+    state0, goal = frenet_query_problem(x)
+    return solve_frenet(state0, goal, dyn_params, T=T, **kw)
+
+
 def make_table(x, dyn_params, T: int = 5, save: Optional[str] = None, **kw):
     """Label table of the queries x [N,7]: -> (inputs [N,7], outputs [N,T,2]) NumPy float32, the reference's ``.npz`` layout
     (tables.py).  A row whose solve did not converge holds ``tables.INFEASIBLE`` in every output, so
     ``tables.remove_infeasible`` drops it; ``tables.flatten_outputs`` / ``tables.mirror`` apply unchanged.  ``save``: also
     written there with ``np.savez`` (keys ``inputs``, ``outputs``)."""
-    res = solve_queries(x, dyn_params, T=T, **kw)
+    return _table(solve_queries(x, dyn_params, T=T, **kw), x, save)
+
+
+def make_table_frenet(x, dyn_params, T: int = 5, save: Optional[str] = None, **kw):
+    """``make_table`` for the Frenet planner's nets: queries x [N,8] -> (inputs [N,8], outputs [N,T,2]), the same layout and the
+    same ``tables.INFEASIBLE`` fill of the rows that did not converge, labels from ``solve_queries_frenet``."""
+    return _table(solve_queries_frenet(x, dyn_params, T=T, **kw), x, save)
+
+
+def _table(res, x, save):
     u = res.controls.cpu().numpy()
     ok = res.status.cpu().numpy() == _lib.NMPC_CONVERGED
     inputs = np.ascontiguousarray(np.asarray(x.detach().cpu() if hasattr(x, "detach") else x, dtype=np.float32))
@@ -191,20 +263,49 @@ def closed_loop(track, state0, ticks: int, dyn_params, plant_params=None, T: int
     car drives on.  Same statistics and status words as ``simulate.closed_loop``.  A frozen car is solved like any other row
     and ignored by ``advance``.  Further keywords go to ``solve``: its weights and iteration constants (the start and the
     gradient are the loop's own business)."""
+    return _closed_loop(False, track, state0, ticks, dyn_params, plant_params, T, n_sub, mode, record_every, kw)
+
+
+def closed_loop_frenet(track, state0, ticks: int, dyn_params, plant_params=None, T: int = 5, n_sub: int = 1,
+                       mode: int = _lib.ROLLOUT_ST_SELECT, record_every: int = 0, **kw) -> simulate.SimResult:
+    """``closed_loop`` with ``solve_frenet``: per tick one ``simulate.advance_frenet`` (plant, way-point search, Frenet pose on
+    the polyline, goal) and one ``solve_frenet`` on the float32 pose with s = 0 and the goal (0, 0, 0, the goal way-point's
+    speed) -- back onto the line at the line's speed -- warm-started in the same way.  ``state0`` is still the single-track
+    [B,7]; ``mode`` and ``plant_params`` describe the Cartesian plant, ``dyn_params`` the solver's Frenet model.  Further keywords
+    go to ``solve_frenet`` (default weights: ``FrenetWeights``)."""
+    return _closed_loop(True, track, state0, ticks, dyn_params, plant_params, T, n_sub, mode, record_every, kw)
+
+
+def _frenet_tick_problem(pose, goal):
+    """what ``closed_loop_frenet`` solves each tick, from the outputs of ``simulate.advance_frenet`` (float64 device tensors pose
+    [B,8], goal [B,4]) -> (state0 [B,8], goal [B,4]) float32: the pose with s = 0, and (0, 0, 0, the goal way-point's speed)"""
+    import torch
+    state0 = pose.to(torch.float32)
+    state0[:, 0] = 0.0
+    g = torch.zeros((pose.shape[0], 4), dtype=torch.float32, device=pose.device)
+    g[:, 3] = goal[:, 3].to(torch.float32)
+    return state0, g
+
+
+def _closed_loop(frenet, track, state0, ticks, dyn_params, plant_params, T, n_sub, mode, record_every, kw):
+    """``closed_loop`` (frenet false) and ``closed_loop_frenet``: the checks, the arrays, the loop and the result"""
+    name = "closed_loop_frenet" if frenet else "closed_loop"
     if not isinstance(track, simulate.Track):
         raise TypeError(f"track must be a simulate.Track, not {type(track).__name__}")
     extra = sorted(set(kw) - set(_LOOP_SOLVE_KW))
     if extra:
-        raise TypeError(f"closed_loop passes only {', '.join(_LOOP_SOLVE_KW)} on to solve, not {', '.join(extra)}")
+        raise TypeError(f"{name} passes only {', '.join(_LOOP_SOLVE_KW)} on to solve, not {', '.join(extra)}")
     if int(ticks) != ticks or ticks < 0 or int(n_sub) != n_sub or n_sub < 1 or int(record_every) != record_every or record_every < 0:
         raise ValueError("ticks >= 0, n_sub >= 1 and record_every >= 0 must be integers")
     shape = _shape(state0)
     if len(shape) != 2 or shape[1] != 7:
         raise ValueError("state0 must be [B,7] = [x, y, delta, v, psi, psi_dot, beta]")
     B = shape[0]
-    _check_problem(state0, np.empty((B, 4)), None, dyn_params, T, mode)
-    _options(kw.get("weights", Weights()), kw.get("max_iter", 30), kw.get("lambda0", 1e-3), kw.get("lambda_min", 1e-9),
-             kw.get("lambda_max", 1e6), kw.get("tol", 1e-6), kw.get("eps", 1e-6))
+    if frenet and mode not in (_lib.ROLLOUT_ST_SELECT, _lib.ROLLOUT_ST_KS):
+        raise ValueError("the plant's model is ROLLOUT_ST_SELECT or ROLLOUT_ST_KS")
+    _check_problem(np.empty((B, 8 if frenet else 7)), np.empty((B, 4)), None, dyn_params, T, mode, frenet)
+    _options(kw.get("weights", FrenetWeights() if frenet else Weights()), kw.get("max_iter", 30), kw.get("lambda0", 1e-3),
+             kw.get("lambda_min", 1e-9), kw.get("lambda_max", 1e6), kw.get("tol", 1e-6), kw.get("eps", 1e-6))
     kind, plant = simulate._plant(plant_params, dyn_params, B)
     torch = _lib.require_gpu()
     state = to_device_f32(state0, torch).clone()
@@ -214,16 +315,23 @@ def closed_loop(track, state0, ticks: int, dyn_params, plant_params=None, T: int
     seg = track.seed(state[:, :2].to(torch.float64)).contiguous()
     status = torch.zeros((B,), dtype=torch.int32, device=dev)
     record = simulate.new_record(B, torch, dev)
-    x = torch.zeros((B, 7), dtype=torch.float32, device=dev)
+    x = torch.zeros((B, 8 if frenet else 7), dtype=torch.float32, device=dev)
     mirror = torch.zeros((B,), dtype=torch.int32, device=dev)
     goal = torch.zeros((B, 4), dtype=torch.float64, device=dev)
     states = torch.empty((ticks // record_every, B, 7), dtype=torch.float32, device=dev) if record_every else None
-    simulate.advance(track, state, seg, status, record, x, mirror, mode=mode, tick=0, goal_out=goal)
+    if frenet:
+        pose = torch.zeros((B, 8), dtype=torch.float64, device=dev)
+        advance = lambda **a: simulate.advance_frenet(track, state, seg, status, record, x, mirror, mode=mode, frenet_out=pose,
+                                                      goal_out=goal, **a)
+        control = lambda warm: solve_frenet(*_frenet_tick_problem(pose, goal), dyn_params, T=T, u0=warm, **kw).controls
+    else:
+        advance = lambda **a: simulate.advance(track, state, seg, status, record, x, mirror, mode=mode, goal_out=goal, **a)
+        control = lambda warm: solve(state, goal.to(torch.float32), dyn_params, T=T, u0=warm, mode=mode, **kw).controls
+    advance(tick=0)
     warm = None
     for k in range(int(ticks)):
-        ctrl = solve(state, goal.to(torch.float32), dyn_params, T=T, u0=warm, mode=mode, **kw).controls
-        simulate.advance(track, state, seg, status, record, x, mirror, controls=ctrl, plant_params=plant, n_sub=n_sub,
-                         mode=mode, tick=k + 1, goal_out=goal)
+        ctrl = control(warm)
+        advance(controls=ctrl, plant_params=plant, n_sub=n_sub, tick=k + 1)
         warm = shift_controls(ctrl, T)
         if record_every and (k + 1) % record_every == 0:
             states[(k + 1) // record_every - 1].copy_(state)
